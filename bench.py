@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: BLS12-377 G1 MSM throughput (points/s) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n 26] [--c C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n 26] [--c C] [--full] [--dump-outputs DIR]
 
 One "step" = one MSM over resident base points with FRESH scalars already in HBM (the reference's
 protocol: points pre-loaded, new random scalars every run, scripts/msm-weierstrass.ts:12-51).
@@ -9,19 +9,24 @@ N = 1: the whole MSM on one GPU.  N > 1, one rank per GPU: the same MSM sharded 
 `--split windows` (BASELINE configs[4], the north star: every rank holds all points and scalars and computes the
 window sums P_k of its windows; windows are independent until src/msm-batched-affine.ts:312-333); the other split
 (`points`: every rank runs all K windows on its share of the points and needs only that share of the scalars) is
-timed by the same run and reported as `other_splits`.  Either way ONE RCCL all-gather of K x 144 bytes per rank,
+timed by a --full run and reported as `other_splits`.  Either way ONE RCCL all-gather of K x 144 bytes per rank,
 rank 0 does the Horner combination.  Total work is fixed as N grows: scaling = "strong".
 Launch: under torch.distributed.run (the driver's form: WORLD_SIZE must equal --gpus, anything else is an error),
 or plainly as `python bench.py --gpus N`: the script then starts the N ranks itself, as fresh child processes of
 torch.distributed.run, BEFORE it imports torch or touches the GPU, relays their output and exits with their code.
 
-Prints ONE JSON line on rank 0 with the driver's contract plus
-  `roofline`      dominant kernel k_batch_add, HIP-event timed inside the library on its own stream,
-  `cpu_baseline`  the C port of the oracle on the host cores this box grants (its cgroup CPU quota), bounded sample, in a child process,
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes the result of the last
+timed step under DIR if --dump-outputs is given, and prints ONE JSON line on rank 0 with the driver's contract
+(`ms_per_step` = wall time of one timed step), `median_ms` / `std_ms` over the timed steps (scripts/evaluate-util.ts:3-20)
+and the `roofline` figures of the timed steps' own event timings.  --full adds every other leg, each of them still
+switched off by its own --no-* option:
   `verified`      the result of the LAST timed step checked outside the timed region against the known
                   discrete logs of the generated points: sum s_i P_i == (sum s_i a_i mod q) G
                   (the reference compares every size it benchmarks, scripts/msm-weierstrass.ts:97-107),
-  `median_ms` / `std_ms` over the timed steps (scripts/evaluate-util.ts:3-20) and `pcie_inclusive`.
+  `roofline.exclusive`  dominant kernel k_batch_add, HIP-event timed inside the library on one extra step with the window
+                  groups serialised, and one more at c = 16,
+  `cpu_baseline`  the C port of the oracle on the host cores this box grants (its cgroup CPU quota), bounded sample, in a child process,
+  `pcie_inclusive`, `window_tables_leg`, `skewed`, `other_configs`, and for N > 1 `other_splits` and the per-rank `ranks`.
 """
 import argparse
 import json
@@ -165,6 +170,18 @@ def step_stats(step_ms):
             "min_ms": min(step_ms), "max_ms": max(step_ms)}
 
 
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the result of the last timed step as the caller of the path receives it (affine x and y, and whether
+    it is the point at infinity).  The coordinates go out as twelve 32-bit little-endian limbs in float64, which holds
+    them exactly, so that the outputs of two builds compare equal bit for bit."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in (("x", res.x), ("y", res.y)):
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.array([(v >> (32 * i)) & 0xFFFFFFFF for i in range(12)], dtype=np.float64))
+    np.save(os.path.join(out_dir, "is_infinity.npy"), np.array([float(res.isZero)], dtype=np.float64))
+
+
 def timed_config(curve_name, log2n, torch, steps=10, warmup=5, c=0):
     """One more BASELINE config timed in-process with the protocol of scripts/msm-weierstrass.ts:12-51 (15 runs, the
     first 5 discarded, median and sample std-dev): its own context, points P_i = a_i G generated on the GPU, fresh
@@ -244,7 +261,7 @@ def bench_ed377(args, torch):
 
     n = 1 << args.log2n
     ctx = MsmContext(_lib.CURVE_ED_ON_BLS12_377, device=0)
-    a_host = ctx.generate_points(n, seed=20261002, want_scalars=True, raw=True)
+    a_host = ctx.generate_points(n, seed=20261002, want_scalars=args.full, raw=True)
     c, K = ctx.plan(n, args.c or None)
     dev = torch.device("cuda", 0)
     n_sets = min(args.steps + args.warmup, MAX_SCALAR_SETS)
@@ -265,8 +282,12 @@ def bench_ed377(args, torch):
         infos.append(info)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    _, s_host = ctx.generate_scalars(n, seed=1000 + last_set, to_host=True, raw=True)
-    verified = (last.x, last.y) == expected_from_logs("ed377", a_host, s_host, n)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    verified = None
+    if args.full:
+        _, s_host = ctx.generate_scalars(n, seed=1000 + last_set, to_host=True, raw=True)
+        verified = (last.x, last.y) == expected_from_logs("ed377", a_host, s_host, n)
     acc_ms = sum(x["phase_ms"]["accumulate"] for x in infos)
     pairs = sum(x["n_pairs_algo"] for x in infos)
     # one unified extended addition: two 128-byte nodes in, one out; 9 multiplications of 9 limbs (2*81 - 9 MADs)
@@ -278,7 +299,7 @@ def bench_ed377(args, torch):
         "scaling": "strong", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
         "config": {"workload": f"ed-on-bls12-377-msm-2^{args.log2n}", "log2_n": args.log2n, "window_bits": c, "windows": K,
                    "parallelism": "single-gpu"},
-        "verified": bool(verified),
+        "verified": verified,
         **step_stats(step_ms),
         "roofline": {"kernel": "k_te_add (bucket tree, unified extended additions)", "bound": "hbm", "achieved": achieved,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
@@ -290,7 +311,7 @@ def bench_ed377(args, torch):
     }
     print(json.dumps(out), flush=True)
     ctx.close()
-    if not verified:
+    if verified is False:
         sys.exit("bench: the Edwards MSM result failed the known-discrete-log check")
 
 
@@ -341,9 +362,21 @@ def main():
     ap.add_argument("--curve", choices=["bls12-377", "bls12-381", "ed377"], default="bls12-377",
                     help="ed377 = BASELINE configs[3]: twisted Edwards msmBasic path (single GPU, use --log2n 20); "
                          "bls12-381 = the same batched-affine path over the BLS12-381 G1 constants (no CPU baseline leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: the known-discrete-log check, the serialised step and "
+                         "the one at c = 16, host scalars, window tables, skewed scalars, the CPU baseline, the other configs, "
+                         "the other splits and the per-rank summaries (each still off with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the result of the last timed step to DIR/x.npy, y.npy, is_infinity.npy (float64)")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench: --steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps, the outputs, the result line
+        for leg in ("no_verify", "no_cpu_baseline", "no_pcie", "no_skewed", "no_tables_leg", "no_c16", "no_other_configs",
+                    "no_other_splits"):
+            setattr(args, leg, True)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))       # nothing has touched the GPU yet: torch is not even imported
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -495,6 +528,7 @@ def main():
             tmax = torch.tensor([dt], dtype=torch.float64, device=ddev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
+        if sharded and args.full:
             # outside the timed region: what every rank spent where, so that a scaling run explains itself
             mine = [x for x in infos if x]
             summary = {"rank": rank, "shard": (list(point_shards(n, world)[rank]) if how == "points" else [rank, world] if how == "buckets" else list(shards[rank])),
@@ -517,6 +551,8 @@ def main():
 
     failed = None
     dt, step_ms, infos, last, last_set, ranks_info = timed_loop(split, c, K)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     other_splits = None
     if sharded and not args.no_other_splits:
         other_splits = []
@@ -544,7 +580,7 @@ def main():
         # kernels SHARING the GPU.  One extra, untimed step with the groups serialised gives the exclusive figures.
         excl = None
         pcie = None
-        if not sharded:
+        if not sharded and args.full:
             # the same kernel under the round-3 plan (c = 16, K = 8: a third more pair additions, none of them through the
             # chunk-ordered or descriptor paths) when the library picks a bigger window: the per-pair rate of the tree kernel
             # where nothing but the kernel itself is in the way

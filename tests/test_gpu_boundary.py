@@ -189,7 +189,7 @@ def _sharded_bench(world, log2n, split="windows"):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--log2n", str(log2n), "--dist-backend", "gloo", "--no-cpu-baseline", "--split", split]
+           "--log2n", str(log2n), "--dist-backend", "gloo", "--full", "--no-cpu-baseline", "--split", split]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -230,7 +230,7 @@ def test_two_rank_bench_launches_itself():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log2n", "20",
-           "--dist-backend", "gloo", "--no-cpu-baseline"]
+           "--dist-backend", "gloo", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -256,6 +256,45 @@ def test_bench_refuses_a_world_size_other_than_gpus():
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--log2n", "16"], env=env, cwd=root,
                          capture_output=True, text=True, timeout=300)
     assert out.returncode != 0 and not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+@pytest.mark.parametrize("curve", ["bls12-377", "ed377"])
+def test_plain_bench_dumps_the_last_timed_result(tmp_path, curve):
+    """A plain `bench.py` run (no --full) prints the headline line without the other legs, and --dump-outputs writes the
+    result of its last timed step: that point is checked here against the known discrete logs of the generated points."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    from montgomery_amd import _lib
+    from montgomery_amd.api import MsmContext
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    log2n, steps, warmup = 16, 3, 2
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--log2n", str(log2n), "--curve", curve, "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["verified"] is None, d
+    assert not {"cpu_baseline", "other_configs"} & set(d) and not d.get("pcie_inclusive") and not d.get("skewed")
+    got = {k: np.load(os.path.join(tmp_path, k + ".npy")) for k in ("x", "y", "is_infinity")}
+    assert all(a.dtype == np.float64 for a in got.values()) and got["is_infinity"].tolist() == [0.0]
+    xy = tuple(sum(int(v) << (32 * i) for i, v in enumerate(got[k])) for k in ("x", "y"))
+
+    n = 1 << log2n
+    ctx = MsmContext(_lib.CURVE_ED_ON_BLS12_377 if curve == "ed377" else _lib.CURVE_BLS12_377_G1)
+    a_host = ctx.generate_points(n, seed=20261002, want_scalars=True, raw=True)   # the bench's seeds
+    _, s_host = ctx.generate_scalars(n, seed=1000 + (warmup + steps - 1) % min(warmup + steps, 8), to_host=True, raw=True)
+    ctx.close()
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert xy == bench.expected_from_logs(curve, a_host, s_host, n)
 
 
 @pytest.mark.parametrize("n", [(1 << 24) + 777, 1 << 25])
@@ -448,7 +487,7 @@ def test_bench_sharded_path_over_rccl_with_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "2", "--warmup", "1", "--log2n", "18",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -7,9 +7,9 @@ export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/sq1 -- python3 $REPO/bench.py --steps 1 --warmup 0 --log2n $LG --no-cpu-baseline > $OUT/sq1.log 2>&1
-rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM --output-format csv -d $OUT/sq2 -- python3 $REPO/bench.py --steps 1 --warmup 0 --log2n $LG --no-cpu-baseline > $OUT/sq2.log 2>&1
-rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/grbm -- python3 $REPO/bench.py --steps 1 --warmup 0 --log2n $LG --no-cpu-baseline > $OUT/grbm.log 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/sq1 -- python3 $REPO/bench.py --full --steps 1 --warmup 0 --log2n $LG --no-cpu-baseline > $OUT/sq1.log 2>&1
+rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM --output-format csv -d $OUT/sq2 -- python3 $REPO/bench.py --full --steps 1 --warmup 0 --log2n $LG --no-cpu-baseline > $OUT/sq2.log 2>&1
+rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/grbm -- python3 $REPO/bench.py --full --steps 1 --warmup 0 --log2n $LG --no-cpu-baseline > $OUT/grbm.log 2>&1
 python3 - <<PY
 import csv, glob, collections
 for kind in ("sq1", "sq2", "grbm"):
