@@ -73,12 +73,11 @@ void msm_ctx_destroy(msm_ctx* ctx) {
   for (msm_ctx* c : ctx->children) msm_ctx_destroy(c);
   ctx->children.clear();
   (void)hipSetDevice(ctx->device);
-  for (size_t i = 0; i < ctx->sets.size(); i++)
-    if ((int)i != ctx->cur_set) { ctx->release(ctx->sets[i].rows); ctx->release(ctx->sets[i].tabs); }
   for (void* p : ctx->allocs) (void)hipFree(p);
   ctx->allocs.clear();
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  for (DevBuf* b : {&ctx->rows, &ctx->tabs, &ctx->scal, &ctx->errflag, &ctx->misc}) ctx->release(*b);
+  for (auto& s : ctx->sets) s.release(ctx);
+  for (DevBuf* b : {&ctx->scal, &ctx->errflag, &ctx->misc}) ctx->release(*b);
   for (auto& w : ctx->ws) {
     if (w.stream) (void)hipStreamSynchronize(w.stream);
     for (DevBuf* b : w.all) ctx->release(*b);
@@ -106,12 +105,9 @@ static int set_points_one(msm_ctx* ctx, const void* points, uint64_t n, int on_d
   if (n >= (1ull << 30)) return fail(ctx, MSM_ERR_ARG, "msm_set_points: n must be < 2^30");
   const bool te = ctx->is_te();
   const size_t wire_bytes = 2 * ctx->coord_bytes();   // x || y, little-endian
-  const size_t row_words = te ? te::TE_ROW_WORDS : ROW_WORDS;
   try {
     HIPCHK(hipSetDevice(ctx->device));
-    ctx->n_points = 0;
-    ctx->drop_tables();   // window tables belong to the points they were built from
-    ctx->ensure(ctx->rows, std::max<uint64_t>(n, 1) * row_words * 4);
+    uint32_t* rows = ctx->reset_points(n);
     const uint32_t* d_wire = (const uint32_t*)points;
     if (!on_device && n) {
       ctx->ensure(ctx->misc, n * wire_bytes);
@@ -122,10 +118,10 @@ static int set_points_one(msm_ctx* ctx, const void* points, uint64_t n, int on_d
     if (n) {
       uint64_t grid = (n + 255) / 256;
       if (te)
-        hipLaunchKernelGGL(te::k_te_points_from_wire, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, (uint32_t*)ctx->rows.p, d_wire,
+        hipLaunchKernelGGL(te::k_te_points_from_wire, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, rows, d_wire,
                            n, check_curve, (uint32_t*)ctx->errflag.p);
       else
-        W_LAUNCH(ctx, k_points_from_wire, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, (uint32_t*)ctx->rows.p, d_wire, n,
+        W_LAUNCH(ctx, k_points_from_wire, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, rows, d_wire, n,
                            check_curve, (uint32_t*)ctx->errflag.p);
     }
     HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -134,7 +130,7 @@ static int set_points_one(msm_ctx* ctx, const void* points, uint64_t n, int on_d
     if (!on_device) ctx->release(ctx->misc);
     if (ctx->h_info[0] & 1) return fail(ctx, MSM_ERR_POINT, "msm_set_points: coordinate >= p");
     if (ctx->h_info[0] & 2) return fail(ctx, MSM_ERR_POINT, "msm_set_points: point not on curve");
-    ctx->n_points = n;
+    ctx->pts().n = n;
   } MSM_CATCH_ALL(ctx)
   return MSM_OK;
 }
@@ -164,7 +160,7 @@ int msm_plan(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, int32_t* c_ou
   // (a context with resident points answers for msm_run over them, window tables included; msm_window_sums and shards of
   // the points always run the plain plan, which is also what a context without points reports)
   // (msm_opts.merged_sums: the plan of msm_window_sums over a range of the points that may run on range tables)
-  const bool run_like = ctx && n && ((n == ctx->n_points && !(opts && opts->point_lo)) || (opts && opts->merged_sums));
+  const bool run_like = ctx && n && ((n == ctx->pts().n && !point_lo(opts)) || (opts && opts->merged_sums));
   int rc = run_like ? make_run_plan(const_cast<msm_ctx*>(ctx), n, opts, false, pl, tables_wanted) : make_plan(ctx, n, opts, pl);
   if (rc) return rc;
   if (c_out) *c_out = pl.c;
@@ -175,9 +171,7 @@ int msm_plan(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, int32_t* c_ou
 int msm_window_sums(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, const msm_opts* opts, uint8_t* partials_out,
                     msm_result* stats) {
   if (!ctx || !partials_out || (!scalars && n)) return fail(ctx, MSM_ERR_ARG, "msm_window_sums: null argument");
-  if ((opts ? opts->point_lo : 0) + n > ctx->n_points)
-    return fail(ctx, MSM_ERR_NO_POINTS, "msm_window_sums: points [%llu, +%llu) but %llu resident points",
-                (unsigned long long)(opts ? opts->point_lo : 0), (unsigned long long)n, (unsigned long long)ctx->n_points);
+  if (int rc = check_points(ctx, n, opts, MSM_ERR_NO_POINTS, "msm_window_sums")) return rc;
   Plan pl;
   // msm_opts.merged_sums: the caller only combines the sums (msm_combine / msm_combine_groups), so the call may hand them back
   // merged -- and with that run on window tables, those of the whole set or of the range of the points it covers
@@ -193,7 +187,7 @@ int msm_window_sums(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device
   try {
     HIPCHK(hipSetDevice(ctx->device));
     std::vector<uint32_t> words;
-    pl.tables = n && tables_wanted && use_window_tables(ctx, n, opts, pl, /*may_build=*/true);
+    pl.tables = n && tables_wanted && use_window_tables(ctx, n, opts, pl);
     if (ctx->is_te()) {
       // extended point (X : Y : Z : T) sent as X || Y || Z; the receiver rebuilds T (msm_combine: T Z = X Y)
       if (n) any_window_sums(ctx, scalars, n, on_device, opts, k_lo, k_hi, pl, words, stats);
@@ -280,7 +274,7 @@ static int run_piped(msm_ctx* ctx, const void* scalars, uint64_t n, const msm_op
     std::vector<size_t> ends;
     for (uint64_t e : piece_end) ends.push_back((size_t)e * 32);
     PieceUpload pipe(ctx, ctx->scal.p, scalars, n * 32, ends);
-    const uint32_t base_lo = opts ? opts->point_lo : 0;
+    const uint32_t base_lo = (uint32_t)point_lo(opts);
     const size_t Q = piece_end.size();
     struct Range {
       uint64_t lo = 0, cnt = 0;
@@ -336,9 +330,7 @@ static int run_piped(msm_ctx* ctx, const void* scalars, uint64_t n, const msm_op
 
 static int run_impl(msm_ctx* ctx, const void* scalars, const void* const* placed, uint64_t n, int on_device, const msm_opts* opts,
                     msm_result* out, const char* who) {
-  if ((opts ? opts->point_lo : 0) + n > ctx->n_points)
-    return fail(ctx, MSM_ERR_NO_POINTS, "%s: points [%llu, +%llu) but %llu resident points", who,
-                (unsigned long long)(opts ? opts->point_lo : 0), (unsigned long long)n, (unsigned long long)ctx->n_points);
+  if (int rc = check_points(ctx, n, opts, MSM_ERR_NO_POINTS, who)) return rc;
   if (!placed && !on_device && n >= (1ull << 24) && ctx->children.empty() && !ctx->is_te() && !(opts && opts->c))
     return run_piped(ctx, scalars, n, opts, out, who);
   Plan pl;
@@ -357,7 +349,7 @@ static int run_impl(msm_ctx* ctx, const void* scalars, const void* const* placed
     HIPCHK(hipSetDevice(ctx->device));
     std::vector<uint32_t> words;
     // window tables (msm_tables.hip): built here on the first default-plan call over the whole point set
-    pl.tables = tables_wanted && use_window_tables(ctx, n, opts, pl, /*may_build=*/true);
+    pl.tables = tables_wanted && use_window_tables(ctx, n, opts, pl);
     any_window_sums(ctx, scalars, n, on_device, opts, 0, pl.K, pl, words, out, placed);
     HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
     // (a run on tables leaves the whole sum, weights included, in slot 0 and identities in the others: the Horner step over all
@@ -398,8 +390,7 @@ int msm_run_placed(msm_ctx* ctx, const void* const* dev_scalars, uint64_t n, con
 
 int msm_reserve(msm_ctx* ctx, uint64_t n, const msm_opts* opts) {
   if (!ctx) return MSM_ERR_ARG;
-  if ((opts ? opts->point_lo : 0) + n > ctx->n_points)
-    return fail(ctx, MSM_ERR_NO_POINTS, "msm_reserve: %llu points asked for, %llu resident", (unsigned long long)n, (unsigned long long)ctx->n_points);
+  if (int rc = check_points(ctx, n, opts, MSM_ERR_NO_POINTS, "msm_reserve")) return rc;
   if (n == 0) return MSM_OK;
   void* dev = nullptr;
   try {
@@ -418,13 +409,13 @@ int msm_reserve(msm_ctx* ctx, uint64_t n, const msm_opts* opts) {
 }
 
 int msm_get_points(msm_ctx* ctx, uint64_t first, uint64_t count, uint8_t* out_xy) {
-  if (!ctx || !out_xy || first + count > ctx->n_points) return fail(ctx, MSM_ERR_ARG, "msm_get_points: bad argument");
+  if (!ctx || !out_xy || first + count > ctx->pts().n) return fail(ctx, MSM_ERR_ARG, "msm_get_points: bad argument");
   if (ctx->is_te()) {
     try {
       HIPCHK(hipSetDevice(ctx->device));
       std::vector<uint32_t> rows((size_t)count * te::TE_ROW_WORDS);
       if (count)
-        HIPCHK(hipMemcpy(rows.data(), (const uint32_t*)ctx->rows.p + first * te::TE_ROW_WORDS, rows.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(rows.data(), (const uint32_t*)ctx->pts().rows.p + first * te::TE_ROW_WORDS, rows.size() * 4, hipMemcpyDeviceToHost));
       msm_host::Fe6 one = {{1, 0, 0, 0, 0, 0}};
       for (uint64_t i = 0; i < count; i++)
         for (int j = 0; j < 2; j++) {
@@ -443,7 +434,7 @@ int msm_get_points(msm_ctx* ctx, uint64_t first, uint64_t count, uint8_t* out_xy
     HIPCHK(hipSetDevice(ctx->device));
     std::vector<uint32_t> rows((size_t)count * ROW_WORDS);
     if (count)
-      HIPCHK(hipMemcpy(rows.data(), (const uint32_t*)ctx->rows.p + first * ROW_WORDS, rows.size() * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(rows.data(), (const uint32_t*)ctx->pts().rows.p + first * ROW_WORDS, rows.size() * 4, hipMemcpyDeviceToHost));
     const int nw = ctx->nw();
     const size_t cb = ctx->coord_bytes();
     memset(out_xy, 0, (size_t)count * 2 * cb);
@@ -471,22 +462,8 @@ static int pointset_select_one(msm_ctx* ctx, int32_t id) {
   if (id < 0 || id >= (int)ctx->sets.size() || (id != 0 && !ctx->sets[id].live))
     return fail(ctx, MSM_ERR_ARG, "msm_pointset_select: no point set %d", (int)id);
   if (id == ctx->cur_set) return MSM_OK;
-  ctx->sets[ctx->cur_set].rows = ctx->rows;
-  ctx->sets[ctx->cur_set].n = ctx->n_points;
-  ctx->sets[ctx->cur_set].tab_c = ctx->tab_c;
-  ctx->sets[ctx->cur_set].tab_K = ctx->tab_K;
-  ctx->sets[ctx->cur_set].tab_lo = ctx->tab_lo;
-  ctx->sets[ctx->cur_set].tab_n = ctx->tab_n;
-  ctx->sets[ctx->cur_set].tabs = ctx->tabs;
-  ctx->rows = ctx->sets[id].rows;
-  ctx->n_points = ctx->sets[id].n;
-  ctx->tab_c = ctx->sets[id].tab_c;
-  ctx->tab_K = ctx->sets[id].tab_K;
-  ctx->tab_lo = ctx->sets[id].tab_lo;
-  ctx->tab_n = ctx->sets[id].tab_n;
-  ctx->tabs = ctx->sets[id].tabs;
-  ctx->cand_n = 0;
   ctx->cur_set = id;
+  ctx->cand_n = 0;
   return MSM_OK;
 }
 
@@ -521,9 +498,7 @@ int msm_pointset_destroy(msm_ctx* ctx, int32_t id) {
     return on_all_devices(ctx, [&](msm_ctx* c) {
       if (c->cur_set == id) pointset_select_one(c, 0);
       (void)hipSetDevice(c->device);
-      c->release(c->sets[id].rows);
-      c->release(c->sets[id].tabs);
-      c->sets[id] = msm_ctx::PointSet();
+      c->sets[id].release(c);
       return (int)MSM_OK;
     });
   } MSM_CATCH_ALL(ctx)

@@ -165,11 +165,9 @@ int generate_points(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) {
   HIPCHK(hipMemsetAsync(ctx->errflag.p, 0, 4, ctx->stream));
   W_LAUNCH(ctx, msm::k_points_from_wire, dim3((N_BASIS * TBL + 255) / 256), dim3(256), 0, ctx->stream, (uint32_t*)d_tbl.p,
                      (const uint32_t*)d_wire.p, (uint64_t)N_BASIS * TBL, 1, (uint32_t*)ctx->errflag.p);
-  ctx->n_points = 0;
-  ctx->drop_tables();   // window tables belong to the points they were built from
-  ctx->ensure(ctx->rows, std::max<uint64_t>(n, 1) * msm::ROW_WORDS * 4);
+  uint32_t* rows = ctx->reset_points(n);
   if (n)
-    W_LAUNCH(ctx, k_gen_points, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (uint32_t*)ctx->rows.p,
+    W_LAUNCH(ctx, k_gen_points, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, rows,
                        (const uint32_t*)d_tbl.p, n, seed);
   HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -180,7 +178,7 @@ int generate_points(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) {
     ctx->err = "msm_generate_points: table point failed validation";
     return MSM_ERR_POINT;
   }
-  ctx->n_points = n;
+  ctx->pts().n = n;
   if (a_out) write_discrete_logs(a_out, n, seed, tbl_scalar, q);
   return MSM_OK;
 }
@@ -253,14 +251,12 @@ int generate_points_te(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) 
   HIPCHK(hipMemsetAsync(ctx->errflag.p, 0, 4, ctx->stream));
   hipLaunchKernelGGL(msm::te::k_te_points_from_wire, dim3((N_BASIS * TBL + 255) / 256), dim3(256), 0, ctx->stream, (uint32_t*)d_tbl.p,
                      (const uint32_t*)d_wire.p, (uint64_t)N_BASIS * TBL, 1, (uint32_t*)ctx->errflag.p);
-  ctx->n_points = 0;
-  ctx->drop_tables();   // window tables belong to the points they were built from
-  ctx->ensure(ctx->rows, std::max<uint64_t>(n, 1) * msm::te::TE_ROW_WORDS * 4);
+  uint32_t* rows = ctx->reset_points(n);
   if (n) {
     const uint32_t grid = (uint32_t)((n + 255) / 256);
     hipLaunchKernelGGL(msm::te::k_te_gen_points, dim3(grid), dim3(256), 0, ctx->stream, (uint32_t*)d_pts.p, (const uint32_t*)d_tbl.p,
                        n, seed);
-    hipLaunchKernelGGL(msm::te::k_te_points_from_wire, dim3(grid), dim3(256), 0, ctx->stream, (uint32_t*)ctx->rows.p,
+    hipLaunchKernelGGL(msm::te::k_te_points_from_wire, dim3(grid), dim3(256), 0, ctx->stream, rows,
                        (const uint32_t*)d_pts.p, n, 0, (uint32_t*)ctx->errflag.p);
   }
   HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -273,7 +269,7 @@ int generate_points_te(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) 
     ctx->err = "msm_generate_points: table point failed validation";
     return MSM_ERR_POINT;
   }
-  ctx->n_points = n;
+  ctx->pts().n = n;
   if (a_out) write_discrete_logs(a_out, n, seed, tbl_scalar, q);
   return MSM_OK;
 }

@@ -182,38 +182,48 @@ struct msm_ctx {
   std::string err;
   int n_cu = 256;
 
-  // resident points: `rows` / `n_points` are the CURRENT point set; the others wait in `sets` (msm_pointset_*)
-  msmi::DevBuf rows;
-  uint64_t n_points = 0;
+  // Window tables of a point set (msm_tables.hip): K tables of n rows each, table k = 2^(c k) P over the points [lo, lo + n)
+  // (K = 0: none).  Tables of the WHOLE set live in the set's row buffer, which grows to hold them (table 0 is the plain row
+  // table: in_rows); tables of a RANGE of the points -- the share of one rank of a points-split run -- in `buf`, with a copy of
+  // the range's rows as table 0.  K != 0 only while the buffer it names holds all K tables: a build describes them last.
+  struct WindowTables {
+    int c = 0, K = 0;
+    uint64_t lo = 0, n = 0;
+    bool in_rows = false;
+    msmi::DevBuf buf;   // (may outlive a description that is cleared: a range build of the same size reuses it)
+    bool covers(uint64_t l, uint64_t m) const { return K && lo == l && n == m; }
+    bool whole_set_pinned() const { return K && in_rows; }
+    void clear() { c = K = 0; lo = n = 0; in_rows = false; }
+    void drop(msm_ctx* ctx) { clear(); ctx->release(buf); }   // (the description goes first)
+  };
+  // A resident point set (msm_pointset_*): its rows, one per point, and its window tables.  `sets` holds them all; the
+  // CURRENT one, which every call reads, is sets[cur_set] (pts()).
   struct PointSet {
     msmi::DevBuf rows;
     uint64_t n = 0;
-    bool live = false;
-    int tab_c = 0, tab_K = 0;
-    uint64_t tab_lo = 0, tab_n = 0;
-    msmi::DevBuf tabs;
+    bool live = false;   // (slot 0, the default set, always is)
+    WindowTables tab;
+    const uint32_t* table_rows() const { return (const uint32_t*)(tab.in_rows ? rows.p : tab.buf.p); }
+    void release(msm_ctx* ctx) { tab.drop(ctx); ctx->release(rows); *this = PointSet(); }
   };
-  // Window tables of the CURRENT point set (msm_tables.hip): tab_K tables of tab_n rows each, table k = 2^(tab_c k) P over the
-  // points [tab_lo, tab_lo + tab_n) (tab_K = 0: none).  Tables of the WHOLE set live in `rows` (which grows to hold them: table 0
-  // is the plain row table); tables of a RANGE of the points -- the share of one rank of a points-split run -- in `tabs`, with
-  // a copy of the range's rows as table 0.  Travel with the set through msm_pointset_select.
-  int tab_c = 0, tab_K = 0;
-  uint64_t tab_lo = 0, tab_n = 0;
-  msmi::DevBuf tabs;
+  std::vector<PointSet> sets = std::vector<PointSet>(1);   // slot 0 = the default set
+  int cur_set = 0;
+  PointSet& pts() { return sets[cur_set]; }
+  const PointSet& pts() const { return sets[cur_set]; }
+  // new points replace those of the current set: it forgets them and its window tables, and gets room for n rows
+  uint32_t* reset_points(uint64_t n) {
+    PointSet& s = pts();
+    s.n = 0;
+    s.tab.drop(this);   // window tables belong to the points they were built from
+    cand_n = 0;
+    ensure(s.rows, std::max<uint64_t>(n, 1) * row_words() * 4);
+    return (uint32_t*)s.rows.p;
+  }
   // the range the last table-eligible call over a RANGE of the points asked for: range tables are built when a call comes back
   // for the same range (a rank of a sharded run does; a caller walking over the shards of one GPU does not and is spared a build per call)
   uint64_t cand_lo = 0, cand_n = 0;
   int cand_c = 0;
-  const uint32_t* table_rows() const { return (const uint32_t*)(tabs.p ? tabs.p : rows.p); }
-  void drop_tables() {
-    tab_c = tab_K = 0;
-    tab_lo = tab_n = 0;
-    cand_n = 0;
-    release(tabs);
-  }
   uint64_t tables_limit = 0;   // bytes the tables of one point set may take (msm_set_tables_limit; default: 10 % of the device)
-  std::vector<PointSet> sets = std::vector<PointSet>(1);   // slot 0 = the default set
-  int cur_set = 0;
   std::vector<void*> allocs;        // device buffers handed out by msm_device_alloc
   // multi-device context (msm_ctx_create_multi): this context drives devices[0], one child context per further device
   std::vector<msm_ctx*> children;
@@ -261,6 +271,7 @@ struct msm_ctx {
   int nl() const { return (curve == MSM_CURVE_PALLAS || is_te()) ? 9 : 13; }
   int nw() const { return (curve == MSM_CURVE_PALLAS || is_te()) ? 8 : 12; }
   size_t coord_bytes() const { return (size_t)nw() * 4; }
+  uint64_t row_words() const { return is_te() ? (uint64_t)msm::te::TE_ROW_WORDS : (uint64_t)msm::ROW_WORDS; }   // of a point row
 
   void ensure(msmi::DevBuf& b, size_t bytes) {
     if (bytes <= b.cap) return;
@@ -309,6 +320,11 @@ using namespace msm;
 
 int fail(msm_ctx* ctx, int code, const char* fmt, ...);
 int fail_hip(msm_ctx* ctx, const HipFail& f);
+
+// the first resident point a call covers: its points are [point_lo, point_lo + n)
+inline uint64_t point_lo(const msm_opts* opts) { return opts ? opts->point_lo : 0; }
+// MSM_OK if the points of the call are resident (and there are some, unless empty_ok); otherwise fails it with `code`
+int check_points(msm_ctx* ctx, uint64_t n, const msm_opts* opts, int code, const char* who, bool empty_ok = true);
 
 // every extern "C" entry point ends its try block with this: no C++ exception crosses the C ABI
 #define MSM_CATCH_ALL(ctx)                                                                                  \
@@ -426,9 +442,9 @@ void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl
 void sort_kernel_attributes();   // dynamic-LDS limits of the sort kernels (once per process and device)
 
 // ---- msm_tables.hip ---------------------------------------------------------------------------------------------
-// true if the MSM over the resident points [opts->point_lo, + n) under plan `pl` can run on window tables -- `pl` then knows
-// where they are (tab_rows, tab_lo, tab_n); builds them when `may_build`
-bool use_window_tables(msm_ctx* ctx, uint64_t n, const msm_opts* opts, Plan& pl, bool may_build);
+// true if the MSM over the resident points [opts->point_lo, + n) under plan `pl` can run on window tables, built here if they
+// are not there yet and may be -- `pl` then knows where they are (tab_rows, tab_lo, tab_n)
+bool use_window_tables(msm_ctx* ctx, uint64_t n, const msm_opts* opts, Plan& pl);
 
 // ---- msm_upload.hip ---------------------------------------------------------------------------------------------
 void ensure_staging(msm_ctx* ctx);

@@ -435,7 +435,7 @@ namespace msmi {
 // the one entry the ABI functions use: single- or multi-device
 int any_window_sums(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, const msm_opts* opts, int k_lo, int k_hi,
                     const Plan& pl, std::vector<uint32_t>& words, msm_result* stats, const void* const* placed) {
-  const uint64_t p_off = opts ? opts->point_lo : 0;
+  const uint64_t p_off = point_lo(opts);
   if (ctx->children.empty())
     return window_sums_impl(ctx, placed ? placed[0] : scalars, n, placed ? 1 : on_device, opts, k_lo, k_hi, pl, words, stats, p_off);
   return multi_window_sums(ctx, scalars, placed, n, on_device, opts, k_lo, k_hi, pl, words, stats, p_off);

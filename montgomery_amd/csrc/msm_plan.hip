@@ -18,6 +18,13 @@ int fail(msm_ctx* ctx, int code, const char* fmt, ...) {
   return code;
 }
 
+int check_points(msm_ctx* ctx, uint64_t n, const msm_opts* opts, int code, const char* who, bool empty_ok) {
+  const uint64_t lo = point_lo(opts), resident = ctx->pts().n;
+  if (lo + n <= resident && (n || empty_ok)) return MSM_OK;
+  return fail(ctx, code, "%s: points [%llu, +%llu) but %llu resident points", who, (unsigned long long)lo, (unsigned long long)n,
+              (unsigned long long)resident);
+}
+
 static const char* base_name(const char* p) {
   const char* s = strrchr(p ? p : "", '/');
   return s ? s + 1 : (p ? p : "?");

@@ -10,14 +10,17 @@ using namespace msmi;
 namespace msmi {
 
 static uint64_t table_bytes(const msm_ctx* ctx, uint64_t n, int K) {
-  const uint64_t row_words = ctx->is_te() ? (uint64_t)te::TE_ROW_WORDS : (uint64_t)ROW_WORDS;
-  return (uint64_t)K * std::max<uint64_t>(n, 1) * row_words * 4;
+  return (uint64_t)K * std::max<uint64_t>(n, 1) * ctx->row_words() * 4;
 }
 
-// tables of the WHOLE point set live in `rows` (table 0 = the plain rows); tables of a range [lo, lo + n) of the points in `tabs`
+// Tables of the WHOLE point set go into its row buffer (table 0 = the plain rows), those of a range [lo, lo + n) into a buffer
+// of their own.  The old tables are forgotten first and the new ones described last: no way out of here, exceptions included,
+// leaves the set describing tables it does not hold.  (An old buffer goes back before a new one is allocated.)
 static void build_tables(msm_ctx* ctx, const Plan& pl, uint64_t lo, uint64_t n) {
-  const bool whole = lo == 0 && n == ctx->n_points;
-  const uint64_t row_words = ctx->is_te() ? (uint64_t)te::TE_ROW_WORDS : (uint64_t)ROW_WORDS;
+  msm_ctx::PointSet& ps = ctx->pts();
+  msm_ctx::WindowTables& t = ps.tab;
+  const bool whole = lo == 0 && n == ps.n;
+  const uint64_t row_words = ctx->row_words();
   const uint64_t bytes = table_bytes(ctx, n, pl.K);
   HIPCHK(hipStreamSynchronize(ctx->stream));
   auto ensure_or_retry = [&](DevBuf& b) {
@@ -34,22 +37,22 @@ static void build_tables(msm_ctx* ctx, const Plan& pl, uint64_t lo, uint64_t n) 
   };
   uint32_t* rows = nullptr;
   if (whole) {
-    ctx->release(ctx->tabs);   // (range tables of this set, if any, are replaced)
-    if (ctx->rows.cap < bytes) {
+    t.drop(ctx);   // (range tables of this set, if any, are replaced)
+    if (ps.rows.cap < bytes) {
       // a bigger buffer: table 0 (the plain rows) moves over, the old buffer goes back
       DevBuf big;
       ensure_or_retry(big);
-      HIPCHK(hipMemcpyAsync(big.p, ctx->rows.p, n * row_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      HIPCHK(hipMemcpyAsync(big.p, ps.rows.p, n * row_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
       HIPCHK(hipStreamSynchronize(ctx->stream));
-      ctx->release(ctx->rows);
-      ctx->rows = big;
+      ctx->release(ps.rows);
+      ps.rows = big;
     }
-    rows = (uint32_t*)ctx->rows.p;
+    rows = (uint32_t*)ps.rows.p;
   } else {
-    ctx->tab_c = ctx->tab_K = 0;
-    ensure_or_retry(ctx->tabs);
-    rows = (uint32_t*)ctx->tabs.p;
-    HIPCHK(hipMemcpyAsync(rows, (const uint32_t*)ctx->rows.p + lo * row_words, n * row_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    t.clear();   // (a buffer big enough is reused)
+    ensure_or_retry(t.buf);
+    rows = (uint32_t*)t.buf.p;
+    HIPCHK(hipMemcpyAsync(rows, (const uint32_t*)ps.rows.p + lo * row_words, n * row_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
   }
   const uint32_t grid = (uint32_t)((n + 255) / 256);
   for (int k = 1; k < pl.K; k++) {
@@ -60,27 +63,32 @@ static void build_tables(msm_ctx* ctx, const Plan& pl, uint64_t lo, uint64_t n) 
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipGetLastError());
-  ctx->tab_c = pl.c;
-  ctx->tab_K = pl.K;
-  ctx->tab_lo = lo;
-  ctx->tab_n = n;
+  t.c = pl.c;
+  t.K = pl.K;
+  t.lo = lo;
+  t.n = n;
+  t.in_rows = whole;
 }
 
 // can this call run on window tables at all?
 static bool tables_eligible(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, bool placed) {
   if (placed || (opts && (opts->no_tables || opts->bucket_shards > 1))) return false;
   if (!ctx->children.empty()) return false;           // a device list shards by points or windows over plain rows
-  const uint64_t lo = opts ? opts->point_lo : 0;
-  return lo + n <= ctx->n_points && n >= 4096;
+  return point_lo(opts) + n <= ctx->pts().n && n >= 4096;
 }
-static bool whole_set(const msm_ctx* ctx, uint64_t n, const msm_opts* opts) { return n == ctx->n_points && !(opts && opts->point_lo); }
-static bool tables_cover(const msm_ctx* ctx, uint64_t n, const msm_opts* opts) {
-  return ctx->tab_K && ctx->tab_lo == (opts ? opts->point_lo : 0) && ctx->tab_n == n;
+static bool whole_set(const msm_ctx* ctx, uint64_t n, const msm_opts* opts) { return n == ctx->pts().n && point_lo(opts) == 0; }
+// tables of the whole set stay: a call over a range of the points neither replaces them nor builds its own (msm_precompute of
+// the range, which asks for them explicitly, replaces them when it is sure to build)
+static bool whole_set_tables_stay(const msm_ctx* ctx, uint64_t n, const msm_opts* opts) {
+  return ctx->pts().tab.whole_set_pinned() && !whole_set(ctx, n, opts);
 }
-
-// entry indices of a merged window (one per table row and GLV half) travel in 31 bits of the sort's payloads
-static bool tables_addressable(const msm_ctx* ctx, uint64_t n, int K) {
-  return (uint64_t)K * (ctx->is_te() ? n : 2 * n) < (1ull << 31);
+// K tables of n points fit the limit, and their entries (one per table row and GLV half) the 31 bits of the sort's payloads
+static bool tables_fit(const msm_ctx* ctx, uint64_t n, int K) {
+  return table_bytes(ctx, n, K) <= ctx->tables_limit && (uint64_t)K * (ctx->is_te() ? n : 2 * n) < (1ull << 31);
+}
+// tables of plan pl could be built for this call (where tables of the whole set do not stay)
+static bool buildable(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, const Plan& pl) {
+  return tables_eligible(ctx, n, opts, false) && pl.K >= 2 && tables_fit(ctx, n, pl.K);
 }
 
 // A short top window would pile its entries on the lowest buckets of the merged window (a 2-bit top window: an eighth of all
@@ -92,76 +100,63 @@ static bool plan_suits_tables(const Plan& pl) {
   return top_bits >= pl.c - 3;
 }
 
-// Tables that are not there yet may be built by this call: those of the whole set at once (the first default-plan call over it,
-// as since round 5); those of a RANGE of the points when the call comes back for the same range -- the rank of a points-split
-// run does, a caller that walks over the shards on one GPU does not, and a build (c doublings and an inversion per point and
-// table: nine MSMs' worth at 2^23 points) per call would cost it far more than the tables return.
-static bool may_build_for(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, int c) {
-  if (whole_set(ctx, n, opts)) return true;
-  if (ctx->tab_K && !ctx->tabs.p) return false;   // tables of the whole set stay
-  return ctx->cand_n == n && ctx->cand_lo == (opts ? opts->point_lo : 0) && ctx->cand_c == c;
+// Of the calls that may build tables by default, this one builds them now: a call over the whole set at once (the first
+// default-plan call over it, as since round 5); a call over a RANGE of the points when it comes back for the same range -- the
+// rank of a points-split run does, a caller that walks over the shards on one GPU does not, and a build (c doublings and an
+// inversion per point and table: nine MSMs' worth at 2^23 points) per call would cost it far more than the tables return.
+static bool builds_now(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, int c) {
+  return whole_set(ctx, n, opts) || (ctx->cand_n == n && ctx->cand_lo == point_lo(opts) && ctx->cand_c == c);
 }
 
 int make_run_plan(msm_ctx* ctx, uint64_t n, const msm_opts* opts, bool placed, Plan& pl, bool& tables_wanted, bool note_range) {
   tables_wanted = false;
   if (tables_eligible(ctx, n, opts, placed)) {
-    // tables that exist decide: the call uses them if its plan is theirs (an explicit c, or the default plan they were built for)
-    if (tables_cover(ctx, n, opts)) {
-      Plan pt;
-      msm_opts o;
-      if (opts) o = *opts; else memset(&o, 0, sizeof o);
-      if (!o.c) o.c = ctx->tab_c;
-      if (make_plan(ctx, n, &o, pt) == MSM_OK && pt.c == ctx->tab_c && pt.K == ctx->tab_K &&
-          (!(opts && opts->c) || opts->c == ctx->tab_c)) {
-        // (a default-plan call keeps using tables built by msm_precompute for another c only if that is also what it would pick)
-        Plan pd;
-        if ((opts && opts->c) || (make_plan(ctx, n, opts, pd, true) == MSM_OK && pd.c == ctx->tab_c)) {
-          pl = pt;
-          tables_wanted = true;
-          return MSM_OK;
-        }
-      }
+    const msm_ctx::WindowTables& t = ctx->pts().tab;
+    msm_opts o;
+    if (opts) o = *opts; else memset(&o, 0, sizeof o);
+    const int asked = o.c;
+    Plan pt, pd;
+    // tables that exist decide: the call uses them if its plan is theirs -- an explicit c, or the default plan they were built
+    // for (a default-plan call keeps using tables built by msm_precompute for another c only if that is also what it would pick)
+    o.c = asked ? asked : t.c;
+    if (t.covers(point_lo(opts), n) && make_plan(ctx, n, &o, pt) == MSM_OK && pt.c == t.c && pt.K == t.K &&
+        (asked ? asked == t.c : make_plan(ctx, n, opts, pd, true) == MSM_OK && pd.c == t.c)) {
+      pl = pt;
+      tables_wanted = true;
+      return MSM_OK;
     }
     // none yet (or others): a call with the default plan may build them if they fit the limit --
     // opts->c == 0, or the very window the library would pick (a facade that asks msm_plan first and hands its answer back)
-    if (!(opts && opts->no_glv)) {
-      Plan pt;
-      msm_opts o;
-      if (opts) o = *opts; else memset(&o, 0, sizeof o);
-      const int asked = o.c;
-      o.c = 0;
-      if (make_plan(ctx, n, &o, pt, true) == MSM_OK && (asked == 0 || asked == pt.c) && plan_suits_tables(pt) &&
-          table_bytes(ctx, n, pt.K) <= ctx->tables_limit && tables_addressable(ctx, n, pt.K) &&
-          (whole_set(ctx, n, opts) || !(ctx->tab_K && !ctx->tabs.p))) {
-        const bool build_now = may_build_for(ctx, n, opts, pt.c);
-        if (note_range && !whole_set(ctx, n, opts)) {
-          ctx->cand_lo = opts ? opts->point_lo : 0;
-          ctx->cand_n = n;
-          ctx->cand_c = pt.c;
-        }
-        // (msm_plan answers for the call that would build them: the plan of a rank's share of a points split is the tables' plan)
-        if (build_now || !note_range) {
-          pl = pt;
-          tables_wanted = true;
-          return MSM_OK;
-        }
+    o.c = 0;
+    if (!o.no_glv && make_plan(ctx, n, &o, pt, true) == MSM_OK && (asked == 0 || asked == pt.c) && plan_suits_tables(pt) &&
+        buildable(ctx, n, opts, pt) && !whole_set_tables_stay(ctx, n, opts)) {
+      const bool build_now = builds_now(ctx, n, opts, pt.c);
+      if (note_range && !whole_set(ctx, n, opts)) {
+        ctx->cand_lo = point_lo(opts);
+        ctx->cand_n = n;
+        ctx->cand_c = pt.c;
+      }
+      // (msm_plan answers for the call that would build them: the plan of a rank's share of a points split is the tables' plan)
+      if (build_now || !note_range) {
+        pl = pt;
+        tables_wanted = true;
+        return MSM_OK;
       }
     }
   }
   return make_plan(ctx, n, opts, pl);
 }
 
-bool use_window_tables(msm_ctx* ctx, uint64_t n, const msm_opts* opts, Plan& pl, bool may_build) {
-  if (!tables_eligible(ctx, n, opts, false) || pl.K < 2) return false;
-  const uint64_t lo = opts ? opts->point_lo : 0;
-  if (!(tables_cover(ctx, n, opts) && ctx->tab_c == pl.c && ctx->tab_K == pl.K)) {
-    if (!may_build || table_bytes(ctx, n, pl.K) > ctx->tables_limit || !tables_addressable(ctx, n, pl.K)) return false;
-    if (!whole_set(ctx, n, opts) && ctx->tab_K && !ctx->tabs.p) return false;   // tables of the whole set stay
+bool use_window_tables(msm_ctx* ctx, uint64_t n, const msm_opts* opts, Plan& pl) {
+  const msm_ctx::PointSet& ps = ctx->pts();
+  const uint64_t lo = point_lo(opts);
+  if (!(tables_eligible(ctx, n, opts, false) && ps.tab.covers(lo, n) && ps.tab.c == pl.c && ps.tab.K == pl.K)) {
+    if (!buildable(ctx, n, opts, pl) || whole_set_tables_stay(ctx, n, opts)) return false;
     build_tables(ctx, pl, lo, n);
   }
-  pl.tab_rows = ctx->table_rows();
-  pl.tab_lo = ctx->tab_lo;
-  pl.tab_n = ctx->tab_n;
+  pl.tab_rows = ps.table_rows();
+  pl.tab_lo = ps.tab.lo;
+  pl.tab_n = ps.tab.n;
   return true;
 }
 
@@ -171,32 +166,31 @@ extern "C" {
 
 int msm_precompute(msm_ctx* ctx, uint64_t n, const msm_opts* opts) {
   if (!ctx) return MSM_ERR_ARG;
-  const uint64_t lo = opts ? opts->point_lo : 0;
-  if (lo + n > ctx->n_points || n == 0)
-    return fail(ctx, MSM_ERR_ARG, "msm_precompute: points [%llu, +%llu) but %llu resident points", (unsigned long long)lo,
-                (unsigned long long)n, (unsigned long long)ctx->n_points);
+  if (int rc = check_points(ctx, n, opts, MSM_ERR_ARG, "msm_precompute", /*empty_ok=*/false)) return rc;
   Plan pl;
   if (make_plan(ctx, n, opts, pl, /*for_tables=*/true)) return fail(ctx, MSM_ERR_ARG, "msm_precompute: bad window size");
   try {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!(n == ctx->n_points && lo == 0) && ctx->tab_K && !ctx->tabs.p) ctx->tab_c = ctx->tab_K = 0;   // asked for explicitly: a range replaces the whole set's
-    (void)use_window_tables(ctx, n, opts, pl, /*may_build=*/true);   // not an error if they do not fit: the plain path stays
+    // asked for explicitly, tables of a range replace the whole set's -- if the build goes ahead; if not, those stay
+    if (whole_set_tables_stay(ctx, n, opts) && buildable(ctx, n, opts, pl)) ctx->pts().tab.drop(ctx);
+    (void)use_window_tables(ctx, n, opts, pl);   // not an error if they do not fit: the plain path stays
     return MSM_OK;
   } MSM_CATCH_ALL(ctx)
 }
 
 int msm_tables_info(const msm_ctx* ctx, int32_t* c_out, int32_t* K_out, uint64_t* bytes_out) {
   if (!ctx) return MSM_ERR_ARG;
-  if (c_out) *c_out = ctx->tab_c;
-  if (K_out) *K_out = ctx->tab_K;
-  if (bytes_out) *bytes_out = ctx->tab_K ? table_bytes(ctx, ctx->tab_n, ctx->tab_K) : 0;
+  const msm_ctx::WindowTables& t = ctx->pts().tab;
+  if (c_out) *c_out = t.c;
+  if (K_out) *K_out = t.K;
+  if (bytes_out) *bytes_out = t.K ? table_bytes(ctx, t.n, t.K) : 0;
   return MSM_OK;
 }
 
 int msm_tables_range(const msm_ctx* ctx, uint64_t* point_lo_out, uint64_t* n_out) {
   if (!ctx) return MSM_ERR_ARG;
-  if (point_lo_out) *point_lo_out = ctx->tab_K ? ctx->tab_lo : 0;
-  if (n_out) *n_out = ctx->tab_K ? ctx->tab_n : 0;
+  if (point_lo_out) *point_lo_out = ctx->pts().tab.lo;   // (0, 0) without tables
+  if (n_out) *n_out = ctx->pts().tab.n;
   return MSM_OK;
 }
 

@@ -251,3 +251,25 @@ def test_edwards_range_tables():
         assert combine_groups_host(b"".join(parts), 2, K, c, _lib.CURVE_ED_ON_BLS12_377) == (full.x, full.y)
     finally:
         ctx.close()
+
+
+def test_refused_range_build_keeps_the_whole_sets_tables(gpu_ctx):
+    """msm_precompute over a range replaces the whole set's tables only if it goes on to build its own: a range build that the
+    limit refuses leaves the whole set's tables, and the runs on them, as they were."""
+    n = 1 << 16
+    gpu_ctx.generate_points(n, seed=65)
+    dev, _ = gpu_ctx.generate_scalars(n, seed=66)
+    want, _ = gpu_ctx.run_device(dev, n, no_tables=True)
+    got, info = gpu_ctx.run_device(dev, n)
+    c, K = info["c"], info["K"]
+    assert info["tables"] and got.as_tuple() == want.as_tuple()
+    assert gpu_ctx.tables_info() == (c, K, K * n * 256) and gpu_ctx.tables_range() == (0, n)
+    share = n // 4
+    gpu_ctx.set_tables_limit(1)
+    try:
+        assert gpu_ctx.precompute(share, c=c, point_lo=share) == (c, K, K * n * 256)
+        assert gpu_ctx.tables_range() == (0, n)
+        again, ia = gpu_ctx.run_device(dev, n)
+        assert ia["tables"] and again.as_tuple() == want.as_tuple()
+    finally:
+        gpu_ctx.set_tables_limit(28 << 30)
