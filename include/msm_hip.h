@@ -53,8 +53,8 @@ enum {
  * addon compare both at load time and refuse a mismatch.  History: 3 = round 3 (msm_generate_scalars writes to a caller-owned
  * buffer; msm_opts.point_lo / by_window); 4 = msm_result.n_pairs_algo; 5 = window tables (msm_opts.no_tables, msm_result.tables,
  * msm_precompute / msm_tables_info / msm_set_tables_limit), msm_reserve, msm_opts.bucket_shard / bucket_shards; 6 = window tables
- * over a range of the points (msm_opts.merged_sums, msm_precompute with point_lo, msm_tables_range). */
-#define MSM_ABI_VERSION 6
+ * over a range of the points (msm_opts.merged_sums, msm_precompute with point_lo, msm_tables_range); 7 = msm_run_batch. */
+#define MSM_ABI_VERSION 7
 uint32_t msm_abi_version(void);
 uint32_t msm_abi_struct_bytes(int which);
 
@@ -202,6 +202,20 @@ int msm_set_workspace_limit(msm_ctx* ctx, uint64_t bytes);
  * (msm / msmUnsafe, src/msm-batched-affine.ts:69-340, 587-598; for the Edwards curve msmBasic,
  * src/msm-basic.ts:45-164).  on_device != 0: `scalars` already sits in HBM. */
 int msm_run(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, const msm_opts* opts, msm_result* out);
+
+/* B MSMs over the same resident points [point_lo, point_lo + n) of the current point set:
+ * out[b] = sum_i scalars[b][i] * P_(point_lo + i).  scalars[b] is n x 32 bytes, host or device (on_device).
+ * Result by result, equal to B calls of msm_run(ctx, scalars[b], n, on_device, opts, &out[b]): out[b].x / .y / .is_infinity are
+ * bit-identical to what msm_run returns for element b.  Where one MSM is mostly fixed latency (single-device contexts, window
+ * plans of the one-level sort: below 2^20 points on the Weierstrass curves, 2^22 on the Edwards curve) the elements share the
+ * same launches -- element b's window k is window b K + k of one window group -- and the call never builds or uses window
+ * tables; elsewhere it runs element by element through msm_run.  out[b].c / .K report the plan that ran; phase_ms, rounds,
+ * n_pairs, n_pairs_algo and max_bucket describe the whole batched call and are written identically into every element.
+ * Options: c, no_glv, strict (one scalar >= q anywhere fails the whole call), point_lo, serial and no_tables are honoured,
+ * unsafe is ignored as in msm_run; k_lo / k_hi, bucket_shards > 1, merged_sums and by_window fail with MSM_ERR_ARG, as do
+ * B == 0, a null `out` and a null scalars[b] when n > 0.  n == 0 returns B identities. */
+int msm_run_batch(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device, const msm_opts* opts,
+                  msm_result* out /* B entries */);
 
 /* Window-sharded form for multi-GPU runs: computes the partition sums P_k for k in [k_lo, k_hi)
  * only (src/msm-batched-affine.ts:42 "P_k = sum_l l * B_(k,l)") and writes them as

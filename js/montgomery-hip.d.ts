@@ -27,6 +27,8 @@ export interface Parallel {
   randomScalars(n: number, options?: { seed?: number }): Promise<ScalarPtr>;
   /** src/msm-batched-affine.ts:69-340 */
   msm(scalarPtr: ScalarPtr, pointPtr: PointPtr, N: number, verboseTiming?: boolean, options?: MsmOptions): Promise<MsmOutput>;
+  /** many MSMs over one point set in one call (msm_run_batch): [b].result equals (await msm(scalarPtrs[b], pointPtr, N)).result */
+  msmBatch(scalarPtrs: ScalarPtr[], pointPtr: PointPtr, N: number, verboseTiming?: boolean, options?: MsmOptions): Promise<MsmOutput[]>;
   /** src/msm-batched-affine.ts:587-598: msm with useSafeAdditions = false (msm_opts.unsafe) */
   msmUnsafe(scalarPtr: ScalarPtr, pointPtr: PointPtr, N: number, verboseTiming?: boolean, options?: MsmOptions): Promise<MsmOutput>;
   /** src/parallel.ts:69-87: window structure of msmBasic, no endomorphism split */

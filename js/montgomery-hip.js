@@ -1,6 +1,7 @@
 // JS facade over the N-API shim: the reference's curve-module surface for the MSM path.
 //   Weierstraß.create(params) -> { params, Parallel }            src/parallel.ts:40-177
-//   Parallel.{getPointer, getScalarPointer, pointsFromBytes, scalarsFromBytes, msm, msmUnsafe}
+//   Parallel.{getPointer, getScalarPointer, pointsFromBytes, scalarsFromBytes, msm, msmUnsafe}, and Parallel.msmBatch (many MSMs
+//   over one point set in one call)
 //                                                                src/parallel.ts:135-145
 //   compute_msm(points, scalars) -> {x: bigint, y: bigint}       scripts/zprize23/submission-bls377.ts:20-65
 // Plain CommonJS without top-level await so the image's node 12 can load it (the reference's own
@@ -96,6 +97,20 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       const r = hip.msmDevice(ctx, scalarPtr.dev, N, c, options && options.noGlv ? 1 : 0, unsafe);
       const result = { x: leBytesToBigint(r.x), y: leBytesToBigint(r.y), isZero: r.isZero };
       return { result, log: verboseTiming ? buildLog(N, r) : [] };
+    },
+    // many MSMs over one point set in one call (msm_run_batch): [b].result equals (await msm(scalarPtrs[b], pointPtr, N)).result
+    async msmBatch(scalarPtrs, pointPtr, N, verboseTiming, options) {
+      const c = (options && options.c) || 0;
+      if (N > pointPtr.n) throw new Error(`msmBatch: ${N} scalars but ${pointPtr.n} points behind this pointer`);
+      for (const sp of scalarPtrs)
+        if (!sp.dev || N > sp.n) throw new Error(`msmBatch: ${N} scalars requested but a scalar pointer holds ${sp.dev ? sp.n : 0}`);
+      hip.pointsetSelect(ctx, pointPtr.set);
+      const unsafe = options && options.useSafeAdditions === false ? 1 : 0;
+      const rs = hip.msmBatchDevice(ctx, scalarPtrs.map((sp) => sp.dev), N, c, options && options.noGlv ? 1 : 0, unsafe);
+      return rs.map((r) => ({
+        result: { x: leBytesToBigint(r.x), y: leBytesToBigint(r.y), isZero: r.isZero },
+        log: verboseTiming ? buildLog(N, r) : [],
+      }));
     },
     msmProjective(scalarPtr, pointPtr, N, options) {
       // src/parallel.ts:69-87: signed windows of the whole scalar, no endomorphism split (same group element)

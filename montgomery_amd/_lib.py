@@ -17,7 +17,7 @@ CURVE_BLS12_377_G1 = 0
 CURVE_ED_ON_BLS12_377 = 1
 CURVE_BLS12_381_G1 = 2
 CURVE_PALLAS = 3
-ABI_VERSION = 6   # MSM_ABI_VERSION of the include/msm_hip.h this binding was written against
+ABI_VERSION = 7   # MSM_ABI_VERSION of the include/msm_hip.h this binding was written against
 N_PHASES = 8
 PHASE_NAMES = ("total", "upload", "digits", "sort", "accumulate", "reduce", "final", "accumulate_round1")
 
@@ -33,7 +33,7 @@ EXPORTS = (
     "msm_test_fp_raw", "msm_test_curve_op", "msm_test_batch_add_mode",
     "msm_run_placed", "msm_combine_groups", "msm_test_bucket_reduce", "msm_set_workspace_limit",
     "msm_precompute", "msm_tables_info", "msm_tables_range", "msm_set_tables_limit", "msm_reserve",
-    "msm_abi_version", "msm_abi_struct_bytes",
+    "msm_abi_version", "msm_abi_struct_bytes", "msm_run_batch",
 )
 
 
@@ -132,6 +132,7 @@ def load() -> C.CDLL:
     lib.msm_combine_curve.argtypes = [i32, vp, i32, i32, C.POINTER(MsmResult)]
     lib.msm_combine_curve.restype = i32
     lib.msm_combine_groups.argtypes = [i32, vp, i32, i32, i32, C.POINTER(MsmResult)]
+    lib.msm_run_batch.argtypes = [vp, C.POINTER(vp), C.c_uint32, u64, C.c_int, C.POINTER(MsmOpts), C.POINTER(MsmResult)]
     lib.msm_run_placed.argtypes = [vp, C.POINTER(vp), u64, C.POINTER(MsmOpts), C.POINTER(MsmResult)]
     lib.msm_plan.argtypes = [vp, u64, C.POINTER(MsmOpts), C.POINTER(i32), C.POINTER(i32)]
     lib.msm_generate_points.argtypes = [vp, u64, u64, vp]

@@ -341,6 +341,40 @@ class MsmContext:
         )
         return out, _result_to_dict(res)
 
+    def run_batch(self, scalars: Sequence[BytesLike], c: Optional[int] = None, unsafe: bool = False, no_glv: bool = False,
+                  strict: bool = False, serial: bool = False, point_lo: int = 0,
+                  no_tables: bool = False) -> List[Tuple[AffineResult, Dict]]:
+        """B MSMs over the same resident points (msm_run_batch): scalars[b] is the n x 32-byte scalar vector of element b, all
+        of the same length.  Element b equals run(scalars[b]); the info dicts describe the whole batched call."""
+        if not scalars:
+            raise MsmError(_lib.MSM_ERR_ARG, "run_batch: empty batch")
+        n = len(scalars[0]) // 32
+        bufs = []
+        for s in scalars:
+            if len(s) != 32 * n or len(s) % 32:
+                raise MsmError(_lib.MSM_ERR_ARG, "run_batch: the scalar vectors must all be n x 32 bytes")
+            bufs.append(s if isinstance(s, C.Array) else (C.c_uint8 * max(len(s), 1)).from_buffer_copy(bytes(s) or b"\0"))
+        ptrs = [C.cast(b, C.c_void_p).value for b in bufs]
+        return self._run_batch(ptrs, n, 0, c, unsafe, no_glv, strict, serial, point_lo, no_tables)
+
+    def run_batch_device(self, dev_ptrs: Sequence[int], n: int, c: Optional[int] = None, unsafe: bool = False,
+                         no_glv: bool = False, strict: bool = False, serial: bool = False, point_lo: int = 0,
+                         no_tables: bool = False) -> List[Tuple[AffineResult, Dict]]:
+        """run_batch over device scalar buffers (n x 32 bytes each, e.g. from device_alloc)."""
+        return self._run_batch([int(p) for p in dev_ptrs], n, 1, c, unsafe, no_glv, strict, serial, point_lo, no_tables)
+
+    def _run_batch(self, ptrs: Sequence[int], n: int, on_device: int, c, unsafe, no_glv, strict, serial, point_lo,
+                   no_tables) -> List[Tuple[AffineResult, Dict]]:
+        B = len(ptrs)
+        arr = (C.c_void_p * max(B, 1))(*[C.c_void_p(p) for p in ptrs])
+        opts = MsmOpts(c=c or 0, unsafe=int(unsafe), serial=int(serial), no_glv=int(no_glv), strict=int(strict),
+                       point_lo=point_lo, no_tables=int(no_tables))
+        res = (MsmResult * max(B, 1))()
+        self._check(self._lib.msm_run_batch(self._h, arr, B, n, on_device, C.byref(opts), res))
+        nb = self.coord_bytes
+        return [(AffineResult(int.from_bytes(bytes(r.x)[:nb], "little"), int.from_bytes(bytes(r.y)[:nb], "little"),
+                              bool(r.is_infinity)), _result_to_dict(r)) for r in res[:B]]
+
     # -- window tables (msm_precompute, include/msm_hip.h) ------------------------------------
     def precompute(self, n: Optional[int] = None, c: Optional[int] = None, no_glv: bool = False, point_lo: int = 0) -> Tuple[int, int, int]:
         """Builds the window tables of the current point set -- of its points [point_lo, point_lo + n): the share of one rank of a
@@ -620,6 +654,39 @@ class _Parallel:
                                ("bucket reduction (local)", "reduce"), ("final sum", "final"), ("msm total", "total")):
                 log.append([f"{label}... {t[key]:.1f}ms"])
         return {"result": res, "log": log, "info": info}
+
+    def msmBatch(self, scalarPtrs: Sequence[ScalarPtr], pointPtr: PointPtr, N: int, verboseTiming: bool = False,
+                 options: Optional[Dict] = None) -> List[Dict]:
+        """Many MSMs over one point set in one call (msm_run_batch): one dict per scalar pointer, shaped like msm's, whose
+        "result" equals msm(scalarPtrs[b], pointPtr, N)["result"].  The scalar pointers are all on the device or all on the host."""
+        options = options or {}
+        self._ctx.pointset_select(pointPtr.set_id)
+        if N > pointPtr.n or N > self._ctx.n_points:
+            raise MsmError(_lib.MSM_ERR_NO_POINTS, f"{N} scalars but {min(pointPtr.n, self._ctx.n_points)} points behind this pointer")
+        for sp in scalarPtrs:
+            if N > sp.n:
+                raise MsmError(_lib.MSM_ERR_ARG, f"{N} scalars requested but a scalar pointer holds {sp.n}")
+        on_dev = [bool(sp.dev_ptr) for sp in scalarPtrs]
+        if any(on_dev) and not all(on_dev):
+            raise MsmError(_lib.MSM_ERR_ARG, "msmBatch: the scalar pointers must all be on the device or all on the host")
+        unsafe = not options.get("useSafeAdditions", True)
+        no_glv = bool(options.get("noGlv", False))
+        if scalarPtrs and all(on_dev):
+            out = self._ctx.run_batch_device([sp.dev_ptr for sp in scalarPtrs], N, options.get("c"), unsafe, no_glv=no_glv)
+        else:
+            out = self._ctx.run_batch([sp.data[: 32 * N] for sp in scalarPtrs], options.get("c"), unsafe, no_glv=no_glv)
+        dicts = []
+        for res, info in out:
+            log: List = []
+            if verboseTiming:
+                t = info["phase_ms"]
+                log.append([{"n": (N - 1).bit_length() if N > 1 else 0, "K": info["K"], "c": info["c"], "batch": len(scalarPtrs)}])
+                for label, key in (("scalars to device", "upload"), ("slice scalars & count buckets", "digits"), ("sort points", "sort"),
+                                   ("bucket accumulation (first round)", "accumulate_round1"), ("bucket accumulation", "accumulate"),
+                                   ("bucket reduction (local)", "reduce"), ("final sum", "final"), ("msm total", "total")):
+                    log.append([f"{label}... {t[key]:.1f}ms"])
+            dicts.append({"result": res, "log": log, "info": info})
+        return dicts
 
     def msmProjective(self, scalarPtr: ScalarPtr, pointPtr: PointPtr, N: int, options: Optional[Dict] = None) -> Dict:
         """`msmProjective` (src/parallel.ts:69-87: msmBasic over projective points): signed windows of the whole scalar,

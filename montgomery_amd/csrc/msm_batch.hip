@@ -1,0 +1,239 @@
+// msm_run_batch: B MSMs over the same resident points.  Where one MSM is mostly fixed latency (launches, read-backs, short
+// dependent chains: below ~2^20 points), the batch runs FUSED: element b's window k becomes virtual window b K + k of one
+// window group, so B elements share every launch of the digits, the sort, the tree and the bucket reduction -- the sort and
+// the tree do not care which scalar a window came from.  Elsewhere the call runs element by element through msm_run.
+#include "msm_internal.h"
+
+using namespace msm;
+using namespace msmi;
+
+namespace msmi {
+
+// Window of a fused batch.  msm_run's rule (pick_window) takes 16 bits from 2^12 points because a smaller window mostly buys
+// more rounds of fixed latency; in a batch those rounds are shared and the bucket work grows with B.  Measured with
+// tools/batch_time.py --csweep, c = 10 .. 16 (profiles/batch_msm_time.txt): BLS12-377 after GLV wants 13 bits (K = 10) from
+// B = 16 at 2^12 .. 2^18 points (2^14 x 16: 3.44 ms against 7.35 at 16 bits; 2^18 x 64: 61.7 / 63.9) and at B = 4 up to 2^14
+// points (2^14: 1.88 / 2.04), but keeps 16 at B = 4 from 2^16 (2.50 / 2.63).  Ed-on-BLS12-377 wants 12 bits (2^12 x 16: 1.35 ms
+// against 1.78 at the cost model's 7; 2^14 x 64: 5.98 / 6.29 at its 9) and 14 from 2^17 points at B >= 16 (2^18 x 64: 40.9 / 43.1).  Other inputs (fewer than 2^12 points, no_glv) keep msm_run's window.
+int pick_window_batch(bool te, uint64_t n, uint32_t B, int glv_max_bits) {
+  if (te) return n < 4096 ? pick_window(te, n, glv_max_bits) : (n >= (1ull << 17) && B >= 16) ? 14 : 12;
+  if (glv_max_bits && n >= 4096 && (B >= 16 || n <= (1ull << 14))) return 13;
+  return pick_window(te, n, glv_max_bits);
+}
+
+}  // namespace msmi
+
+namespace {
+
+constexpr int GROUP_WINDOWS = 128;   // windows of one group under the one-level sort (window_sums_once)
+
+// the call fuses: one device, a plan of the one-level sort (c <= 16, fewer entries per window than the radix split takes)
+bool fuse(const msm_ctx* ctx, uint64_t n, uint32_t B, const Plan& pl) {
+  if (!ctx->children.empty() || B < 2 || pl.c > 16 || pl.fold) return false;
+  const uint64_t entries = ctx->is_te() ? n : 2 * n;
+  if (entries >= (ctx->is_te() ? 1ull << 22 : 1ull << 21)) return false;
+  return pl.K <= GROUP_WINDOWS / 2;   // (at least two elements per group)
+}
+
+// one group of elements [b0, b0 + cnt): its kc = cnt K window sums -> part (kc x 36 words; 32 on the Edwards path)
+void run_batch_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl_in, const std::vector<const uint32_t*>& sc, int b0, int cnt,
+                     uint64_t n, uint64_t p_lo, bool lone, uint32_t* part, GroupStats& st) {
+  Plan pl = pl_in;
+  pl.batch = cnt;
+  pl.lone = lone;
+  for (int j = 0; j < cnt; j++) pl.batch_sc.p[j] = sc[b0 + j];
+  const int kc = cnt * pl.K;
+  SortOut so;
+  HIPCHK(hipEventRecord(w.ev[0], w.stream));
+  sort_window_group(ctx, w, nullptr, n, pl, 0, kc, st, so);
+  st.max_bucket = std::max<uint64_t>(st.max_bucket, so.max_bucket);
+  HIPCHK(hipEventRecord(w.ev[5], w.stream));
+  TreeOut to;
+  accumulate_window_group(ctx, w, pl, kc, p_lo, so, st, to);
+  // unmerged: a merged reduction would fold the windows of different elements into one slot
+  reduce_buckets(ctx, w, to.fin, to.fin_cap, to.off_fin, to.bucket_proj, pl.L, kc, part, false, pl.c);
+  float ms;
+  HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1])); st.ms_digits += ms;
+  HIPCHK(hipEventElapsedTime(&ms, w.ev[1], w.ev[2])); st.ms_sort += ms;
+  HIPCHK(hipEventElapsedTime(&ms, w.ev[5], w.ev[3])); st.ms_acc += ms;
+  HIPCHK(hipEventElapsedTime(&ms, w.ev[5], w.ev[6])); st.ms_r1 += ms;
+  HIPCHK(hipEventElapsedTime(&ms, w.ev[3], w.ev[4])); st.ms_red += ms;
+}
+
+int run_fused(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device, const msm_opts* opts, const Plan& pl,
+              msm_result* out) {
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipEventRecord(ctx->ev[8], ctx->stream));
+  std::vector<const uint32_t*> sc(B);
+  if (on_device) {
+    for (uint32_t b = 0; b < B; b++) sc[b] = (const uint32_t*)scalars[b];
+  } else {
+    ctx->ensure(ctx->scal, (size_t)B * n * 32);
+    for (uint32_t b = 0; b < B; b++) {
+      sc[b] = (const uint32_t*)ctx->scal.p + (size_t)b * n * 8;
+      upload_staged(ctx, (void*)sc[b], scalars[b], n * 32);
+    }
+  }
+  HIPCHK(hipEventRecord(ctx->ev[9], ctx->stream));
+  // groups of whole elements: at most 128 windows, BATCH_MAX elements, and what the workspace budget gives one group
+  const uint64_t budget = ctx->ws_limit ? ctx->ws_limit : ctx->ws_budget;
+  const long double room = (long double)budget / msm_ctx::N_WS / window_bytes(ctx, n, pl);
+  const int wpg = (int)std::max<long double>(1, std::min<long double>(room, GROUP_WINDOWS));
+  int per = std::max(1, std::min(wpg / pl.K, BATCH_MAX));
+  const int n_groups = (int)((B + per - 1) / per);
+  per = (int)((B + n_groups - 1) / n_groups);   // even groups
+  const int pw = ctx->is_te() ? 32 : 36;
+  std::vector<uint32_t> words((size_t)B * pl.K * pw);
+  HIPCHK(hipMemsetAsync(ctx->errflag.p, 0, 4, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // scalars and the error flag are in place before the group streams start
+  const uint64_t p_lo = point_lo(opts);
+  const bool serial = opts && opts->serial;
+  std::atomic<int> next{0};
+  GroupStats sts[msm_ctx::N_WS];
+  auto worker = [&](int slot) {
+    HIPCHK(hipSetDevice(ctx->device));
+    for (;;) {
+      const int g = next.fetch_add(1);
+      if (g >= n_groups) break;
+      const int b0 = g * per, cnt = std::min<int>(per, (int)B - b0);
+      if (cnt <= 0) break;
+      run_batch_group(ctx, ctx->ws[slot], pl, sc, b0, cnt, n, p_lo, serial, &words[(size_t)b0 * pl.K * pw], sts[slot]);
+    }
+  };
+  {
+    // as window_sums_once: whatever a worker throws is re-raised once both have stopped and both streams are idle
+    const int nthreads = serial ? 1 : std::min<int>(msm_ctx::N_WS, n_groups);
+    std::exception_ptr err;
+    if (nthreads > 1) ctx->helper->run([&] { worker(1); });
+    try { worker(0); } catch (...) { err = std::current_exception(); }
+    if (nthreads > 1) {
+      try { ctx->helper->wait(); } catch (...) { if (!err) err = std::current_exception(); }
+    }
+    if (err) {
+      next.store(n_groups);
+      for (auto& w : ctx->ws) (void)hipStreamSynchronize(w.stream);
+      std::rethrow_exception(err);
+    }
+  }
+  // (ev[10] goes in front of the read-back: the synchronisation below then covers it, and hipEventElapsedTime reads it once it
+  // has completed -- an event recorded behind that synchronisation may still be pending when the host asks)
+  HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (pl.strict && (ctx->h_info[0] & 4u)) throw MsmFail{MSM_ERR_SCALAR, "a scalar is >= the group order q (msm_opts.strict)"};
+  if (ctx->h_info[0] & 8u) throw MsmFail{MSM_ERR_INTERNAL, "a digit of the folded top window exceeds its bucket range (GLV bound violated)"};
+  // per element: the Horner step over its K window sums and the conversion to affine (one field inversion each), spread over
+  // host threads -- ~0.03 ms per element on one thread
+  const auto t0 = std::chrono::steady_clock::now();
+  auto finish = [&](uint32_t b) {
+    const uint32_t* wb = &words[(size_t)b * pl.K * pw];
+    if (ctx->is_te()) {
+      te_horner_to_affine(ctx, std::vector<uint32_t>(wb, wb + (size_t)pl.K * pw), pl.K, pl.c, &out[b]);
+    } else {
+      std::vector<msm_host::Proj6> P(pl.K);
+      for (int k = 0; k < pl.K; k++) P[k] = partial_to_host(ctx, wb + (size_t)k * pw);
+      horner_to_affine(ctx->hc, P, pl.c, &out[b]);
+    }
+  };
+  const uint32_t n_fin = std::min<uint32_t>(8, B / 4);
+  if (n_fin <= 1) {
+    for (uint32_t b = 0; b < B; b++) finish(b);
+  } else {
+    std::atomic<uint32_t> nb{0};
+    auto fin_worker = [&] {
+      for (uint32_t b; (b = nb.fetch_add(1)) < B;) finish(b);
+    };
+    std::vector<std::thread> th;
+    for (uint32_t t = 1; t < n_fin; t++) {
+      try { th.emplace_back(fin_worker); } catch (const std::system_error&) { break; }
+    }
+    fin_worker();
+    for (auto& t : th) t.join();
+  }
+  const float fin_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  GroupStats st;
+  for (int i = 0; i < msm_ctx::N_WS; i++) {
+    st.n_pairs += sts[i].n_pairs;
+    st.n_pairs_algo += sts[i].n_pairs_algo;
+    st.max_bucket = std::max(st.max_bucket, sts[i].max_bucket);
+    st.rounds += sts[i].rounds;
+    st.ms_digits += sts[i].ms_digits; st.ms_sort += sts[i].ms_sort; st.ms_acc += sts[i].ms_acc;
+    st.ms_red += sts[i].ms_red; st.ms_r1 += sts[i].ms_r1;
+  }
+  float up_ms, tot_ms;
+  HIPCHK(hipEventElapsedTime(&up_ms, ctx->ev[8], ctx->ev[9]));
+  HIPCHK(hipEventElapsedTime(&tot_ms, ctx->ev[8], ctx->ev[10]));
+  for (uint32_t b = 0; b < B; b++) {
+    msm_result& r = out[b];
+    r.c = pl.c;
+    r.K = pl.K;
+    r.rounds = st.rounds;
+    r.n_pairs = st.n_pairs;
+    r.n_pairs_algo = st.n_pairs_algo;
+    r.max_bucket = st.max_bucket;
+    r.tables = 0;
+    r.phase_ms[MSM_T_UPLOAD] = up_ms;
+    r.phase_ms[MSM_T_DIGITS] = st.ms_digits;
+    r.phase_ms[MSM_T_SORT] = st.ms_sort;
+    r.phase_ms[MSM_T_ACCUMULATE] = st.ms_acc;
+    r.phase_ms[MSM_T_ACC_ROUND1] = st.ms_r1;
+    r.phase_ms[MSM_T_REDUCE] = st.ms_red;
+    r.phase_ms[MSM_T_FINAL] = fin_ms;
+    r.phase_ms[MSM_T_TOTAL] = tot_ms + fin_ms;
+  }
+  return MSM_OK;
+}
+
+// element by element through msm_run (its window tables included); the statistics of the whole call go into every element
+int run_each(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device, const msm_opts* opts, msm_result* out) {
+  msm_result tot;
+  memset(&tot, 0, sizeof tot);
+  for (uint32_t b = 0; b < B; b++) {
+    if (int rc = msm_run(ctx, scalars[b], n, on_device, opts, &out[b])) return rc;
+    for (int j = 0; j < MSM_N_PHASES; j++) tot.phase_ms[j] += out[b].phase_ms[j];
+    tot.rounds += out[b].rounds;
+    tot.n_pairs += out[b].n_pairs;
+    tot.n_pairs_algo += out[b].n_pairs_algo;
+    tot.max_bucket = std::max(tot.max_bucket, out[b].max_bucket);
+  }
+  for (uint32_t b = 0; b < B; b++) {
+    memcpy(out[b].phase_ms, tot.phase_ms, sizeof tot.phase_ms);
+    out[b].rounds = tot.rounds;
+    out[b].n_pairs = tot.n_pairs;
+    out[b].n_pairs_algo = tot.n_pairs_algo;
+    out[b].max_bucket = tot.max_bucket;
+  }
+  return MSM_OK;
+}
+
+}  // namespace
+
+extern "C" int msm_run_batch(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device, const msm_opts* opts,
+                             msm_result* out) {
+  if (!ctx || !out || !scalars || B == 0) return fail(ctx, MSM_ERR_ARG, "msm_run_batch: null argument or empty batch");
+  for (uint32_t b = 0; b < B && n; b++)
+    if (!scalars[b]) return fail(ctx, MSM_ERR_ARG, "msm_run_batch: no scalars for element %u", b);
+  if (opts && (opts->k_lo || opts->k_hi || opts->bucket_shards > 1 || opts->merged_sums || opts->by_window))
+    return fail(ctx, MSM_ERR_ARG, "msm_run_batch: window shards, bucket shards, merged sums and by_window are not batch options");
+  if (int rc = check_points(ctx, n, opts, MSM_ERR_NO_POINTS, "msm_run_batch")) return rc;
+  try {
+    if (n) {
+      Plan pl;
+      msm_opts o;
+      if (opts) o = *opts; else memset(&o, 0, sizeof o);
+      const bool te = ctx->is_te();
+      const int glv_bits = curve_info(ctx->curve).glv_max_bits;
+      if (o.c <= 0) o.c = pick_window_batch(te, n, B, o.no_glv ? 0 : glv_bits);
+      if (make_plan(ctx, n, &o, pl)) return fail(ctx, MSM_ERR_ARG, "msm_run_batch: bad window size");
+      bool fused = fuse(ctx, n, B, pl);
+      int fuse_knob = -1;
+      MSM_KNOB(fuse_knob, "MSM_BATCH_FUSE", 0);   // (tuning builds: 0 = element by element, the sequential form for A/B runs)
+      if (fuse_knob == 0) fused = false;
+      if (fused) {
+        for (uint32_t b = 0; b < B; b++) memset(&out[b], 0, sizeof(msm_result));
+        return run_fused(ctx, scalars, B, n, on_device, opts, pl, out);
+      }
+    }
+    return run_each(ctx, scalars, B, n, on_device, opts, out);
+  } MSM_CATCH_ALL(ctx)
+}

@@ -353,6 +353,8 @@ struct Plan {
   uint64_t tab_lo = 0, tab_n = 0;       //         [tab_lo, tab_lo + tab_n)
   bool merged = false; // a full MSM (msm_run): a window group may hand back sum_k 2^(c (k - k_first)) P_k in the slot of its
                        // first window instead of one P_k per slot (reduce_buckets); msm_window_sums never sets it
+  int batch = 0;       // msm_run_batch (msm_batch.hip): the group's windows are those of `batch` elements, K each (window
+  BatchScalars batch_sc{};   // kk = virtual window b K + k), their digits come from k_digits_batch over batch_sc
 };
 
 // for_tables: the window a run on window tables wants (bucket work no longer grows with the number of windows)
@@ -587,6 +589,9 @@ int on_all_devices(msm_ctx* ctx, F f) {
     }
   return MSM_OK;
 }
+
+// ---- msm_batch.hip ----------------------------------------------------------------------------------------------
+int pick_window_batch(bool te, uint64_t n, uint32_t B, int glv_max_bits);
 
 // ---- msm_gen.hip ------------------------------------------------------------------------------------------------
 }  // namespace msmi

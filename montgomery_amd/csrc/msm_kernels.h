@@ -357,6 +357,73 @@ __global__ void __launch_bounds__(1024) k_digits(uint32_t* dig, const uint32_t* 
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_digits_batch: the digits of several scalar vectors over the same points (msm_run_batch, msm_batch.hip)
+// ---------------------------------------------------------------------------------------------
+
+// the scalar vectors of one fused group, passed in the kernel arguments: a group holds at most 128 windows of K >= 8
+// (c <= 16), so at most 16 elements
+constexpr int BATCH_MAX = 16;
+struct BatchScalars {
+  const uint32_t* p[BATCH_MAX];   // n x 8 words each
+};
+
+// Element b's window k is "virtual window" b K + k of the group: dig[(b K + k) * 2n + 2 i + {0, 1}], the [window][entry] layout
+// k_digits writes, so the sort and the tree take the group as b_cnt K ordinary windows.  The top-window rules (fold, err) are
+// those of window k of its own element.  One thread per point, its scalars decomposed one after the other.  No slice histogram
+// and no bucket-range shard: a fused batch always takes the one-level sort over the whole bucket range.
+template <class CV>
+__global__ void __launch_bounds__(256) k_digits_batch(uint32_t* dig, BatchScalars sc, uint32_t b_cnt, uint32_t n, int c, int k_total,
+                                                      int glv_flags, int strict, uint32_t* err) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int glv = glv_flags & 1;
+  const bool fold = glv_flags & 2;
+  const uint32_t L = 1u << (c - 1);
+  const uint64_t two_n = 2ull * n;
+  uint32_t q[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) q[j] = CV::G::Q[j];
+#pragma unroll 1
+  for (uint32_t b = 0; b < b_cnt; b++) {
+    uint32_t s[8];
+    {
+      const uint4* p4 = reinterpret_cast<const uint4*>(sc.p[b] + (uint64_t)i * 8);
+      uint4 x = p4[0], y = p4[1];
+      s[0] = x.x; s[1] = x.y; s[2] = x.z; s[3] = x.w; s[4] = y.x; s[5] = y.y; s[6] = y.z; s[7] = y.w;
+    }
+    if (words8_ge(s, q)) {   // as k_digits: reduced mod q, or refused under msm_opts.strict
+      if (strict) atomicOr(err, 4u);
+      for (int it = 0; it < 16 && words8_ge(s, q); it++) bn_addsub<8, 8>(s, q, true);
+    }
+    uint32_t* db = dig + (uint64_t)b * k_total * two_n + 2ull * i;
+    if (!glv) {
+      uint32_t carry = 0;
+      for (int k = 0; k < k_total; k++) {
+        const bool top = fold && k == k_total - 1;
+        uint32_t l = bn_take_bits<8>(s, top ? c + 1 : c) + carry;
+        if (!top && l > L) { l = 2 * L - l; carry = 1; } else { carry = 0; }
+        if (top && l > 2 * L) { atomicOr(err, 8u); l = 2 * L; }
+        *reinterpret_cast<uint2*>(db + (uint64_t)k * two_n) = make_uint2(l | ((l ? carry : 0u) << 31), 0u);
+      }
+      continue;
+    }
+    GlvHalf h[2];
+    glv_decompose<typename CV::G>(h[0], h[1], s);
+    uint32_t carry0 = 0, carry1 = 0;
+    for (int k = 0; k < k_total; k++) {
+      const bool top = fold && k == k_total - 1;
+      uint32_t l0 = bn_take_bits<4>(h[0].mag, top ? c + 1 : c) + carry0;
+      uint32_t l1 = bn_take_bits<4>(h[1].mag, top ? c + 1 : c) + carry1;
+      if (!top && l0 > L) { l0 = 2 * L - l0; carry0 = 1; } else { carry0 = 0; }
+      if (!top && l1 > L) { l1 = 2 * L - l1; carry1 = 1; } else { carry1 = 0; }
+      if (top && (l0 > 2 * L || l1 > 2 * L)) { atomicOr(err, 8u); l0 = min(l0, 2 * L); l1 = min(l1, 2 * L); }
+      const uint32_t neg0 = l0 ? carry0 ^ (h[0].neg ? 1u : 0u) : 0u, neg1 = l1 ? carry1 ^ (h[1].neg ? 1u : 0u) : 0u;
+      *reinterpret_cast<uint2*>(db + (uint64_t)k * two_n) = make_uint2(l0 | (neg0 << 31), l1 | (neg1 << 31));
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // projective points in raw limb form (3 x 13 words) between the reduction kernels
 // ---------------------------------------------------------------------------------------------
 

@@ -89,7 +89,7 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
     for (int kk = 0; kk < kc; kk++) {
       // bits the digits of this window really have: the top window of a scalar is usually short (msm_kernels.h, WinSplit)
       // (a window below the top one holds signed digits of magnitude <= 2^(c - 1); the top one what is left of the scalar)
-      const bool top = k_lo + kk == pl.K - 1;
+      const bool top = (k_lo + kk) % pl.K == pl.K - 1;   // (window k of its element in a batch: msm_run_batch)
       const int eff = pl.tables ? cbits : std::max(1, top ? std::min(cbits, pl.bits - (k_lo + kk) * pl.c) : std::min(cbits, pl.c - 1));
       // up to 10 bits: pass A sorts the window outright; else 2^10 coarse bins (16-entry runs of a 16 k tile), 2^11 if the
       // fine part would otherwise exceed 2^12 buckets per bin
@@ -164,7 +164,18 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
 
   if (consume) HIPCHK(hipStreamWaitEvent(s, share->ready, 0));   // (the producer's launch is timed by the caller, not as this group's wait)
   HIPCHK(hipEventRecord(w.ev[0], s));
-  if (!consume) {
+  if (pl.batch) {
+    // msm_run_batch: the kc_d windows are the K windows of pl.batch elements (virtual windows), one thread per point.  A fused
+    // batch is sized to take the one-level sort (msm_batch.hip), which needs no slice histograms from the digit kernel.
+    if (bin_split || radix || k_lo != 0 || kc_d != pl.batch * pl.K) throw MsmFail{MSM_ERR_INTERNAL, "a batch group outside the one-level sort"};
+    const uint32_t grid = (uint32_t)((n + 255) / 256);
+    if (te)
+      hipLaunchKernelGGL(te::k_te_digits_batch, dim3(grid), dim3(256), 0, s, (uint32_t*)w.dig.p, pl.batch_sc, (uint32_t)pl.batch,
+                         (uint32_t)n, pl.c, pl.K, pl.strict ? 1 : 0, (uint32_t*)ctx->errflag.p);
+    else
+      W_LAUNCH(ctx, k_digits_batch, dim3(grid), dim3(256), 0, s, (uint32_t*)w.dig.p, pl.batch_sc, (uint32_t)pl.batch, (uint32_t)n, pl.c,
+               pl.K, (pl.no_glv ? 0 : 1) | (pl.fold ? 2 : 0), pl.strict ? 1 : 0, (uint32_t*)ctx->errflag.p);
+  } else if (!consume) {
     // digits; the bin split also takes the histogram of its first pass from here (one slice of the points per block)
     const uint32_t grid = bin_split ? sortB : (uint32_t)((n + 255) / 256);
     const uint32_t per = bin_split ? (uint32_t)pps : 256u;

@@ -320,6 +320,43 @@ __global__ void __launch_bounds__(1024) k_te_digits(uint32_t* dig, const uint32_
 }
 #endif
 
+// k_te_digits_batch: the digits of several scalar vectors over the same points (msm_run_batch): element b's window k is virtual
+// window b K + k, dig[(b K + k) * n + i], as k_digits_batch (msm_kernels.h) does it for the Weierstrass curves
+__global__ void __launch_bounds__(256) k_te_digits_batch(uint32_t* dig, BatchScalars sc, uint32_t b_cnt, uint32_t n, int c, int k_total,
+                                                         int strict, uint32_t* err)
+#ifndef MSM_TE_TU
+    ;
+#else
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t L = 1u << (c - 1);
+  uint32_t q[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) q[j] = FRED_Q[j];
+#pragma unroll 1
+  for (uint32_t b = 0; b < b_cnt; b++) {
+    uint32_t s[8];
+    {
+      const uint4* p4 = reinterpret_cast<const uint4*>(sc.p[b] + (uint64_t)i * 8);
+      uint4 x = p4[0], y = p4[1];
+      s[0] = x.x; s[1] = x.y; s[2] = x.z; s[3] = x.w; s[4] = y.x; s[5] = y.y; s[6] = y.z; s[7] = y.w;
+    }
+    if (words8_ge(s, q)) {   // as k_te_digits
+      if (strict) atomicOr(err, 4u);
+      for (int it = 0; it < 64 && words8_ge(s, q); it++) bn_addsub<8, 8>(s, q, true);
+    }
+    uint32_t* db = dig + (uint64_t)b * k_total * n + i;
+    uint32_t carry = 0;
+    for (int k = 0; k < k_total; k++) {
+      uint32_t l = bn_take_bits<8>(s, c) + carry;
+      if (l > L) { l = 2 * L - l; carry = 1; } else { carry = 0; }
+      db[(uint64_t)k * n] = l | ((l ? carry : 0u) << 31);
+    }
+  }
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // k_te_add: one round of the bucket tree, output e = input 2e + input 2e+1 (unified addition)
 // ---------------------------------------------------------------------------------------------

@@ -12,6 +12,8 @@
 //          deviceAlloc(h, bytes) -> device buffer handle, deviceUpload(h, dbuf, Buffer), deviceFree(h, dbuf),
 //          msmDevice(h, dbuf, n, c, noGlv, unsafe) -> as msm: the scalars already sit in HBM (the reference keeps them in the
 //          memory its kernels compute in, src/parallel.ts:119-133, scripts/msm-weierstrass.ts:29-32),
+//          msmBatch(h, [Buffer scalars], c, noGlv, unsafe) / msmBatchDevice(h, [dbuf], n, c, noGlv, unsafe) -> array of results as
+//          msm's: many MSMs over the same points in one call (msm_run_batch),
 //          plan(h, n, c) -> {c, K}, generatePoints(h, n, seed) -> n, generateScalars(h, n, seed[, dbuf]) -> Buffer | n
 //          the fine operator table of the reference's wasm exports (src/field-msm.ts:86-123,190-243, src/scalar-glv.ts:41-51,105-128)
 //          over Buffers instead of wasm pointers: fieldOp(h, op, a, b) -> Buffer (msm_test_fp: multiply / square / add / subtract /
@@ -342,6 +344,98 @@ static napi_value MsmDevice(napi_env env, napi_callback_info info) {  // msm ove
   return result_object(env, h, &res);
 }
 
+// many MSMs over one point set in one call (msm_run_batch): argv[1] is an array of B scalar Buffers (msmBatch) or of B device
+// buffers holding n scalars each (msmBatchDevice); returns an array of B result objects, each as msm's
+static napi_value batch_common(napi_env env, napi_callback_info info, int on_device) {
+  size_t argc = 6;   // (ctx, array, c, noGlv, unsafe) or (ctx, array, n, c, noGlv, unsafe)
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  const char* who = on_device ? "msmBatchDevice" : "msmBatch";
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  bool is_array = false;
+  if (argc > 1) napi_is_array(env, argv[1], &is_array);
+  if (!is_array) {
+    napi_throw_type_error(env, NULL, "expected an array of scalar buffers");
+    return NULL;
+  }
+  uint32_t B = 0;
+  NAPI_OK(napi_get_array_length(env, argv[1], &B));
+  if (B == 0) {
+    napi_throw_range_error(env, NULL, "empty batch");
+    return NULL;
+  }
+  uint64_t n = 0;
+  size_t o = 2;   // first option argument
+  if (on_device) {
+    uint32_t nn = 0;
+    if (argc > 2) NAPI_OK(napi_get_value_uint32(env, argv[2], &nn));
+    n = nn;
+    o = 3;
+  }
+  msm_opts opts;
+  memset(&opts, 0, sizeof opts);
+  if (argc > o) napi_get_value_int32(env, argv[o], &opts.c);
+  if (argc > o + 1) napi_get_value_int32(env, argv[o + 1], &opts.no_glv);
+  if (argc > o + 2) napi_get_value_int32(env, argv[o + 2], &opts.unsafe);
+  const void** ptrs = (const void**)calloc(B, sizeof(void*));
+  msm_result* res = (msm_result*)calloc(B, sizeof(msm_result));
+  if (!ptrs || !res) {
+    free(ptrs);
+    free(res);
+    napi_throw_error(env, NULL, "out of memory");
+    return NULL;
+  }
+  const char* bad = NULL;
+  for (uint32_t b = 0; b < B && !bad; b++) {
+    napi_value e;
+    if (napi_get_element(env, argv[1], b, &e) != napi_ok) { bad = "N-API call failed: napi_get_element"; break; }
+    if (on_device) {
+      js_dbuf* d = get_dbuf(env, h, e);
+      if (!d) { free(ptrs); free(res); return NULL; }
+      if (n * 32 > d->bytes) bad = "more scalars than a device buffer holds";
+      ptrs[b] = d->dev;
+    } else {
+      void* data;
+      size_t len;
+      if (napi_get_buffer_info(env, e, &data, &len) != napi_ok) { bad = "expected an array of Buffers"; break; }
+      if (len % 32) bad = "scalar buffer length is not a multiple of 32";
+      else if (b == 0) n = len / 32;
+      else if (len / 32 != n) bad = "the scalar buffers of a batch must have the same length";
+      ptrs[b] = data;
+    }
+  }
+  if (bad) {
+    free(ptrs);
+    free(res);
+    napi_throw_range_error(env, NULL, bad);
+    return NULL;
+  }
+  int rc = msm_run_batch(h->ctx, ptrs, B, n, on_device, &opts, res);
+  free(ptrs);
+  if (rc != MSM_OK) {
+    free(res);
+    return throw_msm(env, h->ctx, rc, who);
+  }
+  napi_value arr;
+  if (napi_create_array_with_length(env, B, &arr) != napi_ok) {
+    free(res);
+    napi_throw_error(env, NULL, "N-API call failed: napi_create_array_with_length");
+    return NULL;
+  }
+  for (uint32_t b = 0; b < B; b++) {
+    napi_value r = result_object(env, h, &res[b]);
+    if (!r || napi_set_element(env, arr, b, r) != napi_ok) {
+      free(res);
+      return NULL;
+    }
+  }
+  free(res);
+  return arr;
+}
+static napi_value MsmBatch(napi_env env, napi_callback_info info) { return batch_common(env, info, 0); }
+static napi_value MsmBatchDevice(napi_env env, napi_callback_info info) { return batch_common(env, info, 1); }
+
 static napi_value Plan(napi_env env, napi_callback_info info) {  // windowSize, src/msm-common.ts:8-41
   size_t argc = 3;
   napi_value argv[3];
@@ -577,6 +671,7 @@ NAPI_MODULE_INIT() {
       {"createContext", CreateContext}, {"destroyContext", DestroyContext}, {"setPoints", SetPoints}, {"msm", Msm}, {"plan", Plan},
       {"generatePoints", GeneratePoints}, {"generateScalars", GenerateScalars},
       {"deviceAlloc", DeviceAlloc}, {"deviceUpload", DeviceUpload}, {"deviceFree", DeviceFree}, {"msmDevice", MsmDevice},
+      {"msmBatch", MsmBatch}, {"msmBatchDevice", MsmBatchDevice},
       {"pointsetCreate", PointsetCreate}, {"pointsetSelect", PointsetSelect}, {"pointsetDestroy", PointsetDestroy},
       {"fieldOp", FieldOp}, {"batchInverse", BatchInverse}, {"glvDecompose", GlvDecompose}, {"batchAdd", BatchAdd}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
