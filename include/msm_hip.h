@@ -30,7 +30,8 @@ enum {
   MSM_OK = 0,
   MSM_ERR_ARG = 1,         /* null pointer, bad length, bad window size, unknown curve */
   MSM_ERR_HIP = 2,         /* HIP runtime failure (message has the HIP error string) */
-  MSM_ERR_POINT = 3,       /* coordinate >= p, or point not on the curve (when validation is requested) */
+  MSM_ERR_POINT = 3,       /* coordinate >= p, point not on the curve or outside the subgroup (when validation is requested),
+                              undecodable compressed point */
   MSM_ERR_NO_POINTS = 4,   /* msm called before msm_set_points, or with n > resident points */
   MSM_ERR_NO_DEVICE = 5,   /* no usable GPU: there is no CPU fallback */
   MSM_ERR_SCALAR = 6,      /* a scalar >= the group order q and msm_opts.strict was set (default: reduced mod q) */
@@ -53,8 +54,9 @@ enum {
  * addon compare both at load time and refuse a mismatch.  History: 3 = round 3 (msm_generate_scalars writes to a caller-owned
  * buffer; msm_opts.point_lo / by_window); 4 = msm_result.n_pairs_algo; 5 = window tables (msm_opts.no_tables, msm_result.tables,
  * msm_precompute / msm_tables_info / msm_set_tables_limit), msm_reserve, msm_opts.bucket_shard / bucket_shards; 6 = window tables
- * over a range of the points (msm_opts.merged_sums, msm_precompute with point_lo, msm_tables_range); 7 = msm_run_batch. */
-#define MSM_ABI_VERSION 7
+ * over a range of the points (msm_opts.merged_sums, msm_precompute with point_lo, msm_tables_range); 7 = msm_run_batch;
+ * 8 = compressed points and subgroup validation (msm_set_points_ex, msm_validate_points, msm_get_points_ex). */
+#define MSM_ABI_VERSION 8
 uint32_t msm_abi_version(void);
 uint32_t msm_abi_struct_bytes(int which);
 
@@ -149,6 +151,37 @@ const char* msm_last_error(const msm_ctx* ctx);
  * per call as in preparePointsAndScalars, src/msm-batched-affine.ts:350-421).
  * on_device != 0: `points` is a device pointer.  check_curve != 0: verify the curve equation. */
 int msm_set_points(msm_ctx* ctx, const void* points, uint64_t n, int on_device, int check_curve);
+
+/* Point formats and validation levels of msm_set_points_ex / msm_validate_points / msm_get_points_ex.
+ * MSM_POINTS_UNCOMPRESSED is the x || y format of msm_set_points.  MSM_POINTS_COMPRESSED is one coordinate and flag bits:
+ *   BLS12-381 G1 (ZCash / blst)   48 bytes, x BIG-endian; first byte: 0x80 compressed (must be set), 0x40 infinity,
+ *                                 0x20 sign = y > (p-1)/2.  Identity: c0 00 .. 00
+ *   BLS12-377 G1 (arkworks)       48 bytes, x little-endian; last byte: 0x80 sign = y > (p-1)/2, 0x40 infinity.
+ *                                 Identity: last byte 0x40, every other byte 0
+ *   Pallas (pasta / halo2)        32 bytes, x little-endian; bit 255 sign = y odd.  Identity: 32 zero bytes
+ *   Ed-on-BLS12-377 (arkworks)    32 bytes, y little-endian; bit 255 sign = x > (r-1)/2.  Identity: y = 1, sign 0
+ * Decoding refuses a coordinate >= the modulus, invalid flags (a missing 0x80 on BLS12-381; infinity with any other bit set;
+ * both flags on BLS12-377; bits the layout does not use), an x (Edwards: y) without a curve point, and a sign bit set on a
+ * root that is 0.  Validation: NONE; CURVE = the curve equation (a decoded point always satisfies it); SUBGROUP = the curve
+ * equation and [q] P = O (Pallas: cofactor 1, the curve equation is enough). */
+enum { MSM_POINTS_UNCOMPRESSED = 0, MSM_POINTS_COMPRESSED = 1 };
+enum { MSM_VALIDATE_NONE = 0, MSM_VALIDATE_CURVE = 1, MSM_VALIDATE_SUBGROUP = 2 };
+/* msm_set_points with a format and a validation level.  UNCOMPRESSED + CURVE is msm_set_points(check_curve = 1), UNCOMPRESSED
+ * + NONE msm_set_points(check_curve = 0).  Compressed points are decoded on the GPU (one square root per point, written
+ * straight into the resident rows); SUBGROUP runs the subgroup check over the new rows.  A refused point fails the call with
+ * MSM_ERR_POINT and a message that names its index and the reason ("coordinate >= p", "invalid flags", "no curve point",
+ * "not on curve", "not in the prime-order subgroup"); *bad_index_out (may be NULL) gets that index -- the smallest bad one --
+ * or UINT64_MAX when every point passed.  A failed call leaves the current point set as a failed msm_set_points does: empty,
+ * its window tables dropped.  Host or device input, n < 2^30.  Device lists: every device decodes for itself, devices[0]
+ * alone runs the subgroup check. */
+int msm_set_points_ex(msm_ctx* ctx, const void* points, uint64_t n, int on_device, int format, int validate,
+                      uint64_t* bad_index_out);
+/* Checks the resident points [first, first + count) of the current set at `validate` and changes nothing: MSM_OK, or
+ * MSM_ERR_POINT with the first bad index in the message and in *bad_index_out (UINT64_MAX when every point passed). */
+int msm_validate_points(msm_ctx* ctx, uint64_t first, uint64_t count, int validate, uint64_t* bad_index_out);
+/* msm_get_points in either format: count x (2 coordinates) or count x (1 coordinate) bytes.  The compressed encoding is the
+ * inverse of the decoder of msm_set_points_ex. */
+int msm_get_points_ex(msm_ctx* ctx, uint64_t first, uint64_t count, int format, uint8_t* out);
 
 /* Window tables.  For a fixed point set (the bases of a prover: the reference's callers load their points once and run many
  * MSMs over them, scripts/msm-weierstrass.ts:19-35) the library can keep K tables instead of one: table k holds 2^(c k) P_i for

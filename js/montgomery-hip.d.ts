@@ -18,7 +18,9 @@ export interface Parallel {
   getPointer(size: number): PointPtr;
   getScalarPointer(size: number): ScalarPtr;
   /** src/parallel.ts:97-116 (Weierstrass: x || y, packed field size each) / :215-229 (twisted Edwards) */
-  pointsFromBytes(pointPtr: PointPtr, input: Uint8Array, n: number): Promise<void>;
+  /** options.compressed: the curve's compressed encoding; options.validate: "curve" | "subgroup" (default: none) */
+  pointsFromBytes(pointPtr: PointPtr, input: Uint8Array, n: number,
+                  options?: { compressed?: boolean; validate?: "none" | "curve" | "subgroup" }): Promise<void>;
   /** src/parallel.ts:119-133: n x 32 bytes little-endian */
   scalarsFromBytes(scalarPtr: ScalarPtr, input: Uint8Array, n: number): Promise<void>;
   /** src/curve-random.ts:14-92, generated on the GPU (explicit seed; the reference is unseeded) */

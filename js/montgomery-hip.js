@@ -58,7 +58,20 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
     // memory its kernels compute in (src/parallel.ts:119-133), so msm() crosses no PCIe.  free() gives the buffer back at
     // once; a pointer that is simply dropped gives it back when it is collected (the addon registers a finalizer).
     getScalarPointer(size) { return newScalarPtr(size); },
-    async pointsFromBytes(pointPtr, input, n) {
+    // options (optional): {compressed: the curve's compressed encoding (one coordinate and flag bits, INTEGRATION.md),
+    // validate: "curve" | "subgroup" | undefined (none, as the reference)}; a refused point throws with its index
+    async pointsFromBytes(pointPtr, input, n, options) {
+      if (options && (options.compressed || options.validate)) {
+        const levels = { none: hip.VALIDATE_NONE, curve: hip.VALIDATE_CURVE, subgroup: hip.VALIDATE_SUBGROUP };
+        const validate = options.validate ? levels[options.validate] : hip.VALIDATE_NONE;
+        if (validate === undefined) throw new RangeError(`pointsFromBytes: unknown validate level ${options.validate}`);
+        const step = options.compressed ? coordBytes : pointBytes;
+        hip.pointsetSelect(ctx, pointPtr.set);
+        pointPtr.n = 0;
+        pointPtr.n = hip.setPointsEx(ctx, Buffer.from(input.buffer, input.byteOffset, n * step),
+          options.compressed ? hip.POINTS_COMPRESSED : hip.POINTS_UNCOMPRESSED, validate);
+        return;
+      }
       let b = Buffer.from(input.buffer, input.byteOffset, n * 2 * wireBytes);
       if (wireBytes !== coordBytes) {
         const padded = Buffer.alloc(n * pointBytes);

@@ -17,9 +17,13 @@ CURVE_BLS12_377_G1 = 0
 CURVE_ED_ON_BLS12_377 = 1
 CURVE_BLS12_381_G1 = 2
 CURVE_PALLAS = 3
-ABI_VERSION = 7   # MSM_ABI_VERSION of the include/msm_hip.h this binding was written against
+ABI_VERSION = 8   # MSM_ABI_VERSION of the include/msm_hip.h this binding was written against
 N_PHASES = 8
 PHASE_NAMES = ("total", "upload", "digits", "sort", "accumulate", "reduce", "final", "accumulate_round1")
+
+POINTS_UNCOMPRESSED, POINTS_COMPRESSED = 0, 1
+VALIDATE_NONE, VALIDATE_CURVE, VALIDATE_SUBGROUP = 0, 1, 2
+NO_BAD_INDEX = (1 << 64) - 1   # *bad_index_out when every point passed
 
 OP_MUL, OP_SQR, OP_ADD, OP_SUB, OP_INV, OP_TO_MONT, OP_FROM_MONT, OP_INV_FERMAT, OP_INV_KALISKI, OP_INV_WORDSLICED = range(10)
 
@@ -34,6 +38,7 @@ EXPORTS = (
     "msm_run_placed", "msm_combine_groups", "msm_test_bucket_reduce", "msm_set_workspace_limit",
     "msm_precompute", "msm_tables_info", "msm_tables_range", "msm_set_tables_limit", "msm_reserve",
     "msm_abi_version", "msm_abi_struct_bytes", "msm_run_batch",
+    "msm_set_points_ex", "msm_validate_points", "msm_get_points_ex",
 )
 
 
@@ -61,9 +66,12 @@ class MsmResult(C.Structure):
 
 
 class MsmError(RuntimeError):
-    def __init__(self, code: int, message: str):
+    """code: MSM_ERR_*; bad_index: the index of the first refused point (msm_set_points_ex / msm_validate_points), else None."""
+
+    def __init__(self, code: int, message: str, bad_index=None):
         super().__init__(f"msm error {code}: {message}")
         self.code = code
+        self.bad_index = bad_index
 
 
 _lib = None
@@ -138,6 +146,9 @@ def load() -> C.CDLL:
     lib.msm_generate_points.argtypes = [vp, u64, u64, vp]
     lib.msm_generate_scalars.argtypes = [vp, u64, u64, vp, vp]
     lib.msm_get_points.argtypes = [vp, u64, u64, vp]
+    lib.msm_set_points_ex.argtypes = [vp, vp, u64, C.c_int, C.c_int, C.c_int, C.POINTER(u64)]
+    lib.msm_validate_points.argtypes = [vp, u64, u64, C.c_int, C.POINTER(u64)]
+    lib.msm_get_points_ex.argtypes = [vp, u64, u64, C.c_int, vp]
     lib.msm_test_fp.argtypes = [vp, C.c_int, vp, vp, vp, u64]
     lib.msm_test_glv.argtypes = [vp, vp, vp, u64]
     lib.msm_test_batch_add.argtypes = [vp, vp, vp, vp, u64]

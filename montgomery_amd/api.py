@@ -277,10 +277,62 @@ class MsmContext:
             return int(into), out
         return int(into), (bytes(out) if out is not None else None)
 
-    def get_points(self, first: int, count: int) -> bytes:
-        step = 2 * self.coord_bytes
+    _VALIDATE = {None: _lib.VALIDATE_NONE, "none": _lib.VALIDATE_NONE, "curve": _lib.VALIDATE_CURVE,
+                 "subgroup": _lib.VALIDATE_SUBGROUP}
+
+    def _check_points(self, rc: int, bad: C.c_uint64) -> None:
+        if rc != _lib.MSM_OK:
+            idx = bad.value if bad.value != _lib.NO_BAD_INDEX else None
+            raise MsmError(rc, self._lib.msm_last_error(self._h).decode(), bad_index=idx)
+
+    def load_points(self, data: Union[BytesLike, int], *, compressed: bool = False, validate: Optional[str] = "subgroup",
+                    on_device: bool = False, n: Optional[int] = None) -> int:
+        """Resident points from x || y (compressed=False) or from the compressed encoding of the curve (include/msm_hip.h,
+        INTEGRATION.md), validated at `validate`: "subgroup" (default: the curve equation and [q] P = O), "curve" or
+        None / "none" (msm_set_points_ex).  on_device: `data` is a device pointer and `n` the number of points.
+        A refused point raises MsmError(MSM_ERR_POINT) with its index in .bad_index; the point set is then empty."""
+        if validate not in self._VALIDATE:
+            raise MsmError(_lib.MSM_ERR_ARG, f"validate must be one of {sorted(k for k in self._VALIDATE if k)} or None")
+        step = self.coord_bytes if compressed else 2 * self.coord_bytes
+        if on_device:
+            if n is None:
+                raise MsmError(_lib.MSM_ERR_ARG, "load_points(on_device=True) needs n")
+            ptr = C.c_void_p(int(data))
+        else:
+            if len(data) % step:
+                raise MsmError(_lib.MSM_ERR_ARG, f"point buffer length {len(data)} is not a multiple of {step}")
+            n = len(data) // step if n is None else n
+            if n * step > len(data):
+                raise MsmError(_lib.MSM_ERR_ARG, f"{n} points need {n * step} bytes, got {len(data)}")
+            ptr = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
+        bad = C.c_uint64()
+        self.n_points = 0
+        self._set_sizes[self._cur_set] = 0
+        rc = self._lib.msm_set_points_ex(self._h, ptr, n, int(on_device),
+                                         _lib.POINTS_COMPRESSED if compressed else _lib.POINTS_UNCOMPRESSED,
+                                         self._VALIDATE[validate], C.byref(bad))
+        self._check_points(rc, bad)
+        self.n_points = n
+        self._set_sizes[self._cur_set] = n
+        return n
+
+    def validate_points(self, first: int = 0, count: Optional[int] = None, level: Optional[str] = "subgroup") -> None:
+        """Checks the resident points [first, first + count) (default: to the end) and changes nothing; raises MsmError with
+        .bad_index at the first refused point (msm_validate_points)."""
+        if level not in self._VALIDATE:
+            raise MsmError(_lib.MSM_ERR_ARG, f"level must be one of {sorted(k for k in self._VALIDATE if k)} or None")
+        count = self.n_points - first if count is None else count
+        bad = C.c_uint64()
+        self._check_points(self._lib.msm_validate_points(self._h, first, count, self._VALIDATE[level], C.byref(bad)), bad)
+
+    def get_points(self, first: int, count: int, compressed: bool = False) -> bytes:
+        """Resident points [first, first + count) as x || y, or compressed (the encoding load_points(compressed=True) reads)."""
+        step = self.coord_bytes if compressed else 2 * self.coord_bytes
         out = (C.c_uint8 * max(step * count, 1))()
-        self._check(self._lib.msm_get_points(self._h, first, count, out))
+        if compressed:
+            self._check(self._lib.msm_get_points_ex(self._h, first, count, _lib.POINTS_COMPRESSED, out))
+        else:
+            self._check(self._lib.msm_get_points(self._h, first, count, out))
         return bytes(out)[: step * count]
 
     def get_point(self, i: int) -> Optional[Tuple[int, int]]:
@@ -594,8 +646,18 @@ class _Parallel:
     def getScalarPointer(self, size: int) -> ScalarPtr:
         return ScalarPtr(self._ctx, size=size)
 
-    def pointsFromBytes(self, pointPtr: PointPtr, pointInput: BytesLike, n: int) -> None:
-        """src/parallel.ts:97-116 (96 B/point) / :215-229 (64 B/point): x || y little-endian -> resident device points."""
+    def pointsFromBytes(self, pointPtr: PointPtr, pointInput: BytesLike, n: int, compressed: bool = False,
+                        validate: Optional[str] = None) -> None:
+        """src/parallel.ts:97-116 (96 B/point) / :215-229 (64 B/point): x || y little-endian -> resident device points.
+        compressed: the compressed encoding of the curve instead (MsmContext.load_points); validate: None (default, as the
+        reference), "curve" or "subgroup"."""
+        if compressed or validate is not None:
+            self._ctx.pointset_select(pointPtr.set_id)
+            pointPtr.n = 0
+            step = self._ctx.coord_bytes * (1 if compressed else 2)
+            self._ctx.load_points(bytes(pointInput)[: step * n], compressed=compressed, validate=validate)
+            pointPtr.n = n
+            return
         wb, cb = self._wire_bytes, self._ctx.coord_bytes
         buf = bytes(pointInput)[: 2 * wb * n]
         if wb != cb:   # zero-pad every coordinate to the ABI width

@@ -71,7 +71,29 @@ def field_block(struct, p, nl, nw, extra=None, nla=None):
     for k, v in (extra or {}).items():
         s += arr(k, limbs(v * R % p, nw, 32))
         s += arr(k[:-1] + "L", limbs(v * R % p, nl))
+    s += sqrt_consts(p, nl, nw)
     s += "};\n\n"
+    return s
+
+
+def sqrt_consts(p, nl, nw):
+    """Square roots (fe_sqrt, points_ingest.h) and the sign rule of compressed points.  p - 1 = 2^S t with t odd.
+    S = 1 (p = 3 mod 4): sqrt(a) = a^((p + 1) / 4), SQRT_EW = (p + 1) / 4.  S > 1: Tonelli-Shanks from w = a^((t - 1) / 2)
+    (SQRT_EW) and z = g^t (SQRT_ZL, Montgomery form), a primitive 2^S-th root of unity, g the least quadratic non-residue."""
+    R = 1 << (LB * nl)
+    S, t = 0, p - 1
+    while t % 2 == 0:
+        S, t = S + 1, t // 2
+    g = 2
+    while pow(g, (p - 1) // 2, p) != p - 1:
+        g += 1
+    e = (p + 1) // 4 if S == 1 else (t - 1) // 2
+    z = pow(g, t, p) if S > 1 else 1
+    s = f"  static constexpr int TWO_ADICITY = {S};   // p - 1 = 2^S t, t odd\n"
+    s += f"  static constexpr int SQRT_EBITS = {e.bit_length()};\n"
+    s += arr("SQRT_EW", limbs(e, nw, 32))          # exponent of the first step of fe_sqrt (plain integer)
+    s += arr("SQRT_ZL", limbs(z * R % p, nl))      # g^t, Montgomery form (S > 1)
+    s += arr("HALFW", limbs((p - 1) // 2, nw, 32))   # (p - 1) / 2, plain: the "larger root" of the compressed encodings
     return s
 
 

@@ -20,6 +20,9 @@
 //          inverse / toMontgomery / fromMontgomery on n = a.length / coordBytes elements), batchInverse(h, xs, perLane) -> Buffer,
 //          glvDecompose(h, scalars) -> Buffer of n x 40 bytes (|s0|, |s1|: 16 bytes each, neg0, neg1: 4 bytes each),
 //          batchAdd(h, G, H) -> Buffer of n affine sums (wire points, (0, 0) = identity)
+//          setPointsEx(h, Buffer, format, validate) -> n, getPointsEx(h, first, count, format) -> Buffer: compressed points and
+//          subgroup validation (msm_set_points_ex / msm_get_points_ex; constants POINTS_* and VALIDATE_*); a refused point
+//          throws an Error with its index in the message and in `badIndex`
 // The addon is built against include/msm_hip.h and checks at load that the library it found was too (msm_abi_version).
 #include <node_api.h>
 #include <stdio.h>
@@ -191,6 +194,70 @@ static napi_value SetPoints(napi_env env, napi_callback_info info) {  // pointsF
   napi_value n;
   NAPI_OK(napi_create_uint32(env, (uint32_t)(len / point_bytes), &n));
   return n;
+}
+
+// setPointsEx(h, Buffer, format, validate) -> n: msm_set_points_ex over host bytes (format MSM_POINTS_*, validate
+// MSM_VALIDATE_*).  A refused point throws an Error whose message names its index and whose `badIndex` property holds it.
+static napi_value SetPointsEx(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  void* data;
+  size_t len;
+  NAPI_OK(napi_get_buffer_info(env, argv[1], &data, &len));
+  int32_t format = MSM_POINTS_UNCOMPRESSED, validate = MSM_VALIDATE_NONE;
+  if (argc > 2) napi_get_value_int32(env, argv[2], &format);
+  if (argc > 3) napi_get_value_int32(env, argv[3], &validate);
+  const size_t step = format == MSM_POINTS_COMPRESSED ? h->coord_bytes : h->point_bytes;
+  if (len % step) {
+    napi_throw_range_error(env, NULL, "point buffer: expected a multiple of the curve's point size in this format");
+    return NULL;
+  }
+  uint64_t bad = UINT64_MAX;
+  int rc = msm_set_points_ex(h->ctx, data, len / step, 0, format, validate, &bad);
+  if (rc != MSM_OK) {
+    char buf[640];
+    snprintf(buf, sizeof buf, "setPointsEx: msm error %d: %s", rc, msm_last_error(h->ctx));
+    napi_value msg, err, idx;
+    NAPI_OK(napi_create_string_utf8(env, buf, NAPI_AUTO_LENGTH, &msg));
+    NAPI_OK(napi_create_error(env, NULL, msg, &err));
+    if (bad != UINT64_MAX) {
+      NAPI_OK(napi_create_double(env, (double)bad, &idx));
+      NAPI_OK(napi_set_named_property(env, err, "badIndex", idx));
+    }
+    napi_throw(env, err);
+    return NULL;
+  }
+  napi_value n;
+  NAPI_OK(napi_create_uint32(env, (uint32_t)(len / step), &n));
+  return n;
+}
+
+// getPointsEx(h, first, count, format) -> Buffer: resident points read back as x || y or compressed (msm_get_points_ex)
+static napi_value GetPointsEx(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int64_t first = 0, count = 0;
+  int32_t format = MSM_POINTS_UNCOMPRESSED;
+  if (argc > 1) napi_get_value_int64(env, argv[1], &first);
+  if (argc > 2) napi_get_value_int64(env, argv[2], &count);
+  if (argc > 3) napi_get_value_int32(env, argv[3], &format);
+  if (first < 0 || count < 0) {
+    napi_throw_range_error(env, NULL, "getPointsEx: negative range");
+    return NULL;
+  }
+  const size_t step = format == MSM_POINTS_COMPRESSED ? h->coord_bytes : h->point_bytes;
+  void* out;
+  napi_value buf;
+  NAPI_OK(napi_create_buffer(env, (size_t)count * step + (count ? 0 : 1), &out, &buf));
+  int rc = msm_get_points_ex(h->ctx, (uint64_t)first, (uint64_t)count, format, (uint8_t*)out);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "getPointsEx");
+  return buf;
 }
 
 static napi_value result_object(napi_env env, const js_ctx* h, const msm_result* res) {
@@ -669,6 +736,7 @@ NAPI_MODULE_INIT() {
   }
   struct { const char* name; napi_callback fn; } fns[] = {
       {"createContext", CreateContext}, {"destroyContext", DestroyContext}, {"setPoints", SetPoints}, {"msm", Msm}, {"plan", Plan},
+      {"setPointsEx", SetPointsEx}, {"getPointsEx", GetPointsEx},
       {"generatePoints", GeneratePoints}, {"generateScalars", GenerateScalars},
       {"deviceAlloc", DeviceAlloc}, {"deviceUpload", DeviceUpload}, {"deviceFree", DeviceFree}, {"msmDevice", MsmDevice},
       {"msmBatch", MsmBatch}, {"msmBatchDevice", MsmBatchDevice},
@@ -682,7 +750,9 @@ NAPI_MODULE_INIT() {
   napi_value v;
   struct { const char* name; int32_t val; } ops[] = {{"OP_MUL", MSM_OP_MUL}, {"OP_SQR", MSM_OP_SQR}, {"OP_ADD", MSM_OP_ADD}, {"OP_SUB", MSM_OP_SUB},
       {"OP_INV", MSM_OP_INV}, {"OP_TO_MONT", MSM_OP_TO_MONT}, {"OP_FROM_MONT", MSM_OP_FROM_MONT}, {"OP_INV_FERMAT", MSM_OP_INV_FERMAT},
-      {"OP_INV_KALISKI", MSM_OP_INV_KALISKI}, {"OP_INV_WORDSLICED", MSM_OP_INV_WORDSLICED}};
+      {"OP_INV_KALISKI", MSM_OP_INV_KALISKI}, {"OP_INV_WORDSLICED", MSM_OP_INV_WORDSLICED},
+      {"POINTS_UNCOMPRESSED", MSM_POINTS_UNCOMPRESSED}, {"POINTS_COMPRESSED", MSM_POINTS_COMPRESSED},
+      {"VALIDATE_NONE", MSM_VALIDATE_NONE}, {"VALIDATE_CURVE", MSM_VALIDATE_CURVE}, {"VALIDATE_SUBGROUP", MSM_VALIDATE_SUBGROUP}};
   for (size_t i = 0; i < sizeof ops / sizeof ops[0]; i++) {
     napi_create_int32(env, ops[i].val, &v);
     napi_set_named_property(env, exports, ops[i].name, v);
