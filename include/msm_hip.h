@@ -34,7 +34,8 @@ enum {
                               undecodable compressed point */
   MSM_ERR_NO_POINTS = 4,   /* msm called before msm_set_points, or with n > resident points */
   MSM_ERR_NO_DEVICE = 5,   /* no usable GPU: there is no CPU fallback */
-  MSM_ERR_SCALAR = 6,      /* a scalar >= the group order q and msm_opts.strict was set (default: reduced mod q) */
+  MSM_ERR_SCALAR = 6,      /* a scalar >= the group order q and msm_opts.strict was set (default: reduced mod q); a scalar outside
+                              the range a narrow call declared (msm_run_narrow) */
   MSM_ERR_INTERNAL = 7     /* host allocation failure or another unexpected condition; no C++ exception crosses this ABI */
 };
 
@@ -55,7 +56,10 @@ enum {
  * buffer; msm_opts.point_lo / by_window); 4 = msm_result.n_pairs_algo; 5 = window tables (msm_opts.no_tables, msm_result.tables,
  * msm_precompute / msm_tables_info / msm_set_tables_limit), msm_reserve, msm_opts.bucket_shard / bucket_shards; 6 = window tables
  * over a range of the points (msm_opts.merged_sums, msm_precompute with point_lo, msm_tables_range); 7 = msm_run_batch;
- * 8 = compressed points and subgroup validation (msm_set_points_ex, msm_validate_points, msm_get_points_ex). */
+ * 8 = compressed points and subgroup validation (msm_set_points_ex, msm_validate_points, msm_get_points_ex).
+ * Narrow scalars (msm_run_narrow, msm_run_batch_narrow, msm_plan_narrow, msm_scalar_bits) came WITHOUT a new version: they are
+ * new symbols only, msm_opts / msm_result keep their size and fields, so a binding of version 8 reads the same memory as
+ * before.  A binding detects the feature by the presence of the symbol msm_run_narrow. */
 #define MSM_ABI_VERSION 8
 uint32_t msm_abi_version(void);
 uint32_t msm_abi_struct_bytes(int which);
@@ -249,6 +253,37 @@ int msm_run(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, const 
  * B == 0, a null `out` and a null scalars[b] when n > 0.  n == 0 returns B identities. */
 int msm_run_batch(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device, const msm_opts* opts,
                   msm_result* out /* B entries */);
+
+/* Narrow scalars: the MSM of a column whose values are known to be small -- machine words, bits, small signed values -- without
+ * the endomorphism split, which would spread a 64-bit scalar over two halves of ~126 bits: one entry per point and
+ * K = ceil((bits + 1) / c) windows (msm_plan_narrow), e.g. 4 windows of 17 bits for 64-bit scalars instead of 6 x 21 bits over
+ * 2 n entries.  The reference has no counterpart.
+ * width_bytes: 1, 2, 4, 8, 16 (little-endian integers, n x width_bytes, naturally aligned) or 32 (field elements, as msm_run).
+ *   DEVICE scalars must be aligned to min(width_bytes, 16) bytes -- the 16- and 32-byte forms are loaded 16 bytes at a time,
+ *   also by msm_scalar_bits -- or the call fails with MSM_ERR_ARG; host buffers may sit anywhere.
+ * bits: magnitude bits, 1 .. 128; 0 = all the width gives (8 w unsigned, 8 w - 1 signed; not allowed with width 32).
+ * is_signed = 0: values in [0, 2^bits).  is_signed = 1: values in [-2^bits, 2^bits), so that a two's-complement word of
+ *   8 w bits is covered by bits = 8 w - 1; widths 1 .. 16 are two's complement, width 32 holds v >= 0 as v and v < 0 as q - |v|.
+ * A value outside the declared range ALWAYS fails the call with MSM_ERR_SCALAR (never a silently wrong sum).
+ * out->x / y / is_infinity are bit-identical to msm_run over the same values written as 32-byte scalars (negatives as q - |v|);
+ * out->c / K report the plan that ran, phase_ms, n_pairs, n_pairs_algo and max_bucket are those of msm_run.
+ * Options: c (2 .. 24, at most 64 windows), point_lo and serial are honoured; no_glv is implied, unsafe ignored, strict has nothing
+ * to add; k_lo / k_hi, bucket_shards > 1, merged_sums and by_window fail with MSM_ERR_ARG, as do a device-list context, a bad
+ * width, bits beyond the width or beyond 128, B == 0 and null pointers.  n == 0 returns the identity.
+ * A narrow call takes the plain path over table 0: it neither builds, uses nor drops the window tables of the point set.  Host
+ * scalars are uploaded whole before the run.  msm_run_batch_narrow is msm_run_batch over narrow elements: fused where
+ * msm_run_batch fuses (up to 64 elements per group; without opts->c it then picks a window of the one-level sort, at most 13
+ * bits, where a single call would take 17), element by element through msm_run_narrow elsewhere -- bigger inputs, an explicit
+ * c > 16, 1- or 2-byte device elements that do not start on a 4-byte boundary. */
+int msm_run_narrow(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, int32_t width_bytes, int32_t bits, int32_t is_signed,
+                   const msm_opts* opts, msm_result* out);
+int msm_run_batch_narrow(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device, int32_t width_bytes,
+                         int32_t bits, int32_t is_signed, const msm_opts* opts, msm_result* out /* B entries */);
+/* the plan of msm_run_narrow over n points and scalars of `bits` magnitude bits (opts->c forces the window) */
+int msm_plan_narrow(const msm_ctx* ctx, uint64_t n, int32_t bits, const msm_opts* opts, int32_t* c_out, int32_t* K_out);
+/* smallest `bits` under which msm_run_narrow(width 32) accepts these 32-byte scalars, unsigned and signed
+ * (0 for all-zero input; 255 when a scalar needs more than 128 bits or is >= q). */
+int msm_scalar_bits(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, int32_t* unsigned_bits_out, int32_t* signed_bits_out);
 
 /* Window-sharded form for multi-GPU runs: computes the partition sums P_k for k in [k_lo, k_hi)
  * only (src/msm-batched-affine.ts:42 "P_k = sum_l l * B_(k,l)") and writes them as

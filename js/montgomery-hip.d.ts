@@ -11,6 +11,10 @@ export type ScalarPtr = { size: number; n: number; dev: unknown | null; free(): 
 /** canonical affine result: what `Affine.toBigint(Projective.toAffine(result))` yields in the reference */
 export type AffineResult = { x: bigint; y: bigint; isZero: boolean };
 export type MsmOptions = { c?: number; useSafeAdditions?: boolean; noGlv?: boolean };
+export type NarrowScalars = Uint8Array | Uint16Array | Uint32Array | BigUint64Array | Int8Array | Int16Array | Int32Array | BigInt64Array;
+/** bits: magnitude bits, values in [0, 2^bits) or, signed, [-2^bits, 2^bits) (default: all the width gives); width / signed:
+ * for raw bytes (a Buffer): 1, 2, 4, 8, 16 bytes per scalar, or 32 for field elements holding small values (then bits is required) */
+export type NarrowOptions = { c?: number; bits?: number; width?: 1 | 2 | 4 | 8 | 16 | 32; signed?: boolean };
 /** log: the reference's shape (src/msm-common.ts:176-214) -- [{n, K, c}], then ["label... x.xms"] per phase, "msm total" last */
 export type MsmOutput = { result: AffineResult; log: unknown[][] };
 
@@ -31,6 +35,13 @@ export interface Parallel {
   msm(scalarPtr: ScalarPtr, pointPtr: PointPtr, N: number, verboseTiming?: boolean, options?: MsmOptions): Promise<MsmOutput>;
   /** many MSMs over one point set in one call (msm_run_batch): [b].result equals (await msm(scalarPtrs[b], pointPtr, N)).result */
   msmBatch(scalarPtrs: ScalarPtr[], pointPtr: PointPtr, N: number, verboseTiming?: boolean, options?: MsmOptions): Promise<MsmOutput[]>;
+  /** narrow scalars (msm_run_narrow; no counterpart in the reference): width and signedness from the typed array, or a Buffer
+   * with options.width; result equals msm over the same values as 32-byte scalars; a value outside the declared range throws */
+  msmNarrow(scalars: NarrowScalars, pointPtr: PointPtr, N: number, options?: NarrowOptions): Promise<MsmOutput>;
+  /** many narrow MSMs over one point set (msm_run_batch_narrow): one array per element, all of one type */
+  msmBatchNarrow(scalarArrays: NarrowScalars[], pointPtr: PointPtr, N: number, options?: NarrowOptions): Promise<MsmOutput[]>;
+  /** smallest `bits` msmNarrow(width 32) accepts these n x 32-byte scalars under (0: all zero; 255: more than 128 bits needed) */
+  scalarBits(scalars32: Uint8Array): { unsigned: number; signed: number };
   /** src/msm-batched-affine.ts:587-598: msm with useSafeAdditions = false (msm_opts.unsafe) */
   msmUnsafe(scalarPtr: ScalarPtr, pointPtr: PointPtr, N: number, verboseTiming?: boolean, options?: MsmOptions): Promise<MsmOutput>;
   /** src/parallel.ts:69-87: window structure of msmBasic, no endomorphism split */

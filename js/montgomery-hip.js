@@ -125,6 +125,33 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
         log: verboseTiming ? buildLog(N, r) : [],
       }));
     },
+    // Narrow scalars (msm_run_narrow; the reference has no counterpart): `scalars` is a Uint8Array .. BigUint64Array (unsigned) or
+    // Int8Array .. BigInt64Array (signed) -- width and signedness from the array type -- or a Buffer with options {width, signed};
+    // options.bits: magnitude bits (default: all the width gives), options.c: window.  result equals msm over the same values
+    // written as 32-byte scalars (negatives as q - |v|); a value outside the declared range throws (msm error 6).
+    async msmNarrow(scalars, pointPtr, N, options) {
+      const f = narrowFormat(scalars, N, options);
+      if (N > pointPtr.n) throw new Error(`msmNarrow: ${N} scalars but ${pointPtr.n} points behind this pointer`);
+      hip.pointsetSelect(ctx, pointPtr.set);
+      const r = hip.msmNarrow(ctx, f.buf, f.width, f.bits, f.signed, (options && options.c) || 0);
+      return { result: { x: leBytesToBigint(r.x), y: leBytesToBigint(r.y), isZero: r.isZero }, log: buildLog(N, r) };
+    },
+    // many narrow MSMs over one point set (msm_run_batch_narrow): one array per element, all of one type and length
+    async msmBatchNarrow(scalarArrays, pointPtr, N, options) {
+      if (!scalarArrays.length) throw new RangeError("msmBatchNarrow: empty batch");
+      const fs = scalarArrays.map((s) => narrowFormat(s, N, options));
+      for (const f of fs)
+        if (f.width !== fs[0].width || f.signed !== fs[0].signed) throw new TypeError("msmBatchNarrow: the elements must share one format");
+      if (N > pointPtr.n) throw new Error(`msmBatchNarrow: ${N} scalars but ${pointPtr.n} points behind this pointer`);
+      hip.pointsetSelect(ctx, pointPtr.set);
+      const rs = hip.msmBatchNarrow(ctx, fs.map((f) => f.buf), fs[0].width, fs[0].bits, fs[0].signed, (options && options.c) || 0);
+      return rs.map((r) => ({ result: { x: leBytesToBigint(r.x), y: leBytesToBigint(r.y), isZero: r.isZero }, log: buildLog(N, r) }));
+    },
+    // {unsigned, signed}: the smallest `bits` msmNarrow accepts these n x 32-byte scalars under as a Buffer with width 32
+    // (0: all zero; 255: a scalar needs more than 128 bits)
+    scalarBits(scalars32) {
+      return hip.scalarBits(ctx, Buffer.from(scalars32.buffer, scalars32.byteOffset, scalars32.byteLength));
+    },
     msmProjective(scalarPtr, pointPtr, N, options) {
       // src/parallel.ts:69-87: signed windows of the whole scalar, no endomorphism split (same group element)
       return Parallel.msm(scalarPtr, pointPtr, N, false, Object.assign({}, options, { noGlv: true }));
@@ -133,6 +160,19 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       return Parallel.msm(scalarPtr, pointPtr, N, verboseTiming, Object.assign({}, options, { useSafeAdditions: false }));
     },
   };
+  // typed array -> {buf, width, signed, bits} of the first N scalars; a Buffer / Uint8Array with options.width is raw bytes
+  function narrowFormat(scalars, N, options) {
+    const types = [[Int8Array, 1, 1], [Int16Array, 2, 1], [Int32Array, 4, 1], [Uint16Array, 2, 0], [Uint32Array, 4, 0]];
+    if (typeof BigInt64Array !== "undefined") types.push([BigInt64Array, 8, 1], [BigUint64Array, 8, 0]);
+    let width = 0, signed = 0;
+    if (options && options.width) { width = options.width; signed = options.signed ? 1 : 0; }
+    else if (scalars instanceof Uint8Array) { width = 1; signed = 0; }   // (a Buffer is one too)
+    else for (const [T, w, s] of types) if (scalars instanceof T) { width = w; signed = s; }
+    if (![1, 2, 4, 8, 16, 32].includes(width) || !ArrayBuffer.isView(scalars))
+      throw new TypeError("msmNarrow: expected an integer typed array, or a Buffer with options.width in {1, 2, 4, 8, 16, 32}");
+    if (N * width > scalars.byteLength) throw new RangeError(`msmNarrow: ${N} scalars of ${width} bytes requested but the array holds ${scalars.byteLength} bytes`);
+    return { buf: Buffer.from(scalars.buffer, scalars.byteOffset, N * width), width, signed, bits: (options && options.bits) || 0 };
+  }
   function newScalarPtr(size) {
     return { size, n: 0, dev: null, free() { if (this.dev) { const d = this.dev; this.dev = null; this.n = 0; hip.deviceFree(ctx, d); } } };
   }

@@ -39,6 +39,7 @@ EXPORTS = (
     "msm_precompute", "msm_tables_info", "msm_tables_range", "msm_set_tables_limit", "msm_reserve",
     "msm_abi_version", "msm_abi_struct_bytes", "msm_run_batch",
     "msm_set_points_ex", "msm_validate_points", "msm_get_points_ex",
+    "msm_run_narrow", "msm_run_batch_narrow", "msm_plan_narrow", "msm_scalar_bits",
 )
 
 
@@ -141,6 +142,14 @@ def load() -> C.CDLL:
     lib.msm_combine_curve.restype = i32
     lib.msm_combine_groups.argtypes = [i32, vp, i32, i32, i32, C.POINTER(MsmResult)]
     lib.msm_run_batch.argtypes = [vp, C.POINTER(vp), C.c_uint32, u64, C.c_int, C.POINTER(MsmOpts), C.POINTER(MsmResult)]
+    # narrow scalars: new symbols under ABI 8 (a library without msm_run_narrow predates them)
+    if not hasattr(lib, "msm_run_narrow"):
+        raise ImportError(f"{LIB_PATH} predates msm_run_narrow: rebuild it (`make`)")
+    lib.msm_run_narrow.argtypes = [vp, vp, u64, C.c_int, i32, i32, i32, C.POINTER(MsmOpts), C.POINTER(MsmResult)]
+    lib.msm_run_batch_narrow.argtypes = [vp, C.POINTER(vp), C.c_uint32, u64, C.c_int, i32, i32, i32, C.POINTER(MsmOpts),
+                                         C.POINTER(MsmResult)]
+    lib.msm_plan_narrow.argtypes = [vp, u64, i32, C.POINTER(MsmOpts), C.POINTER(i32), C.POINTER(i32)]
+    lib.msm_scalar_bits.argtypes = [vp, vp, u64, C.c_int, C.POINTER(i32), C.POINTER(i32)]
     lib.msm_run_placed.argtypes = [vp, C.POINTER(vp), u64, C.POINTER(MsmOpts), C.POINTER(MsmResult)]
     lib.msm_plan.argtypes = [vp, u64, C.POINTER(MsmOpts), C.POINTER(i32), C.POINTER(i32)]
     lib.msm_generate_points.argtypes = [vp, u64, u64, vp]

@@ -427,6 +427,106 @@ class MsmContext:
         return [(AffineResult(int.from_bytes(bytes(r.x)[:nb], "little"), int.from_bytes(bytes(r.y)[:nb], "little"),
                               bool(r.is_infinity)), _result_to_dict(r)) for r in res[:B]]
 
+    # -- narrow scalars (msm_run_narrow, include/msm_hip.h) -----------------------------------
+    def _narrow_buffer(self, scalars, width: Optional[int], signed: Optional[bool]):
+        """(ctypes buffer, n, width, signed) of a numpy array (format from its dtype) or of bytes with width=."""
+        from . import narrow as N
+
+        if hasattr(scalars, "dtype"):
+            import numpy as np
+
+            w, s = N.dtype_format(scalars.dtype)
+            if width not in (None, w) or signed not in (None, s):
+                raise MsmError(_lib.MSM_ERR_ARG, f"width / signed contradict the array's dtype {scalars.dtype}")
+            raw = np.ascontiguousarray(scalars).tobytes()
+            width, signed = w, s
+        else:
+            if width is None:
+                raise MsmError(_lib.MSM_ERR_ARG, "narrow scalars given as bytes need width=")
+            raw = bytes(scalars)
+            signed = bool(signed)
+        if width <= 0 or len(raw) % width:
+            raise MsmError(_lib.MSM_ERR_ARG, f"scalar buffer length {len(raw)} is not a multiple of the width {width}")
+        return (C.c_uint8 * max(len(raw), 1)).from_buffer_copy(raw or b"\0"), len(raw) // width, width, bool(signed)
+
+    def run_narrow(self, scalars, bits: Optional[int] = None, signed: Optional[bool] = None, c: Optional[int] = None,
+                   point_lo: int = 0, serial: bool = False, width: Optional[int] = None) -> Tuple[AffineResult, Dict]:
+        """MSM over narrow scalars (msm_run_narrow): a numpy array of dtype uint8/16/32/64 or int8/16/32/64 (width and
+        signedness from the dtype), or bytes with width= (1, 2, 4, 8, 16, or 32 for field elements holding small values).
+        bits: magnitude bits, default all the width gives; values in [0, 2^bits), signed [-2^bits, 2^bits).  Equal to run()
+        over the same values widened to 32 bytes (montgomery_amd.narrow.widen); a value outside the range raises
+        MsmError(MSM_ERR_SCALAR)."""
+        buf, n, width, signed = self._narrow_buffer(scalars, width, signed)
+        return self._run_narrow(buf, n, 0, width, bits, signed, c, point_lo, serial)
+
+    def run_narrow_device(self, dev_ptr: int, n: int, width: int, bits: Optional[int] = None, signed: bool = False,
+                          c: Optional[int] = None, point_lo: int = 0, serial: bool = False) -> Tuple[AffineResult, Dict]:
+        """run_narrow over a device buffer of n x width bytes."""
+        return self._run_narrow(C.c_void_p(dev_ptr), n, 1, width, bits, signed, c, point_lo, serial)
+
+    def _run_narrow(self, ptr, n, on_device, width, bits, signed, c, point_lo, serial) -> Tuple[AffineResult, Dict]:
+        opts, res = MsmOpts(c=c or 0, serial=int(serial), point_lo=point_lo), MsmResult()
+        self._check(self._lib.msm_run_narrow(self._h, ptr, n, on_device, width, bits or 0, int(bool(signed)), C.byref(opts),
+                                             C.byref(res)))
+        nb = self.coord_bytes
+        return (AffineResult(int.from_bytes(bytes(res.x)[:nb], "little"), int.from_bytes(bytes(res.y)[:nb], "little"),
+                             bool(res.is_infinity)), _result_to_dict(res))
+
+    def run_batch_narrow(self, scalars: Sequence, bits: Optional[int] = None, signed: Optional[bool] = None,
+                         c: Optional[int] = None, point_lo: int = 0, serial: bool = False,
+                         width: Optional[int] = None) -> List[Tuple[AffineResult, Dict]]:
+        """B narrow MSMs over the same resident points (msm_run_batch_narrow): one array (or bytes with width=) per element,
+        all of one format and length.  Element b equals run_narrow(scalars[b])."""
+        if not len(scalars):
+            raise MsmError(_lib.MSM_ERR_ARG, "run_batch_narrow: empty batch")
+        bufs = [self._narrow_buffer(s, width, signed) for s in scalars]
+        if any(b[1:] != bufs[0][1:] for b in bufs):
+            raise MsmError(_lib.MSM_ERR_ARG, "run_batch_narrow: the elements must share one format and length")
+        _, n, w, sg = bufs[0]
+        ptrs = [C.cast(b[0], C.c_void_p).value for b in bufs]
+        return self._run_batch_narrow(ptrs, n, 0, w, bits, sg, c, point_lo, serial)
+
+    def run_batch_narrow_device(self, dev_ptrs: Sequence[int], n: int, width: int, bits: Optional[int] = None,
+                                signed: bool = False, c: Optional[int] = None, point_lo: int = 0,
+                                serial: bool = False) -> List[Tuple[AffineResult, Dict]]:
+        """run_batch_narrow over device buffers of n x width bytes each."""
+        return self._run_batch_narrow([int(p) for p in dev_ptrs], n, 1, width, bits, signed, c, point_lo, serial)
+
+    def _run_batch_narrow(self, ptrs, n, on_device, width, bits, signed, c, point_lo, serial):
+        B = len(ptrs)
+        arr = (C.c_void_p * max(B, 1))(*[C.c_void_p(p) for p in ptrs])
+        opts = MsmOpts(c=c or 0, serial=int(serial), point_lo=point_lo)
+        res = (MsmResult * max(B, 1))()
+        self._check(self._lib.msm_run_batch_narrow(self._h, arr, B, n, on_device, width, bits or 0, int(bool(signed)),
+                                                   C.byref(opts), res))
+        nb = self.coord_bytes
+        return [(AffineResult(int.from_bytes(bytes(r.x)[:nb], "little"), int.from_bytes(bytes(r.y)[:nb], "little"),
+                              bool(r.is_infinity)), _result_to_dict(r)) for r in res[:B]]
+
+    def plan_narrow(self, n: int, bits: int, c: Optional[int] = None) -> Tuple[int, int]:
+        """(c, K) of run_narrow over n points and scalars of `bits` magnitude bits (msm_plan_narrow)."""
+        opts = MsmOpts(c=c or 0)
+        cc, kk = C.c_int32(), C.c_int32()
+        self._check(self._lib.msm_plan_narrow(self._h, n, bits, C.byref(opts), C.byref(cc), C.byref(kk)))
+        return cc.value, kk.value
+
+    def scalar_bits(self, scalars: Union[BytesLike, int], n: Optional[int] = None) -> Tuple[int, int]:
+        """(unsigned, signed) magnitude bits of n x 32-byte scalars -- host bytes, or a device pointer with n=: the smallest
+        `bits` run_narrow(width=32) accepts them under (0: all zero; 255: a scalar needs more than 128 bits)."""
+        if isinstance(scalars, int):
+            if n is None:
+                raise MsmError(_lib.MSM_ERR_ARG, "scalar_bits over a device pointer needs n")
+            ptr, on_device = C.c_void_p(scalars), 1
+        else:
+            if len(scalars) % 32:
+                raise MsmError(_lib.MSM_ERR_ARG, f"scalar buffer length {len(scalars)} is not a multiple of 32")
+            n = len(scalars) // 32 if n is None else n
+            ptr = scalars if isinstance(scalars, C.Array) else (C.c_uint8 * max(len(scalars), 1)).from_buffer_copy(bytes(scalars) or b"\0")
+            on_device = 0
+        ub, sb = C.c_int32(), C.c_int32()
+        self._check(self._lib.msm_scalar_bits(self._h, ptr, n, on_device, C.byref(ub), C.byref(sb)))
+        return ub.value, sb.value
+
     # -- window tables (msm_precompute, include/msm_hip.h) ------------------------------------
     def precompute(self, n: Optional[int] = None, c: Optional[int] = None, no_glv: bool = False, point_lo: int = 0) -> Tuple[int, int, int]:
         """Builds the window tables of the current point set -- of its points [point_lo, point_lo + n): the share of one rank of a
@@ -749,6 +849,27 @@ class _Parallel:
                     log.append([f"{label}... {t[key]:.1f}ms"])
             dicts.append({"result": res, "log": log, "info": info})
         return dicts
+
+    def msmNarrow(self, scalars, pointPtr: PointPtr, N: int, options: Optional[Dict] = None) -> Dict:
+        """MSM over narrow scalars (msm_run_narrow; the reference has no counterpart): `scalars` is a numpy array of dtype
+        uint8/16/32/64 or int8/16/32/64, or bytes with options["width"]; options: {"c", "bits", "signed", "width"}.
+        Returns msm's shape, {"result", "log", "info"}; "result" equals msm over the same values as 32-byte scalars."""
+        options = options or {}
+        self._ctx.pointset_select(pointPtr.set_id)
+        if N > pointPtr.n or N > self._ctx.n_points:
+            raise MsmError(_lib.MSM_ERR_NO_POINTS, f"{N} scalars but {min(pointPtr.n, self._ctx.n_points)} points behind this pointer")
+        if hasattr(scalars, "dtype"):
+            if N > scalars.size:
+                raise MsmError(_lib.MSM_ERR_ARG, f"{N} scalars requested but the array holds {scalars.size}")
+            scalars = scalars.ravel()[:N]
+        else:
+            w = options.get("width") or 0
+            if w <= 0 or N * w > len(scalars):
+                raise MsmError(_lib.MSM_ERR_ARG, f"{N} scalars of width {w} requested but the buffer holds {len(scalars)} bytes")
+            scalars = bytes(scalars)[: N * w]
+        res, info = self._ctx.run_narrow(scalars, options.get("bits"), options.get("signed"), options.get("c"),
+                                         width=options.get("width"))
+        return {"result": res, "log": [], "info": info}
 
     def msmProjective(self, scalarPtr: ScalarPtr, pointPtr: PointPtr, N: int, options: Optional[Dict] = None) -> Dict:
         """`msmProjective` (src/parallel.ts:69-87: msmBasic over projective points): signed windows of the whole scalar,

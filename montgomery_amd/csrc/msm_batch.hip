@@ -41,7 +41,13 @@ void run_batch_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl_in, con
   Plan pl = pl_in;
   pl.batch = cnt;
   pl.lone = lone;
-  for (int j = 0; j < cnt; j++) pl.batch_sc.p[j] = sc[b0 + j];
+  NarrowBatchScalars nbs{};   // (narrow elements: up to NARROW_BATCH_MAX pointers, k_digits_narrow_batch)
+  if (pl.nar.width) {
+    for (int j = 0; j < cnt; j++) nbs.p[j] = sc[b0 + j];
+    pl.nar.nb = &nbs;
+  } else {
+    for (int j = 0; j < cnt; j++) pl.batch_sc.p[j] = sc[b0 + j];
+  }
   const int kc = cnt * pl.K;
   SortOut so;
   HIPCHK(hipEventRecord(w.ev[0], w.stream));
@@ -68,10 +74,12 @@ int run_fused(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, 
   if (on_device) {
     for (uint32_t b = 0; b < B; b++) sc[b] = (const uint32_t*)scalars[b];
   } else {
-    ctx->ensure(ctx->scal, (size_t)B * n * 32);
+    // (narrow elements, msm_run_batch_narrow: n x width bytes each, every element on a 16-byte boundary)
+    const size_t el_bytes = (size_t)n * (pl.nar.width ? pl.nar.width : 32), el_stride = (el_bytes + 15) & ~(size_t)15;
+    ctx->ensure(ctx->scal, (size_t)B * el_stride);
     for (uint32_t b = 0; b < B; b++) {
-      sc[b] = (const uint32_t*)ctx->scal.p + (size_t)b * n * 8;
-      upload_staged(ctx, (void*)sc[b], scalars[b], n * 32);
+      sc[b] = (const uint32_t*)((const char*)ctx->scal.p + (size_t)b * el_stride);
+      upload_staged(ctx, (void*)sc[b], scalars[b], el_bytes);
     }
   }
   HIPCHK(hipEventRecord(ctx->ev[9], ctx->stream));
@@ -79,7 +87,7 @@ int run_fused(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, 
   const uint64_t budget = ctx->ws_limit ? ctx->ws_limit : ctx->ws_budget;
   const long double room = (long double)budget / msm_ctx::N_WS / window_bytes(ctx, n, pl);
   const int wpg = (int)std::max<long double>(1, std::min<long double>(room, GROUP_WINDOWS));
-  int per = std::max(1, std::min(wpg / pl.K, BATCH_MAX));
+  int per = std::max(1, std::min(wpg / pl.K, pl.nar.width ? NARROW_BATCH_MAX : BATCH_MAX));
   const int n_groups = (int)((B + per - 1) / per);
   per = (int)((B + n_groups - 1) / n_groups);   // even groups
   const int pw = ctx->is_te() ? 32 : 36;
@@ -121,6 +129,7 @@ int run_fused(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, 
   HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (pl.strict && (ctx->h_info[0] & 4u)) throw MsmFail{MSM_ERR_SCALAR, "a scalar is >= the group order q (msm_opts.strict)"};
+  if (ctx->h_info[0] & NARROW_ERR_RANGE) throw MsmFail{MSM_ERR_SCALAR, "a scalar lies outside the declared range (msm_run_batch_narrow)"};
   if (ctx->h_info[0] & 8u) throw MsmFail{MSM_ERR_INTERNAL, "a digit of the folded top window exceeds its bucket range (GLV bound violated)"};
   // per element: the Horner step over its K window sums and the conversion to affine (one field inversion each), spread over
   // host threads -- ~0.03 ms per element on one thread
@@ -235,5 +244,61 @@ extern "C" int msm_run_batch(msm_ctx* ctx, const void* const* scalars, uint32_t 
       }
     }
     return run_each(ctx, scalars, B, n, on_device, opts, out);
+  } MSM_CATCH_ALL(ctx)
+}
+
+// msm_run_batch over narrow scalars (msm_narrow.hip has the format): the same fused groups, their digits from
+// k_digits_narrow_batch; with K as small as 1 .. 5 a group of 128 windows holds up to NARROW_BATCH_MAX elements.  Outside the
+// fused region -- or where a device pointer is not aligned to the load of a lane -- element by element through msm_run_narrow.
+extern "C" int msm_run_batch_narrow(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device, int32_t width_bytes,
+                                    int32_t bits, int32_t is_signed, const msm_opts* opts, msm_result* out) {
+  if (!ctx || !out || !scalars || B == 0) return fail(ctx, MSM_ERR_ARG, "msm_run_batch_narrow: null argument or empty batch");
+  for (uint32_t b = 0; b < B && n; b++)
+    if (!scalars[b]) return fail(ctx, MSM_ERR_ARG, "msm_run_batch_narrow: no scalars for element %u", b);
+  Plan::Narrow nar;
+  if (int rc = narrow_format(ctx, width_bytes, bits, is_signed, opts, "msm_run_batch_narrow", nar)) return rc;
+  if (int rc = check_points(ctx, n, opts, MSM_ERR_NO_POINTS, "msm_run_batch_narrow")) return rc;
+  for (uint32_t b = 0; b < B; b++)
+    if (int rc = narrow_scalars_ok(ctx, scalars[b], n, on_device, width_bytes, "msm_run_batch_narrow")) return rc;
+  try {
+    if (n) {
+      // Where msm_run_batch fuses (B >= 2, one device, fewer than 2^21 entries per window) the elements share every launch only
+      // under the one-level sort, c <= 16 -- so there the single-call rule, which takes 17 bits from 2^18 points for scalars of
+      // up to 32 bits, gives way to its one-level form (the cost model capped at 13 bits).  That choice is NOT measured against
+      // running the elements one by one at 17 bits: tools/narrow_time.py times single calls only.
+      Plan pl;
+      msm_opts o;
+      if (opts) o = *opts; else memset(&o, 0, sizeof o);
+      const uint64_t entries = ctx->is_te() ? n : 2 * n;
+      const bool fuse_region = B >= 2 && ctx->children.empty() && entries < (ctx->is_te() ? 1ull << 22 : 1ull << 21);
+      if (o.c <= 0 && fuse_region) o.c = pick_window_narrow(ctx->is_te(), n, nar.fmt.bits, /*one_level=*/true);
+      if (make_plan(ctx, n, &o, pl, false, nar.fmt.bits)) return fail(ctx, MSM_ERR_ARG, "msm_run_batch_narrow: bad window size");
+      pl.nar = nar;
+      bool fused = fuse(ctx, n, B, pl);
+      // (1- and 2-byte device scalars may start inside a dword; the fused digit kernel wants every element on a dword)
+      for (uint32_t b = 0; b < B && on_device; b++) fused &= ((uintptr_t)scalars[b] & 3) == 0;
+      if (fused) {
+        for (uint32_t b = 0; b < B; b++) memset(&out[b], 0, sizeof(msm_result));
+        return run_fused(ctx, scalars, B, n, on_device, opts, pl, out);
+      }
+    }
+    msm_result tot;
+    memset(&tot, 0, sizeof tot);
+    for (uint32_t b = 0; b < B; b++) {
+      if (int rc = msm_run_narrow(ctx, scalars[b], n, on_device, width_bytes, bits, is_signed, opts, &out[b])) return rc;
+      for (int j = 0; j < MSM_N_PHASES; j++) tot.phase_ms[j] += out[b].phase_ms[j];
+      tot.rounds += out[b].rounds;
+      tot.n_pairs += out[b].n_pairs;
+      tot.n_pairs_algo += out[b].n_pairs_algo;
+      tot.max_bucket = std::max(tot.max_bucket, out[b].max_bucket);
+    }
+    for (uint32_t b = 0; b < B; b++) {
+      memcpy(out[b].phase_ms, tot.phase_ms, sizeof tot.phase_ms);
+      out[b].rounds = tot.rounds;
+      out[b].n_pairs = tot.n_pairs;
+      out[b].n_pairs_algo = tot.n_pairs_algo;
+      out[b].max_bucket = tot.max_bucket;
+    }
+    return MSM_OK;
   } MSM_CATCH_ALL(ctx)
 }

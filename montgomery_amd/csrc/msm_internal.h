@@ -8,7 +8,9 @@
 //   msm_tables.hip    window tables (K resident tables 2^(c k) P: one set of buckets for all windows)
 //   msm_abi.hip       the C ABI of include/msm_hip.h (contexts, points, msm_run, msm_window_sums, handles)
 //   msm_test_abi.hip  the operator-level test entries (msm_test_*) and the input generators
-// Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip and te_kernels.hip; host TUs see declarations.
+//   msm_narrow.hip    msm_run_narrow, msm_plan_narrow, msm_scalar_bits (narrow scalars: no endomorphism split, K from the call's bits)
+// Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip, te_kernels.hip and narrow_kernels.hip; host TUs see
+// declarations.
 // Orchestration follows `createMsm().msm` (reference src/msm-batched-affine.ts:69-340); the per-thread SPMD phases separated
 // by `barrier()` there become kernel launches on one HIP stream here.
 #pragma once
@@ -16,6 +18,7 @@
 #include "sort_kernels.h"
 #include "tree_kernels.h"
 #include "te_kernels.h"
+#include "narrow_kernels.h"
 #include "host_field.h"
 #include "../../include/msm_hip.h"
 
@@ -355,10 +358,24 @@ struct Plan {
                        // first window instead of one P_k per slot (reduce_buckets); msm_window_sums never sets it
   int batch = 0;       // msm_run_batch (msm_batch.hip): the group's windows are those of `batch` elements, K each (window
   BatchScalars batch_sc{};   // kk = virtual window b K + k), their digits come from k_digits_batch over batch_sc
+  // msm_run_narrow (msm_narrow.hip): width != 0 -- the scalars are width-byte integers (32: field elements holding small
+  // values) of `fmt.bits` magnitude bits, their digits come from k_digits_narrow.  The scalar pointer a window group gets is
+  // then the array of the whole CALL, rounded down to the alignment of a lane's load, and scalar `first` + i belongs to the
+  // group's point i (a range of the points may start inside a lane's dword).  nb: the scalars of a fused batch.
+  struct Narrow {
+    int width = 0;
+    uint64_t first = 0;
+    NarrowFmt fmt{};
+    const NarrowBatchScalars* nb = nullptr;
+  } nar;
 };
 
 // for_tables: the window a run on window tables wants (bucket work no longer grows with the number of windows)
-int make_plan(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, Plan& pl, bool for_tables = false);
+// narrow_bits > 0: the plan of a narrow call -- b = narrow_bits instead of the curve's scalar length, no endomorphism split,
+// the window from pick_window_narrow, c down to 2
+int make_plan(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, Plan& pl, bool for_tables = false, int narrow_bits = 0);
+// one_level: the window of a fused batch, which must stay within the one-level sort (msm_batch.hip)
+int pick_window_narrow(bool te, uint64_t n, int bits, bool one_level = false);
 // the plan of msm_run(n, opts) -- on window tables where the call is eligible and they exist or would be built -- and whether
 // it is that plan (msm_tables.hip)
 // note_range: the call is real (not msm_plan): a range of the points it asks for is remembered as the candidate for range tables
@@ -592,6 +609,14 @@ int on_all_devices(msm_ctx* ctx, F f) {
 
 // ---- msm_batch.hip ----------------------------------------------------------------------------------------------
 int pick_window_batch(bool te, uint64_t n, uint32_t B, int glv_max_bits);
+
+// ---- msm_narrow.hip ---------------------------------------------------------------------------------------------
+// checks the format and the options of a narrow call (MSM_ERR_ARG with a message) and resolves it: bits = 0 -> all the width gives
+int narrow_format(msm_ctx* ctx, int32_t width_bytes, int32_t bits, int32_t is_signed, const msm_opts* opts, const char* who,
+                  Plan::Narrow& out);
+// the rest of the argument checks of a narrow entry: n < 2^32 (the digit kernels count points in 32 bits) and device scalars
+// aligned to their width (16 bytes for the 16- and 32-byte forms, which lanes load as uint4)
+int narrow_scalars_ok(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, int32_t width_bytes, const char* who);
 
 // ---- msm_gen.hip ------------------------------------------------------------------------------------------------
 }  // namespace msmi

@@ -11,11 +11,20 @@ namespace {
 // Partition sums P_k for windows [k_lo, k_hi) over the points [p_lo, p_lo + n) -> h_partials_out[(k - k_lo) * 36 ...]
 // scalars: device pointer, n x 8 words.
 // k_base: the first window of the CALL (window tables carry weights relative to it: table j = 2^(c j) P serves window k_base + j)
-void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars_all, uint64_t p_lo, uint64_t n, const Plan& pl,
+// the scalars of the points [p_lo, ...) of a call: 32-byte scalars are addressed; narrow ones (msm_run_narrow) keep the call's
+// array and count from `first`, which the digit kernel resolves (a range may start inside the dword a lane loads)
+const uint32_t* group_scalars(const uint32_t* d_scalars_all, uint64_t p_lo, Plan& pl) {
+  if (!pl.nar.width) return d_scalars_all + p_lo * 8;
+  pl.nar.first += p_lo;
+  return d_scalars_all;
+}
+
+void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars_all, uint64_t p_lo, uint64_t n, const Plan& pl_in,
                       int k_lo, int k_hi, int k_base, uint32_t* h_partials_out, GroupStats& st, uint64_t p_off = 0,
                       GroupDigits* share = nullptr) {
   hipStream_t s = w.stream;
-  const uint32_t* d_scalars = d_scalars_all + p_lo * 8;   // scalar i of the call <-> resident point p_off + i
+  Plan pl = pl_in;
+  const uint32_t* d_scalars = group_scalars(d_scalars_all, p_lo, pl);   // scalar i of the call <-> resident point p_off + i
   p_lo += p_off;
   const int kc = k_hi - k_lo;
   SortOut so;
@@ -181,7 +190,9 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
     SortOut none;
     GroupStats gs;
     HIPCHK(hipEventRecord(ctx->ev_dig[0], ctx->ws[0].stream));
-    sort_window_group(ctx, ctx->ws[0], d_scal + groups[0].p_lo * 8, groups[0].p_n, pl, groups[0].ka, groups[1].kb, gs, none, &share);
+    Plan pd = pl;
+    const uint32_t* d_grp = group_scalars(d_scal, groups[0].p_lo, pd);
+    sort_window_group(ctx, ctx->ws[0], d_grp, groups[0].p_n, pd, groups[0].ka, groups[1].kb, gs, none, &share);
     share.produce = false;
   }
   std::atomic<int> next{0};
@@ -225,6 +236,7 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
     HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (pl.strict && (ctx->h_info[0] & 4u)) throw MsmFail{MSM_ERR_SCALAR, "a scalar is >= the group order q (msm_opts.strict)"};
+    if (ctx->h_info[0] & NARROW_ERR_RANGE) throw MsmFail{MSM_ERR_SCALAR, "a scalar lies outside the declared range (msm_run_narrow)"};
     if (ctx->h_info[0] & 8u) throw MsmFail{MSM_ERR_INTERNAL, "a digit of the folded top window exceeds its bucket range (GLV bound violated)"};
   }
   float upload_ms = -1;

@@ -75,6 +75,49 @@ int pick_window(bool te, uint64_t n, int glv_max_bits) {
   return best;
 }
 
+// Window of a narrow call (msm_run_narrow): b = `bits` magnitude bits, one entry per point, K = ceil((b + 1) / c).  The
+// candidates that matter are the c whose K c wastes few bits (b = 64: 13 x 5, 17 x 4, 22 x 3; b = 32: 11 x 3, 17 x 2; b = 16:
+// 9 x 2, 17 x 1; b = 8: 9 x 1; b = 1: 2 x 1): for every K the smallest c that reaches it.
+// Measured with tools/narrow_time.py --csweep at b = 1, 8, 16, 32, 64, 128 and n = 2^14 .. 2^24 on BLS12-377 and Ed-on-BLS12-377
+// (profiles/narrow_scalar_time.txt section 1, the "c sweep" lines; ms, BLS12-377 first, then the Edwards curve):
+//  * 5 .. 32 bits: one or two 17-bit windows (the bin split of the big windows, which cuts heavy bins into parts) beat the small
+//    windows of the one-level sort as soon as the buckets get deep.  b = 16: 2^18 0.82 against 1.13 at c = 9 (Edwards 0.48 /
+//    0.51), 2^20 1.00 / 2.30 (0.61 / 0.69).  b = 32: 2^18 0.93 against 1.08 at c = 11 (0.57 / 0.58), 2^20 1.24 / 1.70 (0.81 /
+//    0.86).  b = 8: 2^18 c = 9 still wins, 1.03 against 1.19 (0.47 / 0.61); 2^20 1.48 against 1.70 at c = 9 but Edwards 0.70 /
+//    0.57, so there from 2^22; 2^22 2.16 / 3.48 (1.07 / 2.43), 2^24 4.65 / 7.70 (2.55 / 8.56).  Below those sizes the
+//    smallest window that covers the scalar in few windows wins (the model below).  5 .. 7 bits follow the 8-bit rule unmeasured.
+//  * bit columns are the other way round: b = 1 under c = 2 (two buckets) against c = 17: 2^20 1.53 / 2.03, 2^22 2.13 / 3.27,
+//    2^24 3.38 / 7.01 (Edwards 2^22 0.80 / 2.12, 2^24 1.47 / 6.27) -- up to 4 bits the model's window, b + 1, stays.
+//  * above 32 bits, below 2^21 points: 13-bit windows (b = 64 at 2^20 1.92 against 2.35 at c = 11; b = 128 2.86 against 3.59
+//    at c = 12 and 3.60 at c = 15), so the model is capped at 13 there.  From 2^21 points 17 bits for b = 64 (2^22 4.24 against
+//    4.92 at c = 13 and 6.09 at c = 22; 2^24 12.9 / 14.9 / 14.1) and, which the model finds by itself, 19 bits for b = 128 at
+//    2^24 (21.6 against 24.7 at c = 17; Edwards 14.6 / 16.2).  At 2^22 it takes 17 for b = 128, 7.85 where 19 would give 7.21
+//    (not adopted: one point); on the Edwards curve 13 bits win there, 4.85 against 5.17, and stay below 2^23.
+// Everything else is the COST MODEL alone: other bit lengths; BLS12-381 and Pallas, and 2^26 points (c = 22 from 64 bits),
+// which sections 2 and 3 of the file time under this rule but without a sweep.  The model: one pair addition per entry and
+// window, about four per bucket to finish and reduce it, and a fixed 256 per window (launch geometry, host tail) so that tiny
+// inputs do not run dozens of windows -- K (n + 4 buckets + 256).
+// one_level: the window of a fused batch (msm_run_batch_narrow), which must stay inside the one-level sort: the model capped at
+// 13 bits whatever the size -- not measured against running the elements one by one under the rule above.
+int pick_window_narrow(bool te, uint64_t n, int bits, bool one_level) {
+  if (bits > 4 && bits <= 32 && !one_level) {
+    const uint64_t from = bits > 8 ? 1ull << 18 : te ? 1ull << 22 : 1ull << 20;
+    if (n >= from) return 17;
+  }
+  const int c_max = (n >= (1ull << 21) && !one_level && !(te && bits > 64 && n < (1ull << 23))) ? 22 : 13;
+  int best = 2;
+  double best_cost = 1e300;
+  for (int c = 2; c <= c_max; c++) {
+    int K = (bits + c) / c;
+    double buckets = (double)(1u << (c - 1));
+    if (!te && c >= 18 && K > 1 && (bits + 1) - (K - 1) * c == 1) { K -= 1; buckets *= 2; }   // the fold rule of make_plan
+    if (K > 64) continue;   // (make_plan's bound)
+    const double cost = (double)K * ((double)n + 4.0 * buckets + 256.0);
+    if (cost < best_cost) { best_cost = cost; best = c; }
+  }
+  return best;
+}
+
 // On window tables all windows of a group share one set of buckets, so a wider window costs its 2^(c-1) buckets once instead
 // of K times and the optimum moves up.  BLS12-377 after GLV (127 bits: 18- and 21-bit windows fold the carry bit, no short top
 // window to skew the merged buckets), measured with tools/tables_csweep.py (profiles/r05_experiments.txt item 5): 16 bits below
@@ -89,17 +132,21 @@ static int pick_window_tables(bool te, uint64_t n, int glv_max_bits) {
   return pick_window(te, n, glv_max_bits);
 }
 
-int make_plan(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, Plan& pl, bool for_tables) {
+int make_plan(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, Plan& pl, bool for_tables, int narrow_bits) {
   const bool te = ctx && ctx->is_te();
+  const bool narrow = narrow_bits > 0;
   const int glv_bits = curve_info(ctx ? ctx->curve : MSM_CURVE_BLS12_377_G1).glv_max_bits;
   const int glv_arg = (opts && opts->no_glv) ? 0 : glv_bits;
-  int c = (opts && opts->c > 0) ? opts->c : for_tables ? pick_window_tables(te, n, glv_arg) : pick_window(te, n, glv_arg);
+  int c = (opts && opts->c > 0) ? opts->c : narrow ? pick_window_narrow(te, n, narrow_bits)
+          : for_tables ? pick_window_tables(te, n, glv_arg) : pick_window(te, n, glv_arg);
   if (c < 2 || c > 24) return MSM_ERR_ARG;
-  // b = Scalar.maxBits after GLV (src/wasm/glv.ts:216-226), or the bit length of q without it (src/msm-basic.ts:56)
-  pl.no_glv = !te && opts && opts->no_glv;
+  // b = Scalar.maxBits after GLV (src/wasm/glv.ts:216-226), or the bit length of q without it (src/msm-basic.ts:56); a narrow
+  // call (msm_run_narrow) brings its own: the magnitude bits the caller declared, and no endomorphism split
+  pl.no_glv = !te && (narrow || (opts && opts->no_glv));
   pl.strict = opts && opts->strict;
-  const int b = te ? 251 : pl.no_glv ? curve_info(ctx ? ctx->curve : MSM_CURVE_BLS12_377_G1).q_bits : glv_bits;
-  if (pl.no_glv && c < 4) return MSM_ERR_ARG;   // keeps K <= 64
+  const int b = narrow ? narrow_bits : te ? 251 : pl.no_glv ? curve_info(ctx ? ctx->curve : MSM_CURVE_BLS12_377_G1).q_bits : glv_bits;
+  if (pl.no_glv && !narrow && c < 4) return MSM_ERR_ARG;   // keeps K <= 64
+  if (narrow && (b + c) / c > 64) return MSM_ERR_ARG;      // (the same bound: 128 bits under c = 2 would be 65 windows)
   pl.c = c;
   pl.K = (b + 1 + c - 1) / c;  // K = ceil((b + 1) / c), src/msm-batched-affine.ts:90, src/msm-basic.ts:59
   pl.bits = b + 1;

@@ -20,6 +20,53 @@ void sort_kernel_attributes() {
   HIPCHK(hipFuncSetAttribute((const void*)k_digits<CvBls381>, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));
   HIPCHK(hipFuncSetAttribute((const void*)k_digits<CvPallas>, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));
   HIPCHK(hipFuncSetAttribute((const void*)te::k_te_digits, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));
+#define MSM_NARROW_ATTR(W)                                                                                                    \
+  HIPCHK(hipFuncSetAttribute((const void*)k_digits_narrow<W>, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));          \
+  HIPCHK(hipFuncSetAttribute((const void*)k_te_digits_narrow<W>, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));
+  MSM_NARROW_WIDTHS(MSM_NARROW_ATTR)
+#undef MSM_NARROW_ATTR
+}
+
+// The digit launch of a narrow call (msm_run_narrow): k_digits_narrow / k_te_digits_narrow of the call's width write what
+// k_digits / k_te_digits write -- digits and, for the bin split, the slice histograms -- or, for a fused batch, their _batch
+// forms.  A lane of the 1- and 2-byte formats takes 4 / 2 scalars, so a block of the plain launch covers 256 lanes' worth.
+static void narrow_digits(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars, uint64_t n, const Plan& pl, int k_lo, int kc_d,
+                          bool bin_split, bool radix, uint32_t sortB, uint64_t pps, uint32_t hb, const WinSplit& ws) {
+  hipStream_t s = w.stream;
+  const bool te = ctx->is_te();
+  const int W = pl.nar.width, per_lane = W == 1 ? 4 : W == 2 ? 2 : 1;
+  uint32_t* dig = (uint32_t*)w.dig.p;
+  uint32_t* err = (uint32_t*)ctx->errflag.p;
+  const int fold = pl.fold ? 1 : 0;
+  if (pl.batch) {
+    if (bin_split || radix || k_lo != 0 || kc_d != pl.batch * pl.K || !pl.nar.nb) throw MsmFail{MSM_ERR_INTERNAL, "a batch group outside the one-level sort"};
+    const uint32_t grid = (uint32_t)(((n + per_lane - 1) / per_lane + 255) / 256);
+#define MSM_NARROW_LAUNCH_B(WW)                                                                                               \
+  if (W == WW) {                                                                                                              \
+    if (te) hipLaunchKernelGGL(k_te_digits_narrow_batch<WW>, dim3(grid), dim3(256), 0, s, dig, *pl.nar.nb, (uint32_t)pl.batch, \
+                               (uint32_t)n, pl.c, pl.K, fold, pl.nar.fmt, err);                                               \
+    else hipLaunchKernelGGL(k_digits_narrow_batch<WW>, dim3(grid), dim3(256), 0, s, dig, *pl.nar.nb, (uint32_t)pl.batch,      \
+                            (uint32_t)n, pl.c, pl.K, fold, pl.nar.fmt, err);                                                  \
+  }
+    MSM_NARROW_WIDTHS(MSM_NARROW_LAUNCH_B)
+#undef MSM_NARROW_LAUNCH_B
+    return;
+  }
+  const uint32_t per = bin_split ? (uint32_t)pps : 256u * per_lane;
+  const uint32_t grid = bin_split ? sortB : (uint32_t)((n + per - 1) / per);
+  const uint32_t threads = bin_split ? 1024u : 256u;
+  uint32_t* hist = bin_split ? (uint32_t*)w.block_hist.p : nullptr;
+  const size_t lds = bin_split ? (size_t)kc_d * hb * 4 : 0;
+  const uint64_t fbp = pack_fine_bits(ws);
+#define MSM_NARROW_LAUNCH(WW)                                                                                                 \
+  if (W == WW) {                                                                                                              \
+    if (te) hipLaunchKernelGGL(k_te_digits_narrow<WW>, dim3(grid), dim3(threads), lds, s, dig, (const void*)d_scalars,        \
+                               pl.nar.first, (uint32_t)n, pl.c, pl.K, k_lo, kc_d, fold, pl.nar.fmt, err, per, hist, hb, fbp); \
+    else hipLaunchKernelGGL(k_digits_narrow<WW>, dim3(grid), dim3(threads), lds, s, dig, (const void*)d_scalars, pl.nar.first, \
+                            (uint32_t)n, pl.c, pl.K, k_lo, kc_d, fold, pl.nar.fmt, err, per, hist, hb, fbp);                  \
+  }
+  MSM_NARROW_WIDTHS(MSM_NARROW_LAUNCH)
+#undef MSM_NARROW_LAUNCH
 }
 
 // windows [k_lo, k_hi) over n points whose scalars start at d_scalars (n x 8 words); queues everything on w.stream, records
@@ -164,7 +211,10 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
 
   if (consume) HIPCHK(hipStreamWaitEvent(s, share->ready, 0));   // (the producer's launch is timed by the caller, not as this group's wait)
   HIPCHK(hipEventRecord(w.ev[0], s));
-  if (pl.batch) {
+  if (pl.nar.width) {
+    // msm_run_narrow: the same digit array (and, for the bin split, the same slice histograms) from k_digits_narrow
+    if (!consume) narrow_digits(ctx, w, d_scalars, n, pl, k_lo, kc_d, bin_split, radix, sortB, pps, hb, ws);
+  } else if (pl.batch) {
     // msm_run_batch: the kc_d windows are the K windows of pl.batch elements (virtual windows), one thread per point.  A fused
     // batch is sized to take the one-level sort (msm_batch.hip), which needs no slice histograms from the digit kernel.
     if (bin_split || radix || k_lo != 0 || kc_d != pl.batch * pl.K) throw MsmFail{MSM_ERR_INTERNAL, "a batch group outside the one-level sort"};

@@ -14,6 +14,10 @@
 //          memory its kernels compute in, src/parallel.ts:119-133, scripts/msm-weierstrass.ts:29-32),
 //          msmBatch(h, [Buffer scalars], c, noGlv, unsafe) / msmBatchDevice(h, [dbuf], n, c, noGlv, unsafe) -> array of results as
 //          msm's: many MSMs over the same points in one call (msm_run_batch),
+//          msmNarrow(h, Buffer scalars, width, bits, signed, c) -> as msm: narrow scalars (msm_run_narrow) -- width 1, 2, 4, 8, 16
+//          bytes per scalar, or 32 for field elements holding small values; bits 0 = all the width gives,
+//          msmBatchNarrow(h, [Buffer], width, bits, signed, c) -> array of results (msm_run_batch_narrow),
+//          scalarBits(h, Buffer of n x 32 bytes) -> {unsigned, signed} (msm_scalar_bits),
 //          plan(h, n, c) -> {c, K}, generatePoints(h, n, seed) -> n, generateScalars(h, n, seed[, dbuf]) -> Buffer | n
 //          the fine operator table of the reference's wasm exports (src/field-msm.ts:86-123,190-243, src/scalar-glv.ts:41-51,105-128)
 //          over Buffers instead of wasm pointers: fieldOp(h, op, a, b) -> Buffer (msm_test_fp: multiply / square / add / subtract /
@@ -503,6 +507,137 @@ static napi_value batch_common(napi_env env, napi_callback_info info, int on_dev
 static napi_value MsmBatch(napi_env env, napi_callback_info info) { return batch_common(env, info, 0); }
 static napi_value MsmBatchDevice(napi_env env, napi_callback_info info) { return batch_common(env, info, 1); }
 
+// narrow scalars (msm_run_narrow / msm_run_batch_narrow / msm_scalar_bits): host Buffers of n x width bytes
+static int narrow_args(napi_env env, size_t argc, napi_value* argv, int32_t* width, int32_t* bits, int32_t* is_signed, msm_opts* opts) {
+  memset(opts, 0, sizeof *opts);
+  *width = *bits = *is_signed = 0;
+  if (argc > 2) napi_get_value_int32(env, argv[2], width);
+  if (argc > 3) napi_get_value_int32(env, argv[3], bits);
+  if (argc > 4) napi_get_value_int32(env, argv[4], is_signed);
+  if (argc > 5) napi_get_value_int32(env, argv[5], &opts->c);
+  if (*width != 1 && *width != 2 && *width != 4 && *width != 8 && *width != 16 && *width != 32) {
+    napi_throw_range_error(env, NULL, "width must be 1, 2, 4, 8, 16 or 32 bytes");
+    return 0;
+  }
+  return 1;
+}
+
+static napi_value MsmNarrow(napi_env env, napi_callback_info info) {
+  size_t argc = 6;   // (ctx, scalars, width, bits, signed, c)
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  void* data;
+  size_t len;
+  NAPI_OK(napi_get_buffer_info(env, argv[1], &data, &len));
+  int32_t width, bits, is_signed;
+  msm_opts opts;
+  if (!narrow_args(env, argc, argv, &width, &bits, &is_signed, &opts)) return NULL;
+  if (len % (size_t)width) {
+    napi_throw_range_error(env, NULL, "scalar buffer length is not a multiple of the width");
+    return NULL;
+  }
+  msm_result res;
+  int rc = msm_run_narrow(h->ctx, data, len / (size_t)width, 0, width, bits, is_signed, &opts, &res);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "msmNarrow");
+  return result_object(env, h, &res);
+}
+
+static napi_value MsmBatchNarrow(napi_env env, napi_callback_info info) {
+  size_t argc = 6;   // (ctx, [scalars], width, bits, signed, c)
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  bool is_array = false;
+  if (argc > 1) napi_is_array(env, argv[1], &is_array);
+  uint32_t B = 0;
+  if (is_array) NAPI_OK(napi_get_array_length(env, argv[1], &B));
+  if (!is_array || B == 0) {
+    napi_throw_type_error(env, NULL, "expected a non-empty array of scalar Buffers");
+    return NULL;
+  }
+  int32_t width, bits, is_signed;
+  msm_opts opts;
+  if (!narrow_args(env, argc, argv, &width, &bits, &is_signed, &opts)) return NULL;
+  const void** ptrs = (const void**)calloc(B, sizeof(void*));
+  msm_result* res = (msm_result*)calloc(B, sizeof(msm_result));
+  if (!ptrs || !res) {
+    free(ptrs);
+    free(res);
+    napi_throw_error(env, NULL, "out of memory");
+    return NULL;
+  }
+  uint64_t n = 0;
+  const char* bad = NULL;
+  for (uint32_t b = 0; b < B && !bad; b++) {
+    napi_value e;
+    void* data;
+    size_t len;
+    if (napi_get_element(env, argv[1], b, &e) != napi_ok || napi_get_buffer_info(env, e, &data, &len) != napi_ok) {
+      bad = "expected an array of Buffers";
+      break;
+    }
+    if (len % (size_t)width) bad = "scalar buffer length is not a multiple of the width";
+    else if (b == 0) n = len / (size_t)width;
+    else if (len / (size_t)width != n) bad = "the scalar buffers of a batch must have the same length";
+    ptrs[b] = data;
+  }
+  if (bad) {
+    free(ptrs);
+    free(res);
+    napi_throw_range_error(env, NULL, bad);
+    return NULL;
+  }
+  int rc = msm_run_batch_narrow(h->ctx, ptrs, B, n, 0, width, bits, is_signed, &opts, res);
+  free(ptrs);
+  if (rc != MSM_OK) {
+    free(res);
+    return throw_msm(env, h->ctx, rc, "msmBatchNarrow");
+  }
+  napi_value arr;
+  if (napi_create_array_with_length(env, B, &arr) != napi_ok) {
+    free(res);
+    napi_throw_error(env, NULL, "N-API call failed: napi_create_array_with_length");
+    return NULL;
+  }
+  for (uint32_t b = 0; b < B; b++) {
+    napi_value r = result_object(env, h, &res[b]);
+    if (!r || napi_set_element(env, arr, b, r) != napi_ok) {
+      free(res);
+      return NULL;
+    }
+  }
+  free(res);
+  return arr;
+}
+
+static napi_value ScalarBits(napi_env env, napi_callback_info info) {
+  size_t argc = 2;   // (ctx, scalars: n x 32 bytes)
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  void* data;
+  size_t len;
+  NAPI_OK(napi_get_buffer_info(env, argv[1], &data, &len));
+  if (len % 32) {
+    napi_throw_range_error(env, NULL, "scalar buffer length is not a multiple of 32");
+    return NULL;
+  }
+  int32_t ub = 0, sb = 0;
+  int rc = msm_scalar_bits(h->ctx, data, len / 32, 0, &ub, &sb);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarBits");
+  napi_value out, v;
+  NAPI_OK(napi_create_object(env, &out));
+  NAPI_OK(napi_create_int32(env, ub, &v));
+  NAPI_OK(napi_set_named_property(env, out, "unsigned", v));
+  NAPI_OK(napi_create_int32(env, sb, &v));
+  NAPI_OK(napi_set_named_property(env, out, "signed", v));
+  return out;
+}
+
 static napi_value Plan(napi_env env, napi_callback_info info) {  // windowSize, src/msm-common.ts:8-41
   size_t argc = 3;
   napi_value argv[3];
@@ -740,6 +875,7 @@ NAPI_MODULE_INIT() {
       {"generatePoints", GeneratePoints}, {"generateScalars", GenerateScalars},
       {"deviceAlloc", DeviceAlloc}, {"deviceUpload", DeviceUpload}, {"deviceFree", DeviceFree}, {"msmDevice", MsmDevice},
       {"msmBatch", MsmBatch}, {"msmBatchDevice", MsmBatchDevice},
+      {"msmNarrow", MsmNarrow}, {"msmBatchNarrow", MsmBatchNarrow}, {"scalarBits", ScalarBits},
       {"pointsetCreate", PointsetCreate}, {"pointsetSelect", PointsetSelect}, {"pointsetDestroy", PointsetDestroy},
       {"fieldOp", FieldOp}, {"batchInverse", BatchInverse}, {"glvDecompose", GlvDecompose}, {"batchAdd", BatchAdd}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
