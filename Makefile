@@ -6,7 +6,7 @@ LIB := montgomery_amd/libmsm_hip.so
 HIPFLAGS := -O3 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-function -Wno-unused-variable \
             -Iinclude -I$(CSRC)
 BUILD := build
-CURVES := CvBls377 CvBls381 CvPallas
+CURVES := CvBls377 CvBls381 CvPallas CvBn254 CvGrumpkin CvVesta
 CURVE_OBJS := $(CURVES:%=$(BUILD)/kernels_%.o)
 HOST_TUS := msm_plan msm_sort msm_tree msm_reduce msm_upload msm_pipeline msm_batch msm_tables msm_abi msm_test_abi msm_gen msm_ingest msm_narrow sort_kernels te_kernels narrow_kernels
 HOST_OBJS := $(HOST_TUS:%=$(BUILD)/%.o)
@@ -40,7 +40,11 @@ clean:
 
 # CPU build of the field / GLV templates for tests/test_host_field.py (no GPU needed)
 HOSTTEST := tests/csrc/libfield_host.so
-hosttest: $(HOSTTEST)
+HOSTTEST_CYCLES := tests/csrc/libfield_host_cycles.so
+hosttest: $(HOSTTEST) $(HOSTTEST_CYCLES)
+# the cycle curves (BN254 G1, Grumpkin, Vesta), with the square root of points_ingest.h: tests/test_cycle_curves.py
+$(HOSTTEST_CYCLES): tests/csrc/field_host_cycles.hip $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/te_kernels.h
+	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/field_host_cycles.hip -o $(HOSTTEST_CYCLES)
 $(HOSTTEST): tests/csrc/field_host.hip $(CSRC)/field.h $(CSRC)/glv.h $(CSRC)/constants_gen.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -I$(CSRC) tests/csrc/field_host.hip -o $(HOSTTEST)
 

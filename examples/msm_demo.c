@@ -1,6 +1,6 @@
 /* Plain-C host of the C ABI (include/msm_hip.h): no Python, no torch -- what a cgo / JNI / N-API binding would do.
  *   gcc -O2 -Iinclude examples/msm_demo.c -Lmontgomery_amd -lmsm_hip -Wl,-rpath,'$ORIGIN/../montgomery_amd' -o examples/msm_demo
- *   examples/msm_demo [log2_n] [curve id]
+ *   examples/msm_demo [log2_n] [curve id or name: bls12-377, ed-on-bls12-377, bls12-381, pallas, bn254, grumpkin, vesta]
  * Generates N points and scalars on the GPU, runs the MSM twice with different window sizes (the result is a
  * group element: it must not depend on c), then once more as K one-window shards recombined with
  * msm_combine_curve, the way the ranks of a multi-GPU run do.  Exit code 0 = all three agree. */
@@ -14,9 +14,24 @@ static void die(msm_ctx* ctx, const char* what, int rc) {
   exit(1);
 }
 
+static int curve_of(const char* s) {
+  static const char* names[] = {"bls12-377", "ed-on-bls12-377", "bls12-381", "pallas", "bn254", "grumpkin", "vesta"};   /* by curve id */
+  for (int i = 0; i < (int)(sizeof names / sizeof names[0]); i++)
+    if (strcmp(s, names[i]) == 0) return i;
+  char* end = NULL;
+  const long id = strtol(s, &end, 10);
+  if (end == s || *end || id < 0 || id >= (long)(sizeof names / sizeof names[0])) {
+    fprintf(stderr, "unknown curve '%s': a curve id 0 .. 6 or one of", s);
+    for (int i = 0; i < (int)(sizeof names / sizeof names[0]); i++) fprintf(stderr, " %s", names[i]);
+    fprintf(stderr, "\n");
+    exit(1);
+  }
+  return (int)id;
+}
+
 int main(int argc, char** argv) {
   const int lg = argc > 1 ? atoi(argv[1]) : 16;
-  const int curve = argc > 2 ? atoi(argv[2]) : MSM_CURVE_BLS12_377_G1;
+  const int curve = argc > 2 ? curve_of(argv[2]) : MSM_CURVE_BLS12_377_G1;
   const uint64_t n = 1ull << lg;
   msm_ctx* ctx = NULL;
   int rc = msm_ctx_create(&ctx, curve, 0);

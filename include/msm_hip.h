@@ -43,10 +43,16 @@ enum {
   MSM_CURVE_BLS12_377_G1 = 0,     /* Weierstrass + GLV, batched-affine path: src/msm-batched-affine.ts */
   MSM_CURVE_ED_ON_BLS12_377 = 1,  /* twisted Edwards, generic path: src/msm-basic.ts */
   MSM_CURVE_BLS12_381_G1 = 2,     /* Weierstrass + GLV, batched-affine path; src/concrete/bls12-381.params.ts */
-  MSM_CURVE_PALLAS = 3            /* same path on 9 limbs / 8 packed words, src/concrete/pasta.params.ts (the reference sizes
+  MSM_CURVE_PALLAS = 3,           /* same path on 9 limbs / 8 packed words, src/concrete/pasta.params.ts (the reference sizes
                                    * limbs per field, src/parallel.ts:53-57): coordinates at this ABI -- wire points, test
                                    * operands, the used part of msm_result.x / .y -- are 32-byte little-endian integers, as for
                                    * the Edwards curve; window sums stay 144-byte (X, Y, Z) records for every curve */
+  /* The two curve cycles of recursive provers, not in the reference: the Pallas path (9 limbs / 8 words, 32-byte coordinates,
+   * GLV, cofactor 1) with their own constants.  New enum values only: MSM_ABI_VERSION and the struct sizes are unchanged, a
+   * binding detects them by msm_ctx_create not answering MSM_ERR_ARG. */
+  MSM_CURVE_BN254_G1 = 4,         /* alt_bn128 (EIP-196): y^2 = x^3 + 3, generator (1, 2) */
+  MSM_CURVE_GRUMPKIN = 5,         /* BN254's cycle partner: y^2 = x^3 - 17 over BN254's scalar field, of order BN254's p */
+  MSM_CURVE_VESTA = 6             /* Pallas' cycle partner: y^2 = x^3 + 5 over Pallas' scalar field, generator (-1, 2) */
 };
 
 /* Layout version of this header.  The symbol names do not change when a struct grows or an argument changes meaning, so a
@@ -162,12 +168,14 @@ int msm_set_points(msm_ctx* ctx, const void* points, uint64_t n, int on_device, 
  *                                 0x20 sign = y > (p-1)/2.  Identity: c0 00 .. 00
  *   BLS12-377 G1 (arkworks)       48 bytes, x little-endian; last byte: 0x80 sign = y > (p-1)/2, 0x40 infinity.
  *                                 Identity: last byte 0x40, every other byte 0
- *   Pallas (pasta / halo2)        32 bytes, x little-endian; bit 255 sign = y odd.  Identity: 32 zero bytes
+ *   Pallas, Vesta (pasta / halo2) 32 bytes, x little-endian; bit 255 sign = y odd.  Identity: 32 zero bytes
+ *   BN254 G1, Grumpkin (arkworks) 32 bytes, x little-endian; last byte: 0x80 sign = y > (p-1)/2, 0x40 infinity (254-bit
+ *                                 moduli leave both bits free).  Identity: last byte 0x40, every other byte 0
  *   Ed-on-BLS12-377 (arkworks)    32 bytes, y little-endian; bit 255 sign = x > (r-1)/2.  Identity: y = 1, sign 0
  * Decoding refuses a coordinate >= the modulus, invalid flags (a missing 0x80 on BLS12-381; infinity with any other bit set;
- * both flags on BLS12-377; bits the layout does not use), an x (Edwards: y) without a curve point, and a sign bit set on a
+ * both flags on BLS12-377 / BN254 / Grumpkin; bits the layout does not use), an x (Edwards: y) without a curve point, and a sign bit set on a
  * root that is 0.  Validation: NONE; CURVE = the curve equation (a decoded point always satisfies it); SUBGROUP = the curve
- * equation and [q] P = O (Pallas: cofactor 1, the curve equation is enough). */
+ * equation and [q] P = O (Pallas, Vesta, BN254 G1, Grumpkin: cofactor 1, the curve equation is enough). */
 enum { MSM_POINTS_UNCOMPRESSED = 0, MSM_POINTS_COMPRESSED = 1 };
 enum { MSM_VALIDATE_NONE = 0, MSM_VALIDATE_CURVE = 1, MSM_VALIDATE_SUBGROUP = 2 };
 /* msm_set_points with a format and a validation level.  UNCOMPRESSED + CURVE is msm_set_points(check_curve = 1), UNCOMPRESSED

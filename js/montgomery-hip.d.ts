@@ -96,6 +96,10 @@ export const Weierstraß: typeof Weierstrass;
 export const bls12377Params: CurveParams;
 export const bls12381Params: CurveParams;
 export const pallasParams: CurveParams;
+/** BN254 G1 (alt_bn128), Grumpkin and Vesta: 32-byte coordinates, like Pallas */
+export const bn254Params: CurveParams;
+export const grumpkinParams: CurveParams;
+export const vestaParams: CurveParams;
 export const edOnBls12377Params: CurveParams;
 
 /** shared body of the per-curve entries js/submission-bls377.js and js/submission.js, which export the reference's exact

@@ -26,6 +26,22 @@ const pallasParams = {
   modulus: BigInt("0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001"),
   order: BigInt("0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001"),
 };
+// the two curve cycles of recursive provers (not in the reference): 32-byte coordinates like Pallas
+const bn254Params = {
+  label: "bn254",   // alt_bn128 G1 (EIP-196): y^2 = x^3 + 3, generator (1, 2)
+  modulus: BigInt("0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47"),
+  order: BigInt("0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001"),
+};
+const grumpkinParams = {
+  label: "grumpkin",   // y^2 = x^3 - 17 over BN254's scalar field
+  modulus: bn254Params.order,
+  order: bn254Params.modulus,
+};
+const vestaParams = {
+  label: "vesta",   // y^2 = x^3 + 5 over Pallas' scalar field, generator (-1, 2)
+  modulus: pallasParams.order,
+  order: pallasParams.modulus,
+};
 const edOnBls12377Params = {
   label: "ed-on-bls12-377",
   modulus: BigInt("0x12ab655e9a2ca55660b44d1e5c37b00159aa76fed00000010a11800000000001"),
@@ -254,11 +270,13 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
   return { params, Parallel, Field, Scalar, Affine, Projective, Curve, Bigint, close() { hip.destroyContext(ctx); } };
 }
 
-const weierstrassIds = { "bls12-377": hip.CURVE_BLS12_377_G1, "bls12-381": hip.CURVE_BLS12_381_G1, "pallas": hip.CURVE_PALLAS };
+const weierstrassIds = { "bls12-377": hip.CURVE_BLS12_377_G1, "bls12-381": hip.CURVE_BLS12_381_G1, "pallas": hip.CURVE_PALLAS,
+                         "bn254": hip.CURVE_BN254_G1, "grumpkin": hip.CURVE_GRUMPKIN, "vesta": hip.CURVE_VESTA };
+const coordBytesOf = (params) => (params.modulus >> BigInt(256)) === BigInt(0) ? 32 : 48;   // per field, as the C ABI sizes them
 const Weierstrass = {
   create(params, device) {
     if (!(params.label in weierstrassIds)) throw new Error(`curve ${params.label} has no device constants`);
-    return createCurve(params, weierstrassIds[params.label], params.label === "pallas" ? 32 : 48, device);
+    return createCurve(params, weierstrassIds[params.label], coordBytesOf(params), device);
   },
 };
 const TwistedEdwards = { create(params, device) { return createCurve(params, hip.CURVE_ED_ON_BLS12_377, 32, device); } };
@@ -294,4 +312,4 @@ async function compute_msm_on(curve, coordBytes, inputPoints, inputScalars) {
 async function startThreads(_n) {}
 async function stopThreads() {}
 
-module.exports = { hip, startThreads, stopThreads, Weierstrass, Weierstraß: Weierstrass /* the reference's spelling, src/parallel.ts:40 */, TwistedEdwards, bls12377Params, bls12381Params, pallasParams, edOnBls12377Params, compute_msm_on, compute_msm: compute_msm_on, leBytesToBigint, bigintToLeBytes };
+module.exports = { hip, startThreads, stopThreads, Weierstrass, Weierstraß: Weierstrass /* the reference's spelling, src/parallel.ts:40 */, TwistedEdwards, bls12377Params, bls12381Params, pallasParams, bn254Params, grumpkinParams, vestaParams, edOnBls12377Params, compute_msm_on, compute_msm: compute_msm_on, leBytesToBigint, bigintToLeBytes };

@@ -17,6 +17,10 @@ CURVE_BLS12_377_G1 = 0
 CURVE_ED_ON_BLS12_377 = 1
 CURVE_BLS12_381_G1 = 2
 CURVE_PALLAS = 3
+CURVE_BN254_G1 = 4   # the two curve cycles: 32-byte coordinates like Pallas
+CURVE_GRUMPKIN = 5
+CURVE_VESTA = 6
+CURVES_32_BYTE = (CURVE_ED_ON_BLS12_377, CURVE_PALLAS, CURVE_BN254_G1, CURVE_GRUMPKIN, CURVE_VESTA)   # 9 limbs / 8 words
 ABI_VERSION = 8   # MSM_ABI_VERSION of the include/msm_hip.h this binding was written against
 N_PHASES = 8
 PHASE_NAMES = ("total", "upload", "digits", "sort", "accumulate", "reduce", "final", "accumulate_round1")

@@ -89,9 +89,48 @@ PALLAS_PARAMS = WeierstrassParams(  # src/concrete/pasta.params.ts:10-53
     endomorphism=(pow(5, (_PALLAS_Q - 1) // 3, _PALLAS_Q), pow(pow(5, (_PALLAS_P - 1) // 3, _PALLAS_P), 2, _PALLAS_P)),
 )
 
+# The two curve cycles of recursive provers (not in the reference).  BN254 G1 is alt_bn128 of EIP-196; Grumpkin swaps its two
+# fields, Vesta swaps those of Pallas.  (lambda, beta): the cube roots of unity with lambda G = (beta x, y).
+_BN254_P = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
+_BN254_Q = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
+BN254_PARAMS = WeierstrassParams(
+    label="bn254",
+    modulus=_BN254_P,
+    order=_BN254_Q,
+    cofactor=1,
+    a=0,
+    b=3,
+    generator=(1, 2),
+    endomorphism=(0xB3C4D79D41A917585BFC41088D8DAAA78B17EA66B99C90DD, 0x59E26BCEA0D48BACD4F263F1ACDB5C4F5763473177FFFFFE),
+)
+GRUMPKIN_PARAMS = WeierstrassParams(
+    label="grumpkin",
+    modulus=_BN254_Q,
+    order=_BN254_P,
+    cofactor=1,
+    a=0,
+    b=_BN254_Q - 17,
+    generator=(1, 0x2CF135E7506A45D632D270D45F1181294833FC48D823F272C),
+    endomorphism=(0x30644E72E131A0295E6DD9E7E0ACCCB0C28F069FBB966E3DE4BD44E5607CFD48,
+                  0x30644E72E131A029048B6E193FD84104CC37A73FEC2BC5E9B8CA0B2D36636F23),
+)
+VESTA_PARAMS = WeierstrassParams(
+    label="vesta",
+    modulus=_PALLAS_Q,
+    order=_PALLAS_P,
+    cofactor=1,
+    a=0,
+    b=5,
+    generator=(_PALLAS_Q - 1, 2),
+    endomorphism=(0x2D33357CB532458ED3552A23A8554E5005270D29D19FC7D27B7FD22F0201B547,
+                  0x397E65A7D7C1AD71AEE24B27E308F0A61259527EC1D4752E619D1840AF55F1B1),
+)
+BN254, GRUMPKIN, VESTA = BN254_PARAMS, GRUMPKIN_PARAMS, VESTA_PARAMS   # Weierstrass.create(BN254), compute_msm(..., BN254)
+
 # curves with device constants (montgomery_amd/csrc/constants_gen.h), by label
 _WEIERSTRASS_CURVE_IDS = {"bls12-377": _lib.CURVE_BLS12_377_G1, "bls12-381": _lib.CURVE_BLS12_381_G1,
-                          "pallas": _lib.CURVE_PALLAS}
+                          "pallas": _lib.CURVE_PALLAS, "bn254": _lib.CURVE_BN254_G1, "grumpkin": _lib.CURVE_GRUMPKIN,
+                          "vesta": _lib.CURVE_VESTA}
 
 
 @dataclass(frozen=True)
@@ -171,7 +210,7 @@ class MsmContext:
         self.n_points = 0
         self._cur_set = 0
         self._set_sizes: Dict[int, int] = {0: 0}
-        self.coord_bytes = 32 if curve in (_lib.CURVE_ED_ON_BLS12_377, _lib.CURVE_PALLAS) else 48   # per field, as the reference sizes them
+        self.coord_bytes = 32 if curve in _lib.CURVES_32_BYTE else 48   # per field, as the reference sizes them
         self._gen_buf, self._gen_cap = 0, 0   # device buffer of generate_scalars(into=0)
 
     def close(self) -> None:
@@ -619,7 +658,7 @@ class MsmContext:
 
     def test_fp_raw(self, op: int, a_limbs: Sequence[Sequence[int]], b_limbs: Sequence[Sequence[int]]) -> List[List[int]]:
         """fe_mul / fe_sqr on raw 30-bit-limb operands (lists of NL ints per element); returns the raw result limbs."""
-        nl = 9 if self.curve in (_lib.CURVE_ED_ON_BLS12_377, _lib.CURVE_PALLAS) else 13   # limbs are sized per field
+        nl = 9 if self.curve in _lib.CURVES_32_BYTE else 13   # limbs are sized per field
         n = len(a_limbs)
         A = (C.c_uint32 * (nl * n))(*[w for e in a_limbs for w in e])
         B = (C.c_uint32 * (nl * n))(*[w for e in b_limbs for w in e])
@@ -1057,13 +1096,22 @@ def compute_msm_ed(inputPoints, inputScalars, curve: Optional[TwistedEdwards] = 
     return {"x": res.x, "y": res.y}
 
 
-def compute_msm(inputPoints, inputScalars, curve: Optional[Weierstrass] = None) -> Dict[str, int]:
+def compute_msm(inputPoints, inputScalars, curve=None) -> Dict[str, int]:
     """ZPrize entry point, scripts/zprize23/submission-bls377.ts:20-65.
 
-    inputPoints: bytes (n x 96, x || y little-endian) or a list of {"x", "y", "isZero"} dicts;
-    inputScalars: bytes (n x 32 little-endian) or a list of ints.  Returns {"x": int, "y": int}.
+    inputPoints: bytes (x || y little-endian at the curve's coordinate width: n x 96, or n x 64 on a 32-byte curve) or a list of
+    {"x", "y", "isZero"} dicts; inputScalars: bytes (n x 32 little-endian) or a list of ints.  Returns {"x": int, "y": int}.
+    curve: a curve module (Weierstrass.create), or curve parameters (BN254, PALLAS_PARAMS, ...) for a module that lives for
+    this call; default BLS12-377.
     """
+    if isinstance(curve, WeierstrassParams):
+        cv = Weierstrass.create(curve)
+        try:
+            return compute_msm(inputPoints, inputScalars, cv)
+        finally:
+            cv.context.close()
     cv = curve or BLS12377._get()
+    wb = cv.Parallel._wire_bytes
     if isinstance(inputScalars, (bytes, bytearray, memoryview)):
         sbytes = bytes(inputScalars)
     else:
@@ -1075,15 +1123,15 @@ def compute_msm(inputPoints, inputScalars, curve: Optional[Weierstrass] = None) 
         chunks = []
         for P in inputPoints:
             if P.get("isZero"):
-                chunks.append(b"\0" * 96)
+                chunks.append(b"\0" * (2 * wb))
             else:
-                chunks.append(int(P["x"]).to_bytes(48, "little") + int(P["y"]).to_bytes(48, "little"))
+                chunks.append(int(P["x"]).to_bytes(wb, "little") + int(P["y"]).to_bytes(wb, "little"))
         pbytes = b"".join(chunks)
     par = cv.Parallel
     with par.getPointer(len(pbytes)) as pp, par.getScalarPointer(len(sbytes)) as sp:   # freed on every path, errors included
         par.pointsFromBytes(pp, pbytes, n)
         par.scalarsFromBytes(sp, sbytes, n)
-        same = n > 1 and pbytes[:96] == pbytes[96:192]
+        same = n > 1 and pbytes[: 2 * wb] == pbytes[2 * wb : 4 * wb]
         out = par.msm(sp, pp, n) if same else par.msmUnsafe(sp, pp, n)
         res = out["result"]
     return {"x": res.x, "y": res.y}

@@ -406,6 +406,9 @@ __global__ void __launch_bounds__(BA_THREADS, BA_WAVES) k_batch_add(BatchArgs a)
     if (wave == 0) {
       Fe<F> t, ti;
       fe_mul<F>(t, e, acc);
+      // fe_inv wants t != 0 mod p in any representative (p itself, the non-canonical zero, is not inverted to 0): every
+      // denominator is canonical and non-zero -- (x2 - x1) mod p of pk_add with same_x handled apart, 2 y of a doubling
+      // with y != 0, or one -- and fe_mul of factors that are non-zero mod p cannot return a multiple of the prime p
       fe_inv<F>(ti, t);                // 1 / (a0 a1 a2 a3)
 #pragma unroll
       for (int l = 0; l < NLI; l++) xch[l * BA_THREADS + lane] = ti.l[l];

@@ -737,7 +737,8 @@ MSM_DEV void fe_signed_negate(int32_t (&v)[N], int32_t mask) {  // v = mask ? -v
   }
 }
 
-// r = a^-1 in Montgomery form (a in Montgomery form, any value < 2p; a == 0 mod p gives 0).
+// r = a^-1 in Montgomery form (a in Montgomery form, any value < 2p; a == 0 gives 0 -- the other representative of zero,
+// p itself, gives an unspecified value: the kernels invert products of non-zero differences and canonical values only).
 template <class C>
 MSM_DEV void fe_inv(Fe<C>& r, const Fe<C>& a) {
   constexpr int N = C::NL;

@@ -29,6 +29,20 @@ LAMBDA_PALLAS = pow(5, (FQ_PALLAS - 1) // 3, FQ_PALLAS)
 BETA_PALLAS = pow(pow(5, (FP_PALLAS - 1) // 3, FP_PALLAS), 2, FP_PALLAS)
 GX_PALLAS = 1
 GY_PALLAS = 0x1B74B5A30A12937C53DFA9F06378EE548F655BD4333D477119CF7A23CAED2ABB
+# BN254 G1 (alt_bn128, EIP-196): y^2 = x^3 + 3, generator (1, 2).  Grumpkin, its cycle partner: y^2 = x^3 - 17 over BN254's
+# scalar field, of order BN254's p.  Vesta, the partner of Pallas: y^2 = x^3 + 5 over Pallas' scalar field, generator (-1, 2).
+# lambda / beta: the pair of primitive cube roots of unity (mod q / mod p) with lambda G = (beta x_G, y_G), asserted in main()
+FP_BN254 = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
+FQ_BN254 = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
+LAMBDA_BN254 = 0xB3C4D79D41A917585BFC41088D8DAAA78B17EA66B99C90DD
+BETA_BN254 = 0x59E26BCEA0D48BACD4F263F1ACDB5C4F5763473177FFFFFE
+GX_BN254, GY_BN254 = 1, 2
+LAMBDA_GRUMPKIN = 0x30644E72E131A0295E6DD9E7E0ACCCB0C28F069FBB966E3DE4BD44E5607CFD48
+BETA_GRUMPKIN = 0x30644E72E131A029048B6E193FD84104CC37A73FEC2BC5E9B8CA0B2D36636F23
+GX_GRUMPKIN, GY_GRUMPKIN = 1, 0x2CF135E7506A45D632D270D45F1181294833FC48D823F272C
+LAMBDA_VESTA = 0x2D33357CB532458ED3552A23A8554E5005270D29D19FC7D27B7FD22F0201B547
+BETA_VESTA = 0x397E65A7D7C1AD71AEE24B27E308F0A61259527EC1D4752E619D1840AF55F1B1
+GX_VESTA, GY_VESTA = FQ_PALLAS - 1, 2
 ED_D = 3021
 EDGX = 0x9F1B5A5BAF6ACF06FED91C9AE9EBFA06068DD2835790980894E2328F3EBCA05
 EDGY = 0x9A20DF36571AC3CD906B256080BA8454453C177AAF3131BB50A67BF1A806781
@@ -110,6 +124,50 @@ def egcd_stop_early(lam, q):
     return v00, v01, v10, v11
 
 
+def glv_max_bits(lam, q, w=29, n=9):
+    """Bit length bound of the halves glv_decompose returns: the error bounds of src/wasm/glv.ts:216-226 in exact rationals."""
+    from fractions import Fraction
+    n0 = (n + 1) // 2
+    m, k = n0 * w, (n - n0) * w
+    v00, v01, v10, v11 = egcd_stop_early(lam, q)
+    det = v00 * v11 - v10 * v01
+    m0 = tdiv((1 << (m + k)) * -v11, det)
+    m1 = tdiv((1 << (m + k)) * v10, det)
+    m0err = abs(Fraction((1 << (m + k)) * -v11 - m0 * det, det))
+    m1err = abs(Fraction((1 << (m + k)) * v10 - m1 * det, det))
+    x0err = Fraction(1, 2) + Fraction(m0, 1 << m) + m0err * Fraction(q, 1 << (m + k))
+    x1err = Fraction(1, 2) + Fraction(m1, 1 << m) + m1err * Fraction(q, 1 << (m + k))
+    bound = max(x0err * abs(v00) + x1err * abs(v01), x0err * abs(v10) + x1err * abs(v11))
+    return max(-(-bound.numerator // bound.denominator) - 1, 1).bit_length()
+
+
+def aff_scale(k, P, p):
+    """k P on y^2 = x^3 + b by plain double-and-add (affine, None = identity): only for the endomorphism check below."""
+    def add(A, B):
+        if A is None or B is None:
+            return A or B
+        if A[0] == B[0]:
+            if (A[1] + B[1]) % p == 0:
+                return None
+            m = 3 * A[0] * A[0] * pow(2 * A[1], -1, p) % p
+        else:
+            m = (B[1] - A[1]) * pow(B[0] - A[0], -1, p) % p
+        x = (m * m - A[0] - B[0]) % p
+        return x, (m * (A[0] - x) - A[1]) % p
+    acc = None
+    for bit in bin(k)[2:]:
+        acc = add(acc, acc)
+        if bit == "1":
+            acc = add(acc, P)
+    return acc
+
+
+def check_endomorphism(p, q, b, gx, gy, lam, beta):
+    assert (gy * gy - gx ** 3 - b) % p == 0 and aff_scale(q, (gx, gy), p) is None
+    assert lam != 1 and pow(lam, 3, q) == 1 and beta != 1 and pow(beta, 3, p) == 1
+    assert aff_scale(lam, (gx, gy), p) == (beta * gx % p, gy)
+
+
 def tdiv(a, b):
     q = abs(a) // abs(b)
     return q if (a >= 0) == (b >= 0) else -q
@@ -146,9 +204,21 @@ def main():
     # Pallas runs through the same 13-limb / 12-word code path with zero upper limbs (R = 2^390 is a valid
     # Montgomery radix for any odd p < R): a curve "by constants only", at the 381-bit path's cost
     out += field_block("FpPallas", FP_PALLAS, 9, 8, {"BETAW": BETA_PALLAS, "BW": 5, "GXW": GX_PALLAS, "GYW": GY_PALLAS})
+    # the two curve cycles: 254- / 255-bit fields on 9 limbs / 8 words like Pallas.  BN254's p and q are not 1 mod 2^30: the
+    # general reduction row of fe_reduce_row at 9 limbs.  Vesta's p (Pallas' q) is, like Pallas' own.
+    for args in ((FP_BN254, FQ_BN254, 3, GX_BN254, GY_BN254, LAMBDA_BN254, BETA_BN254),
+                 (FQ_BN254, FP_BN254, -17, GX_GRUMPKIN, GY_GRUMPKIN, LAMBDA_GRUMPKIN, BETA_GRUMPKIN),
+                 (FQ_PALLAS, FP_PALLAS, 5, GX_VESTA, GY_VESTA, LAMBDA_VESTA, BETA_VESTA)):
+        check_endomorphism(*args)
+    out += field_block("FpBn254", FP_BN254, 9, 8, {"BETAW": BETA_BN254, "BW": 3, "GXW": GX_BN254, "GYW": GY_BN254})
+    out += field_block("FpGrumpkin", FQ_BN254, 9, 8, {"BETAW": BETA_GRUMPKIN, "BW": FQ_BN254 - 17, "GXW": GX_GRUMPKIN, "GYW": GY_GRUMPKIN})
+    out += field_block("FpVesta", FQ_PALLAS, 9, 8, {"BETAW": BETA_VESTA, "BW": 5, "GXW": GX_VESTA, "GYW": GY_VESTA})
     out += glv_block()
     out += glv_block("GlvPallas", LAMBDA_PALLAS, FQ_PALLAS, 127)
     out += glv_block("GlvBls381", LAMBDA381, FR381, 127)
+    out += glv_block("GlvBn254", LAMBDA_BN254, FQ_BN254, glv_max_bits(LAMBDA_BN254, FQ_BN254))
+    out += glv_block("GlvGrumpkin", LAMBDA_GRUMPKIN, FP_BN254, glv_max_bits(LAMBDA_GRUMPKIN, FP_BN254))
+    out += glv_block("GlvVesta", LAMBDA_VESTA, FP_PALLAS, glv_max_bits(LAMBDA_VESTA, FP_PALLAS))
     out += arr("FR377_Q", limbs(FR377, 8, 32)).replace("  static", "static")
     out += arr("FRED_Q", limbs(FR_ED, 8, 32)).replace("  static", "static")
     out += "\n}  // namespace msm\n"

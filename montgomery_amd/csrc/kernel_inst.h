@@ -33,7 +33,7 @@
 #ifdef MSM_CURVE_TU
 MSM_CURVE_KERNELS(MSM_DEFINE_KERNEL, msm::MSM_CURVE_TU)
 #else
-MSM_CURVE_KERNELS(MSM_EXTERN_KERNEL, msm::CvBls377)
-MSM_CURVE_KERNELS(MSM_EXTERN_KERNEL, msm::CvBls381)
-MSM_CURVE_KERNELS(MSM_EXTERN_KERNEL, msm::CvPallas)
+#define MSM_EXTERN_CURVE(ID, CV) MSM_CURVE_KERNELS(MSM_EXTERN_KERNEL, msm::CV)
+MSM_W_CURVES(MSM_EXTERN_CURVE)
+#undef MSM_EXTERN_CURVE
 #endif

@@ -14,9 +14,7 @@ uint32_t msm_abi_struct_bytes(int which) { return which == 0 ? (uint32_t)sizeof(
 int msm_ctx_create(msm_ctx** out, int curve, int device) {
   if (!out) return MSM_ERR_ARG;
   *out = nullptr;
-  if (curve != MSM_CURVE_BLS12_377_G1 && curve != MSM_CURVE_ED_ON_BLS12_377 && curve != MSM_CURVE_BLS12_381_G1 &&
-      curve != MSM_CURVE_PALLAS)
-    return MSM_ERR_ARG;
+  if (!curve_info_or_null(curve)) return MSM_ERR_ARG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return MSM_ERR_NO_DEVICE;
   msm_ctx* ctx = new (std::nothrow) msm_ctx();

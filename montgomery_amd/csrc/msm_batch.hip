@@ -15,6 +15,7 @@ namespace msmi {
 // B = 16 at 2^12 .. 2^18 points (2^14 x 16: 3.44 ms against 7.35 at 16 bits; 2^18 x 64: 61.7 / 63.9) and at B = 4 up to 2^14
 // points (2^14: 1.88 / 2.04), but keeps 16 at B = 4 from 2^16 (2.50 / 2.63).  Ed-on-BLS12-377 wants 12 bits (2^12 x 16: 1.35 ms
 // against 1.78 at the cost model's 7; 2^14 x 64: 5.98 / 6.29 at its 9) and 14 from 2^17 points at B >= 16 (2^18 x 64: 40.9 / 43.1).  Other inputs (fewer than 2^12 points, no_glv) keep msm_run's window.
+// BN254 G1, Grumpkin and Vesta run under the same rule, model only (not swept).
 int pick_window_batch(bool te, uint64_t n, uint32_t B, int glv_max_bits) {
   if (te) return n < 4096 ? pick_window(te, n, glv_max_bits) : (n >= (1ull << 17) && B >= 16) ? 14 : 12;
   if (glv_max_bits && n >= 4096 && (B >= 16 || n <= (1ull << 14))) return 13;

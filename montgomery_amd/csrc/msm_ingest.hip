@@ -151,7 +151,18 @@ void compress_one(int curve, const uint8_t* xy, uint8_t* out) {
       if (le_greater(xy + 48, Fp377::HALFW, 12)) out[47] |= 0x80;
       return;
     }
+    case MSM_CURVE_BN254_G1:
+    case MSM_CURVE_GRUMPKIN: {   // the BLS12-377 rules at 32 bytes
+      bool zero = true;
+      for (int b = 0; b < 64; b++) zero &= xy[b] == 0;
+      memset(out, 0, 32);
+      if (zero) { out[31] = 0x40; return; }
+      memcpy(out, xy, 32);
+      if (le_greater(xy + 32, curve == MSM_CURVE_BN254_G1 ? FpBn254::HALFW : FpGrumpkin::HALFW, 8)) out[31] |= 0x80;
+      return;
+    }
     case MSM_CURVE_PALLAS:   // the identity reads back as (0, 0): x = 0, y even
+    case MSM_CURVE_VESTA:
       memcpy(out, xy, 32);
       if (xy[32] & 1) out[31] |= 0x80;
       return;

@@ -100,21 +100,41 @@ struct CurveInfo {
   const uint32_t* gy;
   int glv_max_bits;     // Scalar.maxBits after decomposition, src/wasm/glv.ts:216-226
   int q_bits;           // bit length of q
+  int nl, nw;           // 30-bit limbs in registers, packed words per coordinate in memory
 };
 
-inline const CurveInfo& curve_info(int curve) {
-  static const CurveInfo bls377 = {msm::Fp377::PW, msm::GlvBls377::Q, msm::Fp377::GXW, msm::Fp377::GYW, msm::GlvBls377::MAX_BITS, 253};
-  static const CurveInfo bls381 = {msm::Fp381::PW, msm::GlvBls381::Q, msm::Fp381::GXW, msm::Fp381::GYW, msm::GlvBls381::MAX_BITS, 255};
-  // Pallas lives on 8 packed words; the host side reads 12 (zero-extended copies)
-  static uint32_t pal_p[12], pal_gx[12], pal_gy[12];
-  static const bool pal_init = [] {
-    for (int i = 0; i < 8; i++) { pal_p[i] = msm::FpPallas::PW[i]; pal_gx[i] = msm::FpPallas::GXW[i]; pal_gy[i] = msm::FpPallas::GYW[i]; }
-    return true;
+inline int bit_length8(const uint32_t* w) {   // of an 8-word integer
+  for (int b = 255; b >= 0; b--)
+    if ((w[b / 32] >> (b % 32)) & 1u) return b + 1;
+  return 0;
+}
+
+// a Weierstrass configuration's constants, the 8-word fields zero-extended to the 12 words the host side reads
+template <class CV>
+inline const CurveInfo& weierstrass_info() {
+  using F = typename CV::F;
+  static uint32_t pw[12], gx[12], gy[12];
+  static const CurveInfo info = [] {
+    for (int i = 0; i < F::NW; i++) { pw[i] = F::PW[i]; gx[i] = F::GXW[i]; gy[i] = F::GYW[i]; }
+    return CurveInfo{pw, CV::G::Q, gx, gy, CV::G::MAX_BITS, bit_length8(CV::G::Q), F::NL, F::NW};
   }();
-  (void)pal_init;
-  static const CurveInfo pallas = {pal_p, msm::GlvPallas::Q, pal_gx, pal_gy, msm::GlvPallas::MAX_BITS, 255};
-  static const CurveInfo ed377 = {msm::Fp253::PW, msm::FRED_Q, nullptr, nullptr, 251, 251};
-  return curve == MSM_CURVE_BLS12_381_G1 ? bls381 : curve == MSM_CURVE_PALLAS ? pallas : curve == MSM_CURVE_ED_ON_BLS12_377 ? ed377 : bls377;
+  return info;
+}
+
+// nullptr: no such curve id
+inline const CurveInfo* curve_info_or_null(int curve) {
+  static const CurveInfo ed377 = {msm::Fp253::PW, msm::FRED_Q, nullptr, nullptr, 251, 251, msm::Fp253::NL, msm::Fp253::NW};
+  switch (curve) {
+#define MSM_INFO_CASE(ID, CV) case ID: return &weierstrass_info<msm::CV>();
+    MSM_W_CURVES(MSM_INFO_CASE)
+#undef MSM_INFO_CASE
+    case MSM_CURVE_ED_ON_BLS12_377: return &ed377;
+  }
+  return nullptr;
+}
+inline const CurveInfo& curve_info(int curve) {
+  const CurveInfo* ci = curve_info_or_null(curve);
+  return ci ? *ci : *curve_info_or_null(MSM_CURVE_BLS12_377_G1);
 }
 
 // One helper thread per context, started with it: the second window group of a big MSM runs here (the calling thread
@@ -271,8 +291,8 @@ struct msm_ctx {
   bool is_te() const { return curve == MSM_CURVE_ED_ON_BLS12_377; }
   // per-field sizes (the reference sizes limbs per field, src/parallel.ts:53-57): 30-bit limbs in registers, packed words
   // per coordinate in memory, and the coordinate bytes at the ABI (wire points, results, test operands)
-  int nl() const { return (curve == MSM_CURVE_PALLAS || is_te()) ? 9 : 13; }
-  int nw() const { return (curve == MSM_CURVE_PALLAS || is_te()) ? 8 : 12; }
+  int nl() const { return msmi::curve_info(curve).nl; }
+  int nw() const { return msmi::curve_info(curve).nw; }
   size_t coord_bytes() const { return (size_t)nw() * 4; }
   uint64_t row_words() const { return is_te() ? (uint64_t)msm::te::TE_ROW_WORDS : (uint64_t)msm::ROW_WORDS; }   // of a point row
 
@@ -298,18 +318,19 @@ struct msm_ctx {
 };
 
 // curve dispatch for the templated Weierstrass kernels
-#define W_LAUNCH(ctx, KERNEL, ...)                                                         \
-  do {                                                                                     \
-    if ((ctx)->curve == MSM_CURVE_BLS12_381_G1) hipLaunchKernelGGL((KERNEL<msm::CvBls381>), __VA_ARGS__); \
-    else if ((ctx)->curve == MSM_CURVE_PALLAS) hipLaunchKernelGGL((KERNEL<msm::CvPallas>), __VA_ARGS__);  \
-    else hipLaunchKernelGGL((KERNEL<msm::CvBls377>), __VA_ARGS__);                          \
-  } while (0)
-#define W_LAUNCH_MODE(ctx, KERNEL, MODE, ...)                                              \
-  do {                                                                                     \
-    if ((ctx)->curve == MSM_CURVE_BLS12_381_G1) hipLaunchKernelGGL((KERNEL<msm::CvBls381, MODE>), __VA_ARGS__); \
-    else if ((ctx)->curve == MSM_CURVE_PALLAS) hipLaunchKernelGGL((KERNEL<msm::CvPallas, MODE>), __VA_ARGS__);  \
-    else hipLaunchKernelGGL((KERNEL<msm::CvBls377, MODE>), __VA_ARGS__);                    \
-  } while (0)
+template <class Fn>
+inline void for_weierstrass_curve(int curve, Fn&& fn) {
+  switch (curve) {
+#define MSM_DISPATCH_CASE(ID, CV) case ID: fn(msm::CV{}); break;
+    MSM_W_CURVES(MSM_DISPATCH_CASE)
+#undef MSM_DISPATCH_CASE
+    default: throw msmi::HipFail{hipErrorInvalidValue, "Weierstrass kernel launch for a curve id outside MSM_W_CURVES", __LINE__, __FILE__};
+  }
+}
+#define W_LAUNCH(ctx, KERNEL, ...) \
+  for_weierstrass_curve((ctx)->curve, [&](auto cv_) { hipLaunchKernelGGL((KERNEL<decltype(cv_)>), __VA_ARGS__); })
+#define W_LAUNCH_MODE(ctx, KERNEL, MODE, ...) \
+  for_weierstrass_curve((ctx)->curve, [&](auto cv_) { hipLaunchKernelGGL((KERNEL<decltype(cv_), MODE>), __VA_ARGS__); })
 
 // point rows -> tree planes (test ops), by the packed words of the curve's coordinates
 #define ROWS_TO_PLANES(ctx, ...)                                                                       \

@@ -37,6 +37,20 @@ namespace msm {
 struct CvBls377 { using F = Fp377; using G = GlvBls377; };   // src/concrete/bls12-377.params.ts
 struct CvBls381 { using F = Fp381; using G = GlvBls381; };   // src/concrete/bls12-381.params.ts
 struct CvPallas { using F = FpPallas; using G = GlvPallas; }; // src/concrete/pasta.params.ts (255-bit p)
+// the two curve cycles (not in the reference), on the 9-limb / 8-word layout of Pallas: BN254 G1 and Grumpkin (254-bit fields,
+// p != 1 mod 2^30: the general row of fe_reduce_row; 126-bit GLV halves like BLS12-377), Vesta (Pallas' arithmetic, other constants)
+struct CvBn254 { using F = FpBn254; using G = GlvBn254; };
+struct CvGrumpkin { using F = FpGrumpkin; using G = GlvGrumpkin; };
+struct CvVesta { using F = FpVesta; using G = GlvVesta; };
+// every Weierstrass configuration with its curve id (include/msm_hip.h): the one list the host's dispatch, its per-curve
+// constants and the extern templates are made from.  X(curve id, configuration)
+#define MSM_W_CURVES(X)             \
+  X(MSM_CURVE_BLS12_377_G1, CvBls377) \
+  X(MSM_CURVE_BLS12_381_G1, CvBls381) \
+  X(MSM_CURVE_PALLAS, CvPallas)       \
+  X(MSM_CURVE_BN254_G1, CvBn254)      \
+  X(MSM_CURVE_GRUMPKIN, CvGrumpkin)   \
+  X(MSM_CURVE_VESTA, CvVesta)
 constexpr int NL = 13;   // the wide layout; kernels use F::NL / F::NW
 constexpr int NW = 12;
 static_assert(Fp377::NL == NL && Fp377::NW == NW && Fp381::NL == NL && Fp381::NW == NW, "the 12-word layout");

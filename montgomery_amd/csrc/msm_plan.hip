@@ -53,11 +53,17 @@ int pick_window(bool te, uint64_t n, int glv_max_bits) {
   // b = 127 (BLS12-381, Pallas): 128 = 5 * 22 + 18, the 22-bit plan has six whole windows (from 2^25 points, see below).
   // (127 = 7 * 18 + 1 folds too: seven 18-bit windows win from 2^22 points to 2^24 -- with the round-5 sort of the big windows
   // 2^22 11.4 against 12.1 ms, 2^23 20.6 / 21.8, level at 2^21 (6.8), behind the 21-bit plan at 2^24 (41.3 / 39.5): tools/plan_sweep.py)
+  // BN254 G1 and Grumpkin (b = 126 on the 9-limb field: the same K for every c, the 6 x 21 fold included) take these thresholds.
+  // Swept at 2^20, 2^23, 2^24 (profiles/cycle_curves_time.txt; BN254 / Grumpkin, ms): 2^20 c = 16 2.82 / 2.76 against 2.88 / 2.85
+  // at 18; 2^23 c = 18 15.6 / 15.4 against 17.2 / 17.1 (16), 15.9 / 15.6 (19), 16.0 / 16.0 (21); 2^24 c = 21 30.0 / 29.6 against
+  // 31.0 / 30.5 (18), 31.6 / 31.6 (19), 31.9 / 31.3 (22).  The crossovers themselves (2^22, 4096) and 2^25 .. 2^26: model only.
   if (!te && glv_max_bits == 126)
     return n >= (1ull << 24) ? 21 : n >= (1ull << 22) ? 18 : n >= 4096 ? 16 : 8;
   // b = 127 (BLS12-381, Pallas), with the round-5 sort of the big windows (tools/plan_sweep_curve.py, c = 16 / 19 / 22):
   // BLS12-381 2^23 22.6 / 22.1 / 24.7 ms, 2^24 44.0 / 43.3 / 44.0, 2^25 81.6 / 80.5 / 75.0; Pallas 2^23 15.6 / 14.5 / 16.3,
-  // 2^24 32.0 / 30.6 / 29.7, 2^25 58.6 / 59.0 / 55.8; level at 2^22
+  // 2^24 32.0 / 30.6 / 29.7, 2^25 58.6 / 59.0 / 55.8; level at 2^22.  Vesta (Pallas' arithmetic, b = 127) takes
+  // Pallas' thresholds: 2^23 c = 19 15.3 against 16.3 (16) and 19.0 (21); at 2^24 c = 22 is ahead, 29.3 against 30.5 (19), as on Pallas
+  // in the same run (30.0 / 31.6): the shared threshold stays where the sweep above put it (profiles/cycle_curves_time.txt).
   if (!te) return n >= (1ull << 25) ? 22 : n >= (1ull << 23) ? 19 : n >= 4096 ? 16 : 8;
   // Edwards plain path with the bin split of round 5 (tools/plan_sweep_curve.py 1, ms at c = 16 / 18): 2^22 8.6 / 7.9, 2^23 15.0 / 14.2,
   // 2^24 28.0 / 26.3, 2^25 53.4 / 54.4, 2^26 101.8 / 105.7 (its gather round is not tile-ordered: beyond 2^25 the big windows lose)
@@ -93,7 +99,7 @@ int pick_window(bool te, uint64_t n, int glv_max_bits) {
 //    4.92 at c = 13 and 6.09 at c = 22; 2^24 12.9 / 14.9 / 14.1) and, which the model finds by itself, 19 bits for b = 128 at
 //    2^24 (21.6 against 24.7 at c = 17; Edwards 14.6 / 16.2).  At 2^22 it takes 17 for b = 128, 7.85 where 19 would give 7.21
 //    (not adopted: one point); on the Edwards curve 13 bits win there, 4.85 against 5.17, and stay below 2^23.
-// Everything else is the COST MODEL alone: other bit lengths; BLS12-381 and Pallas, and 2^26 points (c = 22 from 64 bits),
+// Everything else is the COST MODEL alone: other bit lengths; BLS12-381, Pallas, Vesta, BN254 G1 and Grumpkin, and 2^26 points (c = 22 from 64 bits),
 // which sections 2 and 3 of the file time under this rule but without a sweep.  The model: one pair addition per entry and
 // window, about four per bucket to finish and reduce it, and a fixed 256 per window (launch geometry, host tail) so that tiny
 // inputs do not run dozens of windows -- K (n + 4 buckets + 256).
@@ -122,7 +128,8 @@ int pick_window_narrow(bool te, uint64_t n, int bits, bool one_level) {
 // of K times and the optimum moves up.  BLS12-377 after GLV (127 bits: 18- and 21-bit windows fold the carry bit, no short top
 // window to skew the merged buckets), measured with tools/tables_csweep.py (profiles/r05_experiments.txt item 5): 16 bits below
 // 2^16 points, 18 from there (2^18 1.58 against 1.76 ms plain, 2^20 3.65 / 3.90, 2^22 11.0 / 11.9, 2^23 20.3 / 21.7), 21 from
-// 2^24 (36.7 / 40.1).  BLS12-381 and Pallas keep the plain choice (their 18-bit plan would end in a two-bit top window).
+// 2^24 (36.7 / 40.1).  BN254 G1 and Grumpkin (127 bits too) take the same rule, model only.  BLS12-381, Pallas and Vesta keep the
+// plain choice (their 18-bit plan would end in a two-bit top window).
 // Ed-on-BLS12-377 (252 bits, no endomorphism: K = 13 .. 28 windows on the plain path, whose reduction and host tail grow with K):
 // 14 bits below 2^17 points, 17 from there (K = 15; 2^18 0.98 against 1.09 ms plain, 2^20 2.11 / 2.63, 2^22 7.3 / 8.6; 16 bits
 // 2.28, 18 bits 2.17 at 2^20) -- with the merged window's sums finished bit-sliced (reduce_buckets).

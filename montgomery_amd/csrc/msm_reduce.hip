@@ -325,9 +325,10 @@ void te_horner_to_affine(const msm_ctx* ctx, const std::vector<uint32_t>& words,
 
 // host curve constants without a context (rank 0 of a sharded run may combine without touching a GPU)
 const msm_host::Curve6* static_host_curve(int curve) {
-  static msm_host::Curve6 hc[4];
-  static std::atomic<int> ready[4];
-  if (curve < 0 || curve > 3 || curve == MSM_CURVE_ED_ON_BLS12_377) return nullptr;
+  constexpr int N_IDS = MSM_CURVE_VESTA + 1;
+  static msm_host::Curve6 hc[N_IDS];
+  static std::atomic<int> ready[N_IDS];
+  if (curve < 0 || curve >= N_IDS || curve == MSM_CURVE_ED_ON_BLS12_377) return nullptr;
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
   if (!ready[curve].load()) {

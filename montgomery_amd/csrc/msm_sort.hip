@@ -16,9 +16,9 @@ void sort_kernel_attributes() {
   HIPCHK(hipFuncSetAttribute((const void*)k_bin_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_pairs_lds(1u << BS_MAX_FB)));
   HIPCHK(hipFuncSetAttribute((const void*)k_bin_slots, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_slots_lds(1u << BS_MAX_FB)));
   const int dig_lds = 16 * (1 << BS_MAX_AB) * 4;   // the fused histogram of up to 16 windows
-  HIPCHK(hipFuncSetAttribute((const void*)k_digits<CvBls377>, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));
-  HIPCHK(hipFuncSetAttribute((const void*)k_digits<CvBls381>, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));
-  HIPCHK(hipFuncSetAttribute((const void*)k_digits<CvPallas>, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));
+#define MSM_DIGITS_ATTR(ID, CV) HIPCHK(hipFuncSetAttribute((const void*)k_digits<CV>, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));
+  MSM_W_CURVES(MSM_DIGITS_ATTR)
+#undef MSM_DIGITS_ATTR
   HIPCHK(hipFuncSetAttribute((const void*)te::k_te_digits, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));
 #define MSM_NARROW_ATTR(W)                                                                                                    \
   HIPCHK(hipFuncSetAttribute((const void*)k_digits_narrow<W>, hipFuncAttributeMaxDynamicSharedMemorySize, dig_lds));          \

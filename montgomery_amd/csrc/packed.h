@@ -10,6 +10,8 @@
 //
 // gfx9 allows one SGPR-or-literal read per VALU instruction and the carry-in is one, so constants
 // enter the chains through VGPRs (v_and / v_mov with a literal first).
+//
+// A CPU build (the unit tests of tests/csrc) gets the same chains in plain C++: pk_sub_host / pk_add_host.
 #pragma once
 #include "field.h"
 
@@ -22,8 +24,30 @@ struct PkW {
 using Pk = PkW<12>;    // the 377- / 381-bit fields
 using Pk8 = PkW<8>;    // 255-bit fields (Pallas): 8 words
 
+// the same chains in plain C++: the CPU build of the unit tests (tests/csrc/field_host_cycles.hip), never device code
+template <int W>
+inline uint32_t pk_sub_host(PkW<W>& r, const PkW<W>& a, const PkW<W>& b) {
+  uint64_t borrow = 0;
+  for (int i = 0; i < W; i++) {
+    const uint64_t d = (uint64_t)a.w[i] - b.w[i] - borrow;
+    r.w[i] = (uint32_t)d;
+    borrow = (d >> 32) & 1u;
+  }
+  return borrow ? 0xFFFFFFFFu : 0u;
+}
+template <int W>
+inline void pk_add_host(PkW<W>& r, const PkW<W>& a, const PkW<W>& b) {
+  uint64_t c = 0;
+  for (int i = 0; i < W; i++) {
+    c += (uint64_t)a.w[i] + b.w[i];
+    r.w[i] = (uint32_t)c;
+    c >>= 32;
+  }
+}
+
 // r = a - b over 384 bits; returns all-ones if the subtraction borrowed (a < b), else 0
-__device__ __forceinline__ uint32_t pk_sub(Pk& r, const Pk& a, const Pk& b) {
+MSM_DEV uint32_t pk_sub(Pk& r, const Pk& a, const Pk& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
   uint64_t c;
   uint32_t m;
   asm volatile(
@@ -48,10 +72,14 @@ __device__ __forceinline__ uint32_t pk_sub(Pk& r, const Pk& a, const Pk& b) {
       : "v"(a.w[6]), "v"(a.w[7]), "v"(a.w[8]), "v"(a.w[9]), "v"(a.w[10]), "v"(a.w[11]), "v"(b.w[6]), "v"(b.w[7]), "v"(b.w[8]),
         "v"(b.w[9]), "v"(b.w[10]), "v"(b.w[11]));
   return m;
+#else
+  return pk_sub_host(r, a, b);
+#endif
 }
 
 // r = a + b over 384 bits (carry out dropped)
-__device__ __forceinline__ void pk_add(Pk& r, const Pk& a, const Pk& b) {
+MSM_DEV void pk_add(Pk& r, const Pk& a, const Pk& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
   uint64_t c;
   asm volatile(
       "v_add_co_u32 %0, %6, %7, %13\n\t"
@@ -73,10 +101,14 @@ __device__ __forceinline__ void pk_add(Pk& r, const Pk& a, const Pk& b) {
       : "=&v"(r.w[6]), "=&v"(r.w[7]), "=&v"(r.w[8]), "=&v"(r.w[9]), "=&v"(r.w[10]), "=&v"(r.w[11]), "+s"(c)
       : "v"(a.w[6]), "v"(a.w[7]), "v"(a.w[8]), "v"(a.w[9]), "v"(a.w[10]), "v"(a.w[11]), "v"(b.w[6]), "v"(b.w[7]), "v"(b.w[8]),
         "v"(b.w[9]), "v"(b.w[10]), "v"(b.w[11]));
+#else
+  pk_add_host(r, a, b);
+#endif
 }
 
 // the same chains over 256 bits
-__device__ __forceinline__ uint32_t pk_sub(Pk8& r, const Pk8& a, const Pk8& b) {
+MSM_DEV uint32_t pk_sub(Pk8& r, const Pk8& a, const Pk8& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
   uint64_t c;
   uint32_t m;
   asm volatile(
@@ -94,8 +126,12 @@ __device__ __forceinline__ uint32_t pk_sub(Pk8& r, const Pk8& a, const Pk8& b) {
       : "v"(a.w[0]), "v"(a.w[1]), "v"(a.w[2]), "v"(a.w[3]), "v"(a.w[4]), "v"(a.w[5]), "v"(a.w[6]), "v"(a.w[7]), "v"(b.w[0]), "v"(b.w[1]),
         "v"(b.w[2]), "v"(b.w[3]), "v"(b.w[4]), "v"(b.w[5]), "v"(b.w[6]), "v"(b.w[7]));
   return m;
+#else
+  return pk_sub_host(r, a, b);
+#endif
 }
-__device__ __forceinline__ void pk_add(Pk8& r, const Pk8& a, const Pk8& b) {
+MSM_DEV void pk_add(Pk8& r, const Pk8& a, const Pk8& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
   uint64_t c;
   asm volatile(
       "v_add_co_u32 %0, %8, %9, %17\n\t"
@@ -109,17 +145,20 @@ __device__ __forceinline__ void pk_add(Pk8& r, const Pk8& a, const Pk8& b) {
       : "=&v"(r.w[0]), "=&v"(r.w[1]), "=&v"(r.w[2]), "=&v"(r.w[3]), "=&v"(r.w[4]), "=&v"(r.w[5]), "=&v"(r.w[6]), "=&v"(r.w[7]), "=&s"(c)
       : "v"(a.w[0]), "v"(a.w[1]), "v"(a.w[2]), "v"(a.w[3]), "v"(a.w[4]), "v"(a.w[5]), "v"(a.w[6]), "v"(a.w[7]), "v"(b.w[0]), "v"(b.w[1]),
         "v"(b.w[2]), "v"(b.w[3]), "v"(b.w[4]), "v"(b.w[5]), "v"(b.w[6]), "v"(b.w[7]));
+#else
+  pk_add_host(r, a, b);
+#endif
 }
 
 template <class C>
-__device__ __forceinline__ void pk_set_p_masked(PkW<C::NW>& t, uint32_t mask) {
+MSM_DEV void pk_set_p_masked(PkW<C::NW>& t, uint32_t mask) {
 #pragma unroll
   for (int i = 0; i < C::NW; i++) t.w[i] = C::PW[i] & mask;
 }
 
 // r = (a - b) mod p for a in [0, p + eps), b in [0, p): result in [0, p + eps)
 template <class C>
-__device__ __forceinline__ void pk_sub_mod(PkW<C::NW>& r, const PkW<C::NW>& a, const PkW<C::NW>& b) {
+MSM_DEV void pk_sub_mod(PkW<C::NW>& r, const PkW<C::NW>& a, const PkW<C::NW>& b) {
   PkW<C::NW> d, t;
   uint32_t borrow = pk_sub(d, a, b);
   pk_set_p_masked<C>(t, borrow);
@@ -128,7 +167,7 @@ __device__ __forceinline__ void pk_sub_mod(PkW<C::NW>& r, const PkW<C::NW>& a, c
 
 // r -= p if r >= p  (r < 2p)
 template <class C>
-__device__ __forceinline__ void pk_cond_sub_p(PkW<C::NW>& r) {
+MSM_DEV void pk_cond_sub_p(PkW<C::NW>& r) {
   PkW<C::NW> t, d;
   pk_set_p_masked<C>(t, 0xFFFFFFFFu);
   uint32_t borrow = pk_sub(d, r, t);
@@ -138,7 +177,7 @@ __device__ __forceinline__ void pk_cond_sub_p(PkW<C::NW>& r) {
 }
 
 template <int W>
-__device__ __forceinline__ bool pk_is_zero(const PkW<W>& a) {
+MSM_DEV bool pk_is_zero(const PkW<W>& a) {
   uint32_t o = 0;
 #pragma unroll
   for (int i = 0; i < W; i++) o |= a.w[i];
@@ -146,7 +185,7 @@ __device__ __forceinline__ bool pk_is_zero(const PkW<W>& a) {
 }
 
 template <int W>
-__device__ __forceinline__ bool pk_equal(const PkW<W>& a, const PkW<W>& b) {
+MSM_DEV bool pk_equal(const PkW<W>& a, const PkW<W>& b) {
   uint32_t o = 0;
 #pragma unroll
   for (int i = 0; i < W; i++) o |= a.w[i] ^ b.w[i];
@@ -154,8 +193,8 @@ __device__ __forceinline__ bool pk_equal(const PkW<W>& a, const PkW<W>& b) {
 }
 
 template <class C>
-__device__ __forceinline__ void pk_unpack(Fe<C>& r, const PkW<C::NW>& a) { fe_unpack<C>(r, a.w); }
+MSM_DEV void pk_unpack(Fe<C>& r, const PkW<C::NW>& a) { fe_unpack<C>(r, a.w); }
 template <class C>
-__device__ __forceinline__ void pk_pack(PkW<C::NW>& r, const Fe<C>& a) { fe_pack<C>(r.w, a); }
+MSM_DEV void pk_pack(PkW<C::NW>& r, const Fe<C>& a) { fe_pack<C>(r.w, a); }
 
 }  // namespace msm

@@ -112,8 +112,14 @@ MSM_DEV bool fe_sqrt(Fe<C>& r, const Fe<C>& a_in) {
   return fe_equal<C>(xx, a);
 }
 
+// the pasta encoding (sign = y odd, no infinity flag: x = 0 is no point of y^2 = x^3 + 5 and stands for the identity)
 template <class CV>
-constexpr bool cofactor_one() { return std::is_same<CV, CvPallas>::value; }
+constexpr bool pasta_format() { return std::is_same<CV, CvPallas>::value || std::is_same<CV, CvVesta>::value; }
+// the curve group has prime order: every point of the curve is in the subgroup
+template <class CV>
+constexpr bool cofactor_one() {
+  return pasta_format<CV>() || std::is_same<CV, CvBn254>::value || std::is_same<CV, CvGrumpkin>::value;
+}
 
 // bit length of the group order q (8 words)
 constexpr int order_bits(const uint32_t* q) {
@@ -127,7 +133,8 @@ constexpr int order_bits(const uint32_t* q) {
 // k_points_decompress: N compressed Weierstrass points -> point rows (the rows k_points_from_wire makes from x || y)
 //   BLS12-381 (ZCash): 48 bytes, x big-endian; first byte 0x80 compressed (required), 0x40 infinity, 0x20 sign (y > (p-1)/2)
 //   BLS12-377 (arkworks): 48 bytes, x little-endian; last byte 0x80 sign (y > (p-1)/2), 0x40 infinity; bits 377-381 unused
-//   Pallas (pasta): 32 bytes, x little-endian; bit 255 sign (y odd); all-zero bytes = the identity
+//   BN254 G1, Grumpkin (arkworks): the BLS12-377 rules at 32 bytes (bit 255 sign, bit 254 infinity; a 254-bit x leaves both free)
+//   Pallas, Vesta (pasta): 32 bytes, x little-endian; bit 255 sign (y odd); all-zero bytes = the identity
 // ---------------------------------------------------------------------------------------------
 
 template <class CV>
@@ -150,14 +157,16 @@ __global__ void __launch_bounds__(256) k_points_decompress(uint32_t* rows, const
     inf = (fl & 2u) != 0;
     sign = (fl & 1u) != 0;
     bad_flags = !(fl & 4u) || (inf && sign);
-  } else if constexpr (std::is_same<CV, CvBls377>::value) {
+  } else if constexpr (!pasta_format<CV>()) {   // arkworks: the two top bits of the last word are flags
 #pragma unroll
     for (int j = 0; j < NW; j++) xw[j] = w[j];
+    constexpr uint32_t XMASK = (1u << (F::BITS - 32 * (NW - 1))) - 1u;   // the bits of x in the last word
+    static_assert(F::BITS > 32 * (NW - 1) && F::BITS <= 32 * NW - 2, "x must leave the two flag bits free");
     const uint32_t top = xw[NW - 1];
     sign = (top >> 31) != 0;
     inf = ((top >> 30) & 1u) != 0;
-    bad_flags = (inf && sign) || (top & 0x3E000000u);   // bits 377-381 are not used
-    xw[NW - 1] &= 0x01FFFFFFu;
+    bad_flags = (inf && sign) || (top & (0x3FFFFFFFu & ~XMASK));   // BLS12-377: bits 377-381 are not used
+    xw[NW - 1] &= XMASK;
   } else {
 #pragma unroll
     for (int j = 0; j < NW; j++) xw[j] = w[j];
@@ -166,7 +175,7 @@ __global__ void __launch_bounds__(256) k_points_decompress(uint32_t* rows, const
   }
 #pragma unroll
   for (int j = 0; j < NW; j++) rest |= xw[j];
-  if constexpr (cofactor_one<CV>()) inf = !sign && rest == 0;   // x = 0 is no point of y^2 = x^3 + 5
+  if constexpr (pasta_format<CV>()) inf = !sign && rest == 0;   // x = 0 is no point of y^2 = x^3 + 5
   if (inf && rest) bad_flags = true;
   if (bad_flags || inf) {
     store_row_identity<NW / 4>(row);
@@ -194,7 +203,7 @@ __global__ void __launch_bounds__(256) k_points_decompress(uint32_t* rows, const
   }
   uint32_t yp[NW];
   fe_plain_words<F>(yp, y);
-  const bool odd = cofactor_one<CV>() ? (yp[0] & 1u) != 0 : words_gt<NW>(yp, F::HALFW);
+  const bool odd = pasta_format<CV>() ? (yp[0] & 1u) != 0 : words_gt<NW>(yp, F::HALFW);
   if (odd != sign) {
     uint32_t any = 0;
 #pragma unroll
@@ -213,7 +222,7 @@ __global__ void __launch_bounds__(256) k_points_decompress(uint32_t* rows, const
 
 // ---------------------------------------------------------------------------------------------
 // k_points_validate: resident rows [first, first + count): the curve equation, and with `subgroup` [q] P = O by double-and-add
-// over the fixed bits of q (proj_double / proj_add_mixed).  Pallas has cofactor 1: every curve point is in the group.
+// over the fixed bits of q (proj_double / proj_add_mixed).  Pallas, Vesta, BN254 G1 and Grumpkin have cofactor 1: every curve point is in the group.
 // (No endomorphism shortcut: [q] P is right without a torsion argument per curve, see DESIGN.md "Point ingest".)
 // ---------------------------------------------------------------------------------------------
 

@@ -157,7 +157,7 @@ static napi_value CreateContext(napi_env env, napi_callback_info info) {
   h->ctx = ctx;
   h->refs = 1;
   h->curve = curve;
-  h->coord_bytes = (curve == MSM_CURVE_ED_ON_BLS12_377 || curve == MSM_CURVE_PALLAS) ? 32 : 48;   /* per field */
+  h->coord_bytes = (curve == MSM_CURVE_BLS12_377_G1 || curve == MSM_CURVE_BLS12_381_G1) ? 48 : 32;   /* per field */
   h->point_bytes = 2 * h->coord_bytes;
   napi_value out;
   NAPI_OK(napi_create_external(env, h, finalize_handle, NULL, &out));
@@ -190,7 +190,7 @@ static napi_value SetPoints(napi_env env, napi_callback_info info) {  // pointsF
   if (argc > 2) napi_get_value_int32(env, argv[2], &point_bytes);
   if (argc > 3) napi_get_value_int32(env, argv[3], &check);
   if ((size_t)point_bytes != h->point_bytes || len % h->point_bytes) {   // the C ABI reads n x point_bytes of this curve
-    napi_throw_range_error(env, NULL, "point buffer: expected a multiple of the curve's point size (96 bytes; Ed-on-BLS12-377 and Pallas: 64)");
+    napi_throw_range_error(env, NULL, "point buffer: expected a multiple of the curve's point size (96 bytes for BLS12-377 / BLS12-381; 64 for the 32-byte curves: Ed-on-BLS12-377, Pallas, Vesta, BN254, Grumpkin)");
     return NULL;
   }
   int rc = msm_set_points(ctx, data, len / point_bytes, 0, check);
@@ -903,5 +903,11 @@ NAPI_MODULE_INIT() {
   napi_set_named_property(env, exports, "CURVE_BLS12_381_G1", v);
   napi_create_int32(env, MSM_CURVE_PALLAS, &v);
   napi_set_named_property(env, exports, "CURVE_PALLAS", v);
+  napi_create_int32(env, MSM_CURVE_BN254_G1, &v);
+  napi_set_named_property(env, exports, "CURVE_BN254_G1", v);
+  napi_create_int32(env, MSM_CURVE_GRUMPKIN, &v);
+  napi_set_named_property(env, exports, "CURVE_GRUMPKIN", v);
+  napi_create_int32(env, MSM_CURVE_VESTA, &v);
+  napi_set_named_property(env, exports, "CURVE_VESTA", v);
   return exports;
 }

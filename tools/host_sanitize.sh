@@ -38,7 +38,7 @@ gcc -O1 -g -fopenmp -fsanitize=address,undefined -fno-omit-frame-pointer oracle/
 OMP_NUM_THREADS=16 $T/drv $T 1 2 33 1000 65536
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-O1 -g -pthread -std=c++17 --offload-arch=gfx950 -fPIC -Iinclude -Imontgomery_amd/csrc -fsanitize=address,undefined -fno-omit-frame-pointer"
-for c in CvBls377 CvBls381 CvPallas; do $HIPCC $SAN -DMSM_CURVE_TU=$c -c montgomery_amd/csrc/kernels_curve.hip -o $T/k_$c.o & done
+for c in CvBls377 CvBls381 CvPallas CvBn254 CvGrumpkin CvVesta; do $HIPCC $SAN -DMSM_CURVE_TU=$c -c montgomery_amd/csrc/kernels_curve.hip -o $T/k_$c.o & done
 $HIPCC $SAN -c montgomery_amd/csrc/msm_api.hip -o $T/api.o; wait
 $HIPCC --offload-arch=gfx950 -shared -pthread -fsanitize=address,undefined $T/*.o -o $T/libmsm_asan.so
 RT=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so | head -1)
