@@ -1,19 +1,22 @@
-"""Randomised differential run of the HIP path against the C oracle (BLS12-377) and the Python oracle (other curves):
+"""Randomised differential run of the HIP path against the C oracle (BLS12-377) and the Python oracle (BLS12-381, Pallas, BN254 G1, Grumpkin, Vesta, Ed-on-BLS12-377):
 random N, window sizes (FUZZ_CS=21,22,23,24 picks them; 0 = the default policy), point multisets with repeats / negations / identities, scalar patterns.  Usage:
     python tools/fuzz_parity.py [seconds] [seed]"""
-import random, sys, time
-sys.path.insert(0, "/root/repo")
+import os, random, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from oracle import msm_oracle as O
 from oracle import c_oracle
 from montgomery_amd import _lib
 from montgomery_amd.api import MsmContext
 
-import os
+from test_cycle_curves import CURVES as CYCLE_CURVES   # BN254 G1, Grumpkin, Vesta: the oracle has no entry of its own for them
+
 CS = [int(x) or None for x in os.environ["FUZZ_CS"].split(",")] if os.environ.get("FUZZ_CS") else [None, None, 2, 3, 4, 5, 7, 8, 10, 11, 13, 15, 16, 17, 19, 20]
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rnd = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 c_oracle.load()
 curves = [(_lib.CURVE_BLS12_377_G1, O.BLS12_377, 48), (_lib.CURVE_BLS12_381_G1, O.BLS12_381, 48), (_lib.CURVE_PALLAS, O.PALLAS, 32)]
+curves += [(entry[0], entry[1], 32) for _, entry in sorted(CYCLE_CURVES.items())]   # checked by the Python oracle at n <= 300, like BLS12-381
 ctxs = {cid: MsmContext(cid) for cid, _, _ in curves}
 pools = {cid: O.random_points_bls377(f"fuzz/{B.label}", 300, B)[0] for cid, B, _ in curves}
 E = O.ED_ON_BLS12_377
