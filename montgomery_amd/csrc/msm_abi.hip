@@ -36,7 +36,7 @@ int msm_ctx_create(msm_ctx** out, int curve, int device) {
       HIPCHK(hipStreamCreateWithFlags(&w.side, hipStreamNonBlocking));
       for (auto& e : w.ev) HIPCHK(hipEventCreate(&e));
       HIPCHK(hipHostMalloc((void**)&w.h_info, 64 * 4, hipHostMallocDefault));
-      HIPCHK(hipHostMalloc((void**)&w.h_part, 128 * 20 * 36 * 4, hipHostMallocDefault));
+      HIPCHK(hipHostMalloc((void**)&w.h_part, 128 * 20 * W_SUM_WORDS * 4, hipHostMallocDefault));
     }
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
@@ -186,38 +186,9 @@ int msm_window_sums(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device
     HIPCHK(hipSetDevice(ctx->device));
     std::vector<uint32_t> words;
     pl.tables = n && tables_wanted && use_window_tables(ctx, n, opts, pl);
-    if (ctx->is_te()) {
-      // extended point (X : Y : Z : T) sent as X || Y || Z; the receiver rebuilds T (msm_combine: T Z = X Y)
-      if (n) any_window_sums(ctx, scalars, n, on_device, opts, k_lo, k_hi, pl, words, stats);
-      const auto& C = ctx->hte;
-      msm_host::Fe6 one = {{1, 0, 0, 0, 0, 0}}, t;
-      for (int k = 0; k < k_hi - k_lo; k++) {
-        const msm_host::Ext6 P = n ? te_partial_to_host(ctx, &words[(size_t)k * 32]) : C.zero();
-        C.F.mul(t, P.X, one); fe6_to_bytes(partials_out + (size_t)k * 144, t);
-        C.F.mul(t, P.Y, one); fe6_to_bytes(partials_out + (size_t)k * 144 + 48, t);
-        C.F.mul(t, P.Z, one); fe6_to_bytes(partials_out + (size_t)k * 144 + 96, t);
-      }
-      if (stats) { stats->c = pl.c; stats->K = pl.K; }
-      return MSM_OK;
-    }
-    if (n == 0) {
-      words.assign((size_t)(k_hi - k_lo) * 36, 0);
-    } else {
-      any_window_sums(ctx, scalars, n, on_device, opts, k_lo, k_hi, pl, words, stats);
-    }
-    // to 48-byte canonical integers (leave device Montgomery form on the host)
-    for (int k = 0; k < k_hi - k_lo; k++) {
-      const uint32_t* w = &words[(size_t)k * 36];
-      bool zero_z = true;
-      for (int j = 0; j < 12; j++) zero_z &= w[24 + j] == 0;
-      msm_host::Proj6 P;
-      if (n == 0 || zero_z) P = ctx->hc.zero();
-      else P = partial_to_host(ctx, w);
-      msm_host::Fe6 one = {{1, 0, 0, 0, 0, 0}}, t;
-      ctx->hc.F.mul(t, P.X, one); fe6_to_bytes(partials_out + (size_t)k * 144, t);
-      ctx->hc.F.mul(t, P.Y, one); fe6_to_bytes(partials_out + (size_t)k * 144 + 48, t);
-      ctx->hc.F.mul(t, P.Z, one); fe6_to_bytes(partials_out + (size_t)k * 144 + 96, t);
-    }
+    if (n) any_window_sums(ctx, scalars, n, on_device, opts, k_lo, k_hi, pl, words, stats);
+    for (int k = 0; k < k_hi - k_lo; k++)   // (no points: every sum is the identity)
+      sum_to_wire(ctx, n ? &words[(size_t)k * ctx->sum_words()] : nullptr, partials_out + (size_t)k * SUM_WIRE_BYTES);
     if (stats) { stats->c = pl.c; stats->K = pl.K; }
   } MSM_CATCH_ALL(ctx)
   return MSM_OK;
@@ -262,12 +233,7 @@ static int run_piped(msm_ctx* ctx, const void* scalars, uint64_t n, const msm_op
   try {
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipEventRecord(ctx->ev[8], ctx->stream));
-    const uint64_t gran = msm_ctx::STAGE_CHUNK / 32;   // scalars per staging chunk
-    const int big = n >= (1ull << 25);
-    std::vector<uint64_t> piece_end;
-    std::vector<int> shifts = {big ? 4 : 3, big ? 2 : 1};
-    for (int sh : shifts) piece_end.push_back(((n >> sh) / gran) * gran);
-    piece_end.push_back(n);
+    const std::vector<uint64_t> piece_end = pipelined_piece_ends(n);
     ctx->ensure(ctx->scal, n * 32);   // before any workspace is sized from what the device has free
     std::vector<size_t> ends;
     for (uint64_t e : piece_end) ends.push_back((size_t)e * 32);
@@ -279,7 +245,7 @@ static int run_piped(msm_ctx* ctx, const void* scalars, uint64_t n, const msm_op
       Plan pq;
       msm_opts o;
       msm_result st;
-      std::vector<uint32_t> words;
+      std::vector<uint32_t> words, sum;   // its window sums; their Horner sum, one slot
     };
     std::vector<Range> R(Q);
     for (size_t q = 0; q < Q; q++) {
@@ -300,23 +266,22 @@ static int run_piped(msm_ctx* ctx, const void* scalars, uint64_t n, const msm_op
       HIPCHK(hipStreamSynchronize(ctx->stream));       // the range's scalars are in HBM
       window_sums_impl(ctx, (const uint32_t*)ctx->scal.p + r.lo * 8, r.cnt, 1, &r.o, 0, r.pq.K, r.pq, r.words, &r.st, r.o.point_lo);
     }
-    msm_host::Proj6 acc = ctx->hc.zero();
+    // the ranges' results are added as group elements: one field inversion for the call
+    std::vector<const uint32_t*> sums;
     for (size_t q = 0; q < Q; q++) {
-      const Range& r = R[q];
+      Range& r = R[q];
       if (r.cnt == 0) continue;
-      std::vector<msm_host::Proj6> P(r.pq.K);
-      for (int k = 0; k < r.pq.K; k++) P[k] = partial_to_host(ctx, &r.words[(size_t)k * 36]);
-      acc = ctx->hc.add(acc, horner_points(ctx->hc, P, r.pq.c));
-      for (int j = 0; j < MSM_N_PHASES; j++) out->phase_ms[j] += r.st.phase_ms[j];
-      out->n_pairs += r.st.n_pairs;
-      out->n_pairs_algo += r.st.n_pairs_algo;
-      out->rounds += r.st.rounds;
-      out->max_bucket = std::max(out->max_bucket, r.st.max_bucket);
+      r.sum.resize(ctx->sum_words());
+      sums_horner(ctx, r.words.data(), r.pq.K, r.pq.c, r.sum.data());
+      sums.push_back(r.sum.data());
+      add_call_stats(*out, r.st);
       out->c = r.pq.c;   // the plan of the last, biggest range
       out->K = r.pq.K;
     }
     out->phase_ms[MSM_T_UPLOAD] = pipe.finish();   // wall time of the background transfer
-    proj_to_result(ctx->hc, acc, out);
+    std::vector<uint32_t> total(ctx->sum_words());
+    sum_slots(ctx, sums, total.data());
+    sums_finish(ctx, total.data(), 1, 0, out);
     HIPCHK(hipEventRecord(ctx->ev[11], ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     float ms;
@@ -329,7 +294,7 @@ static int run_piped(msm_ctx* ctx, const void* scalars, uint64_t n, const msm_op
 static int run_impl(msm_ctx* ctx, const void* scalars, const void* const* placed, uint64_t n, int on_device, const msm_opts* opts,
                     msm_result* out, const char* who) {
   if (int rc = check_points(ctx, n, opts, MSM_ERR_NO_POINTS, who)) return rc;
-  if (!placed && !on_device && n >= (1ull << 24) && ctx->children.empty() && !ctx->is_te() && !(opts && opts->c))
+  if (!placed && !on_device && pipelines_host_scalars(n) && ctx->children.empty() && !ctx->is_te() && !(opts && opts->c))
     return run_piped(ctx, scalars, n, opts, out, who);
   Plan pl;
   bool tables_wanted = false;   // window tables (msm_tables.hip): the plan is then the one tables want
@@ -339,8 +304,7 @@ static int run_impl(msm_ctx* ctx, const void* scalars, const void* const* placed
   out->c = pl.c;
   out->K = pl.K;
   if (n == 0) {
-    if (ctx->is_te()) out->y[0] = 1;   // identity (0, 1)
-    else out->is_infinity = 1;
+    identity_to_result(ctx, out);
     return MSM_OK;
   }
   try {
@@ -352,14 +316,7 @@ static int run_impl(msm_ctx* ctx, const void* scalars, const void* const* placed
     HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
     // (a run on tables leaves the whole sum, weights included, in slot 0 and identities in the others: the Horner step over all
     // K slots returns it unchanged, and is what a call that had to leave the tables -- ranges of the points -- needs)
-    const int slots = pl.K;
-    if (ctx->is_te()) {
-      te_horner_to_affine(ctx, words, slots, pl.c, out);
-    } else {
-      std::vector<msm_host::Proj6> P(slots);
-      for (int k = 0; k < slots; k++) P[k] = partial_to_host(ctx, &words[(size_t)k * 36]);
-      horner_to_affine(ctx->hc, P, pl.c, out);
-    }
+    sums_finish(ctx, words.data(), pl.K, pl.c, out);
     HIPCHK(hipEventRecord(ctx->ev[11], ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     float ms;
@@ -414,17 +371,9 @@ int msm_get_points(msm_ctx* ctx, uint64_t first, uint64_t count, uint8_t* out_xy
       std::vector<uint32_t> rows((size_t)count * te::TE_ROW_WORDS);
       if (count)
         HIPCHK(hipMemcpy(rows.data(), (const uint32_t*)ctx->pts().rows.p + first * te::TE_ROW_WORDS, rows.size() * 4, hipMemcpyDeviceToHost));
-      msm_host::Fe6 one = {{1, 0, 0, 0, 0, 0}};
       for (uint64_t i = 0; i < count; i++)
-        for (int j = 0; j < 2; j++) {
-          msm_host::Fe6 t = {{0, 0, 0, 0, 0, 0}};
-          const uint32_t* w = &rows[(size_t)i * te::TE_ROW_WORDS + 8 * j];
-          for (int q = 0; q < 4; q++) t.v[q] = (uint64_t)w[2 * q] | ((uint64_t)w[2 * q + 1] << 32);
-          ctx->hte.F.mul(t, t, ctx->k_te_to_host);
-          ctx->hte.F.mul(t, t, one);
-          for (int q = 0; q < 4; q++)
-            for (int b = 0; b < 8; b++) out_xy[i * 64 + 32 * j + 8 * q + b] = (uint8_t)(t.v[q] >> (8 * b));
-        }
+        for (int j = 0; j < 2; j++)
+          device_coord_to_wire(ctx->hte.F, ctx->k_te_to_host, &rows[(size_t)i * te::TE_ROW_WORDS + 8 * j], 8, out_xy + i * 64 + 32 * j);
     } MSM_CATCH_ALL(ctx)
     return MSM_OK;
   }
@@ -436,19 +385,10 @@ int msm_get_points(msm_ctx* ctx, uint64_t first, uint64_t count, uint8_t* out_xy
     const int nw = ctx->nw();
     const size_t cb = ctx->coord_bytes();
     memset(out_xy, 0, (size_t)count * 2 * cb);
-    msm_host::Fe6 one = {{1, 0, 0, 0, 0, 0}};
     for (uint64_t i = 0; i < count; i++) {
       const uint32_t* row = &rows[(size_t)i * ROW_WORDS];
       if (row[nw - 1] == INF_WORD) continue;
-      for (int j = 0; j < 2; j++) {
-        msm_host::Fe6 t;
-        words_to_fe6(t, row + nw * j, nw);
-        ctx->hc.F.mul(t, t, ctx->k_dev_to_host);  // host Montgomery
-        ctx->hc.F.mul(t, t, one);                 // plain
-        uint8_t b48[48];
-        fe6_to_bytes(b48, t);
-        memcpy(out_xy + i * 2 * cb + cb * j, b48, cb);
-      }
+      for (int j = 0; j < 2; j++) device_coord_to_wire(ctx->hc.F, ctx->k_dev_to_host, row + nw * j, nw, out_xy + i * 2 * cb + cb * j);
     }
   } MSM_CATCH_ALL(ctx)
   return MSM_OK;

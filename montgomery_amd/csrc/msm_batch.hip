@@ -28,15 +28,19 @@ namespace {
 
 constexpr int GROUP_WINDOWS = 128;   // windows of one group under the one-level sort (window_sums_once)
 
-// the call fuses: one device, a plan of the one-level sort (c <= 16, fewer entries per window than the radix split takes)
-bool fuse(const msm_ctx* ctx, uint64_t n, uint32_t B, const Plan& pl) {
-  if (!ctx->children.empty() || B < 2 || pl.c > 16 || pl.fold) return false;
+// where a batch may fuse at all: B >= 2, one device, fewer entries per window than the radix split takes
+bool fuse_region(const msm_ctx* ctx, uint64_t n, uint32_t B) {
   const uint64_t entries = ctx->is_te() ? n : 2 * n;
-  if (entries >= (ctx->is_te() ? 1ull << 22 : 1ull << 21)) return false;
+  return B >= 2 && ctx->children.empty() && entries < one_level_entry_limit(ctx->is_te());
+}
+
+// the call fuses: inside the region, under a plan of the one-level sort (c <= 16)
+bool fuse(const msm_ctx* ctx, uint64_t n, uint32_t B, const Plan& pl) {
+  if (!fuse_region(ctx, n, B) || pl.c > 16 || pl.fold) return false;
   return pl.K <= GROUP_WINDOWS / 2;   // (at least two elements per group)
 }
 
-// one group of elements [b0, b0 + cnt): its kc = cnt K window sums -> part (kc x 36 words; 32 on the Edwards path)
+// one group of elements [b0, b0 + cnt): its kc = cnt K window sums -> part (kc slots)
 void run_batch_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl_in, const std::vector<const uint32_t*>& sc, int b0, int cnt,
                      uint64_t n, uint64_t p_lo, bool lone, uint32_t* part, GroupStats& st) {
   Plan pl = pl_in;
@@ -59,12 +63,7 @@ void run_batch_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl_in, con
   accumulate_window_group(ctx, w, pl, kc, p_lo, so, st, to);
   // unmerged: a merged reduction would fold the windows of different elements into one slot
   reduce_buckets(ctx, w, to.fin, to.fin_cap, to.off_fin, to.bucket_proj, pl.L, kc, part, false, pl.c);
-  float ms;
-  HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1])); st.ms_digits += ms;
-  HIPCHK(hipEventElapsedTime(&ms, w.ev[1], w.ev[2])); st.ms_sort += ms;
-  HIPCHK(hipEventElapsedTime(&ms, w.ev[5], w.ev[3])); st.ms_acc += ms;
-  HIPCHK(hipEventElapsedTime(&ms, w.ev[5], w.ev[6])); st.ms_r1 += ms;
-  HIPCHK(hipEventElapsedTime(&ms, w.ev[3], w.ev[4])); st.ms_red += ms;
+  add_group_times(w, st);
 }
 
 int run_fused(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device, const msm_opts* opts, const Plan& pl,
@@ -91,60 +90,25 @@ int run_fused(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, 
   int per = std::max(1, std::min(wpg / pl.K, pl.nar.width ? NARROW_BATCH_MAX : BATCH_MAX));
   const int n_groups = (int)((B + per - 1) / per);
   per = (int)((B + n_groups - 1) / n_groups);   // even groups
-  const int pw = ctx->is_te() ? 32 : 36;
+  const int pw = ctx->sum_words();
   std::vector<uint32_t> words((size_t)B * pl.K * pw);
   HIPCHK(hipMemsetAsync(ctx->errflag.p, 0, 4, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));   // scalars and the error flag are in place before the group streams start
   const uint64_t p_lo = point_lo(opts);
   const bool serial = opts && opts->serial;
-  std::atomic<int> next{0};
   GroupStats sts[msm_ctx::N_WS];
-  auto worker = [&](int slot) {
-    HIPCHK(hipSetDevice(ctx->device));
-    for (;;) {
-      const int g = next.fetch_add(1);
-      if (g >= n_groups) break;
-      const int b0 = g * per, cnt = std::min<int>(per, (int)B - b0);
-      if (cnt <= 0) break;
-      run_batch_group(ctx, ctx->ws[slot], pl, sc, b0, cnt, n, p_lo, serial, &words[(size_t)b0 * pl.K * pw], sts[slot]);
-    }
-  };
-  {
-    // as window_sums_once: whatever a worker throws is re-raised once both have stopped and both streams are idle
-    const int nthreads = serial ? 1 : std::min<int>(msm_ctx::N_WS, n_groups);
-    std::exception_ptr err;
-    if (nthreads > 1) ctx->helper->run([&] { worker(1); });
-    try { worker(0); } catch (...) { err = std::current_exception(); }
-    if (nthreads > 1) {
-      try { ctx->helper->wait(); } catch (...) { if (!err) err = std::current_exception(); }
-    }
-    if (err) {
-      next.store(n_groups);
-      for (auto& w : ctx->ws) (void)hipStreamSynchronize(w.stream);
-      std::rethrow_exception(err);
-    }
-  }
+  run_on_workspaces(ctx, n_groups, serial, [&](int slot, int g) {
+    const int b0 = g * per, cnt = std::min<int>(per, (int)B - b0);
+    run_batch_group(ctx, ctx->ws[slot], pl, sc, b0, cnt, n, p_lo, serial, &words[(size_t)b0 * pl.K * pw], sts[slot]);
+  });
   // (ev[10] goes in front of the read-back: the synchronisation below then covers it, and hipEventElapsedTime reads it once it
   // has completed -- an event recorded behind that synchronisation may still be pending when the host asks)
   HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
-  HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (pl.strict && (ctx->h_info[0] & 4u)) throw MsmFail{MSM_ERR_SCALAR, "a scalar is >= the group order q (msm_opts.strict)"};
-  if (ctx->h_info[0] & NARROW_ERR_RANGE) throw MsmFail{MSM_ERR_SCALAR, "a scalar lies outside the declared range (msm_run_batch_narrow)"};
-  if (ctx->h_info[0] & 8u) throw MsmFail{MSM_ERR_INTERNAL, "a digit of the folded top window exceeds its bucket range (GLV bound violated)"};
+  check_scalar_flags(ctx, pl, "msm_run_batch_narrow");
   // per element: the Horner step over its K window sums and the conversion to affine (one field inversion each), spread over
   // host threads -- ~0.03 ms per element on one thread
   const auto t0 = std::chrono::steady_clock::now();
-  auto finish = [&](uint32_t b) {
-    const uint32_t* wb = &words[(size_t)b * pl.K * pw];
-    if (ctx->is_te()) {
-      te_horner_to_affine(ctx, std::vector<uint32_t>(wb, wb + (size_t)pl.K * pw), pl.K, pl.c, &out[b]);
-    } else {
-      std::vector<msm_host::Proj6> P(pl.K);
-      for (int k = 0; k < pl.K; k++) P[k] = partial_to_host(ctx, wb + (size_t)k * pw);
-      horner_to_affine(ctx->hc, P, pl.c, &out[b]);
-    }
-  };
+  auto finish = [&](uint32_t b) { sums_finish(ctx, &words[(size_t)b * pl.K * pw], pl.K, pl.c, &out[b]); };
   const uint32_t n_fin = std::min<uint32_t>(8, B / 4);
   if (n_fin <= 1) {
     for (uint32_t b = 0; b < B; b++) finish(b);
@@ -162,14 +126,7 @@ int run_fused(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, 
   }
   const float fin_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   GroupStats st;
-  for (int i = 0; i < msm_ctx::N_WS; i++) {
-    st.n_pairs += sts[i].n_pairs;
-    st.n_pairs_algo += sts[i].n_pairs_algo;
-    st.max_bucket = std::max(st.max_bucket, sts[i].max_bucket);
-    st.rounds += sts[i].rounds;
-    st.ms_digits += sts[i].ms_digits; st.ms_sort += sts[i].ms_sort; st.ms_acc += sts[i].ms_acc;
-    st.ms_red += sts[i].ms_red; st.ms_r1 += sts[i].ms_r1;
-  }
+  for (const GroupStats& g : sts) st += g;
   float up_ms, tot_ms;
   HIPCHK(hipEventElapsedTime(&up_ms, ctx->ev[8], ctx->ev[9]));
   HIPCHK(hipEventElapsedTime(&tot_ms, ctx->ev[8], ctx->ev[10]));
@@ -177,34 +134,23 @@ int run_fused(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, 
     msm_result& r = out[b];
     r.c = pl.c;
     r.K = pl.K;
-    r.rounds = st.rounds;
-    r.n_pairs = st.n_pairs;
-    r.n_pairs_algo = st.n_pairs_algo;
-    r.max_bucket = st.max_bucket;
     r.tables = 0;
+    stats_to_result(st, &r);
     r.phase_ms[MSM_T_UPLOAD] = up_ms;
-    r.phase_ms[MSM_T_DIGITS] = st.ms_digits;
-    r.phase_ms[MSM_T_SORT] = st.ms_sort;
-    r.phase_ms[MSM_T_ACCUMULATE] = st.ms_acc;
-    r.phase_ms[MSM_T_ACC_ROUND1] = st.ms_r1;
-    r.phase_ms[MSM_T_REDUCE] = st.ms_red;
     r.phase_ms[MSM_T_FINAL] = fin_ms;
     r.phase_ms[MSM_T_TOTAL] = tot_ms + fin_ms;
   }
   return MSM_OK;
 }
 
-// element by element through msm_run (its window tables included); the statistics of the whole call go into every element
-int run_each(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device, const msm_opts* opts, msm_result* out) {
+// element by element through run_one(b), which fills out[b] -- msm_run (its window tables included) or msm_run_narrow; the
+// statistics of the whole call go into every element
+int run_each(uint32_t B, msm_result* out, const std::function<int(uint32_t)>& run_one) {
   msm_result tot;
   memset(&tot, 0, sizeof tot);
   for (uint32_t b = 0; b < B; b++) {
-    if (int rc = msm_run(ctx, scalars[b], n, on_device, opts, &out[b])) return rc;
-    for (int j = 0; j < MSM_N_PHASES; j++) tot.phase_ms[j] += out[b].phase_ms[j];
-    tot.rounds += out[b].rounds;
-    tot.n_pairs += out[b].n_pairs;
-    tot.n_pairs_algo += out[b].n_pairs_algo;
-    tot.max_bucket = std::max(tot.max_bucket, out[b].max_bucket);
+    if (int rc = run_one(b)) return rc;
+    add_call_stats(tot, out[b]);
   }
   for (uint32_t b = 0; b < B; b++) {
     memcpy(out[b].phase_ms, tot.phase_ms, sizeof tot.phase_ms);
@@ -244,7 +190,7 @@ extern "C" int msm_run_batch(msm_ctx* ctx, const void* const* scalars, uint32_t 
         return run_fused(ctx, scalars, B, n, on_device, opts, pl, out);
       }
     }
-    return run_each(ctx, scalars, B, n, on_device, opts, out);
+    return run_each(B, out, [&](uint32_t b) { return msm_run(ctx, scalars[b], n, on_device, opts, &out[b]); });
   } MSM_CATCH_ALL(ctx)
 }
 
@@ -270,9 +216,7 @@ extern "C" int msm_run_batch_narrow(msm_ctx* ctx, const void* const* scalars, ui
       Plan pl;
       msm_opts o;
       if (opts) o = *opts; else memset(&o, 0, sizeof o);
-      const uint64_t entries = ctx->is_te() ? n : 2 * n;
-      const bool fuse_region = B >= 2 && ctx->children.empty() && entries < (ctx->is_te() ? 1ull << 22 : 1ull << 21);
-      if (o.c <= 0 && fuse_region) o.c = pick_window_narrow(ctx->is_te(), n, nar.fmt.bits, /*one_level=*/true);
+      if (o.c <= 0 && fuse_region(ctx, n, B)) o.c = pick_window_narrow(ctx->is_te(), n, nar.fmt.bits, /*one_level=*/true);
       if (make_plan(ctx, n, &o, pl, false, nar.fmt.bits)) return fail(ctx, MSM_ERR_ARG, "msm_run_batch_narrow: bad window size");
       pl.nar = nar;
       bool fused = fuse(ctx, n, B, pl);
@@ -283,23 +227,8 @@ extern "C" int msm_run_batch_narrow(msm_ctx* ctx, const void* const* scalars, ui
         return run_fused(ctx, scalars, B, n, on_device, opts, pl, out);
       }
     }
-    msm_result tot;
-    memset(&tot, 0, sizeof tot);
-    for (uint32_t b = 0; b < B; b++) {
-      if (int rc = msm_run_narrow(ctx, scalars[b], n, on_device, width_bytes, bits, is_signed, opts, &out[b])) return rc;
-      for (int j = 0; j < MSM_N_PHASES; j++) tot.phase_ms[j] += out[b].phase_ms[j];
-      tot.rounds += out[b].rounds;
-      tot.n_pairs += out[b].n_pairs;
-      tot.n_pairs_algo += out[b].n_pairs_algo;
-      tot.max_bucket = std::max(tot.max_bucket, out[b].max_bucket);
-    }
-    for (uint32_t b = 0; b < B; b++) {
-      memcpy(out[b].phase_ms, tot.phase_ms, sizeof tot.phase_ms);
-      out[b].rounds = tot.rounds;
-      out[b].n_pairs = tot.n_pairs;
-      out[b].n_pairs_algo = tot.n_pairs_algo;
-      out[b].max_bucket = tot.max_bucket;
-    }
-    return MSM_OK;
+    return run_each(B, out, [&](uint32_t b) {
+      return msm_run_narrow(ctx, scalars[b], n, on_device, width_bytes, bits, is_signed, opts, &out[b]);
+    });
   } MSM_CATCH_ALL(ctx)
 }

@@ -1,13 +1,16 @@
-// Host-side internals of libmsm_hip.so shared by its translation units (round 5 split msm_api.hip into them):
+// Host-side internals of libmsm_hip.so shared by its translation units (HOST_TUS in the Makefile):
 //   msm_plan.hip      window size, plan, launch geometry, workspace budget model, error helpers
 //   msm_sort.hip      digits + counting sort of one window group (driver of sort_kernels.h)
 //   msm_tree.hip      accumulation tree of one window group (driver of k_batch_add / k_te_add) + k_bucket_finish
-//   msm_reduce.hip    bucket reduction, window sums, host tail (Horner, to-affine, combine)
+//   msm_reduce.hip    bucket reduction, and the host tail over window sums (sum, Horner, to-affine, wire form, combine)
 //   msm_upload.hip    staged and pipelined host -> device transfers
-//   msm_pipeline.hip  window groups on two streams, point ranges, multi-device fan-out
+//   msm_pipeline.hip  window groups on two streams, point ranges, multi-device fan-out, call statistics
+//   msm_batch.hip     msm_run_batch, msm_run_batch_narrow: B MSMs over one point set, fused into shared window groups
 //   msm_tables.hip    window tables (K resident tables 2^(c k) P: one set of buckets for all windows)
 //   msm_abi.hip       the C ABI of include/msm_hip.h (contexts, points, msm_run, msm_window_sums, handles)
-//   msm_test_abi.hip  the operator-level test entries (msm_test_*) and the input generators
+//   msm_test_abi.hip  the operator-level test entries (msm_test_*)
+//   msm_gen.hip       the input generators (msm_generate_points, msm_generate_scalars)
+//   msm_ingest.hip    msm_set_points_ex, msm_validate_points, msm_get_points_ex: compressed points, subgroup checks
 //   msm_narrow.hip    msm_run_narrow, msm_plan_narrow, msm_scalar_bits (narrow scalars: no endomorphism split, K from the call's bits)
 // Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip, te_kernels.hip and narrow_kernels.hip; host TUs see
 // declarations.
@@ -136,6 +139,11 @@ inline const CurveInfo& curve_info(int curve) {
   const CurveInfo* ci = curve_info_or_null(curve);
   return ci ? *ci : *curve_info_or_null(MSM_CURVE_BLS12_377_G1);
 }
+
+// A window sum travels through the host pipeline as one "slot" of packed words in device Montgomery form: X, Y, Z of 12 words
+// each on the Weierstrass curves, X, Y, Z, T of 8 words each on the Edwards curve (msm_ctx::sum_words()); msm_window_sums
+// hands it out as X || Y || Z of 48 bytes each.  Only the helpers of msm_reduce.hip look inside a slot.
+constexpr int W_SUM_WORDS = 36, TE_SUM_WORDS = 32, SUM_WIRE_BYTES = 144;
 
 // One helper thread per context, started with it: the second window group of a big MSM runs here (the calling thread
 // takes the first), so no thread is created per call.  run() hands over a job, wait() returns when it is done and
@@ -295,6 +303,7 @@ struct msm_ctx {
   int nw() const { return msmi::curve_info(curve).nw; }
   size_t coord_bytes() const { return (size_t)nw() * 4; }
   uint64_t row_words() const { return is_te() ? (uint64_t)msm::te::TE_ROW_WORDS : (uint64_t)msm::ROW_WORDS; }   // of a point row
+  int sum_words() const { return is_te() ? msmi::TE_SUM_WORDS : msmi::W_SUM_WORDS; }                            // of a window-sum slot
 
   void ensure(msmi::DevBuf& b, size_t bytes) {
     if (bytes <= b.cap) return;
@@ -408,6 +417,15 @@ struct GroupStats {
   uint64_t max_bucket = 0;
   int rounds = 0;
   float ms_digits = 0, ms_sort = 0, ms_acc = 0, ms_red = 0, ms_r1 = 0;
+  // the groups of a call: everything adds up (tree rounds of ALL window groups, like n_pairs and ms_acc) but the largest bucket
+  GroupStats& operator+=(const GroupStats& o) {
+    n_pairs += o.n_pairs;
+    n_pairs_algo += o.n_pairs_algo;
+    max_bucket = std::max(max_bucket, o.max_bucket);
+    rounds += o.rounds;
+    ms_digits += o.ms_digits; ms_sort += o.ms_sort; ms_acc += o.ms_acc; ms_red += o.ms_red; ms_r1 += o.ms_r1;
+    return *this;
+  }
 };
 
 // launch geometry of one tree round
@@ -425,18 +443,25 @@ uint64_t point_pieces(const msm_ctx* ctx, uint64_t n, const Plan& pl);
 // ---- msm_reduce.hip ---------------------------------------------------------------------------------------------
 void words_to_fe6(msm_host::Fe6& r, const uint32_t* w, int nw = 12);
 void fe6_to_bytes(uint8_t* out, const msm_host::Fe6& a);
+// one packed coordinate of nw words in device Montgomery form -> its value as 4 nw little-endian bytes; k_to_host: the
+// context's k_dev_to_host (F = hc.F) or k_te_to_host (F = hte.F)
+void device_coord_to_wire(const msm_host::Field6& F, const msm_host::Fe6& k_to_host, const uint32_t* w, int nw, uint8_t* out);
 void plane_element_to_wire(const msm_ctx* ctx, const uint32_t* planes, uint64_t cap, uint64_t e, uint8_t* out_xy);
-msm_host::Proj6 partial_to_host(const msm_ctx* ctx, const uint32_t* w);
-void host_to_partial(const msm_ctx*, const msm_host::Proj6& P, uint32_t* out36);
 void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint64_t fin_cap, const uint32_t* off_fin,
                     const uint32_t* bucket_proj, uint32_t L, int kc, uint32_t* h_partials_out, bool merged = false, int stride = 0);
-msm_host::Proj6 horner_points(const msm_host::Curve6& C, const std::vector<msm_host::Proj6>& P, int c);
-void proj_to_result(const msm_host::Curve6& C, const msm_host::Proj6& acc, msm_result* out);
-void horner_to_affine(const msm_host::Curve6& C, const std::vector<msm_host::Proj6>& P, int c, msm_result* out);
-void te_horner_points(const msm_host::TeCurve6& C, const std::vector<msm_host::Ext6>& P, int c, msm_result* out);
-msm_host::Ext6 te_partial_to_host(const msm_ctx* ctx, const uint32_t* w);
-void te_host_to_partial(const msm_ctx*, const msm_host::Ext6& P, uint32_t* out32);
-void te_horner_to_affine(const msm_ctx* ctx, const std::vector<uint32_t>& words, int K, int c, msm_result* out);
+// The host tail: what happens to window sums between the bucket reduction and the caller.  A slot is ctx->sum_words() words;
+// `words` are K slots in a row.  These read the context's curve constants only, so any number of host threads may call them.
+void sum_set_identity(const msm_ctx* ctx, uint32_t* slot);
+// out = the sum of the slots of `parts` as group elements (none: the identity); out may be one of them
+void sum_slots(const msm_ctx* ctx, const std::vector<const uint32_t*>& parts, uint32_t* out);
+// out_slot = sum_k 2^(c k) words[k] (src/msm-batched-affine.ts:322-333)
+void sums_horner(const msm_ctx* ctx, const uint32_t* words, int K, int c, uint32_t* out_slot);
+// the same sum as the canonical affine point: x, y and is_infinity of `out`
+void sums_finish(const msm_ctx* ctx, const uint32_t* words, int K, int c, msm_result* out);
+// the result of an MSM over no points: infinity on a Weierstrass curve, the affine point (0, 1) on the Edwards curve
+void identity_to_result(const msm_ctx* ctx, msm_result* out);
+// slot -> X || Y || Z, SUM_WIRE_BYTES of canonical integers (slot = nullptr, or Z = 0 on a Weierstrass curve: the identity)
+void sum_to_wire(const msm_ctx* ctx, const uint32_t* slot, uint8_t* out);
 const msm_host::Curve6* static_host_curve(int curve);
 int combine_impl(msm_ctx* ctx, const msm_host::Curve6& C, const uint8_t* partials, int32_t K, int32_t c, msm_result* out, int32_t G);
 int te_combine_impl(const uint8_t* partials, int32_t K, int32_t c, msm_result* out, int32_t G = 1);
@@ -479,6 +504,9 @@ struct TreeOut {
 // kc: windows of the group as the tree sees them (1 on window tables); row_off: first row of the point table the payloads count from
 void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl, int kc, uint64_t row_off, const SortOut& so,
                              GroupStats& st, TreeOut& to);
+// entries per window from which the sort leaves its one-level form for the radix split (measured: msm_sort.hip); callers that
+// depend on the one-level sort -- 128 windows in a group, a fused batch -- ask here
+uint64_t one_level_entry_limit(bool te);
 void sort_kernel_attributes();   // dynamic-LDS limits of the sort kernels (once per process and device)
 
 // ---- msm_tables.hip ---------------------------------------------------------------------------------------------
@@ -498,6 +526,16 @@ int stage_scalars(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, 
 // Chunks go out in address order over the staging threads as in upload_staged; when a thread has queued its last chunk of
 // piece q it records piece_ev[q][t] on its copy stream, and wait_piece(q, stream) makes `stream` wait for all of them.
 // The reference's counterpart is scalarsFromBytes into shared wasm memory before the call, src/parallel.ts:119-133.
+// Host scalars are pipelined from 2^24 points; the ranges end at 1/16, 3/16 and the rest from 2^25 points, 1/8, 3/8 and the
+// rest below, rounded down to whole staging chunks: the link moves scalars ~4x as fast as the GPU consumes them (2 GB in ~40 ms
+// against ~154 ms of MSM at 2^26), so every range may be ~4x its predecessor and still arrive before the GPU is done with the
+// one before.  The first range is what the GPU waits for (2-3 ms); few ranges keep the sub-MSMs near full-size efficiency.
+inline bool pipelines_host_scalars(uint64_t n) { return n >= (1ull << 24); }
+inline std::vector<uint64_t> pipelined_piece_ends(uint64_t n) {   // point index where piece q ends (the last = n)
+  const uint64_t gran = msm_ctx::STAGE_CHUNK / 32;   // scalars per staging chunk
+  const int big = n >= (1ull << 25);
+  return {((n >> (big ? 4 : 3)) / gran) * gran, ((n >> (big ? 2 : 1)) / gran) * gran, n};
+}
 class PieceUpload {
  public:
   static constexpr int T = msm_ctx::STAGE_THREADS, S = msm_ctx::STAGE_SLOTS;
@@ -604,6 +642,22 @@ int window_sums_impl(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
                      const Plan& pl, std::vector<uint32_t>& words, msm_result* stats, uint64_t p_off = 0);
 int any_window_sums(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, const msm_opts* opts, int k_lo, int k_hi,
                     const Plan& pl, std::vector<uint32_t>& words, msm_result* stats, const void* const* placed = nullptr);
+
+// The two-stream runner of a call: job(slot, i) for i = 0 .. n_jobs - 1, each on one of the context's two workspaces (slot), the
+// second worker on the context's helper thread unless `serial`.  Whatever a job throws is re-raised only after both workers have
+// stopped and both group streams are idle.
+void run_on_workspaces(msm_ctx* ctx, int n_jobs, bool serial, const std::function<void(int slot, int index)>& job);
+// adds the five intervals between the events a window group has recorded on w (sort_window_group .. reduce_buckets) to st
+void add_group_times(const msm_ctx::Workspace& w, GroupStats& st);
+// phases (digits .. reduce), pairs, rounds and the largest bucket of a call's window groups -> its msm_result
+void stats_to_result(const GroupStats& st, msm_result* r);
+// tot += the statistics of one call of several that make up an entry: phases, pairs and rounds add up, the largest bucket is
+// the largest; side_by_side (the devices of a multi-device call) takes the longest of every phase instead of their sum
+void add_call_stats(msm_result& tot, const msm_result& r, bool side_by_side = false);
+// error word of the digit kernels (ctx->errflag) after the window groups of a call: throws what the plan does not tolerate.
+// `who`: the narrow entry point (it alone declares a range)
+constexpr uint32_t ERR_SCALAR_GE_Q = 4u, ERR_FOLD_DIGIT = 8u;   // (bits 1 and 2: the point loaders; NARROW_ERR_RANGE: narrow_kernels.h)
+void check_scalar_flags(msm_ctx* ctx, const Plan& pl, const char* who);
 
 // runs f(child) for every child of a multi-device context on the fan-out threads, and f(ctx) on the calling thread;
 // returns the first error code

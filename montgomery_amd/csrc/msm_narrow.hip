@@ -68,8 +68,7 @@ int msm_run_narrow(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device,
   out->c = pl.c;
   out->K = pl.K;
   if (n == 0) {
-    if (ctx->is_te()) out->y[0] = 1;   // identity (0, 1)
-    else out->is_infinity = 1;
+    identity_to_result(ctx, out);
     return MSM_OK;
   }
   try {
@@ -95,13 +94,7 @@ int msm_run_narrow(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device,
     std::vector<uint32_t> words;
     window_sums_impl(ctx, dev - off, n, 1, opts, 0, pl.K, pl, words, out, point_lo(opts));
     HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
-    if (ctx->is_te()) {
-      te_horner_to_affine(ctx, words, pl.K, pl.c, out);
-    } else {
-      std::vector<msm_host::Proj6> P(pl.K);
-      for (int k = 0; k < pl.K; k++) P[k] = partial_to_host(ctx, &words[(size_t)k * 36]);
-      horner_to_affine(ctx->hc, P, pl.c, out);
-    }
+    sums_finish(ctx, words.data(), pl.K, pl.c, out);
     HIPCHK(hipEventRecord(ctx->ev[11], ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     float ms;

@@ -8,7 +8,7 @@ using namespace msmi;
 
 namespace {
 
-// Partition sums P_k for windows [k_lo, k_hi) over the points [p_lo, p_lo + n) -> h_partials_out[(k - k_lo) * 36 ...]
+// Partition sums P_k for windows [k_lo, k_hi) over the points [p_lo, p_lo + n) -> slot k - k_lo of h_partials_out
 // scalars: device pointer, n x 8 words.
 // k_base: the first window of the CALL (window tables carry weights relative to it: table j = 2^(c j) P serves window k_base + j)
 // the scalars of the points [p_lo, ...) of a call: 32-byte scalars are addressed; narrow ones (msm_run_narrow) keep the call's
@@ -38,21 +38,12 @@ void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sca
     // call's first window) already.  It goes into the group's first slot, identities into the others.
     accumulate_window_group(ctx, w, pl, 1, (uint64_t)(k_lo - k_base) * pl.tab_n, so, st, to);
     reduce_buckets(ctx, w, to.fin, to.fin_cap, to.off_fin, to.bucket_proj, pl.L, 1, h_partials_out, pl.merged, pl.c);
-    const int pw = ctx->is_te() ? 32 : 36;
-    for (int kk = 1; kk < kc; kk++) {
-      if (ctx->is_te()) te_host_to_partial(ctx, ctx->hte.zero(), h_partials_out + (size_t)kk * pw);
-      else memset(h_partials_out + (size_t)kk * pw, 0, (size_t)pw * 4);
-    }
+    for (int kk = 1; kk < kc; kk++) sum_set_identity(ctx, h_partials_out + (size_t)kk * ctx->sum_words());
   } else {
     accumulate_window_group(ctx, w, pl, kc, p_lo, so, st, to);
     reduce_buckets(ctx, w, to.fin, to.fin_cap, to.off_fin, to.bucket_proj, pl.L, kc, h_partials_out, pl.merged, pl.c);
   }
-  float ms;
-  HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1])); st.ms_digits += ms;
-  HIPCHK(hipEventElapsedTime(&ms, w.ev[1], w.ev[2])); st.ms_sort += ms;
-  HIPCHK(hipEventElapsedTime(&ms, w.ev[5], w.ev[3])); st.ms_acc += ms;
-  HIPCHK(hipEventElapsedTime(&ms, w.ev[5], w.ev[6])); st.ms_r1 += ms;
-  HIPCHK(hipEventElapsedTime(&ms, w.ev[3], w.ev[4])); st.ms_red += ms;
+  add_group_times(w, st);
 }
 
 // windows [k_lo, k_hi) over the resident points [p_off, p_off + n); scalars[i] belongs to point p_off + i
@@ -64,22 +55,15 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
   // Host scalars of a big call cross PCIe BEHIND the computation, range by range of the points (PieceUpload); everything
   // else is staged before the window groups start.
   std::vector<uint64_t> piece_end;   // pipelined upload: point index where piece q ends (the last = n)
-  if (!on_device && n >= (1ull << 24)) {
-    // The link moves scalars ~4x as fast as the GPU consumes them (2 GB in ~40 ms against ~154 ms of MSM at 2^26), so
-    // every range may be ~4x its predecessor and still arrive before the GPU is done with the one before: 1/16, 3/16, the
-    // rest from 2^25 points; 1/8, 3/8, the rest below.  The first range is what the GPU waits for (2-3 ms); few ranges keep
-    // the sub-MSMs near full-size efficiency.
-    const uint64_t gran = msm_ctx::STAGE_CHUNK / 32;   // scalars per staging chunk
-    const int big = n >= (1ull << 25);
-    for (int sh : {big ? 4 : 3, big ? 2 : 1}) piece_end.push_back(((n >> sh) / gran) * gran);
-    piece_end.push_back(n);
+  if (!on_device && pipelines_host_scalars(n)) {
+    piece_end = pipelined_piece_ends(n);
     ctx->ensure(ctx->scal, n * 32);   // before the workspace budget is taken from what the device has free
   }
   std::unique_ptr<PieceUpload> pipe;
   if (piece_end.empty()) stage_scalars(ctx, scalars, n, on_device, &d_scal);
   HIPCHK(hipEventRecord(ctx->ev[9], ctx->stream));
   GroupStats st;
-  const int pw = ctx->is_te() ? 32 : 36;
+  const int pw = ctx->sum_words();
   words.assign((size_t)(k_hi - k_lo) * pw, 0);
   // window groups: as large as the workspace budget allows; for big inputs two of them on two streams.  The streams
   // run in step (both sort, both gather, ...): what the second one buys is two tree kernels sharing the chip -- forward
@@ -106,7 +90,7 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
   {
     const uint64_t entries = ctx->is_te() ? n : 2 * n;
     const bool fits_lds = ((size_t)pl.L * 4 <= 128 * 1024);
-    if (pl.c - 1 > (int)RX_FINE_BITS && (!fits_lds || entries >= (ctx->is_te() ? 1ull << 22 : 1ull << 21))) wpg = std::min(wpg, 16);
+    if (pl.c - 1 > (int)RX_FINE_BITS && (!fits_lds || entries >= one_level_entry_limit(ctx->is_te()))) wpg = std::min(wpg, 16);
     // (on window tables the merged window of a group may take the bin split whatever a single digit window would have taken,
     // and the digit kernel describes the fine bits of at most 16 windows: pack_fine_bits)
     if (pl.tables) wpg = std::min(wpg, 16);
@@ -195,86 +179,41 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
     sort_window_group(ctx, ctx->ws[0], d_grp, groups[0].p_n, pd, groups[0].ka, groups[1].kb, gs, none, &share);
     share.produce = false;
   }
-  std::atomic<int> next{0};
   GroupStats sts[msm_ctx::N_WS];
-  const int nthreads = (opts && opts->serial) ? 1 : std::min<int>(msm_ctx::N_WS, (int)groups.size());
-  auto worker = [&](int slot) {
-    HIPCHK(hipSetDevice(ctx->device));
-    for (;;) {
-      int gi = next.fetch_add(1);
-      if (gi >= (int)groups.size()) break;
-      const int ka = groups[gi].ka, kb = groups[gi].kb;
-      std::vector<uint32_t> part((size_t)(kb - ka) * pw);
-      Plan pg = pl;
-      // a launch that has the chip to itself -- the one-window shard, or every launch of a serialised call (msm_opts.serial,
-      // the exclusive timing of the roofline) -- walks its pairs in four short batches instead of one long one (round_geom)
-      pg.lone = (groups.size() == 1 && (kb - ka == 1 || pl.tables)) || (opts && opts->serial);
-      if (groups[gi].piece >= 0) pipe->wait_piece(groups[gi].piece, ctx->ws[slot].stream);
-      run_window_group(ctx, ctx->ws[slot], d_scal, groups[gi].p_lo, groups[gi].p_n, pg, ka, kb, k_lo, part.data(), sts[slot], p_off,
-                       share.valid ? &share : nullptr);
-      if (split_points || pl.tables) split_part[gi] = part;
-      else memcpy(&words[(size_t)(ka - k_lo) * pw], part.data(), part.size() * 4);
-    }
-  };
-  {
-    // Whatever either worker throws (HIP failure, bad_alloc, ...) is re-raised here only after BOTH have stopped and both
-    // group streams are idle: no queued kernel of a failed call may still run when the context is used again.
-    std::exception_ptr err;
-    if (nthreads > 1) ctx->helper->run([&] { worker(1); });
-    try { worker(0); } catch (...) { err = std::current_exception(); }
-    if (nthreads > 1) {
-      try { ctx->helper->wait(); } catch (...) { if (!err) err = std::current_exception(); }
-    }
-    if (err) {
-      next.store((int)groups.size());
-      for (auto& w : ctx->ws) (void)hipStreamSynchronize(w.stream);
-      std::rethrow_exception(err);
-    }
-  }
-  {
-    // scalars >= q seen by k_digits: refused under msm_opts.strict (otherwise they were reduced mod q)
-    HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (pl.strict && (ctx->h_info[0] & 4u)) throw MsmFail{MSM_ERR_SCALAR, "a scalar is >= the group order q (msm_opts.strict)"};
-    if (ctx->h_info[0] & NARROW_ERR_RANGE) throw MsmFail{MSM_ERR_SCALAR, "a scalar lies outside the declared range (msm_run_narrow)"};
-    if (ctx->h_info[0] & 8u) throw MsmFail{MSM_ERR_INTERNAL, "a digit of the folded top window exceeds its bucket range (GLV bound violated)"};
-  }
+  run_on_workspaces(ctx, (int)groups.size(), opts && opts->serial, [&](int slot, int gi) {
+    const int ka = groups[gi].ka, kb = groups[gi].kb;
+    std::vector<uint32_t> part((size_t)(kb - ka) * pw);
+    Plan pg = pl;
+    // a launch that has the chip to itself -- the one-window shard, or every launch of a serialised call (msm_opts.serial,
+    // the exclusive timing of the roofline) -- walks its pairs in four short batches instead of one long one (round_geom)
+    pg.lone = (groups.size() == 1 && (kb - ka == 1 || pl.tables)) || (opts && opts->serial);
+    if (groups[gi].piece >= 0) pipe->wait_piece(groups[gi].piece, ctx->ws[slot].stream);
+    run_window_group(ctx, ctx->ws[slot], d_scal, groups[gi].p_lo, groups[gi].p_n, pg, ka, kb, k_lo, part.data(), sts[slot], p_off,
+                     share.valid ? &share : nullptr);
+    if (split_points || pl.tables) split_part[gi] = part;
+    else memcpy(&words[(size_t)(ka - k_lo) * pw], part.data(), part.size() * 4);
+  });
+  check_scalar_flags(ctx, pl, "msm_run_narrow");
   float upload_ms = -1;
   if (pipe) upload_ms = pipe->finish();   // joins the staging threads; their last copy is done
   if (pl.tables) {
     // every group's first slot holds the sum of its windows WITH their weights: the call's sum is their plain sum, kept in
     // slot 0 (identities elsewhere: the caller's Horner step over such slots would return the same element)
-    if (ctx->is_te()) {
-      msm_host::Ext6 acc = ctx->hte.zero();
-      for (size_t gi = 0; gi < groups.size(); gi++)
-        if (!split_part[gi].empty()) acc = ctx->hte.add(acc, te_partial_to_host(ctx, split_part[gi].data()));
-      for (int k = k_lo; k < k_hi; k++) te_host_to_partial(ctx, k == k_lo ? acc : ctx->hte.zero(), &words[(size_t)(k - k_lo) * pw]);
-    } else {
-      msm_host::Proj6 acc = ctx->hc.zero();
-      for (size_t gi = 0; gi < groups.size(); gi++)
-        if (!split_part[gi].empty()) acc = ctx->hc.add(acc, partial_to_host(ctx, split_part[gi].data()));
-      std::fill(words.begin(), words.end(), 0u);
-      host_to_partial(ctx, acc, words.data());
-    }
+    std::vector<const uint32_t*> firsts;
+    for (const auto& part : split_part)
+      if (!part.empty()) firsts.push_back(part.data());
+    sum_slots(ctx, firsts, words.data());
+    for (int k = k_lo + 1; k < k_hi; k++) sum_set_identity(ctx, &words[(size_t)(k - k_lo) * pw]);
   } else if (split_points) {
     // P_k = sum over the ranges of the points (groups of one or several windows each); an all-zero partial (Z = 0) is the
     // identity.  (Plan.merged: a group then carries sum_kk 2^(c kk) P_kk in its first slot and identities in the others --
     // slot-wise sums of such groups are still a valid set of slots for the Horner step.)
     for (int k = k_lo; k < k_hi; k++) {
-      uint32_t* out = &words[(size_t)(k - k_lo) * pw];
-      if (ctx->is_te()) {
-        msm_host::Ext6 acc = ctx->hte.zero();
-        for (size_t gi = 0; gi < groups.size(); gi++)
-          if (groups[gi].ka <= k && k < groups[gi].kb && !split_part[gi].empty())
-            acc = ctx->hte.add(acc, te_partial_to_host(ctx, split_part[gi].data() + (size_t)(k - groups[gi].ka) * pw));
-        te_host_to_partial(ctx, acc, out);
-      } else {
-        msm_host::Proj6 acc = ctx->hc.zero();
-        for (size_t gi = 0; gi < groups.size(); gi++)
-          if (groups[gi].ka <= k && k < groups[gi].kb && !split_part[gi].empty())
-            acc = ctx->hc.add(acc, partial_to_host(ctx, split_part[gi].data() + (size_t)(k - groups[gi].ka) * pw));
-        host_to_partial(ctx, acc, out);
-      }
+      std::vector<const uint32_t*> ranges;
+      for (size_t gi = 0; gi < groups.size(); gi++)
+        if (groups[gi].ka <= k && k < groups[gi].kb && !split_part[gi].empty())
+          ranges.push_back(split_part[gi].data() + (size_t)(k - groups[gi].ka) * pw);
+      sum_slots(ctx, ranges, &words[(size_t)(k - k_lo) * pw]);
     }
   }
   if (share.valid) {
@@ -282,14 +221,7 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
     HIPCHK(hipEventElapsedTime(&ms, ctx->ev_dig[0], ctx->ev_dig[1]));
     st.ms_digits += ms;
   }
-  for (int i = 0; i < msm_ctx::N_WS; i++) {
-    st.n_pairs += sts[i].n_pairs;
-    st.n_pairs_algo += sts[i].n_pairs_algo;
-    st.max_bucket = std::max(st.max_bucket, sts[i].max_bucket);
-    st.rounds += sts[i].rounds;   // tree rounds (k_batch_add launches) of ALL window groups, like n_pairs and ms_acc
-    st.ms_digits += sts[i].ms_digits; st.ms_sort += sts[i].ms_sort; st.ms_acc += sts[i].ms_acc;
-    st.ms_red += sts[i].ms_red; st.ms_r1 += sts[i].ms_r1;
-  }
+  for (const GroupStats& g : sts) st += g;
   HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (stats) {
@@ -298,15 +230,7 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
     stats->phase_ms[MSM_T_UPLOAD] = upload_ms >= 0 ? upload_ms : ms;   // pipelined: host clock of the background transfer
     HIPCHK(hipEventElapsedTime(&ms, ctx->ev[8], ctx->ev[10]));
     stats->phase_ms[MSM_T_TOTAL] = ms;
-    stats->phase_ms[MSM_T_DIGITS] = st.ms_digits;
-    stats->phase_ms[MSM_T_SORT] = st.ms_sort;
-    stats->phase_ms[MSM_T_ACCUMULATE] = st.ms_acc;
-    stats->phase_ms[MSM_T_ACC_ROUND1] = st.ms_r1;
-    stats->phase_ms[MSM_T_REDUCE] = st.ms_red;
-    stats->n_pairs = st.n_pairs;
-    stats->n_pairs_algo = st.n_pairs_algo;
-    stats->max_bucket = st.max_bucket;
-    stats->rounds = st.rounds;
+    stats_to_result(st, stats);
     stats->c = pl.c;
     stats->K = pl.K;
     stats->tables = pl.tables ? 1 : 0;
@@ -317,6 +241,67 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
 }  // namespace
 
 namespace msmi {
+
+void run_on_workspaces(msm_ctx* ctx, int n_jobs, bool serial, const std::function<void(int slot, int index)>& job) {
+  std::atomic<int> next{0};
+  auto worker = [&](int slot) {
+    HIPCHK(hipSetDevice(ctx->device));
+    for (int i; (i = next.fetch_add(1)) < n_jobs;) job(slot, i);
+  };
+  // Whatever either worker throws (HIP failure, bad_alloc, ...) is re-raised here only after BOTH have stopped and both
+  // group streams are idle: no queued kernel of a failed call may still run when the context is used again.
+  const int nthreads = serial ? 1 : std::min<int>(msm_ctx::N_WS, n_jobs);
+  std::exception_ptr err;
+  if (nthreads > 1) ctx->helper->run([&] { worker(1); });
+  try { worker(0); } catch (...) { err = std::current_exception(); }
+  if (nthreads > 1) {
+    try { ctx->helper->wait(); } catch (...) { if (!err) err = std::current_exception(); }
+  }
+  if (err) {
+    for (auto& w : ctx->ws) (void)hipStreamSynchronize(w.stream);
+    std::rethrow_exception(err);
+  }
+}
+
+void add_group_times(const msm_ctx::Workspace& w, GroupStats& st) {
+  float ms;
+  HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1])); st.ms_digits += ms;
+  HIPCHK(hipEventElapsedTime(&ms, w.ev[1], w.ev[2])); st.ms_sort += ms;
+  HIPCHK(hipEventElapsedTime(&ms, w.ev[5], w.ev[3])); st.ms_acc += ms;
+  HIPCHK(hipEventElapsedTime(&ms, w.ev[5], w.ev[6])); st.ms_r1 += ms;
+  HIPCHK(hipEventElapsedTime(&ms, w.ev[3], w.ev[4])); st.ms_red += ms;
+}
+
+void stats_to_result(const GroupStats& st, msm_result* r) {
+  r->phase_ms[MSM_T_DIGITS] = st.ms_digits;
+  r->phase_ms[MSM_T_SORT] = st.ms_sort;
+  r->phase_ms[MSM_T_ACCUMULATE] = st.ms_acc;
+  r->phase_ms[MSM_T_ACC_ROUND1] = st.ms_r1;
+  r->phase_ms[MSM_T_REDUCE] = st.ms_red;
+  r->n_pairs = st.n_pairs;
+  r->n_pairs_algo = st.n_pairs_algo;
+  r->max_bucket = st.max_bucket;
+  r->rounds = st.rounds;
+}
+
+void add_call_stats(msm_result& tot, const msm_result& r, bool side_by_side) {
+  for (int j = 0; j < MSM_N_PHASES; j++)
+    tot.phase_ms[j] = side_by_side ? std::max(tot.phase_ms[j], r.phase_ms[j]) : tot.phase_ms[j] + r.phase_ms[j];
+  tot.n_pairs += r.n_pairs;
+  tot.n_pairs_algo += r.n_pairs_algo;
+  tot.rounds += r.rounds;
+  tot.max_bucket = std::max(tot.max_bucket, r.max_bucket);
+}
+
+void check_scalar_flags(msm_ctx* ctx, const Plan& pl, const char* who) {
+  HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const uint32_t flags = ctx->h_info[0];
+  // scalars >= q seen by k_digits: refused under msm_opts.strict (otherwise they were reduced mod q)
+  if (pl.strict && (flags & ERR_SCALAR_GE_Q)) throw MsmFail{MSM_ERR_SCALAR, "a scalar is >= the group order q (msm_opts.strict)"};
+  if (flags & NARROW_ERR_RANGE) throw MsmFail{MSM_ERR_SCALAR, std::string("a scalar lies outside the declared range (") + who + ")"};
+  if (flags & ERR_FOLD_DIGIT) throw MsmFail{MSM_ERR_INTERNAL, "a digit of the folded top window exceeds its bucket range (GLV bound violated)"};
+}
 
 // Workspace buffers only grow, and a call with another shape (window size, curve of the point set, sort path) leaves buffers
 // behind that the next shape does not use: if the device runs out of memory the workspaces are dropped and the call runs
@@ -361,7 +346,7 @@ namespace {
 int multi_window_sums(msm_ctx* ctx, const void* scalars, const void* const* placed, uint64_t n, int on_device, const msm_opts* opts,
                       int k_lo, int k_hi, const Plan& pl, std::vector<uint32_t>& words, msm_result* stats, uint64_t p_off) {
   const int ndev = 1 + (int)ctx->children.size();
-  const int nwin = k_hi - k_lo, pw = ctx->is_te() ? 32 : 36;
+  const int nwin = k_hi - k_lo, pw = ctx->sum_words();
   const bool by_window = opts && opts->by_window;
   words.assign((size_t)nwin * pw, 0);
   std::vector<int> lo(ndev, k_lo), hi(ndev, k_hi);
@@ -414,27 +399,14 @@ int multi_window_sums(msm_ctx* ctx, const void* scalars, const void* const* plac
   } else {
     // P_k = sum over the devices; an all-zero partial (Z = 0) is the identity, a device without points has none at all
     for (int k = 0; k < nwin; k++) {
-      if (ctx->is_te()) {
-        msm_host::Ext6 acc = ctx->hte.zero();
-        for (int d = 0; d < ndev; d++)
-          if (!part[d].empty()) acc = ctx->hte.add(acc, te_partial_to_host(ctx, &part[d][(size_t)k * pw]));
-        te_host_to_partial(ctx, acc, &words[(size_t)k * pw]);
-      } else {
-        msm_host::Proj6 acc = ctx->hc.zero();
-        for (int d = 0; d < ndev; d++)
-          if (!part[d].empty()) acc = ctx->hc.add(acc, partial_to_host(ctx, &part[d][(size_t)k * pw]));
-        host_to_partial(ctx, acc, &words[(size_t)k * pw]);
-      }
+      std::vector<const uint32_t*> devs;
+      for (int d = 0; d < ndev; d++)
+        if (!part[d].empty()) devs.push_back(&part[d][(size_t)k * pw]);
+      sum_slots(ctx, devs, &words[(size_t)k * pw]);
     }
   }
   if (stats) {
-    for (int d = 0; d < ndev; d++) {
-      stats->n_pairs += st[d].n_pairs;
-      stats->n_pairs_algo += st[d].n_pairs_algo;
-      stats->rounds += st[d].rounds;
-      stats->max_bucket = std::max(stats->max_bucket, st[d].max_bucket);
-      for (int j = 0; j < MSM_N_PHASES; j++) stats->phase_ms[j] = std::max(stats->phase_ms[j], st[d].phase_ms[j]);
-    }
+    for (int d = 0; d < ndev; d++) add_call_stats(*stats, st[d], /*side_by_side=*/true);   // the devices ran at the same time
     stats->c = pl.c;
     stats->K = pl.K;
   }

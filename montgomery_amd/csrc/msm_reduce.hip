@@ -1,6 +1,7 @@
 // Bucket reduction of a window group (P_k = sum_l l B_(k,l): reduceBucketsColumnProjective + partition sums,
-// src/msm-batched-affine.ts:556-583, :312-319) and the host tail: Horner combination of the window sums, projective ->
-// affine (:322-333, src/curve-projective.ts:335-349), msm_combine.
+// src/msm-batched-affine.ts:556-583, :312-319) and the host tail over window sums: their sum as group elements, the Horner
+// combination, projective -> affine (:322-333, src/curve-projective.ts:335-349), the wire form, msm_combine.  The fork
+// between the Weierstrass and the Edwards form of a window sum is taken here and nowhere else on the host.
 #include "msm_internal.h"
 
 using namespace msm;
@@ -18,11 +19,14 @@ void fe6_to_bytes(uint8_t* out, const msm_host::Fe6& a) {
     for (int j = 0; j < 8; j++) out[8 * i + j] = (uint8_t)(a.v[i] >> (8 * j));
 }
 
+static msm_host::Ext6 te_partial_to_host(const msm_ctx* ctx, const uint32_t* w);
+static void te_host_to_partial(const msm_ctx*, const msm_host::Ext6& P, uint32_t* out32);
+
 // Window sums travel as 36 words (X, Y, Z: 12 packed words each, device Montgomery form, below 2p).  A projective point is a
 // class of triples, so the host neither converts them on the way in nor on the way out: read as host Montgomery values the
 // three words of a device point carry one common factor (2^6 for 13 limbs), which is the same point, and so is every sum the
 // host forms of such points.  Only affine values need the exact radix (horner_to_affine divides the factor out with Z).
-msm_host::Proj6 partial_to_host(const msm_ctx* ctx, const uint32_t* w) {
+static msm_host::Proj6 partial_to_host(const msm_ctx* ctx, const uint32_t* w) {
   const auto& F = ctx->hc.F;
   msm_host::Proj6 P;
   msm_host::Fe6* co[3] = {&P.X, &P.Y, &P.Z};
@@ -34,7 +38,7 @@ msm_host::Proj6 partial_to_host(const msm_ctx* ctx, const uint32_t* w) {
 }
 
 // host projective point -> the packed form the pipeline carries (canonical values; see above for the radix)
-void host_to_partial(const msm_ctx*, const msm_host::Proj6& P, uint32_t* out36) {
+static void host_to_partial(const msm_ctx*, const msm_host::Proj6& P, uint32_t* out36) {
   const msm_host::Fe6* co[3] = {&P.X, &P.Y, &P.Z};
   for (int j = 0; j < 3; j++)
     for (int q = 0; q < 6; q++) {
@@ -53,7 +57,7 @@ void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint6
   hipStream_t s = w.stream;
   const bool te = ctx->is_te();
   const uint64_t nb = (uint64_t)kc * L;
-  const int part_words = te ? 32 : 36;
+  const int part_words = ctx->sum_words();
   // buckets per lane: enough lanes to fill the chip, but never more than 16 buckets deep (2 additions each)
   // (millions of buckets -- the big windows -- go 32 deep: 2^26 at c = 22, with the two policies below, 150.6 -> 149.3 ms)
   uint32_t TC = 2;
@@ -72,7 +76,7 @@ void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint6
   const bool bit_sliced = nchunks >= 64 && (TC & (TC - 1)) == 0 && (!te || kc <= 2);
   const size_t raw_words = te ? (size_t)4 * te::TL : (size_t)3 * NL;   // raw limb words of one point between the reduction kernels
   ctx->ensure(w.columns, (size_t)kc * nchunks * 4 * NL * 4);
-  ctx->ensure(w.partials, (size_t)kc * 36 * 4);
+  ctx->ensure(w.partials, (size_t)kc * W_SUM_WORDS * 4);
   {
     uint32_t threads = nchunks * (uint32_t)kc;
     if (bit_sliced) {
@@ -87,7 +91,7 @@ void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint6
       // have half as many elements as the triangle sum and get half as many blocks; second stage: one wave per
       // (window, bit) over the block sums it finds (the slots a masked sum did not fill are never read)
       const uint32_t nblk = std::max<uint32_t>(2, nchunks / (8 * BT_THREADS));
-      ctx->ensure(w.partials, (size_t)kc * (nbits + 1) * 36 * 4);
+      ctx->ensure(w.partials, (size_t)kc * (nbits + 1) * W_SUM_WORDS * 4);
       // Two-dimensional form (msm_kernels.h, bit_tree_body): row sums A_hi and column sums B_lo of the chunk matrix first --
       // 2 additions per chunk instead of nbits / 2 -- then the nbits masked sums over those 2^(nbits / 2) + ... points.  Measured
       // (profiles/r06_experiments.txt): 2^20 on tables 0.42 -> 0.2x ms for the two launches, 2^26 0.5 -> 0.3x per window group.
@@ -155,7 +159,7 @@ void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint6
     while ((1u << (cbits - 1)) < L) cbits++;
     const int adv = stride ? stride : (int)cbits;
     // one implementation for both kinds of point: zero, doubling, addition, a packed sum in, a packed sum out
-    auto finish = [&](auto zero, auto dbl, auto add, auto from_part, auto to_part, auto ident_part) {
+    auto finish = [&](auto zero, auto dbl, auto add, auto from_part, auto to_part) {
       if (merged) {
         // The caller only wants S_g = sum_kk 2^(c kk) P_kk of the whole group (a full MSM on this device: the Horner step over
         // the windows follows anyway).  One double-and-add pass over the c kc bit positions then does both jobs -- inside window
@@ -177,7 +181,7 @@ void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint6
             if (pos == 0) acc = add(acc, from_part(base + (size_t)nbits * part_words));
           }
         }
-        for (int kk = 1; kk < kc; kk++) ident_part(h_partials_out + (size_t)kk * part_words);
+        for (int kk = 1; kk < kc; kk++) sum_set_identity(ctx, h_partials_out + (size_t)kk * part_words);
         to_part(acc, h_partials_out);
         return;
       }
@@ -198,15 +202,13 @@ void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint6
       finish([&] { return C.zero(); }, [&](const msm_host::Ext6& a) { return C.add(a, a); },
              [&](const msm_host::Ext6& a, const msm_host::Ext6& b) { return C.add(a, b); },
              [&](const uint32_t* p) { return te_partial_to_host(ctx, p); },
-             [&](const msm_host::Ext6& a, uint32_t* out) { te_host_to_partial(ctx, a, out); },
-             [&](uint32_t* out) { te_host_to_partial(ctx, C.zero(), out); });
+             [&](const msm_host::Ext6& a, uint32_t* out) { te_host_to_partial(ctx, a, out); });
     } else {
       const auto& C = ctx->hc;
       finish([&] { return C.zero(); }, [&](const msm_host::Proj6& a) { return C.dbl(a); },
              [&](const msm_host::Proj6& a, const msm_host::Proj6& b) { return C.add(a, b); },
              [&](const uint32_t* p) { return partial_to_host(ctx, p); },
-             [&](const msm_host::Proj6& a, uint32_t* out) { host_to_partial(ctx, a, out); },
-             [&](uint32_t* out) { memset(out, 0, 36 * 4); });
+             [&](const msm_host::Proj6& a, uint32_t* out) { host_to_partial(ctx, a, out); });
     }
     return;
   }
@@ -217,6 +219,17 @@ void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint6
   memcpy(h_partials_out, w.h_part, (size_t)kc * part_words * 4);
 }
 
+void device_coord_to_wire(const msm_host::Field6& F, const msm_host::Fe6& k_to_host, const uint32_t* w, int nw, uint8_t* out) {
+  const msm_host::Fe6 one = {{1, 0, 0, 0, 0, 0}};
+  msm_host::Fe6 t;
+  words_to_fe6(t, w, nw);
+  F.mul(t, t, k_to_host);   // host Montgomery
+  F.mul(t, t, one);         // plain
+  uint8_t b48[48];
+  fe6_to_bytes(b48, t);
+  memcpy(out, b48, (size_t)nw * 4);
+}
+
 void plane_element_to_wire(const msm_ctx* ctx, const uint32_t* planes, uint64_t cap, uint64_t e, uint8_t* out_xy) {
   const int nw = ctx->nw(), np = nw / 4;
   const size_t cb = ctx->coord_bytes();
@@ -225,20 +238,11 @@ void plane_element_to_wire(const msm_ctx* ctx, const uint32_t* planes, uint64_t 
     for (int q = 0; q < 4; q++) w[4 * cpl + q] = planes[((uint64_t)cpl * cap + e) * 4 + q];
   memset(out_xy, 0, 2 * cb);
   if (w[nw - 1] == INF_WORD) return;
-  msm_host::Fe6 one = {{1, 0, 0, 0, 0, 0}};
-  for (int j = 0; j < 2; j++) {
-    msm_host::Fe6 t;
-    words_to_fe6(t, w + nw * j, nw);
-    ctx->hc.F.mul(t, t, ctx->k_dev_to_host);
-    ctx->hc.F.mul(t, t, one);
-    uint8_t b48[48];
-    fe6_to_bytes(b48, t);
-    memcpy(out_xy + cb * j, b48, cb);
-  }
+  for (int j = 0; j < 2; j++) device_coord_to_wire(ctx->hc.F, ctx->k_dev_to_host, w + nw * j, nw, out_xy + cb * j);
 }
 
 // S = sum_k 2^(ck) P_k (src/msm-batched-affine.ts:322-333)
-msm_host::Proj6 horner_points(const msm_host::Curve6& C, const std::vector<msm_host::Proj6>& P, int c) {
+static msm_host::Proj6 horner_points(const msm_host::Curve6& C, const std::vector<msm_host::Proj6>& P, int c) {
   int K = (int)P.size();
   msm_host::Proj6 acc = P[K - 1];
   for (int k = K - 2; k >= 0; k--) {
@@ -249,7 +253,7 @@ msm_host::Proj6 horner_points(const msm_host::Curve6& C, const std::vector<msm_h
 }
 
 // projective -> the canonical affine result (src/curve-projective.ts:335-349)
-void proj_to_result(const msm_host::Curve6& C, const msm_host::Proj6& acc, msm_result* out) {
+static void proj_to_result(const msm_host::Curve6& C, const msm_host::Proj6& acc, msm_result* out) {
   memset(out->x, 0, 48);
   memset(out->y, 0, 48);
   if (C.is_zero(acc)) {
@@ -267,18 +271,19 @@ void proj_to_result(const msm_host::Curve6& C, const msm_host::Proj6& acc, msm_r
   fe6_to_bytes(out->y, y);
 }
 
-void horner_to_affine(const msm_host::Curve6& C, const std::vector<msm_host::Proj6>& P, int c, msm_result* out) {
-  proj_to_result(C, horner_points(C, P, c), out);
-}
-
-// twisted Edwards tail: S = sum_k 2^(ck) P_k with unified additions (src/msm-basic.ts:142-158), then x = X/Z, y = Y/Z
-void te_horner_points(const msm_host::TeCurve6& C, const std::vector<msm_host::Ext6>& P, int c, msm_result* out) {
+// twisted Edwards tail: S = sum_k 2^(ck) P_k with unified additions (src/msm-basic.ts:142-158) ...
+static msm_host::Ext6 te_horner_points(const msm_host::TeCurve6& C, const std::vector<msm_host::Ext6>& P, int c) {
   const int K = (int)P.size();
   msm_host::Ext6 acc = P[K - 1];
   for (int k = K - 2; k >= 0; k--) {
     for (int j = 0; j < c; j++) acc = C.add(acc, acc);
     acc = C.add(acc, P[k]);
   }
+  return acc;
+}
+
+// ... then x = X/Z, y = Y/Z (the identity is the affine point (0, 1): is_infinity stays 0)
+static void ext_to_result(const msm_host::TeCurve6& C, const msm_host::Ext6& acc, msm_result* out) {
   msm_host::Fe6 zi, x, y, one = {{1, 0, 0, 0, 0, 0}};
   C.F.inv(zi, acc.Z);
   C.F.mul(x, acc.X, zi);
@@ -294,7 +299,7 @@ void te_horner_points(const msm_host::TeCurve6& C, const std::vector<msm_host::E
 
 // device window sum (X, Y, Z, T: 8 words each, below 2p) -> host extended point: as for the Weierstrass sums no change of
 // radix -- (X, Y, Z, T) with T = X Y / Z stays a valid extended point when all four carry one common factor
-msm_host::Ext6 te_partial_to_host(const msm_ctx* ctx, const uint32_t* w) {
+static msm_host::Ext6 te_partial_to_host(const msm_ctx* ctx, const uint32_t* w) {
   const auto& C = ctx->hte;
   msm_host::Ext6 P;
   msm_host::Fe6* dst[4] = {&P.X, &P.Y, &P.Z, &P.T};
@@ -308,7 +313,7 @@ msm_host::Ext6 te_partial_to_host(const msm_ctx* ctx, const uint32_t* w) {
 }
 
 // host extended point -> the window-sum form (X, Y, Z, T: 8 words each)
-void te_host_to_partial(const msm_ctx*, const msm_host::Ext6& P, uint32_t* out32) {
+static void te_host_to_partial(const msm_ctx*, const msm_host::Ext6& P, uint32_t* out32) {
   const msm_host::Fe6* co[4] = {&P.X, &P.Y, &P.Z, &P.T};
   for (int j = 0; j < 4; j++)
     for (int i = 0; i < 4; i++) {
@@ -317,10 +322,77 @@ void te_host_to_partial(const msm_ctx*, const msm_host::Ext6& P, uint32_t* out32
     }
 }
 
-void te_horner_to_affine(const msm_ctx* ctx, const std::vector<uint32_t>& words, int K, int c, msm_result* out) {
+// ---- the host tail over slots: each helper takes the fork between the two forms of a window sum once ---------------------
+
+// the Weierstrass identity is the all-zero slot (Z = 0), the Edwards identity the extended point (0, 1, 1, 0)
+void sum_set_identity(const msm_ctx* ctx, uint32_t* slot) {
+  if (ctx->is_te()) te_host_to_partial(ctx, ctx->hte.zero(), slot);
+  else memset(slot, 0, W_SUM_WORDS * 4);
+}
+
+void sum_slots(const msm_ctx* ctx, const std::vector<const uint32_t*>& parts, uint32_t* out) {
+  if (ctx->is_te()) {
+    msm_host::Ext6 acc = ctx->hte.zero();
+    for (const uint32_t* p : parts) acc = ctx->hte.add(acc, te_partial_to_host(ctx, p));
+    te_host_to_partial(ctx, acc, out);
+  } else {
+    msm_host::Proj6 acc = ctx->hc.zero();
+    for (const uint32_t* p : parts) acc = ctx->hc.add(acc, partial_to_host(ctx, p));
+    host_to_partial(ctx, acc, out);
+  }
+}
+
+static msm_host::Proj6 w_horner(const msm_ctx* ctx, const uint32_t* words, int K, int c) {
+  std::vector<msm_host::Proj6> P(K);
+  for (int k = 0; k < K; k++) P[k] = partial_to_host(ctx, words + (size_t)k * W_SUM_WORDS);
+  return horner_points(ctx->hc, P, c);
+}
+static msm_host::Ext6 te_horner(const msm_ctx* ctx, const uint32_t* words, int K, int c) {
   std::vector<msm_host::Ext6> P(K);
-  for (int k = 0; k < K; k++) P[k] = te_partial_to_host(ctx, &words[(size_t)k * 32]);
-  te_horner_points(ctx->hte, P, c, out);
+  for (int k = 0; k < K; k++) P[k] = te_partial_to_host(ctx, words + (size_t)k * TE_SUM_WORDS);
+  return te_horner_points(ctx->hte, P, c);
+}
+
+void sums_horner(const msm_ctx* ctx, const uint32_t* words, int K, int c, uint32_t* out_slot) {
+  if (ctx->is_te()) te_host_to_partial(ctx, te_horner(ctx, words, K, c), out_slot);
+  else host_to_partial(ctx, w_horner(ctx, words, K, c), out_slot);
+}
+
+void sums_finish(const msm_ctx* ctx, const uint32_t* words, int K, int c, msm_result* out) {
+  if (ctx->is_te()) ext_to_result(ctx->hte, te_horner(ctx, words, K, c), out);
+  else proj_to_result(ctx->hc, w_horner(ctx, words, K, c), out);
+}
+
+void identity_to_result(const msm_ctx* ctx, msm_result* out) {
+  memset(out->x, 0, 48);
+  memset(out->y, 0, 48);
+  out->y[0] = ctx->is_te();
+  out->is_infinity = !ctx->is_te();
+}
+
+void sum_to_wire(const msm_ctx* ctx, const uint32_t* slot, uint8_t* out) {
+  const msm_host::Fe6 one = {{1, 0, 0, 0, 0, 0}};
+  msm_host::Fe6 X, Y, Z;
+  const msm_host::Field6* F;
+  if (ctx->is_te()) {
+    // extended point (X : Y : Z : T) sent as X || Y || Z; the receiver rebuilds T (msm_combine: T Z = X Y)
+    const msm_host::Ext6 P = slot ? te_partial_to_host(ctx, slot) : ctx->hte.zero();
+    X = P.X; Y = P.Y; Z = P.Z;
+    F = &ctx->hte.F;
+  } else {
+    bool zero_z = true;
+    for (int j = 0; slot && j < 12; j++) zero_z &= slot[24 + j] == 0;
+    const msm_host::Proj6 P = zero_z ? ctx->hc.zero() : partial_to_host(ctx, slot);
+    X = P.X; Y = P.Y; Z = P.Z;
+    F = &ctx->hc.F;
+  }
+  // to 48-byte canonical integers (leave Montgomery form on the host)
+  const msm_host::Fe6* co[3] = {&X, &Y, &Z};
+  for (int j = 0; j < 3; j++) {
+    msm_host::Fe6 t;
+    F->mul(t, *co[j], one);
+    fe6_to_bytes(out + 48 * j, t);
+  }
 }
 
 // host curve constants without a context (rank 0 of a sharded run may combine without touching a GPU)
@@ -353,7 +425,7 @@ int te_combine_impl(const uint8_t* partials, int32_t K, int32_t c, msm_result* o
     for (int g = 0; g < G; g++) {   // group g's sum of window k
       msm_host::Fe6 t[3];
       for (int j = 0; j < 3; j++) {
-        const uint8_t* b = partials + ((size_t)g * K + k) * 144 + 48 * j;
+        const uint8_t* b = partials + ((size_t)g * K + k) * SUM_WIRE_BYTES + 48 * j;
         for (int i = 0; i < 6; i++) {
           uint64_t v = 0;
           for (int q = 0; q < 8; q++) v |= (uint64_t)b[8 * i + q] << (8 * q);
@@ -371,7 +443,7 @@ int te_combine_impl(const uint8_t* partials, int32_t K, int32_t c, msm_result* o
     }
   }
   memset(out, 0, sizeof(*out));
-  te_horner_points(C, P, c, out);
+  ext_to_result(C, te_horner_points(C, P, c), out);
   out->c = c;
   out->K = K;
   return MSM_OK;
@@ -384,7 +456,7 @@ int combine_impl(msm_ctx* ctx, const msm_host::Curve6& C, const uint8_t* partial
     for (int g = 0; g < G; g++) {   // group g's sum of window k
       msm_host::Fe6 t[3];
       for (int j = 0; j < 3; j++) {
-        const uint8_t* b = partials + ((size_t)g * K + k) * 144 + 48 * j;
+        const uint8_t* b = partials + ((size_t)g * K + k) * SUM_WIRE_BYTES + 48 * j;
         for (int i = 0; i < 6; i++) {
           uint64_t v = 0;
           for (int q = 0; q < 8; q++) v |= (uint64_t)b[8 * i + q] << (8 * q);
@@ -399,7 +471,7 @@ int combine_impl(msm_ctx* ctx, const msm_host::Curve6& C, const uint8_t* partial
     }
   }
   memset(out, 0, sizeof(*out));
-  horner_to_affine(C, P, c, out);
+  proj_to_result(C, horner_points(C, P, c), out);
   out->c = c;
   out->K = K;
   return MSM_OK;

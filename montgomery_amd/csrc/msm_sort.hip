@@ -8,6 +8,10 @@ using namespace msmi;
 
 namespace msmi {
 
+// measured (round 5, with one ds_add per key as the ranking: tools/sortpath_sweep.sh): the split wins from 2^21 entries per
+// window -- 2^20 points: sort 0.31 against 0.36 ms, 2^21: 0.51 / 0.85; 2^19: level, below: the one-level sort (2^16 0.11 / 0.14)
+uint64_t one_level_entry_limit(bool te) { return te ? 1ull << 22 : 1ull << 21; }
+
 void sort_kernel_attributes() {
   // dynamic LDS above the 64 KB a launch gets by default
   HIPCHK(hipFuncSetAttribute((const void*)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
@@ -121,9 +125,7 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
   //                of round 1 in an order that keeps its row gathers local
   const int cbits = pl.L_log;   // bits of a bucket index
   const bool fits_lds = (size_t)L * 4 <= 128 * 1024;
-  // measured (round 5, with one ds_add per key as the ranking: tools/sortpath_sweep.sh): the split wins from 2^21 entries per
-  // window -- 2^20 points: sort 0.31 against 0.36 ms, 2^21: 0.51 / 0.85; 2^19: level, below: the one-level sort (2^16 0.11 / 0.14)
-  const bool want_radix = fits_lds && cbits > (int)RX_FINE_BITS && two_n >= (te ? 1ull << 22 : 1ull << 21);
+  const bool want_radix = fits_lds && cbits > (int)RX_FINE_BITS && two_n >= one_level_entry_limit(te);
   // (the merged window of a run on window tables has kc = 1: the radix split would give its last pass one block per coarse bin,
   // 2^(c-8) of them for the whole chip -- the bin split cuts it into 2^10 bins whatever the window is)
   const bool want_bins = !fits_lds || (pl.tables && two_n >= (1ull << 22));

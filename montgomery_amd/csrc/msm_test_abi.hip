@@ -267,7 +267,7 @@ int msm_test_bucket_reduce(msm_ctx* ctx, const uint8_t* buckets, int32_t K, uint
              nb, 0, (uint32_t*)ctx->errflag.p);
     ROWS_TO_PLANES(ctx, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, (uint4*)planes.p, cap, (const uint32_t*)rows.p,
                    (uint32_t)nb);
-    std::vector<uint32_t> parts((size_t)K * 36, 0);
+    std::vector<uint32_t> parts((size_t)K * W_SUM_WORDS, 0);
     float ms = 0;
     if (mode == 0) {
       // every bucket holds exactly one element of the tree buffer: offsets 0, 1, 2, ...
@@ -363,25 +363,17 @@ int msm_test_bucket_reduce(msm_ctx* ctx, const uint8_t* buckets, int32_t K, uint
       for (int k = 0; k < K; k++) {
         const uint32_t* q = &el[(size_t)k * 24];
         if (q[nw - 1] == INF_WORD) continue;   // identity: the partial stays all-zero
-        memcpy(&parts[(size_t)k * 36], q, nw * 4);            // X, Y at words 0 and 12 of the partial (upper words zero)
-        memcpy(&parts[(size_t)k * 36 + 12], q + nw, nw * 4);
+        uint32_t* part = &parts[(size_t)k * W_SUM_WORDS];
+        memcpy(part, q, nw * 4);            // X, Y at words 0 and 12 of the partial (upper words zero)
+        memcpy(part + 12, q + nw, nw * 4);
         const msm_host::Fe6 one_dev = ctx->hc.F.pow2(30 * ctx->nl());   // Z = 1 in the form x and y are in: device Montgomery
         for (int q2 = 0; q2 < 6; q2++) {
-          parts[(size_t)k * 36 + 24 + 2 * q2] = (uint32_t)one_dev.v[q2];
-          parts[(size_t)k * 36 + 24 + 2 * q2 + 1] = (uint32_t)(one_dev.v[q2] >> 32);
+          part[24 + 2 * q2] = (uint32_t)one_dev.v[q2];
+          part[24 + 2 * q2 + 1] = (uint32_t)(one_dev.v[q2] >> 32);
         }
       }
     }
-    for (int k = 0; k < K; k++) {
-      const uint32_t* q = &parts[(size_t)k * 36];
-      bool zero_z = true;
-      for (int j = 0; j < 12; j++) zero_z &= q[24 + j] == 0;
-      const msm_host::Proj6 P = zero_z ? ctx->hc.zero() : partial_to_host(ctx, q);
-      msm_host::Fe6 one = {{1, 0, 0, 0, 0, 0}}, t;
-      ctx->hc.F.mul(t, P.X, one); fe6_to_bytes(partials_out + (size_t)k * 144, t);
-      ctx->hc.F.mul(t, P.Y, one); fe6_to_bytes(partials_out + (size_t)k * 144 + 48, t);
-      ctx->hc.F.mul(t, P.Z, one); fe6_to_bytes(partials_out + (size_t)k * 144 + 96, t);
-    }
+    for (int k = 0; k < K; k++) sum_to_wire(ctx, &parts[(size_t)k * W_SUM_WORDS], partials_out + (size_t)k * SUM_WIRE_BYTES);
     if (ms_out) *ms_out = ms;
     for (DevBuf* b : {&wire, &rows, &planes, &desc, &scr}) ctx->release(*b);
     return MSM_OK;

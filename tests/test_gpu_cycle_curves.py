@@ -454,6 +454,48 @@ def test_window_sums_and_combine_groups(cv):
     assert D.combine_groups_host(g0 + g1, 2, K, 13, cv.cid) == full.as_tuple()
 
 
+def test_windows_over_point_ranges(cv):
+    """The sums of the ranges of the points a tight msm_set_workspace_limit cuts every window into, added on the host, on an
+    8-word field (tests/test_gpu_boundary.py has the 12-word and the Edwards case).  A range is never shorter than 4096 points,
+    so n = 2^13 + 321 is the smallest size that still splits in three; at c = 16 the bucket counters of one window alone exceed
+    the boundary test's 60 MB limit.  Against the known discrete logs, through msm_run and through msm_window_sums."""
+    n = (1 << 13) + 321
+    dev, s, exp = generated(cv, n, 710)
+    ref, info0 = cv.ctx.run_device(dev, n, c=16, no_tables=True)
+    assert ref.as_tuple() == exp
+    cv.ctx.set_workspace_limit(60 << 20)
+    try:
+        got, info1 = cv.ctx.run_device(dev, n, c=16, no_tables=True)
+        assert got.as_tuple() == exp
+        assert info1["rounds"] > info0["rounds"], (info0["rounds"], info1["rounds"])
+        K = info0["K"]
+        part, _ = cv.ctx.window_sums(dev, n, 0, K, c=16, on_device=True)
+        assert cv.ctx.combine(part, K, 16).as_tuple() == exp
+    finally:
+        cv.ctx.set_workspace_limit(0)
+
+
+def test_device_list_sums_over_the_devices(cv):
+    """A device list [0, 0]: every device runs all windows over half of the points, the two sums of every window are added on the
+    host (8-word field; tests/test_gpu_boundary.py has the 12-word and the Edwards case).  Several windows (c = 8), against the
+    known discrete logs, through msm_run and through msm_window_sums."""
+    from montgomery_amd.api import MsmContext
+    from oracle import c_oracle
+
+    n = (1 << 11) + 77
+    multi = MsmContext(cv.cid, devices=[0, 0])
+    try:
+        a = multi.generate_points(n, seed=720, want_scalars=True)
+        _, s = multi.generate_scalars(n, seed=721, to_host=True)
+        exp = cv.dlog_point(c_oracle.dot_mod(a, s, n, cv.B.q))
+        res, info = multi.run(s, c=8)
+        assert res.as_tuple() == exp and info["K"] > 2, info
+        part, _ = multi.window_sums(s, n, 0, info["K"], c=8)
+        assert multi.combine(part, info["K"], 8).as_tuple() == exp
+    finally:
+        multi.close()
+
+
 def test_skewed_scalars(cv):
     n = 1 << 18
     dev, s, exp = generated(cv, n, 718)
