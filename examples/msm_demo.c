@@ -3,7 +3,8 @@
  *   examples/msm_demo [log2_n] [curve id or name: bls12-377, ed-on-bls12-377, bls12-381, pallas, bn254, grumpkin, vesta]
  * Generates N points and scalars on the GPU, runs the MSM twice with different window sizes (the result is a
  * group element: it must not depend on c), then once more as K one-window shards recombined with
- * msm_combine_curve, the way the ranks of a multi-GPU run do.  Exit code 0 = all three agree. */
+ * msm_combine_curve, the way the ranks of a multi-GPU run do, and once through the indexed entry point (msm_run_indexed) with
+ * every point named once.  Exit code 0 = all four agree. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -66,6 +67,18 @@ int main(int argc, char** argv) {
     if ((rc = msm_combine_curve(curve, parts, K, cc, &c3))) die(ctx, "msm_combine_curve", rc);
     free(parts);
     ok = ok && memcmp(a.x, c3.x, 48) == 0 && memcmp(a.y, c3.y, 48) == 0;
+  }
+  { /* the indexed form: scalars[j] belongs to point indices[j]; naming every point once, in order, is the dense MSM */
+    msm_result d;
+    void* d_indices = NULL;
+    uint32_t* indices = (uint32_t*)malloc((size_t)n * 4);
+    for (uint64_t j = 0; j < n; j++) indices[j] = (uint32_t)j;
+    if ((rc = msm_device_alloc(ctx, n * 4, &d_indices))) die(ctx, "msm_device_alloc", rc);
+    if ((rc = msm_device_upload(ctx, d_indices, indices, n * 4))) die(ctx, "msm_device_upload", rc);
+    free(indices);
+    memset(&opts, 0, sizeof opts);
+    if ((rc = msm_run_indexed(ctx, d_scalars, (const uint32_t*)d_indices, n, 1, &opts, &d))) die(ctx, "msm_run_indexed", rc);
+    ok = ok && memcmp(a.x, d.x, 48) == 0 && memcmp(a.y, d.y, 48) == 0 && a.is_infinity == d.is_infinity;
   }
   msm_ctx_destroy(ctx);
   printf(ok ? "OK: result independent of the window size and of the sharding\n" : "MISMATCH\n");

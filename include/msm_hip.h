@@ -65,7 +65,9 @@ enum {
  * 8 = compressed points and subgroup validation (msm_set_points_ex, msm_validate_points, msm_get_points_ex).
  * Narrow scalars (msm_run_narrow, msm_run_batch_narrow, msm_plan_narrow, msm_scalar_bits) came WITHOUT a new version: they are
  * new symbols only, msm_opts / msm_result keep their size and fields, so a binding of version 8 reads the same memory as
- * before.  A binding detects the feature by the presence of the symbol msm_run_narrow. */
+ * before.  A binding detects the feature by the presence of the symbol msm_run_narrow.
+ * The indexed (sparse) MSM (msm_run_indexed, msm_run_indexed_narrow) came the same way: two new symbols, version 8 and both struct
+ * sizes unchanged.  A binding detects the feature by the presence of the symbol msm_run_indexed. */
 #define MSM_ABI_VERSION 8
 uint32_t msm_abi_version(void);
 uint32_t msm_abi_struct_bytes(int which);
@@ -292,6 +294,38 @@ int msm_plan_narrow(const msm_ctx* ctx, uint64_t n, int32_t bits, const msm_opts
 /* smallest `bits` under which msm_run_narrow(width 32) accepts these 32-byte scalars, unsigned and signed
  * (0 for all-zero input; 255 when a scalar needs more than 128 bits or is >= q). */
 int msm_scalar_bits(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, int32_t* unsigned_bits_out, int32_t* signed_bits_out);
+
+/* Indexed (sparse) MSM: out = sum_j scalars[j] * P[indices[j]], j < m, over the current point set -- a sparse witness or error
+ * column, lookup multiplicities scattered over a big table -- without the dense vector of mostly zeros the other entry points
+ * need.  The call pays for its m entries, not for the resident count: digits, sort and pairing run over the m positions, and the
+ * payloads are rewritten to name the resident rows before round 1 of the tree gathers them.  The reference has no counterpart.
+ * Indices: m 32-bit unsigned positions in the current point set, each < the resident count, in any order and with repeats --
+ *   the sum is over the multiset: the same point several times, or a point under a scalar and under its negative, are ordinary
+ *   input.  m may be smaller or larger than the resident count, m < 2^30; m == 0 returns the identity.  on_device covers BOTH
+ *   buffers; device indices must be aligned to 4 bytes.  Host buffers are uploaded whole before the run.
+ * An index >= the resident count ALWAYS fails the call with MSM_ERR_ARG; the message names the smallest bad position j and its
+ *   value ("indices[j] = v but n resident points").  The check runs on the GPU before anything is gathered: no row outside the
+ *   table is ever read.  A failed call leaves the context usable and the point set untouched.  A call before any points are
+ *   set fails with MSM_ERR_NO_POINTS.
+ * Result: out->x / y / is_infinity are bit-identical to msm_run over the dense equivalent, the vector t of resident length with
+ *   t[i] = sum of scalars[j] over indices[j] == i, mod q.  out->c / K report the plan that ran; phase_ms (MSM_T_UPLOAD: indices
+ *   and host scalars into HBM and the index check), n_pairs, n_pairs_algo, max_bucket and rounds are as for msm_run.
+ * Plan: the window is picked from m, not from the resident count -- the plain-path plan msm_plan(ctx, m, {no_tables}) reports
+ *   (narrow: msm_plan_narrow(ctx, m, bits)); opts->c forces it.
+ * Window tables: the call takes the plain path over table 0.  It neither builds, uses nor drops the window tables of the point
+ *   set and does not count as a call over a range for the automatic range-table build.
+ * Options: c, no_glv, strict and serial are honoured, unsafe is ignored as elsewhere; point_lo != 0, k_lo / k_hi,
+ *   bucket_shards > 1, merged_sums and by_window fail with MSM_ERR_ARG, as do a device-list context and null pointers with m > 0.
+ *   Scalars >= q under strict fail with MSM_ERR_SCALAR as in msm_run.
+ * An input too big for the workspace runs over ranges of the ENTRIES as the dense path runs over ranges of the points: scalars
+ *   and indices of a range are sliced together.
+ * msm_run_indexed_narrow is the same over narrow scalars: width_bytes / bits / is_signed exactly as msm_run_narrow, which also
+ *   says what it refuses (a bad width, bits beyond the width, misaligned device scalars) and that a value outside the declared
+ *   range fails with MSM_ERR_SCALAR; equal to msm_run_narrow over the dense equivalent where that fits the declared range. */
+int msm_run_indexed(msm_ctx* ctx, const void* scalars, const uint32_t* indices, uint64_t m, int on_device, const msm_opts* opts,
+                    msm_result* out);
+int msm_run_indexed_narrow(msm_ctx* ctx, const void* scalars, const uint32_t* indices, uint64_t m, int on_device, int32_t width_bytes,
+                           int32_t bits, int32_t is_signed, const msm_opts* opts, msm_result* out);
 
 /* Window-sharded form for multi-GPU runs: computes the partition sums P_k for k in [k_lo, k_hi)
  * only (src/msm-batched-affine.ts:42 "P_k = sum_l l * B_(k,l)") and writes them as

@@ -40,6 +40,11 @@ export interface Parallel {
   msmNarrow(scalars: NarrowScalars, pointPtr: PointPtr, N: number, options?: NarrowOptions): Promise<MsmOutput>;
   /** many narrow MSMs over one point set (msm_run_batch_narrow): one array per element, all of one type */
   msmBatchNarrow(scalarArrays: NarrowScalars[], pointPtr: PointPtr, N: number, options?: NarrowOptions): Promise<MsmOutput[]>;
+  /** indexed (sparse) MSM (msm_run_indexed): sum_j scalars[j] * P[indices[j]]; scalars m x 32 bytes, indices in any order, repeats
+   *  allowed; equals msm over the dense equivalent.  An index >= the number of points throws (msm error 1, the position in the message) */
+  msmIndexed(scalars: Uint8Array, indices: Uint32Array | number[], pointPtr: PointPtr, options?: { c?: number; noGlv?: boolean }): Promise<MsmOutput>;
+  /** the same over narrow scalars (msm_run_indexed_narrow): scalars and options as for msmNarrow */
+  msmIndexedNarrow(scalars: NarrowScalars, indices: Uint32Array | number[], pointPtr: PointPtr, options?: NarrowOptions): Promise<MsmOutput>;
   /** smallest `bits` msmNarrow(width 32) accepts these n x 32-byte scalars under (0: all zero; 255: more than 128 bits needed) */
   scalarBits(scalars32: Uint8Array): { unsigned: number; signed: number };
   /** src/msm-batched-affine.ts:587-598: msm with useSafeAdditions = false (msm_opts.unsafe) */

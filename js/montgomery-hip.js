@@ -163,6 +163,28 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       const rs = hip.msmBatchNarrow(ctx, fs.map((f) => f.buf), fs[0].width, fs[0].bits, fs[0].signed, (options && options.c) || 0);
       return rs.map((r) => ({ result: { x: leBytesToBigint(r.x), y: leBytesToBigint(r.y), isZero: r.isZero }, log: buildLog(N, r) }));
     },
+    // Indexed (sparse) MSM (msm_run_indexed; the reference has no counterpart): sum_j scalars[j] * P[indices[j]] over the points
+    // behind pointPtr.  scalars: a Buffer / Uint8Array of m x 32 bytes; indices: a Uint32Array, or an array of m non-negative
+    // integers -- any order, repeats allowed.  options: {c, noGlv}.  result equals msm over the dense equivalent (the vector with
+    // t[i] = sum of scalars[j] over indices[j] == i); an index >= the number of points throws (msm error 1) naming its position.
+    async msmIndexed(scalars, indices, pointPtr, options) {
+      const idx = indexBuffer(indices, "msmIndexed");
+      if (!ArrayBuffer.isView(scalars) || scalars.byteLength !== 32 * idx.m)
+        throw new RangeError(`msmIndexed: ${idx.m} indices need ${32 * idx.m} bytes of scalars`);
+      hip.pointsetSelect(ctx, pointPtr.set);
+      const r = hip.msmIndexed(ctx, Buffer.from(scalars.buffer, scalars.byteOffset, scalars.byteLength), idx.buf,
+        (options && options.c) || 0, options && options.noGlv ? 1 : 0);
+      return { result: { x: leBytesToBigint(r.x), y: leBytesToBigint(r.y), isZero: r.isZero }, log: buildLog(idx.m, r) };
+    },
+    // the same over narrow scalars (msm_run_indexed_narrow): scalars and options {bits, width, signed, c} as for msmNarrow
+    async msmIndexedNarrow(scalars, indices, pointPtr, options) {
+      const idx = indexBuffer(indices, "msmIndexedNarrow");
+      const f = narrowFormat(scalars, idx.m, options);
+      if (f.width * idx.m !== scalars.byteLength) throw new RangeError(`msmIndexedNarrow: ${idx.m} indices but ${scalars.byteLength / f.width} scalars`);
+      hip.pointsetSelect(ctx, pointPtr.set);
+      const r = hip.msmIndexedNarrow(ctx, f.buf, idx.buf, f.width, f.bits, f.signed, (options && options.c) || 0);
+      return { result: { x: leBytesToBigint(r.x), y: leBytesToBigint(r.y), isZero: r.isZero }, log: buildLog(idx.m, r) };
+    },
     // {unsigned, signed}: the smallest `bits` msmNarrow accepts these n x 32-byte scalars under as a Buffer with width 32
     // (0: all zero; 255: a scalar needs more than 128 bits)
     scalarBits(scalars32) {
@@ -188,6 +210,19 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       throw new TypeError("msmNarrow: expected an integer typed array, or a Buffer with options.width in {1, 2, 4, 8, 16, 32}");
     if (N * width > scalars.byteLength) throw new RangeError(`msmNarrow: ${N} scalars of ${width} bytes requested but the array holds ${scalars.byteLength} bytes`);
     return { buf: Buffer.from(scalars.buffer, scalars.byteOffset, N * width), width, signed, bits: (options && options.bits) || 0 };
+  }
+  // indices of an indexed call -> {buf: m x 4 bytes, uint32 little-endian, m}; a Uint32Array is taken as it is
+  function indexBuffer(indices, who) {
+    let arr = indices;
+    if (!(arr instanceof Uint32Array)) {
+      if (!Array.isArray(arr) && !ArrayBuffer.isView(arr)) throw new TypeError(`${who}: indices must be a Uint32Array or an array of integers`);
+      if (arr instanceof Float32Array || arr instanceof Float64Array) throw new TypeError(`${who}: indices must be integers`);
+      const list = Array.from(arr, (v) => (typeof v === "bigint" ? Number(v) : v));
+      for (const v of list)
+        if (!Number.isInteger(v) || v < 0 || v > 0xFFFFFFFF) throw new RangeError(`${who}: index ${v} is not an integer in [0, 2^32)`);
+      arr = Uint32Array.from(list);
+    }
+    return { buf: Buffer.from(arr.buffer, arr.byteOffset, arr.byteLength), m: arr.length };
   }
   function newScalarPtr(size) {
     return { size, n: 0, dev: null, free() { if (this.dev) { const d = this.dev; this.dev = null; this.n = 0; hip.deviceFree(ctx, d); } } };

@@ -44,6 +44,7 @@ EXPORTS = (
     "msm_abi_version", "msm_abi_struct_bytes", "msm_run_batch",
     "msm_set_points_ex", "msm_validate_points", "msm_get_points_ex",
     "msm_run_narrow", "msm_run_batch_narrow", "msm_plan_narrow", "msm_scalar_bits",
+    "msm_run_indexed", "msm_run_indexed_narrow",
 )
 
 
@@ -154,6 +155,12 @@ def load() -> C.CDLL:
                                          C.POINTER(MsmResult)]
     lib.msm_plan_narrow.argtypes = [vp, u64, i32, C.POINTER(MsmOpts), C.POINTER(i32), C.POINTER(i32)]
     lib.msm_scalar_bits.argtypes = [vp, vp, u64, C.c_int, C.POINTER(i32), C.POINTER(i32)]
+    # indexed (sparse) MSM: new symbols under ABI 8 as well
+    if not hasattr(lib, "msm_run_indexed"):
+        raise ImportError(f"{LIB_PATH} predates msm_run_indexed: rebuild it (`make`)")
+    lib.msm_run_indexed.argtypes = [vp, vp, C.POINTER(C.c_uint32), u64, C.c_int, C.POINTER(MsmOpts), C.POINTER(MsmResult)]
+    lib.msm_run_indexed_narrow.argtypes = [vp, vp, C.POINTER(C.c_uint32), u64, C.c_int, i32, i32, i32, C.POINTER(MsmOpts),
+                                           C.POINTER(MsmResult)]
     lib.msm_run_placed.argtypes = [vp, C.POINTER(vp), u64, C.POINTER(MsmOpts), C.POINTER(MsmResult)]
     lib.msm_plan.argtypes = [vp, u64, C.POINTER(MsmOpts), C.POINTER(i32), C.POINTER(i32)]
     lib.msm_generate_points.argtypes = [vp, u64, u64, vp]

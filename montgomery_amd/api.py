@@ -158,6 +158,95 @@ ED_ON_BLS12_377_PARAMS = TwistedEdwardsParams(
 )
 
 
+
+# ---------------------------------------------------------------------------------------------
+# indexed (sparse) MSM: host-side input handling (msm_run_indexed, include/msm_hip.h)
+# ---------------------------------------------------------------------------------------------
+
+
+def _as_numpy(a):
+    """numpy view of a numpy array or a torch tensor (copied to the host); anything else is returned as it is."""
+    if hasattr(a, "detach") and hasattr(a, "cpu"):   # torch.Tensor, without importing torch
+        return a.detach().cpu().numpy()
+    return a
+
+
+def _index_array(indices, m: Optional[int] = None):
+    """Indices of an indexed call as a contiguous little-endian uint32 array: a 1-d integer numpy array / torch tensor or a
+    sequence of ints, none negative, all below 2^32; m: the length the scalars ask for.  (Whether they are below the resident
+    count is checked on the GPU, which names the first bad position.)"""
+    import numpy as np
+
+    a = _as_numpy(indices)
+    if not hasattr(a, "dtype"):
+        vals = list(a)
+        if any(not isinstance(v, (int, np.integer)) or isinstance(v, bool) for v in vals):
+            raise MsmError(_lib.MSM_ERR_ARG, "indices must be integers")
+        if any(v < 0 or v >> 32 for v in vals):
+            raise MsmError(_lib.MSM_ERR_ARG, "indices must lie in [0, 2^32)")
+        a = np.array(vals, dtype="<u4")
+    if a.dtype.kind not in "iu":
+        raise MsmError(_lib.MSM_ERR_ARG, f"indices must have an integer dtype, got {a.dtype}")
+    if a.ndim != 1:
+        raise MsmError(_lib.MSM_ERR_ARG, f"indices must be one-dimensional, got shape {a.shape}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >> 32):
+        raise MsmError(_lib.MSM_ERR_ARG, "indices must lie in [0, 2^32)")
+    if m is not None and a.size != m:
+        raise MsmError(_lib.MSM_ERR_ARG, f"{m} scalars but {a.size} indices")
+    if a.size >> 30:
+        raise MsmError(_lib.MSM_ERR_ARG, "an indexed call takes fewer than 2^30 entries")
+    return np.ascontiguousarray(a, dtype="<u4")
+
+
+def _wide_scalar_bytes(scalars) -> bytes:
+    """32-byte scalars of an indexed call: bytes of m x 32, or a uint8 array / tensor of shape (m, 32) or (32 m,)."""
+    a = _as_numpy(scalars)
+    if hasattr(a, "dtype"):
+        import numpy as np
+
+        if a.dtype != np.uint8 or a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[1] != 32):
+            raise MsmError(_lib.MSM_ERR_ARG, f"32-byte scalars must be bytes or a uint8 array of shape (m, 32), got {a.dtype} {a.shape}")
+        raw = np.ascontiguousarray(a).tobytes()
+    else:
+        raw = bytes(a)
+    if len(raw) % 32:
+        raise MsmError(_lib.MSM_ERR_ARG, f"scalar buffer length {len(raw)} is not a multiple of 32")
+    return raw
+
+
+def sparse_from_dense(scalars):
+    """(indices, nonzero_scalars) of a dense scalar vector: the positions of its non-zero scalars as a uint32 array, ascending,
+    and those scalars in the same order -- what msm_indexed takes in place of the vector.  scalars: bytes of n x 32 (or a
+    uint8 array of shape (n, 32)) -> bytes of m x 32; an integer numpy array (narrow scalars) -> the array of its non-zeros."""
+    import numpy as np
+
+    a = _as_numpy(scalars)
+    if hasattr(a, "dtype") and not (a.dtype == np.uint8 and a.ndim == 2):
+        if a.dtype.kind not in "iu" or a.ndim != 1:
+            raise MsmError(_lib.MSM_ERR_ARG, f"a dense vector is bytes, a uint8 array (n, 32) or a 1-d integer array, got {a.dtype} {a.shape}")
+        idx = np.flatnonzero(a)
+        if idx.size >> 32:
+            raise MsmError(_lib.MSM_ERR_ARG, "more than 2^32 - 1 positions")
+        return idx.astype("<u4"), np.ascontiguousarray(a[idx])
+    rows = np.frombuffer(_wide_scalar_bytes(a), dtype=np.uint8).reshape(-1, 32)
+    idx = np.flatnonzero(rows.any(axis=1))
+    return idx.astype("<u4"), rows[idx].tobytes()
+
+
+def dense_from_sparse(indices, scalars: BytesLike, n: int, q: int) -> bytes:
+    """The dense equivalent of an indexed call over n points: t[i] = sum of scalars[j] over indices[j] == i, mod q, as n x 32
+    bytes -- the vector msm_run gives the same result for (tests, tools/bench_indexed.py)."""
+    idx = _index_array(indices)
+    raw = _wide_scalar_bytes(scalars)
+    if len(raw) != 32 * idx.size:
+        raise MsmError(_lib.MSM_ERR_ARG, f"{len(raw) // 32} scalars but {idx.size} indices")
+    t = [0] * n
+    for j, i in enumerate(idx.tolist()):
+        if i >= n:
+            raise MsmError(_lib.MSM_ERR_ARG, f"indices[{j}] = {i} but {n} points")
+        t[i] = (t[i] + int.from_bytes(raw[32 * j:32 * j + 32], "little")) % q
+    return b"".join(v.to_bytes(32, "little") for v in t)
+
 # ---------------------------------------------------------------------------------------------
 # low-level context
 # ---------------------------------------------------------------------------------------------
@@ -566,6 +655,53 @@ class MsmContext:
         self._check(self._lib.msm_scalar_bits(self._h, ptr, n, on_device, C.byref(ub), C.byref(sb)))
         return ub.value, sb.value
 
+    # -- indexed (sparse) MSM (msm_run_indexed, include/msm_hip.h) -----------------------------
+    def _affine(self, res: MsmResult) -> AffineResult:
+        nb = self.coord_bytes
+        return AffineResult(int.from_bytes(bytes(res.x)[:nb], "little"), int.from_bytes(bytes(res.y)[:nb], "little"),
+                            bool(res.is_infinity))
+
+    def msm_indexed(self, scalars, indices, *, c: Optional[int] = None, no_glv: bool = False, strict: bool = False,
+                    serial: bool = False) -> Tuple[AffineResult, Dict]:
+        """sum_j scalars[j] * P[indices[j]] over the current point set (msm_run_indexed): scalars as bytes of m x 32 (or a
+        uint8 numpy array / torch tensor of shape (m, 32)), indices as a 1-d integer array / tensor or a sequence of ints, in
+        any order and with repeats.  Equal to run() over the dense equivalent (dense_from_sparse); the window is picked for m.
+        An index >= the resident count raises MsmError(MSM_ERR_ARG) naming its position."""
+        raw = _wide_scalar_bytes(scalars)
+        idx = _index_array(indices, len(raw) // 32)
+        sbuf = (C.c_uint8 * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
+        return self._run_indexed(sbuf, idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx.size, 0, c, no_glv, strict, serial)
+
+    def msm_indexed_device(self, dev_scalars: int, dev_indices: int, m: int, *, c: Optional[int] = None, no_glv: bool = False,
+                           strict: bool = False, serial: bool = False) -> Tuple[AffineResult, Dict]:
+        """msm_indexed over device buffers: m x 32 bytes of scalars and m uint32 indices (4-byte aligned)."""
+        return self._run_indexed(C.c_void_p(dev_scalars), C.cast(C.c_void_p(dev_indices), C.POINTER(C.c_uint32)), m, 1, c, no_glv,
+                                 strict, serial)
+
+    def _run_indexed(self, sptr, iptr, m, on_device, c, no_glv, strict, serial) -> Tuple[AffineResult, Dict]:
+        opts, res = MsmOpts(c=c or 0, no_glv=int(no_glv), strict=int(strict), serial=int(serial)), MsmResult()
+        self._check(self._lib.msm_run_indexed(self._h, sptr, iptr, m, on_device, C.byref(opts), C.byref(res)))
+        return self._affine(res), _result_to_dict(res)
+
+    def msm_indexed_narrow(self, scalars, indices, *, bits: Optional[int] = None, signed: Optional[bool] = None,
+                           c: Optional[int] = None, serial: bool = False, width: Optional[int] = None) -> Tuple[AffineResult, Dict]:
+        """msm_indexed over narrow scalars (msm_run_indexed_narrow): scalars, bits, signed and width as for run_narrow."""
+        buf, m, width, signed = self._narrow_buffer(_as_numpy(scalars), width, signed)
+        idx = _index_array(indices, m)
+        return self._run_indexed_narrow(buf, idx.ctypes.data_as(C.POINTER(C.c_uint32)), m, 0, width, bits, signed, c, serial)
+
+    def msm_indexed_narrow_device(self, dev_scalars: int, dev_indices: int, m: int, width: int, *, bits: Optional[int] = None,
+                                  signed: bool = False, c: Optional[int] = None, serial: bool = False) -> Tuple[AffineResult, Dict]:
+        """msm_indexed_narrow over device buffers: m x width bytes of scalars and m uint32 indices."""
+        return self._run_indexed_narrow(C.c_void_p(dev_scalars), C.cast(C.c_void_p(dev_indices), C.POINTER(C.c_uint32)), m, 1, width,
+                                        bits, signed, c, serial)
+
+    def _run_indexed_narrow(self, sptr, iptr, m, on_device, width, bits, signed, c, serial) -> Tuple[AffineResult, Dict]:
+        opts, res = MsmOpts(c=c or 0, serial=int(serial)), MsmResult()
+        self._check(self._lib.msm_run_indexed_narrow(self._h, sptr, iptr, m, on_device, width, bits or 0, int(bool(signed)),
+                                                     C.byref(opts), C.byref(res)))
+        return self._affine(res), _result_to_dict(res)
+
     # -- window tables (msm_precompute, include/msm_hip.h) ------------------------------------
     def precompute(self, n: Optional[int] = None, c: Optional[int] = None, no_glv: bool = False, point_lo: int = 0) -> Tuple[int, int, int]:
         """Builds the window tables of the current point set -- of its points [point_lo, point_lo + n): the share of one rank of a
@@ -908,6 +1044,24 @@ class _Parallel:
             scalars = bytes(scalars)[: N * w]
         res, info = self._ctx.run_narrow(scalars, options.get("bits"), options.get("signed"), options.get("c"),
                                          width=options.get("width"))
+        return {"result": res, "log": [], "info": info}
+
+    def msmIndexed(self, scalars, indices, pointPtr: PointPtr, options: Optional[Dict] = None) -> Dict:
+        """Indexed (sparse) MSM (msm_run_indexed; the reference has no counterpart): sum_j scalars[j] * P[indices[j]] over the
+        points behind pointPtr.  scalars: bytes of m x 32 or a uint8 array (m, 32); indices: m integers, any order, repeats
+        allowed; options: {"c", "noGlv"}.  Returns msm's shape; "result" equals msm over the dense equivalent."""
+        options = options or {}
+        self._ctx.pointset_select(pointPtr.set_id)
+        res, info = self._ctx.msm_indexed(scalars, indices, c=options.get("c"), no_glv=bool(options.get("noGlv", False)))
+        return {"result": res, "log": [], "info": info}
+
+    def msmIndexedNarrow(self, scalars, indices, pointPtr: PointPtr, options: Optional[Dict] = None) -> Dict:
+        """msmIndexed over narrow scalars (msm_run_indexed_narrow): scalars and options {"c", "bits", "signed", "width"} as for
+        msmNarrow."""
+        options = options or {}
+        self._ctx.pointset_select(pointPtr.set_id)
+        res, info = self._ctx.msm_indexed_narrow(scalars, indices, bits=options.get("bits"), signed=options.get("signed"),
+                                                 c=options.get("c"), width=options.get("width"))
         return {"result": res, "log": [], "info": info}
 
     def msmProjective(self, scalarPtr: ScalarPtr, pointPtr: PointPtr, N: int, options: Optional[Dict] = None) -> Dict:

@@ -12,6 +12,8 @@
 //   msm_gen.hip       the input generators (msm_generate_points, msm_generate_scalars)
 //   msm_ingest.hip    msm_set_points_ex, msm_validate_points, msm_get_points_ex: compressed points, subgroup checks
 //   msm_narrow.hip    msm_run_narrow, msm_plan_narrow, msm_scalar_bits (narrow scalars: no endomorphism split, K from the call's bits)
+//   msm_indexed.hip   msm_run_indexed, msm_run_indexed_narrow (scalars over a chosen multiset of the resident points), with their
+//                     two kernels: the index check and the payload translation
 // Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip, te_kernels.hip and narrow_kernels.hip; host TUs see
 // declarations.
 // Orchestration follows `createMsm().msm` (reference src/msm-batched-affine.ts:69-340); the per-thread SPMD phases separated
@@ -398,6 +400,10 @@ struct Plan {
     NarrowFmt fmt{};
     const NarrowBatchScalars* nb = nullptr;
   } nar;
+  // msm_run_indexed (msm_indexed.hip): idx != nullptr -- scalar j of the call belongs to resident point idx[j] (device array of
+  // the whole CALL, checked against the resident count before the run).  Digits, sort and pairing run over the call's positions;
+  // the payloads of a window group are rewritten to name resident rows before round 1 gathers (run_window_group).
+  const uint32_t* idx = nullptr;
 };
 
 // for_tables: the window a run on window tables wants (bucket work no longer grows with the number of windows)
@@ -692,6 +698,12 @@ int narrow_format(msm_ctx* ctx, int32_t width_bytes, int32_t bits, int32_t is_si
 // the rest of the argument checks of a narrow entry: n < 2^32 (the digit kernels count points in 32 bits) and device scalars
 // aligned to their width (16 bytes for the 16- and 32-byte forms, which lanes load as uint4)
 int narrow_scalars_ok(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, int32_t width_bytes, const char* who);
+
+// ---- msm_indexed.hip --------------------------------------------------------------------------------------------
+// Queues on `s` the pass that rewrites the n_slots payloads the sort left for round 1 -- (entry << 1) | sign, entry counting the
+// positions of the group -- so that they name the entries of the resident points idx[position] with the same half and sign
+// (0xFFFFFFFF, the absent marker, stays).  te: one entry per position; otherwise two (2 j and 2 j + 1).
+void translate_payloads(hipStream_t s, const msm_ctx* ctx, uint32_t* slots, uint64_t n_slots, const uint32_t* idx);
 
 // ---- msm_gen.hip ------------------------------------------------------------------------------------------------
 }  // namespace msmi

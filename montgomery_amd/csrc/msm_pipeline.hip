@@ -25,12 +25,20 @@ void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sca
   hipStream_t s = w.stream;
   Plan pl = pl_in;
   const uint32_t* d_scalars = group_scalars(d_scalars_all, p_lo, pl);   // scalar i of the call <-> resident point p_off + i
+  const uint32_t* idx = pl.idx ? pl.idx + p_lo : nullptr;               // (indexed call: <-> resident point idx[i])
   p_lo += p_off;
   const int kc = k_hi - k_lo;
   SortOut so;
   HIPCHK(hipEventRecord(w.ev[0], s));
   sort_window_group(ctx, w, d_scalars, n, pl, k_lo, k_hi, st, so, share);
   st.max_bucket = std::max<uint64_t>(st.max_bucket, so.max_bucket);
+  if (idx) {
+    // msm_run_indexed: the payloads name positions of the group; round 1 gathers rows of the whole resident table by them, so
+    // they are rewritten to name the rows of idx[position] first (one coalesced pass whatever sort path wrote them)
+    if (pl.tables || p_off) throw MsmFail{MSM_ERR_INTERNAL, "an indexed group on window tables or over a range of the points"};
+    translate_payloads(s, ctx, const_cast<uint32_t*>(so.round1_slots), so.total_slots, idx);
+    p_lo = 0;
+  }
   HIPCHK(hipEventRecord(w.ev[5], s));   // the tree starts here
   TreeOut to;
   if (pl.tables) {

@@ -18,6 +18,9 @@
 //          bytes per scalar, or 32 for field elements holding small values; bits 0 = all the width gives,
 //          msmBatchNarrow(h, [Buffer], width, bits, signed, c) -> array of results (msm_run_batch_narrow),
 //          scalarBits(h, Buffer of n x 32 bytes) -> {unsigned, signed} (msm_scalar_bits),
+//          msmIndexed(h, Buffer scalars of m x 32 bytes, Buffer indices of m x 4 bytes (uint32 LE), c, noGlv) -> as msm:
+//          sum_j scalars[j] * P[indices[j]] (msm_run_indexed); an index >= the resident count throws (msm error 1, the position
+//          in the message), msmIndexedNarrow(h, Buffer scalars, Buffer indices, width, bits, signed, c) (msm_run_indexed_narrow),
 //          plan(h, n, c) -> {c, K}, generatePoints(h, n, seed) -> n, generateScalars(h, n, seed[, dbuf]) -> Buffer | n
 //          the fine operator table of the reference's wasm exports (src/field-msm.ts:86-123,190-243, src/scalar-glv.ts:41-51,105-128)
 //          over Buffers instead of wasm pointers: fieldOp(h, op, a, b) -> Buffer (msm_test_fp: multiply / square / add / subtract /
@@ -544,6 +547,66 @@ static napi_value MsmNarrow(napi_env env, napi_callback_info info) {
   return result_object(env, h, &res);
 }
 
+// indexed (sparse) MSM (msm_run_indexed / msm_run_indexed_narrow): host Buffers, the indices as m x 4 bytes (uint32, little-endian)
+static int indexed_buffers(napi_env env, napi_value* argv, size_t width, void** sc, void** idx, size_t* m) {
+  size_t slen, ilen;
+  if (napi_get_buffer_info(env, argv[1], sc, &slen) != napi_ok || napi_get_buffer_info(env, argv[2], idx, &ilen) != napi_ok) {
+    napi_throw_type_error(env, NULL, "scalars and indices must be Buffers");
+    return 0;
+  }
+  if (slen % width || ilen % 4 || slen / width != ilen / 4) {
+    napi_throw_range_error(env, NULL, "scalars and indices must hold the same number of entries (m x width and m x 4 bytes)");
+    return 0;
+  }
+  *m = ilen / 4;
+  return 1;
+}
+
+static napi_value MsmIndexed(napi_env env, napi_callback_info info) {
+  size_t argc = 5;   // (ctx, scalars, indices, c, noGlv)
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  if (argc < 3) {
+    napi_throw_type_error(env, NULL, "msmIndexed(ctx, scalars, indices[, c, noGlv])");
+    return NULL;
+  }
+  void *sc, *idx;
+  size_t m;
+  if (!indexed_buffers(env, argv, 32, &sc, &idx, &m)) return NULL;
+  msm_opts opts;
+  memset(&opts, 0, sizeof opts);
+  if (argc > 3) napi_get_value_int32(env, argv[3], &opts.c);
+  if (argc > 4) napi_get_value_int32(env, argv[4], &opts.no_glv);
+  msm_result res;
+  int rc = msm_run_indexed(h->ctx, sc, (const uint32_t*)idx, m, 0, &opts, &res);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "msmIndexed");
+  return result_object(env, h, &res);
+}
+
+static napi_value MsmIndexedNarrow(napi_env env, napi_callback_info info) {
+  size_t argc = 7;   // (ctx, scalars, indices, width, bits, signed, c)
+  napi_value argv[7];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  if (argc < 4) {
+    napi_throw_type_error(env, NULL, "msmIndexedNarrow(ctx, scalars, indices, width[, bits, signed, c])");
+    return NULL;
+  }
+  int32_t width, bits, is_signed;
+  msm_opts opts;
+  if (!narrow_args(env, argc - 1, argv + 1, &width, &bits, &is_signed, &opts)) return NULL;   // (the formats sit one argument later)
+  void *sc, *idx;
+  size_t m;
+  if (!indexed_buffers(env, argv, (size_t)width, &sc, &idx, &m)) return NULL;
+  msm_result res;
+  int rc = msm_run_indexed_narrow(h->ctx, sc, (const uint32_t*)idx, m, 0, width, bits, is_signed, &opts, &res);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "msmIndexedNarrow");
+  return result_object(env, h, &res);
+}
+
 static napi_value MsmBatchNarrow(napi_env env, napi_callback_info info) {
   size_t argc = 6;   // (ctx, [scalars], width, bits, signed, c)
   napi_value argv[6];
@@ -876,6 +939,7 @@ NAPI_MODULE_INIT() {
       {"deviceAlloc", DeviceAlloc}, {"deviceUpload", DeviceUpload}, {"deviceFree", DeviceFree}, {"msmDevice", MsmDevice},
       {"msmBatch", MsmBatch}, {"msmBatchDevice", MsmBatchDevice},
       {"msmNarrow", MsmNarrow}, {"msmBatchNarrow", MsmBatchNarrow}, {"scalarBits", ScalarBits},
+      {"msmIndexed", MsmIndexed}, {"msmIndexedNarrow", MsmIndexedNarrow},
       {"pointsetCreate", PointsetCreate}, {"pointsetSelect", PointsetSelect}, {"pointsetDestroy", PointsetDestroy},
       {"fieldOp", FieldOp}, {"batchInverse", BatchInverse}, {"glvDecompose", GlvDecompose}, {"batchAdd", BatchAdd}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
