@@ -67,7 +67,9 @@ enum {
  * new symbols only, msm_opts / msm_result keep their size and fields, so a binding of version 8 reads the same memory as
  * before.  A binding detects the feature by the presence of the symbol msm_run_narrow.
  * The indexed (sparse) MSM (msm_run_indexed, msm_run_indexed_narrow) came the same way: two new symbols, version 8 and both struct
- * sizes unchanged.  A binding detects the feature by the presence of the symbol msm_run_indexed. */
+ * sizes unchanged.  A binding detects the feature by the presence of the symbol msm_run_indexed.
+ * Point-set linear combinations (msm_points_lincomb, msm_pointset_size) came the same way: two new symbols, version 8 and both
+ * struct sizes unchanged.  A binding detects the feature by the presence of the symbol msm_points_lincomb. */
 #define MSM_ABI_VERSION 8
 uint32_t msm_abi_version(void);
 uint32_t msm_abi_struct_bytes(int which);
@@ -326,6 +328,45 @@ int msm_run_indexed(msm_ctx* ctx, const void* scalars, const uint32_t* indices, 
                     msm_result* out);
 int msm_run_indexed_narrow(msm_ctx* ctx, const void* scalars, const uint32_t* indices, uint64_t m, int on_device, int32_t width_bytes,
                            int32_t bits, int32_t is_signed, const msm_opts* opts, msm_result* out);
+
+/* Point-set linear combinations: D[i] = a * A[a_lo + i] + b * B[b_lo + i], i < count, written as the rows [0, count) of point set
+ * `dst`, which then holds exactly `count` points -- resident points made from resident points, on the GPU.  With a = 1 or
+ * a = u^-1, b = u over the two halves of one set it is the generator fold between two rounds of an inner-product argument
+ * (Halo2, Bulletproofs); with one term it scales, copies or negates a set; with a = b = 1 it adds two sets element-wise.  The
+ * reference has no counterpart.
+ * Operands: src_a, src_b and dst are point-set ids of this context (msm_pointset_create; 0 = the default set), any mix of equal
+ *   and different ids.  src_b < 0: no second term, D[i] = a * A[a_lo + i] (b and b_lo are ignored).  The CURRENT set
+ *   (msm_pointset_select) is not changed by the call.
+ * Scalars: a and b are host values, 32 bytes little-endian, < q.  A value >= q fails with MSM_ERR_SCALAR: there is no silent
+ *   reduction, which on the curves with a cofactor would change the result for points outside the subgroup.  Both scalars are
+ *   the same for every point, so the host recodes them once into a short program of doublings and additions that every lane
+ *   walks (Weierstrass curves: the endomorphism split and non-adjacent forms, at most 128 doublings; the Edwards curve: up to
+ *   251).  The scalars 0, 1 and q - 1 are ordinary input and cost no multiplication: 0 drops the term, 1 adds the row as it is,
+ *   q - 1 adds its negative.  a = 1 with src_b < 0 is a copy; a = b = 0 gives `count` identity rows.
+ * Result rows are bit-identical to what msm_set_points writes for the same affine points (canonical Montgomery x and y, and the
+ *   beta x line on the Weierstrass curves); the identity takes the identity row of msm_set_points (the Edwards curve: the row of
+ *   (0, 1)).  Every later call on dst works unchanged: msm_run with and without the endomorphism, msm_get_points(_ex),
+ *   msm_validate_points, msm_precompute.
+ * Every input is handled: source rows that are the identity, A[i] and B[i] equal or opposite, a sum that is the identity, an
+ *   accumulator that passes through the identity or meets its addend on the way -- next to ordinary points in one wave.
+ * Points outside the prime-order subgroup: the Weierstrass path uses the endomorphism, and 1 and q - 1 are taken as +-1 on every
+ *   curve, so -- as for msm_run with the endomorphism -- the result is a * A + b * B only for points of the subgroup
+ *   (phi(T) != lambda T for a torsion point T).
+ * Replacement: dst is replaced as by msm_set_points -- its window tables are dropped, the range-table candidate is reset, its
+ *   size becomes `count`.  Window tables of OTHER sets, the sources included, are untouched.
+ * In place: dst may be one of the sources.  A source range inside dst must then be either its rows [0, count) -- lane i reads
+ *   and writes row i only -- or lie entirely at or above row `count`, disjoint from the rows written; both at once is the fold
+ *   (src_a = src_b = dst, a_lo = 0, b_lo = count).  Any other overlap fails with MSM_ERR_ARG.  No new row buffer is allocated
+ *   in place (a 2^26-point set is 17 GB): the set is truncated to `count`.  A dst that is not a source gets room for `count`
+ *   rows as msm_set_points gives it.
+ * Errors: all checks run before anything is written, so a failed call leaves every set as it was and the context usable.
+ *   MSM_ERR_ARG: an id that does not name a live set, a null `a`, a null `b` with src_b >= 0, a device-list context,
+ *   count >= 2^30, a forbidden overlap.  MSM_ERR_NO_POINTS: a source range that ends beyond its set's size.  MSM_ERR_SCALAR:
+ *   a scalar >= q.  count == 0 is valid and leaves dst empty.  The call returns when the rows are written. */
+int msm_points_lincomb(msm_ctx* ctx, int32_t src_a, uint64_t a_lo, const uint8_t* a /* 32 B LE */, int32_t src_b, uint64_t b_lo,
+                       const uint8_t* b /* 32 B LE; ignored when src_b < 0 */, uint64_t count, int32_t dst);
+/* number of resident points of a point set (ids as msm_pointset_create returns them; 0 = the default set) */
+int msm_pointset_size(const msm_ctx* ctx, int32_t id, uint64_t* n_out);
 
 /* Window-sharded form for multi-GPU runs: computes the partition sums P_k for k in [k_lo, k_hi)
  * only (src/msm-batched-affine.ts:42 "P_k = sum_l l * B_(k,l)") and writes them as

@@ -45,6 +45,14 @@ export interface Parallel {
   msmIndexed(scalars: Uint8Array, indices: Uint32Array | number[], pointPtr: PointPtr, options?: { c?: number; noGlv?: boolean }): Promise<MsmOutput>;
   /** the same over narrow scalars (msm_run_indexed_narrow): scalars and options as for msmNarrow */
   msmIndexedNarrow(scalars: NarrowScalars, indices: Uint32Array | number[], pointPtr: PointPtr, options?: NarrowOptions): Promise<MsmOutput>;
+  /** point-set linear combinations (msm_points_lincomb): dst[i] = a * A[aLo + i] + b * B[bLo + i], i < count; a, b below the group
+   *  order (BigInt, number or 32 little-endian bytes), b and ptrB null for one term; dstPtr may be a source.  Returns dstPtr */
+  pointsLincomb(dstPtr: PointPtr, a: bigint | number | Uint8Array, ptrA: PointPtr, b?: bigint | number | Uint8Array | null, ptrB?: PointPtr | null,
+                options?: { aLo?: number; bLo?: number; count?: number }): PointPtr;
+  /** points behind a pointer, as the library counts them (msm_pointset_size) */
+  pointsetSize(pointPtr: PointPtr): number;
+  /** in-place fold: P[i] <- a * P[i] + b * P[i + n/2], i < n/2 (n even); the pointer then holds n/2 points */
+  foldPoints(pointPtr: PointPtr, a: bigint | number | Uint8Array, b: bigint | number | Uint8Array): PointPtr;
   /** smallest `bits` msmNarrow(width 32) accepts these n x 32-byte scalars under (0: all zero; 255: more than 128 bits needed) */
   scalarBits(scalars32: Uint8Array): { unsigned: number; signed: number };
   /** src/msm-batched-affine.ts:587-598: msm with useSafeAdditions = false (msm_opts.unsafe) */

@@ -185,6 +185,25 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       const r = hip.msmIndexedNarrow(ctx, f.buf, idx.buf, f.width, f.bits, f.signed, (options && options.c) || 0);
       return { result: { x: leBytesToBigint(r.x), y: leBytesToBigint(r.y), isZero: r.isZero }, log: buildLog(idx.m, r) };
     },
+    // Point-set linear combinations (msm_points_lincomb; the reference has no counterpart): the points behind dstPtr become
+    // dst[i] = a * A[aLo + i] + b * B[bLo + i], i < count.  a, b: BigInt / number or 32 little-endian bytes, < the group order
+    // (a larger value throws msm error 6); b and ptrB null: one term.  options: {aLo, bLo, count} (count: default all of ptrA from
+    // aLo on).  dstPtr may be ptrA or ptrB: a source range inside it is its rows [0, count) or starts at or above row count.
+    pointsLincomb(dstPtr, a, ptrA, b, ptrB, options) {
+      const o = options || {}, aLo = o.aLo || 0, bLo = o.bLo || 0;
+      if ((b === null || b === undefined) !== (ptrB === null || ptrB === undefined)) throw new TypeError("pointsLincomb: b and ptrB come together");
+      const count = o.count === undefined ? Math.max(ptrA.n - aLo, 0) : o.count;
+      dstPtr.n = hip.pointsLincomb(ctx, ptrA.set, aLo, scalarBuffer(a, "a"), ptrB ? ptrB.set : -1, bLo, ptrB ? scalarBuffer(b, "b") : null, count, dstPtr.set);
+      return dstPtr;
+    },
+    // points behind a pointer, as the library counts them (msm_pointset_size)
+    pointsetSize(pointPtr) { return hip.pointsetSize(ctx, pointPtr.set); },
+    // the in-place fold of an inner-product argument: P[i] <- a * P[i] + b * P[i + n/2], i < n/2; the pointer then holds n/2 points
+    foldPoints(pointPtr, a, b) {
+      const n = pointPtr.n;
+      if (n % 2) throw new RangeError(`foldPoints: the pointer holds ${n} points, an odd number`);
+      return Parallel.pointsLincomb(pointPtr, a, pointPtr, b, pointPtr, { aLo: 0, bLo: n / 2, count: n / 2 });
+    },
     // {unsigned, signed}: the smallest `bits` msmNarrow accepts these n x 32-byte scalars under as a Buffer with width 32
     // (0: all zero; 255: a scalar needs more than 128 bits)
     scalarBits(scalars32) {
@@ -212,6 +231,17 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
     return { buf: Buffer.from(scalars.buffer, scalars.byteOffset, N * width), width, signed, bits: (options && options.bits) || 0 };
   }
   // indices of an indexed call -> {buf: m x 4 bytes, uint32 little-endian, m}; a Uint32Array is taken as it is
+  // one scalar of pointsLincomb as 32 little-endian bytes: a BigInt / non-negative integer below 2^256, or 32 bytes
+  function scalarBuffer(v, what) {
+    if (typeof v === "bigint" || typeof v === "number") {
+      if (typeof v === "number" && !Number.isSafeInteger(v)) throw new RangeError(`pointsLincomb: ${what} is not an integer`);
+      const big = BigInt(v);
+      if (big < BigInt(0) || big >> BigInt(256)) throw new RangeError(`pointsLincomb: ${what} must lie in [0, 2^256)`);
+      return bigintToLeBytes(big, 32);
+    }
+    if (ArrayBuffer.isView(v) && v.byteLength === 32) return Buffer.from(v.buffer, v.byteOffset, 32);
+    throw new TypeError(`pointsLincomb: ${what} must be a BigInt or 32 bytes`);
+  }
   function indexBuffer(indices, who) {
     let arr = indices;
     if (!(arr instanceof Uint32Array)) {

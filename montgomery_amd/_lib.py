@@ -45,6 +45,7 @@ EXPORTS = (
     "msm_set_points_ex", "msm_validate_points", "msm_get_points_ex",
     "msm_run_narrow", "msm_run_batch_narrow", "msm_plan_narrow", "msm_scalar_bits",
     "msm_run_indexed", "msm_run_indexed_narrow",
+    "msm_points_lincomb", "msm_pointset_size",
 )
 
 
@@ -161,6 +162,11 @@ def load() -> C.CDLL:
     lib.msm_run_indexed.argtypes = [vp, vp, C.POINTER(C.c_uint32), u64, C.c_int, C.POINTER(MsmOpts), C.POINTER(MsmResult)]
     lib.msm_run_indexed_narrow.argtypes = [vp, vp, C.POINTER(C.c_uint32), u64, C.c_int, i32, i32, i32, C.POINTER(MsmOpts),
                                            C.POINTER(MsmResult)]
+    # point-set linear combinations: new symbols under ABI 8 as well
+    if not hasattr(lib, "msm_points_lincomb"):
+        raise ImportError(f"{LIB_PATH} predates msm_points_lincomb: rebuild it (`make`)")
+    lib.msm_points_lincomb.argtypes = [vp, i32, u64, vp, i32, u64, vp, u64, i32]
+    lib.msm_pointset_size.argtypes = [vp, i32, C.POINTER(u64)]
     lib.msm_run_placed.argtypes = [vp, C.POINTER(vp), u64, C.POINTER(MsmOpts), C.POINTER(MsmResult)]
     lib.msm_plan.argtypes = [vp, u64, C.POINTER(MsmOpts), C.POINTER(i32), C.POINTER(i32)]
     lib.msm_generate_points.argtypes = [vp, u64, u64, vp]

@@ -247,6 +247,23 @@ def dense_from_sparse(indices, scalars: BytesLike, n: int, q: int) -> bytes:
         t[i] = (t[i] + int.from_bytes(raw[32 * j:32 * j + 32], "little")) % q
     return b"".join(v.to_bytes(32, "little") for v in t)
 
+def _scalar32(v, what: str = "scalar") -> bytes:
+    """One scalar of msm_points_lincomb as 32 little-endian bytes: an int in [0, 2^256) or 32 bytes.  (Whether it is below q is
+    the library's check: MSM_ERR_SCALAR.)"""
+    if isinstance(v, bool):
+        raise MsmError(_lib.MSM_ERR_ARG, f"{what} must be an int or 32 bytes")
+    if isinstance(v, int):
+        if v < 0 or v >> 256:
+            raise MsmError(_lib.MSM_ERR_ARG, f"{what} must lie in [0, 2^256)")
+        return v.to_bytes(32, "little")
+    try:
+        raw = bytes(v)
+    except TypeError:
+        raise MsmError(_lib.MSM_ERR_ARG, f"{what} must be an int or 32 bytes") from None
+    if len(raw) != 32:
+        raise MsmError(_lib.MSM_ERR_ARG, f"{what} must be 32 bytes, got {len(raw)}")
+    return raw
+
 # ---------------------------------------------------------------------------------------------
 # low-level context
 # ---------------------------------------------------------------------------------------------
@@ -702,6 +719,47 @@ class MsmContext:
                                                      C.byref(opts), C.byref(res)))
         return self._affine(res), _result_to_dict(res)
 
+    # -- point-set linear combinations (msm_points_lincomb, include/msm_hip.h) -----------------
+    def pointset_size(self, set_id: Optional[int] = None) -> int:
+        """Resident points of a point set (default: the current one), as the library counts them (msm_pointset_size)."""
+        n = C.c_uint64()
+        self._check(self._lib.msm_pointset_size(self._h, self._cur_set if set_id is None else set_id, C.byref(n)))
+        return int(n.value)
+
+    def points_lincomb(self, a, b=None, *, src_a: Optional[int] = None, a_lo: int = 0, src_b: Optional[int] = None, b_lo: int = 0,
+                       count: Optional[int] = None, dst: Optional[int] = None) -> int:
+        """D[i] = a * A[a_lo + i] + b * B[b_lo + i], i < count, as the rows [0, count) of point set `dst`, which then holds
+        `count` points (msm_points_lincomb).  a, b: ints or 32 little-endian bytes, < q; b None: no second term.  src_a, src_b,
+        dst: point-set ids, default the current set; count: default all of A from a_lo on.  dst may be a source (see
+        include/msm_hip.h for the overlaps allowed); the current set stays selected.  Returns count."""
+        sa = _scalar32(a, "a")
+        sb = None if b is None else _scalar32(b, "b")
+        if a_lo < 0 or b_lo < 0 or (count is not None and count < 0):
+            raise MsmError(_lib.MSM_ERR_ARG, "points_lincomb: a_lo, b_lo and count must not be negative")
+        cur = self._cur_set
+        ia = cur if src_a is None else src_a
+        ib = -1 if sb is None else (cur if src_b is None else src_b)
+        idst = cur if dst is None else dst
+        if count is None:
+            count = max(self.pointset_size(ia) - a_lo, 0)
+        abuf = (C.c_uint8 * 32).from_buffer_copy(sa)
+        bbuf = (C.c_uint8 * 32).from_buffer_copy(sb) if sb is not None else None
+        self._check(self._lib.msm_points_lincomb(self._h, ia, a_lo, abuf, ib, b_lo, bbuf, count, idst))
+        self._set_sizes[idst] = count
+        if idst == cur:
+            self.n_points = count
+        return count
+
+    def fold_points(self, lo_scalar, hi_scalar) -> int:
+        """The in-place fold of the current set: P[i] <- lo_scalar * P[i] + hi_scalar * P[i + n/2], i < n/2 (n even); the set
+        shrinks to n/2 points and loses its window tables.  The generator fold of an inner-product argument: (1, u) in Halo2,
+        (u^-1, u) in Bulletproofs.  Returns n/2."""
+        sa, sb = _scalar32(lo_scalar, "lo_scalar"), _scalar32(hi_scalar, "hi_scalar")
+        n = self.n_points
+        if n % 2:
+            raise MsmError(_lib.MSM_ERR_ARG, f"fold_points: the set holds {n} points, an odd number")
+        return self.points_lincomb(sa, sb, a_lo=0, b_lo=n // 2, count=n // 2)
+
     # -- window tables (msm_precompute, include/msm_hip.h) ------------------------------------
     def precompute(self, n: Optional[int] = None, c: Optional[int] = None, no_glv: bool = False, point_lo: int = 0) -> Tuple[int, int, int]:
         """Builds the window tables of the current point set -- of its points [point_lo, point_lo + n): the share of one rank of a
@@ -1063,6 +1121,28 @@ class _Parallel:
         res, info = self._ctx.msm_indexed_narrow(scalars, indices, bits=options.get("bits"), signed=options.get("signed"),
                                                  c=options.get("c"), width=options.get("width"))
         return {"result": res, "log": [], "info": info}
+
+    def pointsLincomb(self, dstPtr: PointPtr, a, ptrA: PointPtr, b=None, ptrB: Optional[PointPtr] = None,
+                      options: Optional[Dict] = None) -> PointPtr:
+        """dstPtr[i] = a * ptrA[aLo + i] + b * ptrB[bLo + i], i < count (msm_points_lincomb; the reference has no counterpart).
+        a, b: ints or 32 bytes, < q; b None: one term.  options: {"aLo", "bLo", "count"} (count: default all of ptrA from aLo on).
+        dstPtr may be ptrA or ptrB; it then holds `count` points.  Returns dstPtr."""
+        options = options or {}
+        if (b is None) != (ptrB is None):
+            raise MsmError(_lib.MSM_ERR_ARG, "pointsLincomb: b and ptrB come together")
+        a_lo, b_lo = int(options.get("aLo", 0)), int(options.get("bLo", 0))
+        count = options.get("count")
+        count = self._ctx.points_lincomb(a, b, src_a=ptrA.set_id, a_lo=a_lo, src_b=None if ptrB is None else ptrB.set_id, b_lo=b_lo,
+                                         count=max(ptrA.n - a_lo, 0) if count is None else count, dst=dstPtr.set_id)
+        dstPtr.n = count
+        return dstPtr
+
+    def foldPoints(self, pointPtr: PointPtr, a, b) -> PointPtr:
+        """The in-place fold of the points behind pointPtr: P[i] <- a * P[i] + b * P[i + n/2]; the pointer then holds n/2 points
+        (MsmContext.fold_points)."""
+        self._ctx.pointset_select(pointPtr.set_id)
+        pointPtr.n = self._ctx.fold_points(a, b)
+        return pointPtr
 
     def msmProjective(self, scalarPtr: ScalarPtr, pointPtr: PointPtr, N: int, options: Optional[Dict] = None) -> Dict:
         """`msmProjective` (src/parallel.ts:69-87: msmBasic over projective points): signed windows of the whole scalar,

@@ -14,6 +14,8 @@
 //   msm_narrow.hip    msm_run_narrow, msm_plan_narrow, msm_scalar_bits (narrow scalars: no endomorphism split, K from the call's bits)
 //   msm_indexed.hip   msm_run_indexed, msm_run_indexed_narrow (scalars over a chosen multiset of the resident points), with their
 //                     two kernels: the index check and the payload translation
+//   msm_lincomb.hip   msm_points_lincomb, msm_pointset_size (resident points from resident points: D = a A + b B), with the
+//                     kernels of points_lincomb.h
 // Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip, te_kernels.hip and narrow_kernels.hip; host TUs see
 // declarations.
 // Orchestration follows `createMsm().msm` (reference src/msm-batched-affine.ts:69-340); the per-thread SPMD phases separated
@@ -244,8 +246,9 @@ struct msm_ctx {
   PointSet& pts() { return sets[cur_set]; }
   const PointSet& pts() const { return sets[cur_set]; }
   // new points replace those of the current set: it forgets them and its window tables, and gets room for n rows
-  uint32_t* reset_points(uint64_t n) {
-    PointSet& s = pts();
+  uint32_t* reset_points(uint64_t n) { return reset_points(pts(), n); }
+  // the same for any set of the context (msm_points_lincomb writes into sets that are not current)
+  uint32_t* reset_points(PointSet& s, uint64_t n) {
     s.n = 0;
     s.tab.drop(this);   // window tables belong to the points they were built from
     cand_n = 0;

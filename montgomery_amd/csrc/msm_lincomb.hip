@@ -1,0 +1,112 @@
+// msm_points_lincomb: D[i] = a * A[a_lo + i] + b * B[b_lo + i] over resident rows, written as the rows [0, count) of a point set --
+// the one entry point that PRODUCES resident points from resident points (the generator fold of an inner-product argument,
+// scaling, element-wise sums, negation).  The host recodes (a, b) into a program once (points_lincomb.h), copies it to the
+// device and launches one lane per output point; a copy (a = 1, no second term) moves rows without a kernel.
+// Every check runs before anything is written; msm_pointset_size reports what a set holds.
+#include "msm_internal.h"
+#include "points_lincomb.h"
+
+using namespace msm;
+using namespace msmi;
+
+namespace {
+
+const char* const WHO = "msm_points_lincomb";
+
+bool live_set(const msm_ctx* ctx, int32_t id) {
+  return id >= 0 && id < (int)ctx->sets.size() && (id == 0 || ctx->sets[id].live);
+}
+
+void scalar_words(uint32_t (&w)[8], const uint8_t* s) {
+  for (int j = 0; j < 8; j++) w[j] = (uint32_t)s[4 * j] | ((uint32_t)s[4 * j + 1] << 8) | ((uint32_t)s[4 * j + 2] << 16) | ((uint32_t)s[4 * j + 3] << 24);
+}
+
+// a source range inside dst: the rows [0, count) themselves (lane i reads and writes row i only) or rows at and above `count`
+bool overlap_ok(uint64_t lo, uint64_t count) { return count == 0 || lo == 0 || lo >= count; }
+
+void make_program(const msm_ctx* ctx, lincomb::Program& P, const uint32_t* a, const uint32_t* b) {
+  if (ctx->is_te()) {
+    lincomb::make_program_te(P, a, b);
+    return;
+  }
+  for_weierstrass_curve(ctx->curve, [&](auto cv) { lincomb::make_program<typename decltype(cv)::G>(P, a, b); });
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_pointset_size(const msm_ctx* ctx, int32_t id, uint64_t* n_out) {
+  msm_ctx* c = const_cast<msm_ctx*>(ctx);
+  if (!ctx || !n_out) return fail(c, MSM_ERR_ARG, "msm_pointset_size: null argument");
+  if (!live_set(ctx, id)) return fail(c, MSM_ERR_ARG, "msm_pointset_size: no point set %d", (int)id);
+  *n_out = ctx->sets[id].n;
+  return MSM_OK;
+}
+
+int msm_points_lincomb(msm_ctx* ctx, int32_t src_a, uint64_t a_lo, const uint8_t* a, int32_t src_b, uint64_t b_lo, const uint8_t* b,
+                       uint64_t count, int32_t dst) {
+  if (!ctx || !a || (src_b >= 0 && !b)) return fail(ctx, MSM_ERR_ARG, "%s: null argument", WHO);
+  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "%s: runs on single-device contexts only", WHO);
+  if (count >= (1ull << 30)) return fail(ctx, MSM_ERR_ARG, "%s: count must be < 2^30", WHO);
+  for (int32_t id : {src_a, dst})
+    if (!live_set(ctx, id)) return fail(ctx, MSM_ERR_ARG, "%s: no point set %d", WHO, (int)id);
+  if (src_b >= 0 && !live_set(ctx, src_b)) return fail(ctx, MSM_ERR_ARG, "%s: no point set %d", WHO, (int)src_b);
+  const uint32_t* q = curve_info(ctx->curve).q;
+  uint32_t aw[8], bw[8] = {0};
+  scalar_words(aw, a);
+  if (src_b >= 0) scalar_words(bw, b);
+  if (!lincomb::words8_less(aw, q) || !lincomb::words8_less(bw, q))
+    return fail(ctx, MSM_ERR_SCALAR, "%s: scalar >= q (scalars of this call are never reduced)", WHO);
+  if (a_lo + count > ctx->sets[src_a].n)
+    return fail(ctx, MSM_ERR_NO_POINTS, "%s: rows [%llu, %llu) of set %d, which holds %llu", WHO, (unsigned long long)a_lo,
+                (unsigned long long)(a_lo + count), (int)src_a, (unsigned long long)ctx->sets[src_a].n);
+  if (src_b >= 0 && b_lo + count > ctx->sets[src_b].n)
+    return fail(ctx, MSM_ERR_NO_POINTS, "%s: rows [%llu, %llu) of set %d, which holds %llu", WHO, (unsigned long long)b_lo,
+                (unsigned long long)(b_lo + count), (int)src_b, (unsigned long long)ctx->sets[src_b].n);
+  if ((src_a == dst && !overlap_ok(a_lo, count)) || (src_b == dst && !overlap_ok(b_lo, count)))
+    return fail(ctx, MSM_ERR_ARG, "%s: a source range inside the destination must be its rows [0, count) or start at or above row count", WHO);
+  // a term under the scalar 0 is no term; the call is then about the other one (0 * A + b * B = b * B)
+  bool has_b = src_b >= 0 && !lincomb::words8_zero(bw);
+  if (has_b && lincomb::words8_zero(aw)) {
+    src_a = src_b;
+    a_lo = b_lo;
+    memcpy(aw, bw, sizeof aw);
+    has_b = false;
+  }
+  try {
+    HIPCHK(hipSetDevice(ctx->device));
+    lincomb::Program P;
+    make_program(ctx, P, aw, has_b ? bw : nullptr);
+    const uint64_t rw = ctx->row_words();
+    msm_ctx::PointSet& D = ctx->sets[dst];
+    // dst is replaced as by msm_set_points: tables dropped, room for `count` rows.  A dst that is a source keeps its buffer --
+    // the checked ranges lie inside what it holds -- so the fold of a 2^26-point set allocates nothing.
+    uint32_t* out = ctx->reset_points(D, count);
+    if (count) {
+      const uint32_t* rows_a = (const uint32_t*)ctx->sets[src_a].rows.p + a_lo * rw;
+      const uint32_t* rows_b = has_b ? (const uint32_t*)ctx->sets[src_b].rows.p + b_lo * rw : rows_a;
+      if (P.copy) {
+        if (rows_a != out) HIPCHK(hipMemcpyAsync(out, rows_a, count * rw * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      } else {
+        // the program, four ops to a word, behind 256 bytes of ctx->misc (the index check's word lives there)
+        uint32_t words[lincomb::MAX_OPS / 4] = {0};
+        for (int k = 0; k < P.n; k++) words[k >> 2] |= (uint32_t)P.ops[k] << (8 * (k & 3));
+        ctx->ensure(ctx->misc, 256 + sizeof words);
+        uint32_t* d_prog = (uint32_t*)((char*)ctx->misc.p + 256);
+        HIPCHK(hipMemcpyAsync(d_prog, words, sizeof words, hipMemcpyHostToDevice, ctx->stream));
+        const dim3 grid((uint32_t)((count + 255) / 256)), block(256);
+        if (ctx->is_te())
+          hipLaunchKernelGGL(lincomb::k_te_points_lincomb, grid, block, 0, ctx->stream, out, rows_a, rows_b, count, d_prog, (uint32_t)P.n);
+        else
+          W_LAUNCH(ctx, lincomb::k_points_lincomb, grid, block, 0, ctx->stream, out, rows_a, rows_b, count, d_prog, (uint32_t)P.n);
+        HIPCHK(hipGetLastError());
+      }
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    D.n = count;
+  } MSM_CATCH_ALL(ctx)
+  return MSM_OK;
+}
+
+}  // extern "C"

@@ -21,6 +21,8 @@
 //          msmIndexed(h, Buffer scalars of m x 32 bytes, Buffer indices of m x 4 bytes (uint32 LE), c, noGlv) -> as msm:
 //          sum_j scalars[j] * P[indices[j]] (msm_run_indexed); an index >= the resident count throws (msm error 1, the position
 //          in the message), msmIndexedNarrow(h, Buffer scalars, Buffer indices, width, bits, signed, c) (msm_run_indexed_narrow),
+//          pointsLincomb(h, srcA, aLo, Buffer a of 32 bytes, srcB (-1: no second term), bLo, Buffer b | null, count, dst) -> count:
+//          rows [0, count) of point set dst = a * A[aLo + i] + b * B[bLo + i] (msm_points_lincomb), pointsetSize(h, id) -> n,
 //          plan(h, n, c) -> {c, K}, generatePoints(h, n, seed) -> n, generateScalars(h, n, seed[, dbuf]) -> Buffer | n
 //          the fine operator table of the reference's wasm exports (src/field-msm.ts:86-123,190-243, src/scalar-glv.ts:41-51,105-128)
 //          over Buffers instead of wasm pointers: fieldOp(h, op, a, b) -> Buffer (msm_test_fp: multiply / square / add / subtract /
@@ -805,6 +807,65 @@ static napi_value PointsetOp(napi_env env, napi_callback_info info, int destroy)
 static napi_value PointsetSelect(napi_env env, napi_callback_info info) { return PointsetOp(env, info, 0); }
 static napi_value PointsetDestroy(napi_env env, napi_callback_info info) { return PointsetOp(env, info, 1); }
 
+// point-set linear combinations (msm_points_lincomb): pointsLincomb(h, srcA, aLo, a, srcB, bLo, b, count, dst) -> count
+static int scalar_arg(napi_env env, napi_value v, const uint8_t** out) {
+  bool is_buf = false;
+  void* p = NULL;
+  size_t len = 0;
+  if (napi_is_buffer(env, v, &is_buf) != napi_ok || !is_buf || napi_get_buffer_info(env, v, &p, &len) != napi_ok || len != 32) {
+    napi_throw_type_error(env, NULL, "pointsLincomb: a scalar is a Buffer of 32 bytes");
+    return 0;
+  }
+  *out = (const uint8_t*)p;
+  return 1;
+}
+static napi_value PointsLincomb(napi_env env, napi_callback_info info) {
+  size_t argc = 9;
+  napi_value argv[9];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 9) {
+    napi_throw_type_error(env, NULL, "pointsLincomb(ctx, srcA, aLo, a, srcB, bLo, b, count, dst)");
+    return NULL;
+  }
+  msm_ctx* ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  int32_t src_a = 0, src_b = -1, dst = 0;
+  int64_t a_lo = 0, b_lo = 0, count = 0;
+  NAPI_OK(napi_get_value_int32(env, argv[1], &src_a));
+  NAPI_OK(napi_get_value_int64(env, argv[2], &a_lo));
+  NAPI_OK(napi_get_value_int32(env, argv[4], &src_b));
+  NAPI_OK(napi_get_value_int64(env, argv[5], &b_lo));
+  NAPI_OK(napi_get_value_int64(env, argv[7], &count));
+  NAPI_OK(napi_get_value_int32(env, argv[8], &dst));
+  if (a_lo < 0 || b_lo < 0 || count < 0) {
+    napi_throw_range_error(env, NULL, "pointsLincomb: aLo, bLo and count must not be negative");
+    return NULL;
+  }
+  const uint8_t *a = NULL, *b = NULL;
+  if (!scalar_arg(env, argv[3], &a)) return NULL;
+  if (src_b >= 0 && !scalar_arg(env, argv[6], &b)) return NULL;
+  int rc = msm_points_lincomb(ctx, src_a, (uint64_t)a_lo, a, src_b, (uint64_t)b_lo, b, (uint64_t)count, dst);
+  if (rc != MSM_OK) return throw_msm(env, ctx, rc, "pointsLincomb");
+  napi_value out;
+  NAPI_OK(napi_create_int64(env, count, &out));
+  return out;
+}
+static napi_value PointsetSize(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msm_ctx* ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  int32_t id = 0;
+  NAPI_OK(napi_get_value_int32(env, argv[1], &id));
+  uint64_t n = 0;
+  int rc = msm_pointset_size(ctx, id, &n);
+  if (rc != MSM_OK) return throw_msm(env, ctx, rc, "pointsetSize");
+  napi_value out;
+  NAPI_OK(napi_create_int64(env, (int64_t)n, &out));
+  return out;
+}
+
 /* ---- the fine operator table: element-wise field / GLV / curve operators over Buffers -------------------------------- */
 
 static int buffer_arg(napi_env env, napi_value v, uint8_t** data, size_t* len) {
@@ -941,6 +1002,7 @@ NAPI_MODULE_INIT() {
       {"msmNarrow", MsmNarrow}, {"msmBatchNarrow", MsmBatchNarrow}, {"scalarBits", ScalarBits},
       {"msmIndexed", MsmIndexed}, {"msmIndexedNarrow", MsmIndexedNarrow},
       {"pointsetCreate", PointsetCreate}, {"pointsetSelect", PointsetSelect}, {"pointsetDestroy", PointsetDestroy},
+      {"pointsLincomb", PointsLincomb}, {"pointsetSize", PointsetSize},
       {"fieldOp", FieldOp}, {"batchInverse", BatchInverse}, {"glvDecompose", GlvDecompose}, {"batchAdd", BatchAdd}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
     napi_value f;
