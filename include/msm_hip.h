@@ -214,8 +214,13 @@ int msm_get_points_ex(msm_ctx* ctx, uint64_t first, uint64_t count, int format, 
  * the resident points in every step; msm_precompute with opts->point_lo builds the tables of exactly that range (2^23 points x 7
  * tables = 15 GB, in a buffer of their own next to the plain rows), and msm_run / msm_window_sums (with msm_opts.merged_sums)
  * over that range run on them.  Without msm_precompute they are built when a call comes back for the same range a second
- * time in a row -- a caller that walks over several ranges on one GPU is spared a build per call.  A point set holds the tables
- * of ONE range (or of the whole set, which a range never replaces by itself).
+ * time in a row -- a caller that walks over several ranges on one GPU is spared a build per call.  The first call already runs
+ * under the plan the tables will have (on the plain path: msm_result.tables = 0), so every call over one range reports the
+ * (c, K) msm_plan gives for it, before and after the build.  A point set holds the tables
+ * of ONE range (or of the whole set, which a range never replaces by itself): while the whole set's tables exist, a default-plan
+ * call over a range runs -- and msm_plan reports -- the plain plan.
+ * msm_precompute with opts->c == 0 builds for the plan a default-plan call over those points picks on tables: such a call then
+ * runs on them from the first time on.
  * msm_tables_info: window size and number of tables present (0, 0: none) and their bytes; msm_tables_range: the points they cover. */
 int msm_precompute(msm_ctx* ctx, uint64_t n, const msm_opts* opts);
 int msm_tables_info(const msm_ctx* ctx, int32_t* c_out, int32_t* K_out, uint64_t* bytes_out);
@@ -374,7 +379,12 @@ int msm_pointset_size(const msm_ctx* ctx, int32_t id, uint64_t* n_out);
  * integers (twisted Edwards: the extended point without T, which msm_combine rebuilds from T Z = X Y).
  * Ranks exchange these with one all-gather; msm_combine finishes.  With msm_opts.merged_sums the slots may come back merged
  * (first slot: sum_k 2^(c (k - k_lo)) P_k, the others the identity), which either combine takes unchanged, and the call may run
- * on window tables (msm_result.tables says whether it did). */
+ * on window tables (msm_result.tables says whether it did).
+ * k_lo == k_hi == 0 asks for all K windows: partials_out then takes K x 144 bytes, K as msm_plan reports it for the same n and
+ * opts (merged_sums and point_lo included) in the same state of the context; a shard [k_lo, k_hi) is cut from that K too.
+ * With opts->c == 0 a merged_sums call runs under that plan whether the tables it names exist yet or not: the call that comes
+ * before the build takes the plain path under the tables' window, so msm_result.c / K never differ from msm_plan's answer and
+ * do not change from one call over a range to the next. */
 int msm_window_sums(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, const msm_opts* opts,
                     uint8_t* partials_out, msm_result* stats);
 
@@ -395,7 +405,10 @@ int msm_combine_groups(int curve, const uint8_t* partials, int32_t G, int32_t K,
 /* Window plan for n points: the c the library would pick (opts->c forces one) and the resulting K (see msm_opts.c).  It is the
  * plan of msm_run over DEVICE-RESIDENT scalars: over the whole current point set that is the plan on window tables where they
  * exist or would be built (opts->no_tables: the plain plan, which msm_window_sums without merged_sums and bucket-range shards run;
- * opts->merged_sums: the plan of msm_window_sums(merged_sums) over the range [point_lo, point_lo + n), on its tables where they fit).
+ * opts->merged_sums: the plan of msm_window_sums(merged_sums) -- and of msm_run -- over the range [point_lo, point_lo + n), on its
+ * tables where they fit).  The answer is the plan of the very next such call and of every call after it: it does not depend on
+ * whether the tables have been built yet.  Only a change of the context's state moves it -- new points or another point set,
+ * msm_set_tables_limit, msm_precompute, or tables of the whole set taking the place of a range's (see msm_precompute).
  * Host scalars of 2^24 points and more cross PCIe behind the computation: msm_run then runs whole MSMs over growing ranges of
  * the points, each under the plan of ITS size, and msm_result reports the plan of the last, biggest range. */
 int msm_plan(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, int32_t* c_out, int32_t* K_out);

@@ -490,8 +490,10 @@ class MsmContext:
     def plan(self, n: int, c: Optional[int] = None, no_tables: bool = False, merged: bool = False, point_lo: int = 0) -> Tuple[int, int]:
         """(c, K) of msm_run over n points; over the whole resident point set that is the plan on window tables where they
         exist or would be built -- no_tables: the plain plan (what msm_window_sums without `merged` and bucket shards run);
-        merged: the plan of window_sums(..., merged=True) over the points [point_lo, point_lo + n), which may run on the window
-        tables of that range."""
+        merged: the plan of window_sums(..., merged=True), and of run_device, over the points [point_lo, point_lo + n), which may
+        run on the window tables of that range.  It is the (c, K) the very next such call reports and every one after it, whether
+        the tables exist yet or not (the call before the build runs the plain path under the tables' window); only new points,
+        set_tables_limit, precompute or tables of the whole set replacing a range's move it."""
         opts = MsmOpts(c=c or 0, no_tables=int(no_tables), merged_sums=int(merged), point_lo=point_lo)
         cc, kk = C.c_int32(), C.c_int32()
         self._check(self._lib.msm_plan(self._h, n, C.byref(opts), C.byref(cc), C.byref(kk)))
@@ -795,7 +797,9 @@ class MsmContext:
         """Partition sums P_k, k in [k_lo, k_hi), over the resident points [point_lo, point_lo + n) (scalar i belongs to
         point point_lo + i): (k_hi - k_lo) x 144 bytes (X, Y, Z).  merged (msm_opts.merged_sums): the caller only combines the
         sums, so they may come back merged -- the first slot carries sum_k 2^(c (k - k_lo)) P_k, the others the identity -- and
-        the call may run on window tables (of the whole set, or of exactly this range of the points)."""
+        the call may run on window tables (of the whole set, or of exactly this range of the points).  With c=None such a call
+        runs under plan(n, merged=True, point_lo=point_lo) from the first time on: take k_hi and the window for the combine from
+        there; info["c"], info["K"] repeat it on every call, info["tables"] says whether the tables were there."""
         if k_hi <= k_lo or k_lo < 0:   # (0, 0) would mean "all windows" to the C side and overrun the 144-byte buffer below
             raise MsmError(_lib.MSM_ERR_ARG, f"empty or negative window range [{k_lo}, {k_hi})")
         # bucket_shard = (g, G): only the buckets [L g / G, L (g + 1) / G) of every window (msm_opts.bucket_shard)

@@ -136,12 +136,12 @@ int make_run_plan(msm_ctx* ctx, uint64_t n, const msm_opts* opts, bool placed, P
         ctx->cand_n = n;
         ctx->cand_c = pt.c;
       }
-      // (msm_plan answers for the call that would build them: the plan of a rank's share of a points split is the tables' plan)
-      if (build_now || !note_range) {
-        pl = pt;
-        tables_wanted = true;
-        return MSM_OK;
-      }
+      // The plan is the tables' plan from the first call on, which is what msm_plan (note_range = false) answers: a call that
+      // does not build yet runs the plain path under it.  A caller sizes its slots and cuts its window shards from msm_plan's K,
+      // and the sums of the ranks of a points split meet slot by slot: calls 1, 2, 3 ... over one range share one (c, K).
+      pl = pt;
+      tables_wanted = build_now || !note_range;
+      return MSM_OK;
     }
   }
   return make_plan(ctx, n, opts, pl);
