@@ -69,7 +69,10 @@ enum {
  * The indexed (sparse) MSM (msm_run_indexed, msm_run_indexed_narrow) came the same way: two new symbols, version 8 and both struct
  * sizes unchanged.  A binding detects the feature by the presence of the symbol msm_run_indexed.
  * Point-set linear combinations (msm_points_lincomb, msm_pointset_size) came the same way: two new symbols, version 8 and both
- * struct sizes unchanged.  A binding detects the feature by the presence of the symbol msm_points_lincomb. */
+ * struct sizes unchanged.  A binding detects the feature by the presence of the symbol msm_points_lincomb.
+ * The resident scalar-vector operations (msm_scalars_lincomb, msm_scalars_mul, msm_scalars_inner, msm_scalars_powers) and
+ * msm_device_download came the same way: five new symbols, version 8 and both struct sizes unchanged.  A binding detects the
+ * feature by the presence of the symbol msm_scalars_lincomb. */
 #define MSM_ABI_VERSION 8
 uint32_t msm_abi_version(void);
 uint32_t msm_abi_struct_bytes(int which);
@@ -244,6 +247,39 @@ int msm_pointset_destroy(msm_ctx* ctx, int32_t id);
 int msm_device_alloc(msm_ctx* ctx, uint64_t bytes, void** dev_ptr_out);
 int msm_device_free(msm_ctx* ctx, void* dev_ptr);
 int msm_device_upload(msm_ctx* ctx, void* dev_ptr, const void* host, uint64_t bytes);
+/* the way back: `bytes` bytes from device memory of the context's device (a buffer of msm_device_alloc or any allocation of the
+ * caller, at any offset) into host memory; returns when they have arrived */
+int msm_device_download(msm_ctx* ctx, void* host, const void* dev_ptr, uint64_t bytes);
+
+/* Resident scalar-vector operations: arithmetic mod q -- the group order of the context's curve -- over vectors of scalars that
+ * stay in device memory: the scalar half of a round of an inner-product argument (the fold a' = u a_lo + u^-1 a_hi, the inner
+ * products <a_lo, b_hi> and <a_hi, b_lo>) beside msm_points_lincomb and msm_run, the powers (1, z, z^2, ...) of an evaluation
+ * point, a polynomial evaluation <coeffs, powers(z)>, a random linear combination or the element-wise product of two columns.
+ * The reference has no counterpart.  All seven curves.
+ * Vectors: dst, a and b are device pointers on the context's device, n x 32 bytes each: from msm_device_alloc or any allocation
+ *   of the caller, at any 32-byte offset inside one; aligned to 16 bytes, else MSM_ERR_ARG.  Elements are the 32-byte little-endian
+ *   integers msm_run reads (no Montgomery form); an element >= q is taken as its residue, msm_run's rule without `strict`.  Every
+ *   element written is canonical, in [0, q).  n < 2^30; n == 0 is valid, writes nothing, and msm_scalars_inner then returns 0.
+ * Host scalars: x, y and s are 32 bytes little-endian; a value >= q fails with MSM_ERR_SCALAR (the rule of msm_points_lincomb).
+ *   0 and 1 are ordinary input.
+ * Aliasing: dst may be exactly a, exactly b, or disjoint from both -- lane i reads its inputs before its one store.  The in-place
+ *   fold of a vector v of 2 h elements is dst = a = v, b = v + 32 h, n = h; the upper half is left as it was.  A dst range that
+ *   overlaps a source range in part fails with MSM_ERR_ARG before anything is launched.  The sources may overlap each other freely.
+ * Errors: null pointers with n > 0 (a null b of msm_scalars_lincomb is its one-term form), a null host scalar or `out`, a
+ *   device-list context, n >= 2^30: MSM_ERR_ARG.  All checks run before anything is written; a failed call leaves the context
+ *   usable.
+ * Ordering: every call returns when its result is in place (it synchronises the context's stream, as msm_points_lincomb does):
+ *   an msm_run over the same buffer needs no extra step.  No call touches point sets, window tables or the range-table candidate.
+ * msm_scalars_inner returns the same bits whatever the launch geometry: field addition is exact. */
+/* dst[i] = x * a[i] + y * b[i] mod q.  b == NULL: one term, dst[i] = x * a[i] (y is ignored) */
+int msm_scalars_lincomb(msm_ctx* ctx, void* dst, const uint8_t* x /* 32 B LE */, const void* a, const uint8_t* y /* 32 B LE */,
+                        const void* b, uint64_t n);
+/* dst[i] = a[i] * b[i] mod q */
+int msm_scalars_mul(msm_ctx* ctx, void* dst, const void* a, const void* b, uint64_t n);
+/* out = sum_i a[i] * b[i] mod q, 32 bytes little-endian on the host */
+int msm_scalars_inner(msm_ctx* ctx, const void* a, const void* b, uint64_t n, uint8_t* out);
+/* dst[i] = s * x^i mod q, i < n */
+int msm_scalars_powers(msm_ctx* ctx, void* dst, const uint8_t* s /* 32 B LE */, const uint8_t* x /* 32 B LE */, uint64_t n);
 
 /* Device memory the working buffers of one call may take (digits, sort records, tree nodes: the reference sizes them per call
  * in wasm memory, src/msm-batched-affine.ts:96-130).  0 = automatic: 85 % of what the device has free when a big call starts.

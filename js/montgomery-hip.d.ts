@@ -53,6 +53,20 @@ export interface Parallel {
   pointsetSize(pointPtr: PointPtr): number;
   /** in-place fold: P[i] <- a * P[i] + b * P[i + n/2], i < n/2 (n even); the pointer then holds n/2 points */
   foldPoints(pointPtr: PointPtr, a: bigint | number | Uint8Array, b: bigint | number | Uint8Array): PointPtr;
+  /** resident scalar vectors (msm_scalars_lincomb): dst[i] = x * A[aLo + i] + y * B[bLo + i] mod the group order, i < count, over
+   *  scalars that stay on the device; x, y below the group order, y and ptrB null for one term; dstPtr may be a source.  Returns dstPtr */
+  scalarsLincomb(dstPtr: ScalarPtr, x: bigint | number | Uint8Array, ptrA: ScalarPtr, y?: bigint | number | Uint8Array | null, ptrB?: ScalarPtr | null,
+                 options?: { aLo?: number; bLo?: number; dstLo?: number; count?: number }): ScalarPtr;
+  /** dst[i] = A[i] * B[i] mod the group order, i < N (msm_scalars_mul) */
+  scalarsMul(dstPtr: ScalarPtr, ptrA: ScalarPtr, ptrB: ScalarPtr, N: number): ScalarPtr;
+  /** sum_i A[aLo + i] * B[bLo + i] mod the group order, i < N (msm_scalars_inner) */
+  scalarsInner(ptrA: ScalarPtr, ptrB: ScalarPtr, N: number, options?: { aLo?: number; bLo?: number }): bigint;
+  /** a new scalar pointer holding s * x^i, i < N (msm_scalars_powers); s: default 1 */
+  scalarsPowers(x: bigint | number | Uint8Array, N: number, s?: bigint | number | Uint8Array): ScalarPtr;
+  /** in-place fold: v[i] <- a * v[i] + b * v[i + n/2], i < n/2 (n even); the pointer then holds n/2 scalars */
+  foldScalars(scalarPtr: ScalarPtr, a: bigint | number | Uint8Array, b: bigint | number | Uint8Array): ScalarPtr;
+  /** the first N scalars behind a pointer (default: all) as N x 32 bytes on the host (msm_device_download) */
+  scalarsToBytes(scalarPtr: ScalarPtr, N?: number): Buffer;
   /** smallest `bits` msmNarrow(width 32) accepts these n x 32-byte scalars under (0: all zero; 255: more than 128 bits needed) */
   scalarBits(scalars32: Uint8Array): { unsigned: number; signed: number };
   /** src/msm-batched-affine.ts:587-598: msm with useSafeAdditions = false (msm_opts.unsafe) */

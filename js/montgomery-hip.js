@@ -204,6 +204,59 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       if (n % 2) throw new RangeError(`foldPoints: the pointer holds ${n} points, an odd number`);
       return Parallel.pointsLincomb(pointPtr, a, pointPtr, b, pointPtr, { aLo: 0, bLo: n / 2, count: n / 2 });
     },
+    // Resident scalar vectors (msm_scalars_*; the reference has no counterpart): arithmetic mod the group order over the scalars
+    // behind scalar pointers, which stay on the device.  Host scalars x, y, s: BigInt / number or 32 bytes, below the group order
+    // (a larger value throws msm error 6); elements of the vectors may be any 32-byte integers and are taken mod the order.
+    // dstPtr[i] = x * ptrA[aLo + i] + y * ptrB[bLo + i], i < count; y and ptrB null: one term.  options: {aLo, bLo, dstLo, count}
+    // (count: default all of ptrA from aLo on).  dstPtr may be ptrA or ptrB over the same elements; a pointer without a buffer
+    // that large gets one.
+    scalarsLincomb(dstPtr, x, ptrA, y, ptrB, options) {
+      const o = options || {}, aLo = o.aLo || 0, bLo = o.bLo || 0, dstLo = o.dstLo || 0;
+      if ((y === null || y === undefined) !== (ptrB === null || ptrB === undefined)) throw new TypeError("scalarsLincomb: y and ptrB come together");
+      const count = o.count === undefined ? Math.max(ptrA.n - aLo, 0) : o.count;
+      needScalars(ptrA, aLo + count, "scalarsLincomb");
+      if (ptrB) needScalars(ptrB, bLo + count, "scalarsLincomb");
+      roomFor(dstPtr, dstLo + count);
+      hip.scalarsLincomb(ctx, dstPtr.dev, dstLo, scalarBuffer(x, "x"), ptrA.dev, aLo, ptrB ? scalarBuffer(y, "y") : null,
+        ptrB ? ptrB.dev : null, bLo, count);
+      return dstPtr;
+    },
+    // dstPtr[i] = ptrA[i] * ptrB[i], i < N
+    scalarsMul(dstPtr, ptrA, ptrB, N) {
+      needScalars(ptrA, N, "scalarsMul");
+      needScalars(ptrB, N, "scalarsMul");
+      roomFor(dstPtr, N);
+      hip.scalarsMul(ctx, dstPtr.dev, 0, ptrA.dev, 0, ptrB.dev, 0, N);
+      return dstPtr;
+    },
+    // sum_i ptrA[aLo + i] * ptrB[bLo + i], i < N, as a BigInt.  options: {aLo, bLo}
+    scalarsInner(ptrA, ptrB, N, options) {
+      const o = options || {}, aLo = o.aLo || 0, bLo = o.bLo || 0;
+      needScalars(ptrA, aLo + N, "scalarsInner");
+      needScalars(ptrB, bLo + N, "scalarsInner");
+      return leBytesToBigint(hip.scalarsInner(ctx, ptrA.dev, aLo, ptrB.dev, bLo, N));
+    },
+    // a new scalar pointer holding (s, s x, s x^2, ..., s x^(N-1)); s: default 1
+    scalarsPowers(x, N, s) {
+      const ptr = newScalarPtr(32 * N);
+      roomFor(ptr, N);
+      hip.scalarsPowers(ctx, ptr.dev, 0, scalarBuffer(s === undefined || s === null ? 1 : s, "s"), scalarBuffer(x, "x"), N);
+      return firstOf(ptr);
+    },
+    // the in-place fold of an inner-product argument: v[i] <- a * v[i] + b * v[i + n/2], i < n/2; the pointer then holds n/2 scalars
+    foldScalars(scalarPtr, a, b) {
+      const n = scalarPtr.n;
+      if (n % 2) throw new RangeError(`foldScalars: the pointer holds ${n} scalars, an odd number`);
+      Parallel.scalarsLincomb(scalarPtr, a, scalarPtr, b, scalarPtr, { aLo: 0, bLo: n / 2, count: n / 2 });
+      scalarPtr.n = n / 2;
+      return scalarPtr;
+    },
+    // the first N scalars behind a pointer, back on the host: a Buffer of N x 32 bytes (msm_device_download)
+    scalarsToBytes(scalarPtr, N) {
+      N = N === undefined ? scalarPtr.n : N;
+      needScalars(scalarPtr, N, "scalarsToBytes");
+      return N ? hip.deviceDownload(ctx, scalarPtr.dev, 0, 32 * N) : Buffer.alloc(0);
+    },
     // {unsigned, signed}: the smallest `bits` msmNarrow accepts these n x 32-byte scalars under as a Buffer with width 32
     // (0: all zero; 255: a scalar needs more than 128 bits)
     scalarBits(scalars32) {
@@ -253,6 +306,16 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       arr = Uint32Array.from(list);
     }
     return { buf: Buffer.from(arr.buffer, arr.byteOffset, arr.byteLength), m: arr.length };
+  }
+  function needScalars(ptr, n, who) {
+    if (n > ptr.n || (n && !ptr.dev)) throw new Error(`${who}: ${n} scalars requested but the scalar pointer holds ${ptr.dev ? ptr.n : 0}`);
+  }
+  // a destination of the scalar-vector calls: a pointer that holds fewer than n scalars gets a buffer of n
+  function roomFor(ptr, n) {
+    if (ptr.dev && ptr.n >= n) return;
+    ptr.free();
+    ptr.dev = hip.deviceAlloc(ctx, Math.max(32 * n, 32));
+    ptr.n = n;
   }
   function newScalarPtr(size) {
     return { size, n: 0, dev: null, free() { if (this.dev) { const d = this.dev; this.dev = null; this.n = 0; hip.deviceFree(ctx, d); } } };

@@ -46,6 +46,7 @@ EXPORTS = (
     "msm_run_narrow", "msm_run_batch_narrow", "msm_plan_narrow", "msm_scalar_bits",
     "msm_run_indexed", "msm_run_indexed_narrow",
     "msm_points_lincomb", "msm_pointset_size",
+    "msm_device_download", "msm_scalars_lincomb", "msm_scalars_mul", "msm_scalars_inner", "msm_scalars_powers",
 )
 
 
@@ -167,6 +168,14 @@ def load() -> C.CDLL:
         raise ImportError(f"{LIB_PATH} predates msm_points_lincomb: rebuild it (`make`)")
     lib.msm_points_lincomb.argtypes = [vp, i32, u64, vp, i32, u64, vp, u64, i32]
     lib.msm_pointset_size.argtypes = [vp, i32, C.POINTER(u64)]
+    # resident scalar-vector operations and the download: new symbols under ABI 8 as well
+    if not hasattr(lib, "msm_scalars_lincomb"):
+        raise ImportError(f"{LIB_PATH} predates msm_scalars_lincomb: rebuild it (`make`)")
+    lib.msm_device_download.argtypes = [vp, vp, vp, u64]
+    lib.msm_scalars_lincomb.argtypes = [vp, vp, vp, vp, vp, vp, u64]
+    lib.msm_scalars_mul.argtypes = [vp, vp, vp, vp, u64]
+    lib.msm_scalars_inner.argtypes = [vp, vp, vp, u64, vp]
+    lib.msm_scalars_powers.argtypes = [vp, vp, vp, vp, u64]
     lib.msm_run_placed.argtypes = [vp, C.POINTER(vp), u64, C.POINTER(MsmOpts), C.POINTER(MsmResult)]
     lib.msm_plan.argtypes = [vp, u64, C.POINTER(MsmOpts), C.POINTER(i32), C.POINTER(i32)]
     lib.msm_generate_points.argtypes = [vp, u64, u64, vp]

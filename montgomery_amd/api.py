@@ -762,6 +762,50 @@ class MsmContext:
             raise MsmError(_lib.MSM_ERR_ARG, f"fold_points: the set holds {n} points, an odd number")
         return self.points_lincomb(sa, sb, a_lo=0, b_lo=n // 2, count=n // 2)
 
+    # -- resident scalar-vector operations (msm_scalars_*, include/msm_hip.h) -------------------
+    def device_download(self, dev_ptr: int, nbytes: int) -> bytes:
+        """`nbytes` bytes of device memory, from a buffer of device_alloc or any device address (msm_device_download)."""
+        buf = (C.c_uint8 * max(nbytes, 1))()
+        self._check(self._lib.msm_device_download(self._h, buf, C.c_void_p(dev_ptr), nbytes))
+        return bytes(buf[:nbytes])
+
+    @staticmethod
+    def _scalar_buf(v, what: str):
+        return (C.c_uint8 * 32).from_buffer_copy(_scalar32(v, what))
+
+    def scalars_lincomb(self, dst: int, x, a: int, y=None, b: Optional[int] = None, n: int = 0) -> None:
+        """dst[i] = x * a[i] + y * b[i] mod q, i < n, over vectors of 32-byte scalars in device memory (msm_scalars_lincomb).
+        dst, a, b: device addresses (16-byte aligned); x, y: ints or 32 little-endian bytes, < q.  y and b None: one term.
+        dst may be a or b themselves, or disjoint from both."""
+        if (y is None) != (b is None):
+            raise MsmError(_lib.MSM_ERR_ARG, "scalars_lincomb: y and b come together")
+        ybuf = None if y is None else self._scalar_buf(y, "y")
+        self._check(self._lib.msm_scalars_lincomb(self._h, C.c_void_p(dst), self._scalar_buf(x, "x"), C.c_void_p(a), ybuf,
+                                                  None if b is None else C.c_void_p(b), n))
+
+    def scalars_mul(self, dst: int, a: int, b: int, n: int) -> None:
+        """dst[i] = a[i] * b[i] mod q (msm_scalars_mul)."""
+        self._check(self._lib.msm_scalars_mul(self._h, C.c_void_p(dst), C.c_void_p(a), C.c_void_p(b), n))
+
+    def scalars_inner(self, a: int, b: int, n: int) -> int:
+        """sum_i a[i] * b[i] mod q as an int (msm_scalars_inner); 0 for n == 0."""
+        out = (C.c_uint8 * 32)()
+        self._check(self._lib.msm_scalars_inner(self._h, C.c_void_p(a), C.c_void_p(b), n, out))
+        return int.from_bytes(bytes(out), "little")
+
+    def scalars_powers(self, dst: int, x, n: int, s=1) -> None:
+        """dst[i] = s * x^i mod q, i < n (msm_scalars_powers)."""
+        self._check(self._lib.msm_scalars_powers(self._h, C.c_void_p(dst), self._scalar_buf(s, "s"), self._scalar_buf(x, "x"), n))
+
+    def fold_scalars(self, dev_ptr: int, n: int, lo_scalar, hi_scalar) -> int:
+        """The in-place fold of the n scalars at dev_ptr: v[i] <- lo_scalar * v[i] + hi_scalar * v[i + n/2], i < n/2 (n even); the
+        upper half stays as it was.  The scalar fold of an inner-product argument beside fold_points.  Returns n/2."""
+        if n < 0 or n % 2:
+            raise MsmError(_lib.MSM_ERR_ARG, f"fold_scalars: {n} scalars, not an even number")
+        h = n // 2
+        self.scalars_lincomb(dev_ptr, lo_scalar, dev_ptr, hi_scalar, dev_ptr + 32 * h, h)
+        return h
+
     # -- window tables (msm_precompute, include/msm_hip.h) ------------------------------------
     def precompute(self, n: Optional[int] = None, c: Optional[int] = None, no_glv: bool = False, point_lo: int = 0) -> Tuple[int, int, int]:
         """Builds the window tables of the current point set -- of its points [point_lo, point_lo + n): the share of one rank of a
@@ -1147,6 +1191,65 @@ class _Parallel:
         self._ctx.pointset_select(pointPtr.set_id)
         pointPtr.n = self._ctx.fold_points(a, b)
         return pointPtr
+
+    # -- scalar vectors on the device (msm_scalars_*; the reference has no counterpart) ------------
+    def _scalar_dev(self, ptr: ScalarPtr, n: int, what: str, alloc: bool = False) -> int:
+        """The device address behind a scalar pointer that holds at least n scalars; host bytes move to a buffer of the pointer's
+        own first.  alloc: a destination, which gets a buffer of n scalars if it has none that large."""
+        if alloc and (not ptr.dev_ptr or ptr.n < n):
+            if ptr.dev_ptr:
+                self._ctx.device_free(ptr.dev_ptr)
+            ptr._ctx, ptr.dev_ptr, ptr.data = self._ctx, self._ctx.device_alloc(32 * max(n, 1)), b""
+            ptr.n, ptr.size = n, 32 * n
+        if not ptr.dev_ptr and ptr.data:
+            dev = self._ctx.device_alloc(max(len(ptr.data), 32))
+            self._ctx.device_upload(dev, ptr.data)
+            ptr._ctx, ptr.dev_ptr, ptr.data = self._ctx, dev, b""
+        if n > ptr.n or (n and not ptr.dev_ptr):
+            raise MsmError(_lib.MSM_ERR_ARG, f"{what}: {n} scalars requested but the scalar pointer holds {ptr.n}")
+        return ptr.dev_ptr
+
+    def scalarsLincomb(self, dstPtr: ScalarPtr, x, ptrA: ScalarPtr, y=None, ptrB: Optional[ScalarPtr] = None,
+                       options: Optional[Dict] = None) -> ScalarPtr:
+        """dstPtr[i] = x * ptrA[aLo + i] + y * ptrB[bLo + i] mod q, i < count.  options: {"aLo", "bLo", "count"} (count: default
+        all of ptrA from aLo on).  dstPtr may be ptrA or ptrB (with an offset of 0); it then holds at least `count` scalars."""
+        options = options or {}
+        if (y is None) != (ptrB is None):
+            raise MsmError(_lib.MSM_ERR_ARG, "scalarsLincomb: y and ptrB come together")
+        a_lo, b_lo = int(options.get("aLo", 0)), int(options.get("bLo", 0))
+        count = options.get("count")
+        count = max(ptrA.n - a_lo, 0) if count is None else int(count)
+        a = self._scalar_dev(ptrA, a_lo + count, "scalarsLincomb")
+        b = None if ptrB is None else self._scalar_dev(ptrB, b_lo + count, "scalarsLincomb")
+        d = self._scalar_dev(dstPtr, count, "scalarsLincomb", alloc=True)
+        self._ctx.scalars_lincomb(d, x, a + 32 * a_lo, y, None if b is None else b + 32 * b_lo, count)
+        return dstPtr
+
+    def scalarsMul(self, dstPtr: ScalarPtr, ptrA: ScalarPtr, ptrB: ScalarPtr, N: int) -> ScalarPtr:
+        """dstPtr[i] = ptrA[i] * ptrB[i] mod q, i < N."""
+        a, b = self._scalar_dev(ptrA, N, "scalarsMul"), self._scalar_dev(ptrB, N, "scalarsMul")
+        self._ctx.scalars_mul(self._scalar_dev(dstPtr, N, "scalarsMul", alloc=True), a, b, N)
+        return dstPtr
+
+    def scalarsInner(self, ptrA: ScalarPtr, ptrB: ScalarPtr, N: int, options: Optional[Dict] = None) -> int:
+        """sum_i ptrA[aLo + i] * ptrB[bLo + i] mod q, i < N, as an int.  options: {"aLo", "bLo"}."""
+        options = options or {}
+        a_lo, b_lo = int(options.get("aLo", 0)), int(options.get("bLo", 0))
+        a, b = self._scalar_dev(ptrA, a_lo + N, "scalarsInner"), self._scalar_dev(ptrB, b_lo + N, "scalarsInner")
+        return self._ctx.scalars_inner(a + 32 * a_lo, b + 32 * b_lo, N)
+
+    def scalarsPowers(self, x, N: int, s=1) -> ScalarPtr:
+        """A new scalar pointer holding (s, s x, s x^2, ..., s x^(N-1)) mod q."""
+        ptr = ScalarPtr(self._ctx, size=32 * N)
+        self._ctx.scalars_powers(self._scalar_dev(ptr, N, "scalarsPowers", alloc=True), x, N, s)
+        return ptr
+
+    def foldScalars(self, scalarPtr: ScalarPtr, a, b) -> ScalarPtr:
+        """The in-place fold of the scalars behind scalarPtr: v[i] <- a * v[i] + b * v[i + n/2]; the pointer then holds n/2
+        scalars (MsmContext.fold_scalars)."""
+        dev = self._scalar_dev(scalarPtr, scalarPtr.n, "foldScalars")
+        scalarPtr.n = self._ctx.fold_scalars(dev, scalarPtr.n, a, b)
+        return scalarPtr
 
     def msmProjective(self, scalarPtr: ScalarPtr, pointPtr: PointPtr, N: int, options: Optional[Dict] = None) -> Dict:
         """`msmProjective` (src/parallel.ts:69-87: msmBasic over projective points): signed windows of the whole scalar,

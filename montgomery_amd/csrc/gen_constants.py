@@ -213,6 +213,11 @@ def main():
     out += field_block("FpBn254", FP_BN254, 9, 8, {"BETAW": BETA_BN254, "BW": 3, "GXW": GX_BN254, "GYW": GY_BN254})
     out += field_block("FpGrumpkin", FQ_BN254, 9, 8, {"BETAW": BETA_GRUMPKIN, "BW": FQ_BN254 - 17, "GXW": GX_GRUMPKIN, "GYW": GY_GRUMPKIN})
     out += field_block("FpVesta", FQ_PALLAS, 9, 8, {"BETAW": BETA_VESTA, "BW": 5, "GXW": GX_VESTA, "GYW": GY_VESTA})
+    # the two scalar fields that are no curve's base field (scalar_vec.h: the resident scalar-vector ops work mod the group order
+    # q; the other five group orders are base fields above).  BLS12-381's q is 1 mod 2^30; Ed-on-BLS12-377's is not: the general
+    # reduction row of fe_reduce_row
+    out += field_block("Fr381", FR381, 9, 8)
+    out += field_block("FrEd377", FR_ED, 9, 8)
     out += glv_block()
     out += glv_block("GlvPallas", LAMBDA_PALLAS, FQ_PALLAS, 127)
     out += glv_block("GlvBls381", LAMBDA381, FR381, 127)

@@ -16,6 +16,8 @@
 //                     two kernels: the index check and the payload translation
 //   msm_lincomb.hip   msm_points_lincomb, msm_pointset_size (resident points from resident points: D = a A + b B), with the
 //                     kernels of points_lincomb.h
+//   msm_scalars.hip   msm_scalars_lincomb, _mul, _inner, _powers (vectors of scalars in device memory, mod the group order) and
+//                     msm_device_download, with the kernels of scalar_vec.h
 // Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip, te_kernels.hip and narrow_kernels.hip; host TUs see
 // declarations.
 // Orchestration follows `createMsm().msm` (reference src/msm-batched-affine.ts:69-340); the per-thread SPMD phases separated
@@ -27,6 +29,7 @@
 #include "te_kernels.h"
 #include "narrow_kernels.h"
 #include "host_field.h"
+#include "scalar_vec.h"    // the scalar field of every curve (MSM_SCALAR_FIELDS); its kernels are instantiated by msm_scalars.hip
 #include "../../include/msm_hip.h"
 
 #include <algorithm>
@@ -339,6 +342,17 @@ inline void for_weierstrass_curve(int curve, Fn&& fn) {
     MSM_W_CURVES(MSM_DISPATCH_CASE)
 #undef MSM_DISPATCH_CASE
     default: throw msmi::HipFail{hipErrorInvalidValue, "Weierstrass kernel launch for a curve id outside MSM_W_CURVES", __LINE__, __FILE__};
+  }
+}
+// curve dispatch to the SCALAR field, the integers mod the group order q (scalar_vec.h): fn(field struct) for all seven curves, the
+// Edwards curve included
+template <class Fn>
+inline void for_scalar_field(int curve, Fn&& fn) {
+  switch (curve) {
+#define MSM_DISPATCH_CASE(ID, S) case ID: fn(msm::S{}); break;
+    MSM_SCALAR_FIELDS(MSM_DISPATCH_CASE)
+#undef MSM_DISPATCH_CASE
+    default: throw msmi::HipFail{hipErrorInvalidValue, "scalar-field kernel launch for an unknown curve id", __LINE__, __FILE__};
   }
 }
 #define W_LAUNCH(ctx, KERNEL, ...) \

@@ -23,6 +23,10 @@
 //          in the message), msmIndexedNarrow(h, Buffer scalars, Buffer indices, width, bits, signed, c) (msm_run_indexed_narrow),
 //          pointsLincomb(h, srcA, aLo, Buffer a of 32 bytes, srcB (-1: no second term), bLo, Buffer b | null, count, dst) -> count:
 //          rows [0, count) of point set dst = a * A[aLo + i] + b * B[bLo + i] (msm_points_lincomb), pointsetSize(h, id) -> n,
+//          resident scalar vectors (msm_scalars_*): a vector is a device buffer and an offset in elements of 32 bytes --
+//          deviceDownload(h, dbuf, byteOffset, bytes) -> Buffer, scalarsLincomb(h, dst, dstOff, Buffer x, a, aOff, Buffer y | null,
+//          b | null, bOff, n): dst[i] = x a[i] + y b[i] mod q, scalarsMul(h, dst, dstOff, a, aOff, b, bOff, n),
+//          scalarsInner(h, a, aOff, b, bOff, n) -> Buffer of 32 bytes, scalarsPowers(h, dst, dstOff, Buffer s, Buffer x, n),
 //          plan(h, n, c) -> {c, K}, generatePoints(h, n, seed) -> n, generateScalars(h, n, seed[, dbuf]) -> Buffer | n
 //          the fine operator table of the reference's wasm exports (src/field-msm.ts:86-123,190-243, src/scalar-glv.ts:41-51,105-128)
 //          over Buffers instead of wasm pointers: fieldOp(h, op, a, b) -> Buffer (msm_test_fp: multiply / square / add / subtract /
@@ -866,6 +870,149 @@ static napi_value PointsetSize(napi_env env, napi_callback_info info) {
   return out;
 }
 
+// resident scalar vectors (msm_scalars_*): a vector argument is (device buffer, offset in elements); its n elements must lie
+// inside the buffer -- the library cannot know where a caller's allocation ends
+static int vec_arg(napi_env env, js_ctx* h, napi_value v_buf, napi_value v_off, int64_t n, const char* what, uint8_t** out) {
+  js_dbuf* b = get_dbuf(env, h, v_buf);
+  if (!b) return 0;
+  int64_t off = 0;
+  if (napi_get_value_int64(env, v_off, &off) != napi_ok || off < 0 || n < 0 || ((uint64_t)off + (uint64_t)n) * 32 > b->bytes) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "%s: the elements lie outside the device buffer", what);
+    napi_throw_range_error(env, NULL, buf);
+    return 0;
+  }
+  *out = (uint8_t*)b->dev + (uint64_t)off * 32;
+  return 1;
+}
+static int host_scalar_arg(napi_env env, napi_value v, const uint8_t** out) {
+  bool is_buf = false;
+  void* p = NULL;
+  size_t len = 0;
+  if (napi_is_buffer(env, v, &is_buf) != napi_ok || !is_buf || napi_get_buffer_info(env, v, &p, &len) != napi_ok || len != 32) {
+    napi_throw_type_error(env, NULL, "a host scalar is a Buffer of 32 bytes");
+    return 0;
+  }
+  *out = (const uint8_t*)p;
+  return 1;
+}
+static int is_nullish(napi_env env, napi_value v) {
+  napi_valuetype t;
+  return napi_typeof(env, v, &t) == napi_ok && (t == napi_undefined || t == napi_null);
+}
+static napi_value DeviceDownload(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 4) {
+    napi_throw_type_error(env, NULL, "deviceDownload(ctx, dbuf, byteOffset, bytes)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  js_dbuf* b = get_dbuf(env, h, argv[1]);
+  if (!b) return NULL;
+  int64_t off = 0, bytes = 0;
+  NAPI_OK(napi_get_value_int64(env, argv[2], &off));
+  NAPI_OK(napi_get_value_int64(env, argv[3], &bytes));
+  if (off < 0 || bytes < 0 || (uint64_t)off + (uint64_t)bytes > b->bytes) {
+    napi_throw_range_error(env, NULL, "deviceDownload: the range lies outside the device buffer");
+    return NULL;
+  }
+  napi_value out;
+  void* po = NULL;
+  NAPI_OK(napi_create_buffer(env, (size_t)bytes, &po, &out));
+  if (bytes) {
+    int rc = msm_device_download(h->ctx, po, (uint8_t*)b->dev + off, (uint64_t)bytes);
+    if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "deviceDownload");
+  }
+  return out;
+}
+static napi_value ScalarsLincomb(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value argv[10];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 10) {
+    napi_throw_type_error(env, NULL, "scalarsLincomb(ctx, dst, dstOff, x, a, aOff, y, b, bOff, n)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int64_t n = 0;
+  NAPI_OK(napi_get_value_int64(env, argv[9], &n));
+  uint8_t *dst = NULL, *a = NULL, *b = NULL;
+  const uint8_t *x = NULL, *y = NULL;
+  if (!vec_arg(env, h, argv[1], argv[2], n, "scalarsLincomb", &dst) || !vec_arg(env, h, argv[4], argv[5], n, "scalarsLincomb", &a)) return NULL;
+  if (!host_scalar_arg(env, argv[3], &x)) return NULL;
+  if (!is_nullish(env, argv[7])) {
+    if (!vec_arg(env, h, argv[7], argv[8], n, "scalarsLincomb", &b) || !host_scalar_arg(env, argv[6], &y)) return NULL;
+  }
+  int rc = msm_scalars_lincomb(h->ctx, dst, x, a, y, b, (uint64_t)n);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsLincomb");
+  return NULL;
+}
+static napi_value ScalarsMul(napi_env env, napi_callback_info info) {
+  size_t argc = 8;
+  napi_value argv[8];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 8) {
+    napi_throw_type_error(env, NULL, "scalarsMul(ctx, dst, dstOff, a, aOff, b, bOff, n)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int64_t n = 0;
+  NAPI_OK(napi_get_value_int64(env, argv[7], &n));
+  uint8_t *dst = NULL, *a = NULL, *b = NULL;
+  if (!vec_arg(env, h, argv[1], argv[2], n, "scalarsMul", &dst) || !vec_arg(env, h, argv[3], argv[4], n, "scalarsMul", &a) ||
+      !vec_arg(env, h, argv[5], argv[6], n, "scalarsMul", &b))
+    return NULL;
+  int rc = msm_scalars_mul(h->ctx, dst, a, b, (uint64_t)n);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsMul");
+  return NULL;
+}
+static napi_value ScalarsInner(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 6) {
+    napi_throw_type_error(env, NULL, "scalarsInner(ctx, a, aOff, b, bOff, n)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int64_t n = 0;
+  NAPI_OK(napi_get_value_int64(env, argv[5], &n));
+  uint8_t *a = NULL, *b = NULL;
+  if (!vec_arg(env, h, argv[1], argv[2], n, "scalarsInner", &a) || !vec_arg(env, h, argv[3], argv[4], n, "scalarsInner", &b)) return NULL;
+  napi_value out;
+  void* po = NULL;
+  NAPI_OK(napi_create_buffer(env, 32, &po, &out));
+  int rc = msm_scalars_inner(h->ctx, a, b, (uint64_t)n, (uint8_t*)po);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsInner");
+  return out;
+}
+static napi_value ScalarsPowers(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 6) {
+    napi_throw_type_error(env, NULL, "scalarsPowers(ctx, dst, dstOff, s, x, n)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int64_t n = 0;
+  NAPI_OK(napi_get_value_int64(env, argv[5], &n));
+  uint8_t* dst = NULL;
+  const uint8_t *s = NULL, *x = NULL;
+  if (!vec_arg(env, h, argv[1], argv[2], n, "scalarsPowers", &dst)) return NULL;
+  if (!host_scalar_arg(env, argv[3], &s) || !host_scalar_arg(env, argv[4], &x)) return NULL;
+  int rc = msm_scalars_powers(h->ctx, dst, s, x, (uint64_t)n);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsPowers");
+  return NULL;
+}
+
 /* ---- the fine operator table: element-wise field / GLV / curve operators over Buffers -------------------------------- */
 
 static int buffer_arg(napi_env env, napi_value v, uint8_t** data, size_t* len) {
@@ -1003,6 +1150,8 @@ NAPI_MODULE_INIT() {
       {"msmIndexed", MsmIndexed}, {"msmIndexedNarrow", MsmIndexedNarrow},
       {"pointsetCreate", PointsetCreate}, {"pointsetSelect", PointsetSelect}, {"pointsetDestroy", PointsetDestroy},
       {"pointsLincomb", PointsLincomb}, {"pointsetSize", PointsetSize},
+      {"deviceDownload", DeviceDownload}, {"scalarsLincomb", ScalarsLincomb}, {"scalarsMul", ScalarsMul},
+      {"scalarsInner", ScalarsInner}, {"scalarsPowers", ScalarsPowers},
       {"fieldOp", FieldOp}, {"batchInverse", BatchInverse}, {"glvDecompose", GlvDecompose}, {"batchAdd", BatchAdd}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
     napi_value f;
