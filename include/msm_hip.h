@@ -144,7 +144,7 @@ typedef struct msm_result {
   uint64_t max_bucket;  /* largest bucket population seen */
   uint64_t n_pairs_algo; /* pair additions the bucket sums NEED: sum over the non-empty buckets of (population - 1); the
                             basis of roofline figures (n_pairs is ~2.5 % above it at 2^26) */
-  int32_t tables;        /* != 0: the call ran on window tables (K tables of the point set, one set of buckets per window group) */
+  int32_t tables;        /* != 0: the call ran on window tables (tables 2^(c j) P of the point set, one set of buckets per window group) */
   int32_t reserved_;
 } msm_result;
 
@@ -206,16 +206,20 @@ int msm_get_points_ex(msm_ctx* ctx, uint64_t first, uint64_t count, int format, 
  * MSMs over them, scripts/msm-weierstrass.ts:19-35) the library can keep K tables instead of one: table k holds 2^(c k) P_i for
  * every point, so the digit of window k addresses a point that already carries the window's weight and all K windows share ONE
  * set of 2^(c-1) buckets -- K times fewer buckets to finish and reduce, no Horner step, same group element.  The reference has
- * no counterpart (its heap is 4 GiB); six tables of 2^26 BLS12-377 points are 103 GB of the 288 GB of HBM.
+ * no counterpart (its heap is 4 GiB).
+ * Shared tables: a call that runs as two window groups (BLS12-377 and the other Weierstrass curves from 2^21 points, the
+ * Edwards curve from 2^20) holds only T = ceil(K / 2) tables: both groups read tables 0 .. T - 1, each relative to its own first
+ * window, and the host supplies the weight 2^(c T) between the two sums.  Three tables of 2^26 BLS12-377 points under the
+ * six-window plan are 51.5 GB of the 288 GB of HBM, the plain rows included (six would be 103 GB).
  * msm_run builds them by itself on its first call over the WHOLE current point set with the default window (opts->c == 0)
- * when they fit the limit (default: 10 % of the device memory -- 28 GB: point sets of up to 2^24 BLS12-377 points; what they
- * buy shrinks from 6-10 % below 2^24 points to 1.5 % at 2^26, where they would take 96 GB), and uses them whenever the call's plan is the one they were built
+ * when they fit the limit (default: 20 % of the device memory -- 57.6 GB: point sets of up to 2^26 BLS12-377 points; what they
+ * buy shrinks from 6-10 % below 2^24 points to about 5 % at 2^26), and uses them whenever the call's plan is the one they were built
  * for; any other call -- another window size, a prefix or another range of the points, msm_window_sums without merged_sums, a bucket-range shard, a device-list context --
  * takes the plain path over table 0, which is always the plain row table.  msm_precompute builds them ahead of the first call
  * (also for an explicit opts->c); it is not an error if they do not fit: the plain path stays.  msm_set_points drops them.
  * Tables over a RANGE of the points (round 6): the rank of a points-split run works on its share [point_lo, point_lo + n) of
- * the resident points in every step; msm_precompute with opts->point_lo builds the tables of exactly that range (2^23 points x 7
- * tables = 15 GB, in a buffer of their own next to the plain rows), and msm_run / msm_window_sums (with msm_opts.merged_sums)
+ * the resident points in every step; msm_precompute with opts->point_lo builds the tables of exactly that range (2^23 points x 4
+ * shared tables for 7 windows = 8.6 GB, in a buffer of their own next to the plain rows), and msm_run / msm_window_sums (with msm_opts.merged_sums)
  * over that range run on them.  Without msm_precompute they are built when a call comes back for the same range a second
  * time in a row -- a caller that walks over several ranges on one GPU is spared a build per call.  The first call already runs
  * under the plan the tables will have (on the plain path: msm_result.tables = 0), so every call over one range reports the
@@ -224,7 +228,8 @@ int msm_get_points_ex(msm_ctx* ctx, uint64_t first, uint64_t count, int format, 
  * call over a range runs -- and msm_plan reports -- the plain plan.
  * msm_precompute with opts->c == 0 builds for the plan a default-plan call over those points picks on tables: such a call then
  * runs on them from the first time on.
- * msm_tables_info: window size and number of tables present (0, 0: none) and their bytes; msm_tables_range: the points they cover. */
+ * msm_tables_info: window size and window count K of the plan the tables present serve (0, 0: none) and the bytes they take --
+ * those of the T tables held; msm_tables_range: the points they cover. */
 int msm_precompute(msm_ctx* ctx, uint64_t n, const msm_opts* opts);
 int msm_tables_info(const msm_ctx* ctx, int32_t* c_out, int32_t* K_out, uint64_t* bytes_out);
 int msm_tables_range(const msm_ctx* ctx, uint64_t* point_lo_out, uint64_t* n_out);

@@ -816,7 +816,8 @@ class MsmContext:
         return self.tables_info()
 
     def tables_info(self) -> Tuple[int, int, int]:
-        """(window bits, number of tables, bytes) of the current point set's window tables; (0, 0, 0): none."""
+        """(window bits c, windows K of the plan they serve, bytes held) of the current point set's window tables; (0, 0, 0):
+        none.  The set holds K tables where a run on them is one window group, ceil(K / 2) shared ones where it is two."""
         c, k, b = C.c_int32(), C.c_int32(), C.c_uint64()
         self._check(self._lib.msm_tables_info(self._h, C.byref(c), C.byref(k), C.byref(b)))
         return c.value, k.value, b.value

@@ -42,7 +42,9 @@ int msm_ctx_create(msm_ctx** out, int curve, int device) {
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     // leave room for the resident points (144 B/point at 2^26 = 9.7 GB) and fragmentation
     ctx->ws_budget = (uint64_t)(free_b * 0.55);
-    ctx->tables_limit = (uint64_t)(total_b * 0.10);   // window tables of one point set (msm_set_tables_limit): up to 2^24 points
+    // window tables of one point set (msm_set_tables_limit): 57.6 GB of 288 -- up to 2^26 BLS12-377 points, whose three shared
+    // tables (two window groups over six windows) take 51.5 GB, the plain rows included
+    ctx->tables_limit = (uint64_t)(total_b * 0.20);
     ctx->ensure(ctx->errflag, 16);
     sort_kernel_attributes();
   } catch (const HipFail& f) {

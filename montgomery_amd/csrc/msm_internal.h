@@ -6,7 +6,7 @@
 //   msm_upload.hip    staged and pipelined host -> device transfers
 //   msm_pipeline.hip  window groups on two streams, point ranges, multi-device fan-out, call statistics
 //   msm_batch.hip     msm_run_batch, msm_run_batch_narrow: B MSMs over one point set, fused into shared window groups
-//   msm_tables.hip    window tables (K resident tables 2^(c k) P: one set of buckets for all windows)
+//   msm_tables.hip    window tables (resident tables 2^(c j) P: one set of buckets for all windows of a group)
 //   msm_abi.hip       the C ABI of include/msm_hip.h (contexts, points, msm_run, msm_window_sums, handles)
 //   msm_test_abi.hip  the operator-level test entries (msm_test_*)
 //   msm_gen.hip       the input generators (msm_generate_points, msm_generate_scalars)
@@ -220,18 +220,21 @@ struct msm_ctx {
   std::string err;
   int n_cu = 256;
 
-  // Window tables of a point set (msm_tables.hip): K tables of n rows each, table k = 2^(c k) P over the points [lo, lo + n)
-  // (K = 0: none).  Tables of the WHOLE set live in the set's row buffer, which grows to hold them (table 0 is the plain row
-  // table: in_rows); tables of a RANGE of the points -- the share of one rank of a points-split run -- in `buf`, with a copy of
-  // the range's rows as table 0.  K != 0 only while the buffer it names holds all K tables: a build describes them last.
+  // Window tables of a point set (msm_tables.hip): T tables of n rows each, table j = 2^(c j) P over the points [lo, lo + n),
+  // for a plan of K windows (K = 0: none).  T = K where a run on them is one window group; where it is several, every group
+  // reads the same T = ceil(K / groups) tables, relative to its own first window (msmi::window_groups_wanted).  Tables of the
+  // WHOLE set live in the set's row buffer, which grows to hold them (table 0 is the plain row table: in_rows); tables of a
+  // RANGE of the points -- the share of one rank of a points-split run -- in `buf`, with a copy of the range's rows as table 0.
+  // K, T != 0 only while the buffer they name holds all T tables: a build describes them last.
   struct WindowTables {
     int c = 0, K = 0;
+    int T = 0;   // tables held
     uint64_t lo = 0, n = 0;
     bool in_rows = false;
     msmi::DevBuf buf;   // (may outlive a description that is cleared: a range build of the same size reuses it)
     bool covers(uint64_t l, uint64_t m) const { return K && lo == l && n == m; }
     bool whole_set_pinned() const { return K && in_rows; }
-    void clear() { c = K = 0; lo = n = 0; in_rows = false; }
+    void clear() { T = 0; c = K = 0; lo = n = 0; in_rows = false; }
     void drop(msm_ctx* ctx) { clear(); ctx->release(buf); }   // (the description goes first)
   };
   // A resident point set (msm_pointset_*): its rows, one per point, and its window tables.  `sets` holds them all; the
@@ -262,7 +265,7 @@ struct msm_ctx {
   // for the same range (a rank of a sharded run does; a caller walking over the shards of one GPU does not and is spared a build per call)
   uint64_t cand_lo = 0, cand_n = 0;
   int cand_c = 0;
-  uint64_t tables_limit = 0;   // bytes the tables of one point set may take (msm_set_tables_limit; default: 10 % of the device)
+  uint64_t tables_limit = 0;   // bytes the tables of one point set may take (msm_set_tables_limit; default: 20 % of the device)
   std::vector<void*> allocs;        // device buffers handed out by msm_device_alloc
   // multi-device context (msm_ctx_create_multi): this context drives devices[0], one child context per further device
   std::vector<msm_ctx*> children;
@@ -403,6 +406,7 @@ struct Plan {
                        // group hands back ONE sum that already carries the windows' weights
   const uint32_t* tab_rows = nullptr;   // tables: first row of table 0; its tables are tab_n rows each and cover the points
   uint64_t tab_lo = 0, tab_n = 0;       //         [tab_lo, tab_lo + tab_n)
+  int tab_T = 0;                        //         tables held: a window group on them has at most that many windows
   bool merged = false; // a full MSM (msm_run): a window group may hand back sum_k 2^(c (k - k_first)) P_k in the slot of its
                        // first window instead of one P_k per slot (reduce_buckets); msm_window_sums never sets it
   int batch = 0;       // msm_run_batch (msm_batch.hip): the group's windows are those of `batch` elements, K each (window
@@ -433,6 +437,18 @@ int pick_window_narrow(bool te, uint64_t n, int bits, bool one_level = false);
 // it is that plan (msm_tables.hip)
 // note_range: the call is real (not msm_plan): a range of the points it asks for is remembered as the candidate for range tables
 int make_run_plan(msm_ctx* ctx, uint64_t n, const msm_opts* opts, bool placed, Plan& pl, bool& tables_wanted, bool note_range = false);
+
+// Window groups a call over n points and nwin windows runs as where nothing else (workspace budget, sort limits) asks for more.
+// The run (window_sums_once) and the build of window tables, which holds ceil(K / groups) of them, both ask here.
+// Measured on MI355X: two groups win 14 % at 2^23 / 2^24, 3 % at 2^22, nothing at 2^21 -- below that the fixed per-group
+// latencies (read-backs, bucket reduction depth) cost more than the overlap returns
+// (on window tables from 2^21: 5.87 -> 5.73 ms, Edwards 3.96 -> 3.72; the plain path at 2^21 prefers one group, 6.71 / 6.88; at
+// 2^20 one group wins on tables too, 3.24 / 3.33 -- round 5, tools/knob_sweep.sh MSM_GROUPS)
+// (round 6: the Edwards path on tables from 2^20 -- fifteen digit windows in one group leave the chip to one stream's ramps:
+// 2.19 - 2.24 -> 2.13 - 2.18 ms; BLS12-377 at 2^20 is level, 3.44 / 3.41, and stays on one group)
+inline int window_groups_wanted(bool te, uint64_t n, bool tables, int nwin) {
+  return (nwin >= 2 && (n >= (1ull << 22) || (tables && n >= (te ? 1ull << 20 : 1ull << 21)))) ? 2 : 1;
+}
 
 struct GroupStats {
   uint64_t n_pairs = 0;
@@ -525,6 +541,7 @@ struct TreeOut {
   const uint32_t* bucket_proj = nullptr;   // bucket sums from k_bucket_finish (projective / extended)
 };
 // kc: windows of the group as the tree sees them (1 on window tables); row_off: first row of the point table the payloads count from
+// (0 on window tables: every group reads them from table 0)
 void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl, int kc, uint64_t row_off, const SortOut& so,
                              GroupStats& st, TreeOut& to);
 // entries per window from which the sort leaves its one-level form for the radix split (measured: msm_sort.hip); callers that

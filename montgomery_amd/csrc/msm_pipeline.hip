@@ -10,7 +10,7 @@ namespace {
 
 // Partition sums P_k for windows [k_lo, k_hi) over the points [p_lo, p_lo + n) -> slot k - k_lo of h_partials_out
 // scalars: device pointer, n x 8 words.
-// k_base: the first window of the CALL (window tables carry weights relative to it: table j = 2^(c j) P serves window k_base + j)
+// On window tables every group reads table j = 2^(c j) P for its window k_lo + j: its sum is relative to its OWN first window.
 // the scalars of the points [p_lo, ...) of a call: 32-byte scalars are addressed; narrow ones (msm_run_narrow) keep the call's
 // array and count from `first`, which the digit kernel resolves (a range may start inside the dword a lane loads)
 const uint32_t* group_scalars(const uint32_t* d_scalars_all, uint64_t p_lo, Plan& pl) {
@@ -20,8 +20,7 @@ const uint32_t* group_scalars(const uint32_t* d_scalars_all, uint64_t p_lo, Plan
 }
 
 void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars_all, uint64_t p_lo, uint64_t n, const Plan& pl_in,
-                      int k_lo, int k_hi, int k_base, uint32_t* h_partials_out, GroupStats& st, uint64_t p_off = 0,
-                      GroupDigits* share = nullptr) {
+                      int k_lo, int k_hi, uint32_t* h_partials_out, GroupStats& st, uint64_t p_off = 0, GroupDigits* share = nullptr) {
   hipStream_t s = w.stream;
   Plan pl = pl_in;
   const uint32_t* d_scalars = group_scalars(d_scalars_all, p_lo, pl);   // scalar i of the call <-> resident point p_off + i
@@ -42,9 +41,10 @@ void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sca
   HIPCHK(hipEventRecord(w.ev[5], s));   // the tree starts here
   TreeOut to;
   if (pl.tables) {
-    // one merged window over the tables k_lo - k_base .. k_hi - k_base - 1: its sum carries the windows' weights (relative to the
-    // call's first window) already.  It goes into the group's first slot, identities into the others.
-    accumulate_window_group(ctx, w, pl, 1, (uint64_t)(k_lo - k_base) * pl.tab_n, so, st, to);
+    // one merged window over the tables 0 .. kc - 1: its sum carries the windows' weights relative to the group's first window
+    // already.  It goes into the group's first slot, identities into the others.
+    if (kc > pl.tab_T) throw MsmFail{MSM_ERR_INTERNAL, "a window group on window tables with more windows than tables"};
+    accumulate_window_group(ctx, w, pl, 1, 0, so, st, to);
     reduce_buckets(ctx, w, to.fin, to.fin_cap, to.off_fin, to.bucket_proj, pl.L, 1, h_partials_out, pl.merged, pl.c);
     for (int kk = 1; kk < kc; kk++) sum_set_identity(ctx, h_partials_out + (size_t)kk * ctx->sum_words());
   } else {
@@ -104,15 +104,12 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
     if (pl.tables) wpg = std::min(wpg, 16);
   }
   const int nwin = k_hi - k_lo;
-  // measured on MI355X: two groups win 14 % at 2^23 / 2^24, 3 % at 2^22, nothing at 2^21 -- below that the fixed
-  // per-group latencies (read-backs, bucket reduction depth) cost more than the overlap returns
-  // (on window tables from 2^21: 5.87 -> 5.73 ms, Edwards 3.96 -> 3.72; the plain path at 2^21 prefers one group, 6.71 / 6.88; at
-  // 2^20 one group wins on tables too, 3.24 / 3.33 -- round 5, tools/knob_sweep.sh MSM_GROUPS)
-  // (round 6: the Edwards path on tables from 2^20 -- fifteen digit windows in one group leave the chip to one stream's ramps:
-  // 2.19 - 2.24 -> 2.13 - 2.18 ms; BLS12-377 at 2^20 is level, 3.44 / 3.41, and stays on one group)
-  int want_groups = (nwin >= 2 && (n >= (1ull << 22) || (pl.tables && n >= (ctx->is_te() ? 1ull << 20 : 1ull << 21)))) ? 2 : 1;
+  int want_groups = window_groups_wanted(ctx->is_te(), n, pl.tables, nwin);
   MSM_KNOB(want_groups, "MSM_GROUPS", 1);
   wpg = std::max(1, std::min(wpg, (nwin + want_groups - 1) / want_groups));
+  // on window tables a group reads one table per window, from table 0: no group is wider than the tables the set holds
+  // (whatever the knob, the workspace budget or the window range of msm_window_sums say)
+  if (pl.tables) wpg = std::max(1, std::min(wpg, pl.tab_T));
   struct Group {
     int ka, kb;
     uint64_t p_lo, p_n;
@@ -196,7 +193,7 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
     // the exclusive timing of the roofline) -- walks its pairs in four short batches instead of one long one (round_geom)
     pg.lone = (groups.size() == 1 && (kb - ka == 1 || pl.tables)) || (opts && opts->serial);
     if (groups[gi].piece >= 0) pipe->wait_piece(groups[gi].piece, ctx->ws[slot].stream);
-    run_window_group(ctx, ctx->ws[slot], d_scal, groups[gi].p_lo, groups[gi].p_n, pg, ka, kb, k_lo, part.data(), sts[slot], p_off,
+    run_window_group(ctx, ctx->ws[slot], d_scal, groups[gi].p_lo, groups[gi].p_n, pg, ka, kb, part.data(), sts[slot], p_off,
                      share.valid ? &share : nullptr);
     if (split_points || pl.tables) split_part[gi] = part;
     else memcpy(&words[(size_t)(ka - k_lo) * pw], part.data(), part.size() * 4);
@@ -205,12 +202,13 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
   float upload_ms = -1;
   if (pipe) upload_ms = pipe->finish();   // joins the staging threads; their last copy is done
   if (pl.tables) {
-    // every group's first slot holds the sum of its windows WITH their weights: the call's sum is their plain sum, kept in
-    // slot 0 (identities elsewhere: the caller's Horner step over such slots would return the same element)
-    std::vector<const uint32_t*> firsts;
-    for (const auto& part : split_part)
-      if (!part.empty()) firsts.push_back(part.data());
-    sum_slots(ctx, firsts, words.data());
+    // every group's first slot holds the sum G_g of its windows with their weights relative to the group's first window, and
+    // the groups start wpg windows apart: the call's sum is sum_g 2^(c wpg g) G_g, a Horner step over the first slots under
+    // the window c wpg.  It is kept in slot 0 (identities elsewhere: the caller's Horner step over such slots would return
+    // the same element).
+    std::vector<uint32_t> firsts(groups.size() * (size_t)pw);
+    for (size_t gi = 0; gi < groups.size(); gi++) memcpy(&firsts[gi * pw], split_part[gi].data(), (size_t)pw * 4);
+    sums_horner(ctx, firsts.data(), (int)groups.size(), pl.c * wpg, words.data());
     for (int k = k_lo + 1; k < k_hi; k++) sum_set_identity(ctx, &words[(size_t)(k - k_lo) * pw]);
   } else if (split_points) {
     // P_k = sum over the ranges of the points (groups of one or several windows each); an all-zero partial (Z = 0) is the

@@ -1,7 +1,11 @@
-// Window tables: K resident tables of the point set, table k = 2^(c k) P, so that the K windows of an MSM share one set of
-// buckets (k_table_next, msm_kernels.h).  The reference has no counterpart (4 GiB of wasm memory); it is what 288 GB of HBM are
-// for: six tables of 2^26 points are 103 GB.  Built once per point set and plan -- by the first default-plan msm_run over the
-// whole set, or ahead of it by msm_precompute / msm_reserve -- the way k_points_from_wire precomputes beta x once per set.
+// Window tables: T resident tables of the point set, table j = 2^(c j) P, so that the windows of a window group of an MSM share
+// one set of buckets (k_table_next, msm_kernels.h).  A call that runs as one group holds a table per window, T = K.  From the
+// size at which it runs as two (window_groups_wanted, msm_internal.h) both groups read the SAME T = ceil(K / 2) tables, each
+// relative to its own first window, and the host supplies the weight 2^(c T) between them (window_sums_once): half the memory
+// and half the build.  The reference has no counterpart (4 GiB of wasm memory); it is what 288 GB of HBM are for: the three
+// tables of 2^26 points under the six-window plan are 51.5 GB, the plain rows (table 0) included.  Built once per point set and
+// plan -- by the first default-plan msm_run over the whole set, or ahead of it by msm_precompute / msm_reserve -- the way
+// k_points_from_wire precomputes beta x once per set.
 #include "msm_internal.h"
 
 using namespace msm;
@@ -9,8 +13,13 @@ using namespace msmi;
 
 namespace msmi {
 
-static uint64_t table_bytes(const msm_ctx* ctx, uint64_t n, int K) {
-  return (uint64_t)K * std::max<uint64_t>(n, 1) * ctx->row_words() * 4;
+// tables a set of n points holds under a plan of K windows: one per window of the widest group a run on them will use
+static int tables_held(const msm_ctx* ctx, uint64_t n, int K) {
+  const int groups = window_groups_wanted(ctx->is_te(), n, /*tables=*/true, K);
+  return (K + groups - 1) / groups;
+}
+static uint64_t table_bytes(const msm_ctx* ctx, uint64_t n, int T) {
+  return (uint64_t)T * std::max<uint64_t>(n, 1) * ctx->row_words() * 4;
 }
 
 // Tables of the WHOLE point set go into its row buffer (table 0 = the plain rows), those of a range [lo, lo + n) into a buffer
@@ -21,7 +30,8 @@ static void build_tables(msm_ctx* ctx, const Plan& pl, uint64_t lo, uint64_t n) 
   msm_ctx::WindowTables& t = ps.tab;
   const bool whole = lo == 0 && n == ps.n;
   const uint64_t row_words = ctx->row_words();
-  const uint64_t bytes = table_bytes(ctx, n, pl.K);
+  const int T = tables_held(ctx, n, pl.K);
+  const uint64_t bytes = table_bytes(ctx, n, T);
   HIPCHK(hipStreamSynchronize(ctx->stream));
   auto ensure_or_retry = [&](DevBuf& b) {
     try {
@@ -55,7 +65,7 @@ static void build_tables(msm_ctx* ctx, const Plan& pl, uint64_t lo, uint64_t n) 
     HIPCHK(hipMemcpyAsync(rows, (const uint32_t*)ps.rows.p + lo * row_words, n * row_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
   }
   const uint32_t grid = (uint32_t)((n + 255) / 256);
-  for (int k = 1; k < pl.K; k++) {
+  for (int k = 1; k < T; k++) {
     uint32_t* out = rows + (uint64_t)k * n * row_words;
     const uint32_t* in = rows + (uint64_t)(k - 1) * n * row_words;
     if (ctx->is_te()) hipLaunchKernelGGL(te::k_te_table_next, dim3(grid), dim3(256), 0, ctx->stream, out, in, n, pl.c);
@@ -68,6 +78,7 @@ static void build_tables(msm_ctx* ctx, const Plan& pl, uint64_t lo, uint64_t n) 
   t.lo = lo;
   t.n = n;
   t.in_rows = whole;
+  t.T = T;
 }
 
 // can this call run on window tables at all?
@@ -82,9 +93,11 @@ static bool whole_set(const msm_ctx* ctx, uint64_t n, const msm_opts* opts) { re
 static bool whole_set_tables_stay(const msm_ctx* ctx, uint64_t n, const msm_opts* opts) {
   return ctx->pts().tab.whole_set_pinned() && !whole_set(ctx, n, opts);
 }
-// K tables of n points fit the limit, and their entries (one per table row and GLV half) the 31 bits of the sort's payloads
+// the tables of n points under a plan of K windows fit the limit, and the entries of a group on them (one per table row and GLV
+// half) the 31 bits of the sort's payloads
 static bool tables_fit(const msm_ctx* ctx, uint64_t n, int K) {
-  return table_bytes(ctx, n, K) <= ctx->tables_limit && (uint64_t)K * (ctx->is_te() ? n : 2 * n) < (1ull << 31);
+  const int T = tables_held(ctx, n, K);
+  return table_bytes(ctx, n, T) <= ctx->tables_limit && (uint64_t)T * (ctx->is_te() ? n : 2 * n) < (1ull << 31);
 }
 // tables of plan pl could be built for this call (where tables of the whole set do not stay)
 static bool buildable(const msm_ctx* ctx, uint64_t n, const msm_opts* opts, const Plan& pl) {
@@ -157,6 +170,7 @@ bool use_window_tables(msm_ctx* ctx, uint64_t n, const msm_opts* opts, Plan& pl)
   pl.tab_rows = ps.table_rows();
   pl.tab_lo = ps.tab.lo;
   pl.tab_n = ps.tab.n;
+  pl.tab_T = ps.tab.T;
   return true;
 }
 
@@ -183,7 +197,7 @@ int msm_tables_info(const msm_ctx* ctx, int32_t* c_out, int32_t* K_out, uint64_t
   const msm_ctx::WindowTables& t = ctx->pts().tab;
   if (c_out) *c_out = t.c;
   if (K_out) *K_out = t.K;
-  if (bytes_out) *bytes_out = t.K ? table_bytes(ctx, t.n, t.K) : 0;
+  if (bytes_out) *bytes_out = t.K ? table_bytes(ctx, t.n, t.T) : 0;
   return MSM_OK;
 }
 
