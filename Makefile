@@ -43,7 +43,12 @@ HOSTTEST := tests/csrc/libfield_host.so
 HOSTTEST_CYCLES := tests/csrc/libfield_host_cycles.so
 HOSTTEST_LINCOMB := tests/csrc/liblincomb_host.so
 HOSTTEST_SCALARS := tests/csrc/libscalars_host.so
-hosttest: $(HOSTTEST) $(HOSTTEST_CYCLES) $(HOSTTEST_LINCOMB) $(HOSTTEST_SCALARS)
+HOSTTEST_SCHEDULE := tests/csrc/libschedule_host.so
+# (every shim whose source the tests tree holds: a tests tree from before the schedule shim still builds the others)
+hosttest: $(HOSTTEST) $(HOSTTEST_CYCLES) $(HOSTTEST_LINCOMB) $(HOSTTEST_SCALARS) $(if $(wildcard tests/csrc/schedule_host.hip),$(HOSTTEST_SCHEDULE))
+# the window-group schedule of msm_plan.hip (group_schedule: no HIP call) over a bare context: tests/test_group_schedule.py
+$(HOSTTEST_SCHEDULE): tests/csrc/schedule_host.hip $(CSRC)/msm_plan.hip $(HHDRS)
+	$(HIPCC) -O2 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/schedule_host.hip $(CSRC)/msm_plan.hip -o $(HOSTTEST_SCHEDULE)
 # the lane bodies of scalar_vec.h on the scalar fields of all seven curves: tests/test_scalars_host.py
 $(HOSTTEST_SCALARS): tests/csrc/scalars_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h include/msm_hip.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/scalars_host.hip -o $(HOSTTEST_SCALARS)

@@ -301,30 +301,14 @@ static int run_impl(msm_ctx* ctx, const void* scalars, const void* const* placed
   Plan pl;
   bool tables_wanted = false;   // window tables (msm_tables.hip): the plan is then the one tables want
   if (make_run_plan(ctx, n, opts, placed != nullptr, pl, tables_wanted, /*note_range=*/true)) return fail(ctx, MSM_ERR_ARG, "%s: bad window size", who);
-  pl.merged = true;
-  memset(out, 0, sizeof(*out));
-  out->c = pl.c;
-  out->K = pl.K;
-  if (n == 0) {
-    identity_to_result(ctx, out);
-    return MSM_OK;
-  }
+  if (!call_begin(ctx, pl, n, out)) return MSM_OK;
   try {
     HIPCHK(hipSetDevice(ctx->device));
     std::vector<uint32_t> words;
     // window tables (msm_tables.hip): built here on the first default-plan call over the whole point set
     pl.tables = tables_wanted && use_window_tables(ctx, n, opts, pl);
     any_window_sums(ctx, scalars, n, on_device, opts, 0, pl.K, pl, words, out, placed);
-    HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
-    // (a run on tables leaves the whole sum, weights included, in slot 0 and identities in the others: the Horner step over all
-    // K slots returns it unchanged, and is what a call that had to leave the tables -- ranges of the points -- needs)
-    sums_finish(ctx, words.data(), pl.K, pl.c, out);
-    HIPCHK(hipEventRecord(ctx->ev[11], ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    float ms;
-    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[10], ctx->ev[11]));
-    out->phase_ms[MSM_T_FINAL] = ms;
-    out->phase_ms[MSM_T_TOTAL] += ms;
+    call_finish(ctx, words, pl, out);   // (the upload time the window sums measured stays)
   } MSM_CATCH_ALL(ctx)
   return MSM_OK;
 }

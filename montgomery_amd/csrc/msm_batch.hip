@@ -26,7 +26,7 @@ int pick_window_batch(bool te, uint64_t n, uint32_t B, int glv_max_bits) {
 
 namespace {
 
-constexpr int GROUP_WINDOWS = 128;   // windows of one group under the one-level sort (window_sums_once)
+constexpr int GROUP_WINDOWS = 128;   // windows of one group under the one-level sort (group_schedule)
 
 // where a batch may fuse at all: B >= 2, one device, fewer entries per window than the radix split takes
 bool fuse_region(const msm_ctx* ctx, uint64_t n, uint32_t B) {
@@ -169,8 +169,7 @@ extern "C" int msm_run_batch(msm_ctx* ctx, const void* const* scalars, uint32_t 
   if (!ctx || !out || !scalars || B == 0) return fail(ctx, MSM_ERR_ARG, "msm_run_batch: null argument or empty batch");
   for (uint32_t b = 0; b < B && n; b++)
     if (!scalars[b]) return fail(ctx, MSM_ERR_ARG, "msm_run_batch: no scalars for element %u", b);
-  if (opts && (opts->k_lo || opts->k_hi || opts->bucket_shards > 1 || opts->merged_sums || opts->by_window))
-    return fail(ctx, MSM_ERR_ARG, "msm_run_batch: window shards, bucket shards, merged sums and by_window are not batch options");
+  if (int rc = refuse_shard_opts(ctx, opts, "msm_run_batch", "a batch")) return rc;
   if (int rc = check_points(ctx, n, opts, MSM_ERR_NO_POINTS, "msm_run_batch")) return rc;
   try {
     if (n) {

@@ -83,8 +83,7 @@ int indexed_args_ok(msm_ctx* ctx, const void* scalars, const uint32_t* indices, 
                     msm_result* out, const char* who) {
   if (!ctx || !out || ((!scalars || !indices) && m)) return fail(ctx, MSM_ERR_ARG, "%s: null argument", who);
   if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "%s: indexed calls run on single-device contexts only", who);
-  if (opts && (opts->point_lo || opts->k_lo || opts->k_hi || opts->bucket_shards > 1 || opts->merged_sums || opts->by_window))
-    return fail(ctx, MSM_ERR_ARG, "%s: point_lo, window shards, bucket shards, merged sums and by_window are not options of an indexed call", who);
+  if (int rc = refuse_shard_opts(ctx, opts, who, "an indexed", /*no_point_lo=*/true)) return rc;
   if (m >= (1ull << 30)) return fail(ctx, MSM_ERR_ARG, "%s: m must be < 2^30", who);
   if (on_device && m && (uintptr_t)indices % 4) return fail(ctx, MSM_ERR_ARG, "%s: device indices must be aligned to 4 bytes", who);
   return MSM_OK;
@@ -133,15 +132,7 @@ void stage_indexed(msm_ctx* ctx, const void* scalars, const uint32_t* indices, u
 void run_indexed(msm_ctx* ctx, const void* d_scal, uint64_t m, const msm_opts* opts, const Plan& pl, float up_ms, msm_result* out) {
   std::vector<uint32_t> words;
   window_sums_impl(ctx, d_scal, m, 1, opts, 0, pl.K, pl, words, out, 0);
-  HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
-  sums_finish(ctx, words.data(), pl.K, pl.c, out);
-  HIPCHK(hipEventRecord(ctx->ev[11], ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  float ms;
-  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[10], ctx->ev[11]));
-  out->phase_ms[MSM_T_FINAL] = ms;
-  out->phase_ms[MSM_T_UPLOAD] = up_ms;   // indices and host scalars into HBM, and the index check
-  out->phase_ms[MSM_T_TOTAL] += ms + up_ms;
+  call_finish(ctx, words, pl, out, up_ms);   // (up_ms: indices and host scalars into HBM, and the index check)
 }
 
 }  // namespace
@@ -167,14 +158,7 @@ int msm_run_indexed(msm_ctx* ctx, const void* scalars, const uint32_t* indices, 
   if (int rc = has_points(ctx, who)) return rc;
   Plan pl;
   if (make_plan(ctx, m, opts, pl)) return fail(ctx, MSM_ERR_ARG, "%s: bad window size", who);
-  pl.merged = true;
-  memset(out, 0, sizeof(*out));
-  out->c = pl.c;
-  out->K = pl.K;
-  if (m == 0) {
-    identity_to_result(ctx, out);
-    return MSM_OK;
-  }
+  if (!call_begin(ctx, pl, m, out)) return MSM_OK;
   try {
     HIPCHK(hipSetDevice(ctx->device));
     const char* d_scal = nullptr;
@@ -195,25 +179,15 @@ int msm_run_indexed_narrow(msm_ctx* ctx, const void* scalars, const uint32_t* in
   if (int rc = narrow_scalars_ok(ctx, scalars, m, on_device, width_bytes, who)) return rc;
   if (int rc = has_points(ctx, who)) return rc;
   if (make_plan(ctx, m, opts, pl, false, nar.fmt.bits)) return fail(ctx, MSM_ERR_ARG, "%s: bad window size", who);
-  pl.merged = true;
-  memset(out, 0, sizeof(*out));
-  out->c = pl.c;
-  out->K = pl.K;
-  if (m == 0) {
-    identity_to_result(ctx, out);
-    return MSM_OK;
-  }
+  if (!call_begin(ctx, pl, m, out)) return MSM_OK;
   try {
     HIPCHK(hipSetDevice(ctx->device));
     const char* dev = nullptr;
     float up_ms = 0;
     stage_indexed(ctx, scalars, indices, m, on_device, (size_t)m * width_bytes, who, &dev, &pl.idx, &up_ms);
-    // as msm_run_narrow: the pipeline gets the array rounded down to the alignment of a lane's load, and where the first scalar sits
-    const uintptr_t align = (uintptr_t)std::max(4, std::min(width_bytes, 16));
-    const uintptr_t off = (uintptr_t)dev % align;
-    nar.first = off / width_bytes;
+    dev = narrow_lane_base(dev, width_bytes, nar);   // as msm_run_narrow
     pl.nar = nar;
-    run_indexed(ctx, dev - off, m, opts, pl, up_ms, out);
+    run_indexed(ctx, dev, m, opts, pl, up_ms, out);
   } MSM_CATCH_ALL(ctx)
   return MSM_OK;
 }

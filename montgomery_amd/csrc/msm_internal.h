@@ -1,10 +1,12 @@
 // Host-side internals of libmsm_hip.so shared by its translation units (HOST_TUS in the Makefile):
-//   msm_plan.hip      window size, plan, launch geometry, workspace budget model, error helpers
+//   msm_plan.hip      window size, plan, launch geometry, workspace budget model, the schedule of a call's window groups
+//                     (group_schedule: pure arithmetic, tested on the CPU by tests/test_group_schedule.py), error helpers
 //   msm_sort.hip      digits + counting sort of one window group (driver of sort_kernels.h)
 //   msm_tree.hip      accumulation tree of one window group (driver of k_batch_add / k_te_add) + k_bucket_finish
 //   msm_reduce.hip    bucket reduction, and the host tail over window sums (sum, Horner, to-affine, wire form, combine)
 //   msm_upload.hip    staged and pipelined host -> device transfers
-//   msm_pipeline.hip  window groups on two streams, point ranges, multi-device fan-out, call statistics
+//   msm_pipeline.hip  runs a schedule: window groups on two streams, their sums added back; multi-device fan-out, call statistics,
+//                     and the begin / finish every full-MSM entry point shares (call_begin, call_finish)
 //   msm_batch.hip     msm_run_batch, msm_run_batch_narrow: B MSMs over one point set, fused into shared window groups
 //   msm_tables.hip    window tables (resident tables 2^(c j) P: one set of buckets for all windows of a group)
 //   msm_abi.hip       the C ABI of include/msm_hip.h (contexts, points, msm_run, msm_window_sums, handles)
@@ -380,6 +382,9 @@ int fail_hip(msm_ctx* ctx, const HipFail& f);
 inline uint64_t point_lo(const msm_opts* opts) { return opts ? opts->point_lo : 0; }
 // MSM_OK if the points of the call are resident (and there are some, unless empty_ok); otherwise fails it with `code`
 int check_points(msm_ctx* ctx, uint64_t n, const msm_opts* opts, int code, const char* who, bool empty_ok = true);
+// MSM_ERR_ARG if `opts` asks for a shard of the call -- window shards, bucket shards, merged sums, by_window; no_point_lo: a range of
+// the points too -- which the entry point `who`, `kind` of call ("a narrow", "an indexed", "a batch"), does not run
+int refuse_shard_opts(msm_ctx* ctx, const msm_opts* opts, const char* who, const char* kind, bool no_point_lo = false);
 
 // every extern "C" entry point ends its try block with this: no C++ exception crosses the C ABI
 #define MSM_CATCH_ALL(ctx)                                                                                  \
@@ -439,7 +444,7 @@ int pick_window_narrow(bool te, uint64_t n, int bits, bool one_level = false);
 int make_run_plan(msm_ctx* ctx, uint64_t n, const msm_opts* opts, bool placed, Plan& pl, bool& tables_wanted, bool note_range = false);
 
 // Window groups a call over n points and nwin windows runs as where nothing else (workspace budget, sort limits) asks for more.
-// The run (window_sums_once) and the build of window tables, which holds ceil(K / groups) of them, both ask here.
+// The schedule (group_schedule) and the build of window tables, which holds ceil(K / groups) of them, both ask here.
 // Measured on MI355X: two groups win 14 % at 2^23 / 2^24, 3 % at 2^22, nothing at 2^21 -- below that the fixed per-group
 // latencies (read-backs, bucket reduction depth) cost more than the overlap returns
 // (on window tables from 2^21: 5.87 -> 5.73 ms, Edwards 3.96 -> 3.72; the plain path at 2^21 prefers one group, 6.71 / 6.88; at
@@ -449,6 +454,11 @@ int make_run_plan(msm_ctx* ctx, uint64_t n, const msm_opts* opts, bool placed, P
 inline int window_groups_wanted(bool te, uint64_t n, bool tables, int nwin) {
   return (nwin >= 2 && (n >= (1ull << 22) || (tables && n >= (te ? 1ull << 20 : 1ull << 21)))) ? 2 : 1;
 }
+// entries per window from which the sort leaves its one-level form for the radix split; callers that depend on the one-level
+// sort -- 128 windows in a group, a fused batch -- ask here
+// measured (round 5, with one ds_add per key as the ranking: tools/sortpath_sweep.sh): the split wins from 2^21 entries per
+// window -- 2^20 points: sort 0.31 against 0.36 ms, 2^21: 0.51 / 0.85; 2^19: level, below: the one-level sort (2^16 0.11 / 0.14)
+inline uint64_t one_level_entry_limit(bool te) { return te ? 1ull << 22 : 1ull << 21; }
 
 struct GroupStats {
   uint64_t n_pairs = 0;
@@ -478,6 +488,29 @@ void release_workspaces(msm_ctx* ctx);   // drops every per-call buffer of both 
 long double window_bytes(const msm_ctx* ctx, uint64_t n, const Plan& pl);
 int windows_per_group(const msm_ctx* ctx, uint64_t n, const Plan& pl);
 uint64_t point_pieces(const msm_ctx* ctx, uint64_t n, const Plan& pl);
+
+// How one call -- windows [k_lo, k_hi) over n points -- is cut into window groups and ranges of the points: every (window, point)
+// pair lies in exactly one group.  The runner (window_sums_once) takes the groups in order, two at a time on the two workspaces.
+struct GroupSchedule {
+  struct Group {
+    int ka, kb;            // windows [ka, kb)
+    uint64_t p_lo, p_n;    // points [p_lo, p_lo + p_n) of the call
+    int piece;             // pipelined upload: the piece whose arrival the group waits for (-1: the scalars are in place)
+  };
+  std::vector<Group> groups;
+  int wpg = 1;               // windows per group as capped; the Horner step of a run on tables uses c * wpg
+  bool tables = false;       // the plan's window tables survive the cut
+  bool split_points = false; // several groups contribute to one window: the sums of its ranges are added on the host
+  bool piped = false;        // the pipelined upload survives (it does not when the workspace forces its own ranges)
+  bool share_digits = false; // one launch of the digit kernel serves both groups (GroupDigits)
+  bool lone = false;         // every launch has the chip to itself (Plan.lone)
+};
+// The schedule of a call: plain arithmetic over the plan, the shape of the call and the context's n_cu and ws_budget -- no HIP
+// call, no allocation, no write to the context.  p_off: first resident point of the call; piece_end: the piece ends of host
+// scalars that would cross PCIe behind the computation (pipelined_piece_ends; empty: the scalars are staged); serial:
+// msm_opts.serial.
+GroupSchedule group_schedule(const msm_ctx* ctx, uint64_t n, uint64_t p_off, int k_lo, int k_hi, const Plan& pl,
+                             const std::vector<uint64_t>& piece_end, bool serial);
 
 // ---- msm_reduce.hip ---------------------------------------------------------------------------------------------
 void words_to_fe6(msm_host::Fe6& r, const uint32_t* w, int nw = 12);
@@ -544,9 +577,6 @@ struct TreeOut {
 // (0 on window tables: every group reads them from table 0)
 void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl, int kc, uint64_t row_off, const SortOut& so,
                              GroupStats& st, TreeOut& to);
-// entries per window from which the sort leaves its one-level form for the radix split (measured: msm_sort.hip); callers that
-// depend on the one-level sort -- 128 windows in a group, a fused batch -- ask here
-uint64_t one_level_entry_limit(bool te);
 void sort_kernel_attributes();   // dynamic-LDS limits of the sort kernels (once per process and device)
 
 // ---- msm_tables.hip ---------------------------------------------------------------------------------------------
@@ -561,7 +591,7 @@ int stage_scalars(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, 
 // The same staged transfer running BEHIND the call that consumes it: a host scalar buffer of a big MSM crosses PCIe in the
 // background while the MSM already runs over the ranges of the points ("pieces") whose scalars have arrived -- 2 GB take
 // ~45 ms at the rate of the link, a 2^26 MSM ~150 ms, and the sort of a window needs every digit of its range, so the
-// unit of overlap is a range of the points, not a chunk (window_sums_once picks growing ranges: the first one is small so the
+// unit of overlap is a range of the points, not a chunk (pipelined_piece_ends picks growing ranges: the first one is small so the
 // GPU starts early, the last one is half the input so most of the work runs at full-size efficiency).
 // Chunks go out in address order over the staging threads as in upload_staged; when a thread has queued its last chunk of
 // piece q it records piece_ev[q][t] on its copy stream, and wait_piece(q, stream) makes `stream` wait for all of them.
@@ -698,6 +728,14 @@ void add_call_stats(msm_result& tot, const msm_result& r, bool side_by_side = fa
 // `who`: the narrow entry point (it alone declares a range)
 constexpr uint32_t ERR_SCALAR_GE_Q = 4u, ERR_FOLD_DIGIT = 8u;   // (bits 1 and 2: the point loaders; NARROW_ERR_RANGE: narrow_kernels.h)
 void check_scalar_flags(msm_ctx* ctx, const Plan& pl, const char* who);
+// The two ends of every entry point that returns one MSM (msm_run, msm_run_narrow, msm_run_indexed, msm_run_indexed_narrow).
+// call_begin: the plan is that of a full MSM (Plan.merged), the result is zeroed and told c and K; an empty call is answered
+// with the identity.  Returns whether anything is left to run.
+bool call_begin(const msm_ctx* ctx, Plan& pl, uint64_t n, msm_result* out);
+// call_finish: the window sums `words` (K slots) -> the affine result, timed as MSM_T_FINAL and added to MSM_T_TOTAL.
+// staging_ms >= 0: the entry staged its own input in front of the window sums -- that interval is its MSM_T_UPLOAD and part of its
+// total; otherwise the upload time the window sums measured stays.
+void call_finish(msm_ctx* ctx, const std::vector<uint32_t>& words, const Plan& pl, msm_result* out, float staging_ms = -1);
 
 // runs f(child) for every child of a multi-device context on the fan-out threads, and f(ctx) on the calling thread;
 // returns the first error code
@@ -732,6 +770,9 @@ int narrow_format(msm_ctx* ctx, int32_t width_bytes, int32_t bits, int32_t is_si
 // the rest of the argument checks of a narrow entry: n < 2^32 (the digit kernels count points in 32 bits) and device scalars
 // aligned to their width (16 bytes for the 16- and 32-byte forms, which lanes load as uint4)
 int narrow_scalars_ok(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, int32_t width_bytes, const char* who);
+// The array the pipeline gets for the device scalars `dev` of a narrow call: rounded down to the alignment of a lane's load, with
+// nar.first = where the first scalar sits in it (only the 1- and 2-byte formats can start inside a lane's dword)
+const char* narrow_lane_base(const char* dev, int32_t width_bytes, Plan::Narrow& nar);
 
 // ---- msm_indexed.hip --------------------------------------------------------------------------------------------
 // Queues on `s` the pass that rewrites the n_slots payloads the sort left for round 1 -- (entry << 1) | sign, entry counting the

@@ -23,8 +23,7 @@ int narrow_format(msm_ctx* ctx, int32_t width_bytes, int32_t bits, int32_t is_si
     return fail(ctx, MSM_ERR_ARG, "%s: bits = %d is beyond what %d-byte %s scalars hold (%d; 128 at most)", who, bits, w,
                 is_signed ? "signed" : "unsigned", full);
   if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "%s: narrow scalars run on single-device contexts only", who);
-  if (opts && (opts->k_lo || opts->k_hi || opts->bucket_shards > 1 || opts->merged_sums || opts->by_window))
-    return fail(ctx, MSM_ERR_ARG, "%s: window shards, bucket shards, merged sums and by_window are not options of a narrow call", who);
+  if (int rc = refuse_shard_opts(ctx, opts, who, "a narrow")) return rc;
   out = Plan::Narrow();
   out.width = w;
   out.fmt.bits = bits ? bits : full;
@@ -41,7 +40,31 @@ int narrow_scalars_ok(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devi
   return MSM_OK;
 }
 
+const char* narrow_lane_base(const char* dev, int32_t width_bytes, Plan::Narrow& nar) {
+  const uintptr_t align = (uintptr_t)std::max(4, std::min(width_bytes, 16));
+  const uintptr_t off = (uintptr_t)dev % align;
+  nar.first = off / width_bytes;
+  return dev - off;
+}
+
 }  // namespace msmi
+
+namespace {
+
+// Host scalars are uploaded whole before the run (2 - 32 x smaller than the wide form), timed as up_ms; device scalars stay where
+// they are.  Returns the device array.
+const char* stage_narrow(msm_ctx* ctx, const void* scalars, size_t bytes, int on_device, float* up_ms) {
+  if (on_device) return (const char*)scalars;
+  HIPCHK(hipEventRecord(ctx->ev[11], ctx->stream));
+  ctx->ensure(ctx->scal, bytes + 16);
+  upload_staged(ctx, ctx->scal.p, scalars, bytes);
+  HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipEventElapsedTime(up_ms, ctx->ev[11], ctx->ev[10]));
+  return (const char*)ctx->scal.p;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -63,45 +86,16 @@ int msm_run_narrow(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device,
   if (int rc = check_points(ctx, n, opts, MSM_ERR_NO_POINTS, "msm_run_narrow")) return rc;
   if (int rc = narrow_scalars_ok(ctx, scalars, n, on_device, width_bytes, "msm_run_narrow")) return rc;
   if (make_plan(ctx, n, opts, pl, false, nar.fmt.bits)) return fail(ctx, MSM_ERR_ARG, "msm_run_narrow: bad window size");
-  pl.merged = true;
-  memset(out, 0, sizeof(*out));
-  out->c = pl.c;
-  out->K = pl.K;
-  if (n == 0) {
-    identity_to_result(ctx, out);
-    return MSM_OK;
-  }
+  if (!call_begin(ctx, pl, n, out)) return MSM_OK;
   try {
     HIPCHK(hipSetDevice(ctx->device));
-    // Host scalars are uploaded whole before the run (2 - 32 x smaller than the wide form); device scalars stay where they are.
-    // Either way the pipeline gets the array rounded down to the alignment of a lane's load, and where the first scalar sits in it.
-    const size_t bytes = (size_t)n * width_bytes;
-    const char* dev = (const char*)scalars;
     float up_ms = 0;
-    if (!on_device) {
-      HIPCHK(hipEventRecord(ctx->ev[11], ctx->stream));
-      ctx->ensure(ctx->scal, bytes + 16);
-      upload_staged(ctx, ctx->scal.p, scalars, bytes);
-      HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      HIPCHK(hipEventElapsedTime(&up_ms, ctx->ev[11], ctx->ev[10]));
-      dev = (const char*)ctx->scal.p;
-    }
-    const uintptr_t align = (uintptr_t)std::max(4, std::min(width_bytes, 16));
-    const uintptr_t off = (uintptr_t)dev % align;
-    nar.first = off / width_bytes;   // (only the 1- and 2-byte formats can start inside a lane's dword)
+    const char* dev = stage_narrow(ctx, scalars, (size_t)n * width_bytes, on_device, &up_ms);
+    dev = narrow_lane_base(dev, width_bytes, nar);
     pl.nar = nar;
     std::vector<uint32_t> words;
-    window_sums_impl(ctx, dev - off, n, 1, opts, 0, pl.K, pl, words, out, point_lo(opts));
-    HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
-    sums_finish(ctx, words.data(), pl.K, pl.c, out);
-    HIPCHK(hipEventRecord(ctx->ev[11], ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    float ms;
-    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[10], ctx->ev[11]));
-    out->phase_ms[MSM_T_FINAL] = ms;
-    out->phase_ms[MSM_T_UPLOAD] = up_ms;
-    out->phase_ms[MSM_T_TOTAL] += ms + up_ms;
+    window_sums_impl(ctx, dev, n, 1, opts, 0, pl.K, pl, words, out, point_lo(opts));
+    call_finish(ctx, words, pl, out, up_ms);
   } MSM_CATCH_ALL(ctx)
   return MSM_OK;
 }

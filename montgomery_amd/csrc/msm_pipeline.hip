@@ -1,5 +1,6 @@
 // One MSM as window groups on the context's two streams, ranges of the points where a window does not fit or the scalars
-// arrive over PCIe, and the fan-out over the devices of a multi-device context.
+// arrive over PCIe -- cut as group_schedule (msm_plan.hip) says --, the fan-out over the devices of a multi-device context, and
+// the begin and finish the full-MSM entry points share.
 // (reference: the SPMD threads of src/msm-batched-affine.ts:285-340; windows are independent until :312-333)
 #include "msm_internal.h"
 
@@ -54,30 +55,28 @@ void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sca
   add_group_times(w, st);
 }
 
-// windows [k_lo, k_hi) over the resident points [p_off, p_off + n); scalars[i] belongs to point p_off + i
-int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, const msm_opts* opts, int k_lo, int k_hi,
-                     const Plan& pl_in, std::vector<uint32_t>& words, msm_result* stats, uint64_t p_off) {
-  Plan pl = pl_in;   // (a call that turns out to run over ranges of the points leaves the window tables: see below)
+// ---- one call = prepare (scalars, budget, schedule), run (the schedule's groups on the two workspaces), combine (their sums) ----
+
+// A call of window_sums_once between its steps: where its scalars are and how it is cut
+struct CallSetup {
   const uint32_t* d_scal = nullptr;
+  std::vector<uint64_t> piece_end;   // pipelined upload: point index where piece q ends (the last = n); empty: staged
+  GroupSchedule sch;
+};
+
+// Host scalars of a big call cross PCIe BEHIND the computation, range by range of the points (PieceUpload); everything
+// else is staged before the window groups start.  Records ev[8] .. ev[9] around the staging.
+CallSetup prepare_call(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, bool serial, int k_lo, int k_hi, const Plan& pl,
+                       uint64_t p_off) {
+  CallSetup cs;
   HIPCHK(hipEventRecord(ctx->ev[8], ctx->stream));
-  // Host scalars of a big call cross PCIe BEHIND the computation, range by range of the points (PieceUpload); everything
-  // else is staged before the window groups start.
-  std::vector<uint64_t> piece_end;   // pipelined upload: point index where piece q ends (the last = n)
   if (!on_device && pipelines_host_scalars(n)) {
-    piece_end = pipelined_piece_ends(n);
+    cs.piece_end = pipelined_piece_ends(n);
     ctx->ensure(ctx->scal, n * 32);   // before the workspace budget is taken from what the device has free
+  } else {
+    stage_scalars(ctx, scalars, n, on_device, &cs.d_scal);
   }
-  std::unique_ptr<PieceUpload> pipe;
-  if (piece_end.empty()) stage_scalars(ctx, scalars, n, on_device, &d_scal);
   HIPCHK(hipEventRecord(ctx->ev[9], ctx->stream));
-  GroupStats st;
-  const int pw = ctx->sum_words();
-  words.assign((size_t)(k_hi - k_lo) * pw, 0);
-  // window groups: as large as the workspace budget allows; for big inputs two of them on two streams.  The streams
-  // run in step (both sort, both gather, ...): what the second one buys is two tree kernels sharing the chip -- forward
-  // (memory-heavy) and backward (issue-heavy) sweeps of different waves mix, the small last rounds fill each other's
-  // idle CUs -- not a sort hidden under an accumulation (a sort started under the other group's tree finds no free
-  // registers on any CU and takes four times as long: profiles/r04_experiments.txt item 1)
   if (ctx->ws_limit) {
     ctx->ws_budget = ctx->ws_limit;
   } else if (n >= (1ull << 22)) {
@@ -90,144 +89,108 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
       for (DevBuf* b : w.all) held += b->cap;
     ctx->ws_budget = (uint64_t)((free_b + held) * 0.85L);
   }
-  int wpg = std::min(windows_per_group(ctx, n, pl), 128);
-  // the radix-split and three-pass sorts describe their windows in a WinSplit of 16 entries (sort_kernels.h): a group that
-  // may take one of them holds at most 16 windows (msmProjective with a small explicit window: K = 17 .. 29 at c = 15 .. 9)
-  // (the one-level sort of small inputs -- a window's counters fit the LDS and fewer than 2^22 entries per window -- has no
-  // such table: Ed-on-BLS12-377 at 2^20 keeps its 18 windows in one group)
-  {
-    const uint64_t entries = ctx->is_te() ? n : 2 * n;
-    const bool fits_lds = ((size_t)pl.L * 4 <= 128 * 1024);
-    if (pl.c - 1 > (int)RX_FINE_BITS && (!fits_lds || entries >= one_level_entry_limit(ctx->is_te()))) wpg = std::min(wpg, 16);
-    // (on window tables the merged window of a group may take the bin split whatever a single digit window would have taken,
-    // and the digit kernel describes the fine bits of at most 16 windows: pack_fine_bits)
-    if (pl.tables) wpg = std::min(wpg, 16);
+  cs.sch = group_schedule(ctx, n, p_off, k_lo, k_hi, pl, cs.piece_end, serial);
+  if (cs.sch.piped) {
+    cs.d_scal = (const uint32_t*)ctx->scal.p;
+  } else if (!cs.piece_end.empty()) {
+    // the workspace forces its own ranges: plain staged upload first
+    cs.piece_end.clear();
+    stage_scalars(ctx, scalars, n, on_device, &cs.d_scal);
   }
-  const int nwin = k_hi - k_lo;
-  int want_groups = window_groups_wanted(ctx->is_te(), n, pl.tables, nwin);
-  MSM_KNOB(want_groups, "MSM_GROUPS", 1);
-  wpg = std::max(1, std::min(wpg, (nwin + want_groups - 1) / want_groups));
-  // on window tables a group reads one table per window, from table 0: no group is wider than the tables the set holds
-  // (whatever the knob, the workspace budget or the window range of msm_window_sums say)
-  if (pl.tables) wpg = std::max(1, std::min(wpg, pl.tab_T));
-  struct Group {
-    int ka, kb;
-    uint64_t p_lo, p_n;
-    int piece;   // pipelined upload: the piece whose arrival the group waits for (-1: the scalars are in place)
-  };
-  std::vector<Group> groups;
-  // A single window (the 8-GPU shard) has no second window group to hide its sort and tails under: split it by
-  // points instead -- two half-size sub-MSMs of the same window on the two streams, their sums added on the host.
-  // The same split serves inputs whose single window no longer fits the workspace budget (2^29 points: 165 GB per window
-  // at c = 22 next to a 137 GB row table): every window runs over as many ranges of the points as it takes, one after the
-  // other on the two streams, and the sums of its ranges are added on the host.
-  uint64_t pieces = 1;
-  if (nwin == 1 && want_groups == 1 && !ctx->is_te() && n >= (1ull << 24) && !MSM_KNOB_SET("MSM_GROUPS")) pieces = 2;
-  pieces = std::max(pieces, point_pieces(ctx, n, pl));
-  if (!piece_end.empty() && point_pieces(ctx, n, pl) > 1) {
-    // the workspace forces its own ranges: plain staged upload first (rare: 2^29 points, or a tight msm_set_workspace_limit)
-    piece_end.clear();
-    stage_scalars(ctx, scalars, n, on_device, &d_scal);
-  }
-  if (!piece_end.empty()) {
-    // pipelined host scalars: per arriving range of the points the usual window groups (two above 2^22 points), in order
-    ctx->ensure(ctx->scal, n * 32);
-    d_scal = (const uint32_t*)ctx->scal.p;
-    uint64_t lo = 0;
-    for (size_t q = 0; q < piece_end.size(); q++) {
-      const uint64_t cnt = piece_end[q] - lo;
-      const int g = (nwin >= 2 && cnt >= (1ull << 22)) ? 2 : 1;
-      const int per = std::max(1, std::min(wpg, (nwin + g - 1) / g));
-      for (int k = k_lo; k < k_hi; k += per) groups.push_back({k, std::min(k_hi, k + per), lo, cnt, (int)q});
-      lo = piece_end[q];
-    }
-  } else if (pieces > 1) {
-    for (int k = k_lo; k < k_hi; k++)
-      for (uint64_t q = 0; q < pieces; q++) {
-        const uint64_t lo = n * q / pieces, hi = n * (q + 1) / pieces;
-        groups.push_back({k, k + 1, lo, hi - lo, -1});
-      }
-  } else {
-    for (int k = k_lo; k < k_hi; k += wpg) groups.push_back({k, std::min(k_hi, k + wpg), 0, n, -1});
-  }
-  // does more than one group contribute to a window?  Then the sums of its ranges are added on the host below.
-  bool split_points = false;
-  for (const Group& g : groups) split_points |= g.p_n != n;
-  // Window tables address row k * tab_n + i of the points they cover from the entry index alone, which counts from the GROUP's
-  // first point and in units of the group's own n: a group over another range of the points (a tight workspace limit, the retry
-  // after an out-of-memory error, host scalars arriving range by range) would read other points' rows.  Such a call runs the
-  // plain path under the same window -- table 0 is the plain row table -- and hands back one sum per window slot, which the
-  // caller's Horner step takes like the one weighted sum of a run on tables.
-  if (pl.tables && (split_points || n != pl.tab_n || p_off != pl.tab_lo)) pl.tables = false;
-  std::vector<std::vector<uint32_t>> split_part((split_points || pl.tables) ? groups.size() : 0);
+  return cs;
+}
+
+// Runs the groups of cs.sch under `pl` (the call's plan, its tables as the schedule left them): part[gi] = the sums of group gi,
+// one slot per window of the group; st = the statistics of all groups.  Returns the wall time of a pipelined upload, or -1.
+float run_groups(msm_ctx* ctx, const CallSetup& cs, const void* scalars, uint64_t n, const Plan& pl, bool serial, uint64_t p_off,
+                 std::vector<std::vector<uint32_t>>& part, GroupStats& st) {
+  const std::vector<GroupSchedule::Group>& groups = cs.sch.groups;
+  const int pw = ctx->sum_words();
   HIPCHK(hipMemsetAsync(ctx->errflag.p, 0, 4, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));   // staged scalars are in place before the group streams start
-  if (!piece_end.empty()) {
+  std::unique_ptr<PieceUpload> pipe;
+  if (cs.sch.piped) {
     std::vector<size_t> ends;
-    for (uint64_t e : piece_end) ends.push_back((size_t)e * 32);
+    for (uint64_t e : cs.piece_end) ends.push_back((size_t)e * 32);
     pipe.reset(new PieceUpload(ctx, ctx->scal.p, scalars, n * 32, ends));
   }
-  // The two window groups of a call slice the same scalars: one launch of the digit kernel (on the first workspace's stream)
-  // writes the digits and slice histograms of both -- one GLV decomposition per scalar instead of two (2^26: the two
-  // concurrent launches took 2.3 ms, the one takes 1.5) -- and each group then takes its part (GroupDigits, msm_sort.hip).
   GroupDigits share;
-  if (groups.size() == 2 && !ctx->is_te() && groups[0].piece < 0 && groups[1].piece < 0 &&
-      groups[0].p_lo == groups[1].p_lo && groups[0].p_n == groups[1].p_n && groups[0].kb == groups[1].ka &&
-      groups[1].kb - groups[0].ka <= 16) {   // (the digit kernel describes up to 16 windows: WinSplit)
+  if (cs.sch.share_digits) {
     share.produce = true;
     share.ready = ctx->ev_dig[1];
     SortOut none;
     GroupStats gs;
     HIPCHK(hipEventRecord(ctx->ev_dig[0], ctx->ws[0].stream));
     Plan pd = pl;
-    const uint32_t* d_grp = group_scalars(d_scal, groups[0].p_lo, pd);
+    const uint32_t* d_grp = group_scalars(cs.d_scal, groups[0].p_lo, pd);
     sort_window_group(ctx, ctx->ws[0], d_grp, groups[0].p_n, pd, groups[0].ka, groups[1].kb, gs, none, &share);
     share.produce = false;
   }
+  Plan pg = pl;
+  pg.lone = cs.sch.lone;
   GroupStats sts[msm_ctx::N_WS];
-  run_on_workspaces(ctx, (int)groups.size(), opts && opts->serial, [&](int slot, int gi) {
-    const int ka = groups[gi].ka, kb = groups[gi].kb;
-    std::vector<uint32_t> part((size_t)(kb - ka) * pw);
-    Plan pg = pl;
-    // a launch that has the chip to itself -- the one-window shard, or every launch of a serialised call (msm_opts.serial,
-    // the exclusive timing of the roofline) -- walks its pairs in four short batches instead of one long one (round_geom)
-    pg.lone = (groups.size() == 1 && (kb - ka == 1 || pl.tables)) || (opts && opts->serial);
-    if (groups[gi].piece >= 0) pipe->wait_piece(groups[gi].piece, ctx->ws[slot].stream);
-    run_window_group(ctx, ctx->ws[slot], d_scal, groups[gi].p_lo, groups[gi].p_n, pg, ka, kb, part.data(), sts[slot], p_off,
+  part.assign(groups.size(), {});
+  run_on_workspaces(ctx, (int)groups.size(), serial, [&](int slot, int gi) {
+    const GroupSchedule::Group& g = groups[gi];
+    part[gi].resize((size_t)(g.kb - g.ka) * pw);
+    if (g.piece >= 0) pipe->wait_piece(g.piece, ctx->ws[slot].stream);
+    run_window_group(ctx, ctx->ws[slot], cs.d_scal, g.p_lo, g.p_n, pg, g.ka, g.kb, part[gi].data(), sts[slot], p_off,
                      share.valid ? &share : nullptr);
-    if (split_points || pl.tables) split_part[gi] = part;
-    else memcpy(&words[(size_t)(ka - k_lo) * pw], part.data(), part.size() * 4);
   });
   check_scalar_flags(ctx, pl, "msm_run_narrow");
   float upload_ms = -1;
   if (pipe) upload_ms = pipe->finish();   // joins the staging threads; their last copy is done
-  if (pl.tables) {
-    // every group's first slot holds the sum G_g of its windows with their weights relative to the group's first window, and
-    // the groups start wpg windows apart: the call's sum is sum_g 2^(c wpg g) G_g, a Horner step over the first slots under
-    // the window c wpg.  It is kept in slot 0 (identities elsewhere: the caller's Horner step over such slots would return
-    // the same element).
-    std::vector<uint32_t> firsts(groups.size() * (size_t)pw);
-    for (size_t gi = 0; gi < groups.size(); gi++) memcpy(&firsts[gi * pw], split_part[gi].data(), (size_t)pw * 4);
-    sums_horner(ctx, firsts.data(), (int)groups.size(), pl.c * wpg, words.data());
-    for (int k = k_lo + 1; k < k_hi; k++) sum_set_identity(ctx, &words[(size_t)(k - k_lo) * pw]);
-  } else if (split_points) {
-    // P_k = sum over the ranges of the points (groups of one or several windows each); an all-zero partial (Z = 0) is the
-    // identity.  (Plan.merged: a group then carries sum_kk 2^(c kk) P_kk in its first slot and identities in the others --
-    // slot-wise sums of such groups are still a valid set of slots for the Horner step.)
-    for (int k = k_lo; k < k_hi; k++) {
-      std::vector<const uint32_t*> ranges;
-      for (size_t gi = 0; gi < groups.size(); gi++)
-        if (groups[gi].ka <= k && k < groups[gi].kb && !split_part[gi].empty())
-          ranges.push_back(split_part[gi].data() + (size_t)(k - groups[gi].ka) * pw);
-      sum_slots(ctx, ranges, &words[(size_t)(k - k_lo) * pw]);
-    }
-  }
   if (share.valid) {
     float ms;
     HIPCHK(hipEventElapsedTime(&ms, ctx->ev_dig[0], ctx->ev_dig[1]));
     st.ms_digits += ms;
   }
   for (const GroupStats& g : sts) st += g;
+  return upload_ms;
+}
+
+// words[k - k_lo] = the sum of window k from the sums of the schedule's groups (part[gi]: one slot per window of group gi)
+void combine_group_sums(const msm_ctx* ctx, const GroupSchedule& sch, int c, int k_lo, int k_hi,
+                        const std::vector<std::vector<uint32_t>>& part, std::vector<uint32_t>& words) {
+  const std::vector<GroupSchedule::Group>& groups = sch.groups;
+  const int pw = ctx->sum_words();
+  words.assign((size_t)(k_hi - k_lo) * pw, 0);
+  if (sch.tables) {
+    // every group's first slot holds the sum G_g of its windows with their weights relative to the group's first window, and
+    // the groups start wpg windows apart: the call's sum is sum_g 2^(c wpg g) G_g, a Horner step over the first slots under
+    // the window c wpg.  It is kept in slot 0 (identities elsewhere: the caller's Horner step over such slots would return
+    // the same element).
+    std::vector<uint32_t> firsts(groups.size() * (size_t)pw);
+    for (size_t gi = 0; gi < groups.size(); gi++) memcpy(&firsts[gi * pw], part[gi].data(), (size_t)pw * 4);
+    sums_horner(ctx, firsts.data(), (int)groups.size(), c * sch.wpg, words.data());
+    for (int k = k_lo + 1; k < k_hi; k++) sum_set_identity(ctx, &words[(size_t)(k - k_lo) * pw]);
+  } else if (sch.split_points) {
+    // P_k = sum over the ranges of the points (groups of one or several windows each); an all-zero partial (Z = 0) is the
+    // identity.  (Plan.merged: a group then carries sum_kk 2^(c kk) P_kk in its first slot and identities in the others --
+    // slot-wise sums of such groups are still a valid set of slots for the Horner step.)
+    for (int k = k_lo; k < k_hi; k++) {
+      std::vector<const uint32_t*> ranges;
+      for (size_t gi = 0; gi < groups.size(); gi++)
+        if (groups[gi].ka <= k && k < groups[gi].kb && !part[gi].empty())
+          ranges.push_back(part[gi].data() + (size_t)(k - groups[gi].ka) * pw);
+      sum_slots(ctx, ranges, &words[(size_t)(k - k_lo) * pw]);
+    }
+  } else {
+    for (size_t gi = 0; gi < groups.size(); gi++) memcpy(&words[(size_t)(groups[gi].ka - k_lo) * pw], part[gi].data(), part[gi].size() * 4);
+  }
+}
+
+// windows [k_lo, k_hi) over the resident points [p_off, p_off + n); scalars[i] belongs to point p_off + i
+int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, const msm_opts* opts, int k_lo, int k_hi,
+                     const Plan& pl_in, std::vector<uint32_t>& words, msm_result* stats, uint64_t p_off) {
+  const bool serial = opts && opts->serial;
+  const CallSetup cs = prepare_call(ctx, scalars, n, on_device, serial, k_lo, k_hi, pl_in, p_off);
+  Plan pl = pl_in;   // (a call that turns out to run over ranges of the points leaves the window tables: group_schedule)
+  pl.tables = cs.sch.tables;
+  std::vector<std::vector<uint32_t>> part;
+  GroupStats st;
+  const float upload_ms = run_groups(ctx, cs, scalars, n, pl, serial, p_off, part, st);
+  combine_group_sums(ctx, cs.sch, pl.c, k_lo, k_hi, part, words);
   HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (stats) {
@@ -309,9 +272,35 @@ void check_scalar_flags(msm_ctx* ctx, const Plan& pl, const char* who) {
   if (flags & ERR_FOLD_DIGIT) throw MsmFail{MSM_ERR_INTERNAL, "a digit of the folded top window exceeds its bucket range (GLV bound violated)"};
 }
 
+bool call_begin(const msm_ctx* ctx, Plan& pl, uint64_t n, msm_result* out) {
+  pl.merged = true;
+  memset(out, 0, sizeof(*out));
+  out->c = pl.c;
+  out->K = pl.K;
+  if (n == 0) identity_to_result(ctx, out);
+  return n != 0;
+}
+
+void call_finish(msm_ctx* ctx, const std::vector<uint32_t>& words, const Plan& pl, msm_result* out, float staging_ms) {
+  HIPCHK(hipEventRecord(ctx->ev[10], ctx->stream));
+  // (a run on tables leaves the whole sum, weights included, in slot 0 and identities in the others: the Horner step over all
+  // K slots returns it unchanged, and is what a call that had to leave the tables -- ranges of the points -- needs)
+  sums_finish(ctx, words.data(), pl.K, pl.c, out);
+  HIPCHK(hipEventRecord(ctx->ev[11], ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float ms;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[10], ctx->ev[11]));
+  out->phase_ms[MSM_T_FINAL] = ms;
+  if (staging_ms >= 0) {
+    out->phase_ms[MSM_T_UPLOAD] = staging_ms;
+    ms += staging_ms;
+  }
+  out->phase_ms[MSM_T_TOTAL] += ms;
+}
+
 // Workspace buffers only grow, and a call with another shape (window size, curve of the point set, sort path) leaves buffers
 // behind that the next shape does not use: if the device runs out of memory the workspaces are dropped and the call runs
-// once more from a clean slate, where the budget model of window_sums_once holds again.
+// once more from a clean slate, where the budget model of group_schedule holds again.
 int window_sums_impl(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, const msm_opts* opts, int k_lo, int k_hi,
                      const Plan& pl, std::vector<uint32_t>& words, msm_result* stats, uint64_t p_off) {
   // The budget model is an estimate and other contexts may take memory while the call runs, so one clean-slate retry is not a

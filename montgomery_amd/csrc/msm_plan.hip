@@ -1,5 +1,5 @@
-// Plan of one MSM: window size, number of windows, launch geometry of the tree rounds, workspace budget model; and the
-// error helpers every ABI entry ends in.  (reference: windowSize table src/msm-common.ts:25-41, K = ceil((b + 1) / c)
+// Plan of one MSM: window size, number of windows, launch geometry of the tree rounds, workspace budget model, the schedule of
+// a call's window groups; and the error helpers every ABI entry ends in.  (reference: windowSize table src/msm-common.ts:25-41, K = ceil((b + 1) / c)
 // src/msm-batched-affine.ts:90)
 #include "msm_internal.h"
 
@@ -23,6 +23,14 @@ int check_points(msm_ctx* ctx, uint64_t n, const msm_opts* opts, int code, const
   if (lo + n <= resident && (n || empty_ok)) return MSM_OK;
   return fail(ctx, code, "%s: points [%llu, +%llu) but %llu resident points", who, (unsigned long long)lo, (unsigned long long)n,
               (unsigned long long)resident);
+}
+
+int refuse_shard_opts(msm_ctx* ctx, const msm_opts* opts, const char* who, const char* kind, bool no_point_lo) {
+  if (!opts) return MSM_OK;
+  const bool shard = opts->k_lo || opts->k_hi || opts->bucket_shards > 1 || opts->merged_sums || opts->by_window;
+  if (!shard && !(no_point_lo && opts->point_lo)) return MSM_OK;
+  return fail(ctx, MSM_ERR_ARG, "%s: %swindow shards, bucket shards, merged sums and by_window are not options of %s call", who,
+              no_point_lo ? "point_lo, " : "", kind);
 }
 
 static const char* base_name(const char* p) {
@@ -246,6 +254,86 @@ uint64_t point_pieces(const msm_ctx* ctx, uint64_t n, const Plan& pl) {
   uint64_t pieces = 1;
   while (pieces < 256 && n / pieces > 4096 && window_bytes(ctx, (n + pieces - 1) / pieces, pl) > room) pieces++;
   return pieces;
+}
+
+GroupSchedule group_schedule(const msm_ctx* ctx, uint64_t n, uint64_t p_off, int k_lo, int k_hi, const Plan& pl,
+                             const std::vector<uint64_t>& piece_end, bool serial) {
+  GroupSchedule sc;
+  const bool te = ctx->is_te();
+  // window groups: as large as the workspace budget allows; for big inputs two of them on two streams.  The streams
+  // run in step (both sort, both gather, ...): what the second one buys is two tree kernels sharing the chip -- forward
+  // (memory-heavy) and backward (issue-heavy) sweeps of different waves mix, the small last rounds fill each other's
+  // idle CUs -- not a sort hidden under an accumulation (a sort started under the other group's tree finds no free
+  // registers on any CU and takes four times as long: profiles/r04_experiments.txt item 1)
+  int wpg = std::min(windows_per_group(ctx, n, pl), 128);
+  // the radix-split and three-pass sorts describe their windows in a WinSplit of 16 entries (sort_kernels.h): a group that
+  // may take one of them holds at most 16 windows (msmProjective with a small explicit window: K = 17 .. 29 at c = 15 .. 9)
+  // (the one-level sort of small inputs -- a window's counters fit the LDS and fewer than 2^22 entries per window -- has no
+  // such table: Ed-on-BLS12-377 at 2^20 keeps its 18 windows in one group)
+  {
+    const uint64_t entries = te ? n : 2 * n;
+    const bool fits_lds = ((size_t)pl.L * 4 <= 128 * 1024);
+    if (pl.c - 1 > (int)RX_FINE_BITS && (!fits_lds || entries >= one_level_entry_limit(te))) wpg = std::min(wpg, 16);
+    // (on window tables the merged window of a group may take the bin split whatever a single digit window would have taken,
+    // and the digit kernel describes the fine bits of at most 16 windows: pack_fine_bits)
+    if (pl.tables) wpg = std::min(wpg, 16);
+  }
+  const int nwin = k_hi - k_lo;
+  int want_groups = window_groups_wanted(te, n, pl.tables, nwin);
+  MSM_KNOB(want_groups, "MSM_GROUPS", 1);
+  wpg = std::max(1, std::min(wpg, (nwin + want_groups - 1) / want_groups));
+  // on window tables a group reads one table per window, from table 0: no group is wider than the tables the set holds
+  // (whatever the knob, the workspace budget or the window range of msm_window_sums say)
+  if (pl.tables) wpg = std::max(1, std::min(wpg, pl.tab_T));
+  sc.wpg = wpg;
+  // A single window (the 8-GPU shard) has no second window group to hide its sort and tails under: split it by
+  // points instead -- two half-size sub-MSMs of the same window on the two streams, their sums added on the host.
+  // The same split serves inputs whose single window no longer fits the workspace budget (2^29 points: 165 GB per window
+  // at c = 22 next to a 137 GB row table): every window runs over as many ranges of the points as it takes, one after the
+  // other on the two streams, and the sums of its ranges are added on the host.
+  uint64_t pieces = 1;
+  if (nwin == 1 && want_groups == 1 && !te && n >= (1ull << 24) && !MSM_KNOB_SET("MSM_GROUPS")) pieces = 2;
+  pieces = std::max(pieces, point_pieces(ctx, n, pl));
+  // the workspace forces its own ranges: plain staged upload first (rare: 2^29 points, or a tight msm_set_workspace_limit)
+  sc.piped = !piece_end.empty() && point_pieces(ctx, n, pl) == 1;
+  std::vector<GroupSchedule::Group>& groups = sc.groups;
+  if (sc.piped) {
+    // pipelined host scalars: per arriving range of the points the usual window groups (two above 2^22 points), in order
+    uint64_t lo = 0;
+    for (size_t q = 0; q < piece_end.size(); q++) {
+      const uint64_t cnt = piece_end[q] - lo;
+      const int g = (nwin >= 2 && cnt >= (1ull << 22)) ? 2 : 1;
+      const int per = std::max(1, std::min(wpg, (nwin + g - 1) / g));
+      for (int k = k_lo; k < k_hi; k += per) groups.push_back({k, std::min(k_hi, k + per), lo, cnt, (int)q});
+      lo = piece_end[q];
+    }
+  } else if (pieces > 1) {
+    for (int k = k_lo; k < k_hi; k++)
+      for (uint64_t q = 0; q < pieces; q++) {
+        const uint64_t lo = n * q / pieces, hi = n * (q + 1) / pieces;
+        groups.push_back({k, k + 1, lo, hi - lo, -1});
+      }
+  } else {
+    for (int k = k_lo; k < k_hi; k += wpg) groups.push_back({k, std::min(k_hi, k + wpg), 0, n, -1});
+  }
+  // does more than one group contribute to a window?  Then the sums of its ranges are added on the host (combine_group_sums).
+  for (const GroupSchedule::Group& g : groups) sc.split_points |= g.p_n != n;
+  // Window tables address row k * tab_n + i of the points they cover from the entry index alone, which counts from the GROUP's
+  // first point and in units of the group's own n: a group over another range of the points (a tight workspace limit, the retry
+  // after an out-of-memory error, host scalars arriving range by range) would read other points' rows.  Such a call runs the
+  // plain path under the same window -- table 0 is the plain row table -- and hands back one sum per window slot, which the
+  // caller's Horner step takes like the one weighted sum of a run on tables.
+  sc.tables = pl.tables && !(sc.split_points || n != pl.tab_n || p_off != pl.tab_lo);
+  // The two window groups of a call slice the same scalars: one launch of the digit kernel (on the first workspace's stream)
+  // writes the digits and slice histograms of both -- one GLV decomposition per scalar instead of two (2^26: the two
+  // concurrent launches took 2.3 ms, the one takes 1.5) -- and each group then takes its part (GroupDigits, msm_sort.hip).
+  sc.share_digits = groups.size() == 2 && !te && groups[0].piece < 0 && groups[1].piece < 0 &&
+                    groups[0].p_lo == groups[1].p_lo && groups[0].p_n == groups[1].p_n && groups[0].kb == groups[1].ka &&
+                    groups[1].kb - groups[0].ka <= 16;   // (the digit kernel describes up to 16 windows: WinSplit)
+  // a launch that has the chip to itself -- the one-window shard, or every launch of a serialised call (msm_opts.serial,
+  // the exclusive timing of the roofline) -- walks its pairs in four short batches instead of one long one (round_geom)
+  sc.lone = (groups.size() == 1 && (groups[0].kb - groups[0].ka == 1 || sc.tables)) || serial;
+  return sc;
 }
 
 }  // namespace msmi

@@ -8,10 +8,6 @@ using namespace msmi;
 
 namespace msmi {
 
-// measured (round 5, with one ds_add per key as the ranking: tools/sortpath_sweep.sh): the split wins from 2^21 entries per
-// window -- 2^20 points: sort 0.31 against 0.36 ms, 2^21: 0.51 / 0.85; 2^19: level, below: the one-level sort (2^16 0.11 / 0.14)
-uint64_t one_level_entry_limit(bool te) { return te ? 1ull << 22 : 1ull << 21; }
-
 void sort_kernel_attributes() {
   // dynamic LDS above the 64 KB a launch gets by default
   HIPCHK(hipFuncSetAttribute((const void*)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));

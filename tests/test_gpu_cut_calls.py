@@ -1,6 +1,7 @@
-"""Narrow, indexed, batched and wide MSMs through a CUT call: msm_set_workspace_limit makes window_sums_once run a call as several
-window groups (a later group starts at k_lo != 0) or, tighter, every window over three ranges of the entries whose sums are added
-on the host; run_fused sizes the groups of a batch from the same limit.  `-m gpu`.
+"""Narrow, indexed, batched and wide MSMs through a CUT call: msm_set_workspace_limit makes group_schedule (msm_plan.hip) cut a
+call into several window groups (a later group starts at k_lo != 0) or, tighter, every window into three ranges of the entries whose
+sums window_sums_once adds on the host; run_fused sizes the groups of a batch from the same limit.  `-m gpu`.  (The schedules
+themselves, without a GPU: tests/test_group_schedule.py.)
 
 Every case has three assertions.  (1) The result is (sum_i value_i a_i mod q) G from the discrete logs a_i msm_generate_points
 returns -- the check: a cut and an uncut call share their kernels.  (2) It equals the uncut call of the same entry point bit for
@@ -99,7 +100,7 @@ def _limits(te, m, c, K):
 
 
 def _cut_starts(m):
-    return [m // 3, 2 * m // 3]     # n q / pieces of window_sums_once, pieces = 3
+    return [m // 3, 2 * m // 3]     # n q / pieces of group_schedule, pieces = 3
 
 
 # ---------------------------------------------------------------------------------------------- references
