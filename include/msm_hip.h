@@ -516,6 +516,21 @@ int msm_test_batch_add_mode(msm_ctx* ctx, const uint8_t* g, const uint8_t* h, ui
  *           additions and doublings; 2^c0 = buckets per chunk of its linear part.  SURVEY section 8(f)-3. */
 int msm_test_bucket_reduce(msm_ctx* ctx, const uint8_t* buckets, int32_t K, uint32_t L, int mode, int c0, uint8_t* partials_out,
                            float* ms_out);
+/* The end of every MSM on buckets of the caller, all curves: the bucket finish (k_finish_hist / k_finish_perm, k_bucket_finish or
+ * k_te_bucket_finish) as the accumulation tree runs it, then the bucket reduction of the pipeline on its output.
+ *   pool   n_pool affine wire points (x || y, one coordinate width each); (0, 0) is the identity on the Weierstrass curves,
+ *          (0, 1) on the Edwards curve
+ *   off    K L + 1 ascending offsets, off[0] = 0; elems: off[K L] pool indices.  Bucket l (1-based) of window k holds the
+ *          elements elems[off[k L + l - 1]] .. elems[off[k L + l] - 1]; L a power of two
+ *   merged, stride   as a full MSM asks for them: merged != 0 lets the call hand back sum_k 2^(stride k) P_k in slot 0 and the
+ *          identity in the other slots (the contract is that sum_k 2^(stride k) slot_k is that sum); stride = bits a window
+ *          advances by, 0 = log2(L) + 1; stride = log2(L) is the plan with a folded top window
+ *   tc     buckets per lane of the reduction: 0 = the library's rule, else a power of two in 2 .. 32
+ * Writes K x 144 bytes (X || Y || Z; Z = 0: the identity of a Weierstrass curve), without merged P_k = sum_l l B_(k,l).
+ * perm_out (may be NULL): K L words, the order in which the finish took the buckets -- descending by element count, counts
+ * from 63 up alike -- or 0, 1, 2, ... where it did not order them (fewer than 4096 buckets, or no element at all). */
+int msm_test_bucket_sums(msm_ctx* ctx, const uint8_t* pool, uint64_t n_pool, const uint32_t* off, const uint32_t* elems, int32_t K,
+                         uint32_t L, int merged, int stride, uint32_t tc, uint8_t* sums_out, uint32_t* perm_out);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,7 @@ EXPORTS = (
     "msm_run_indexed", "msm_run_indexed_narrow",
     "msm_points_lincomb", "msm_pointset_size",
     "msm_device_download", "msm_scalars_lincomb", "msm_scalars_mul", "msm_scalars_inner", "msm_scalars_powers",
+    "msm_test_bucket_sums",
 )
 
 
@@ -206,6 +207,10 @@ def load() -> C.CDLL:
     lib.msm_test_curve_op.argtypes = [vp, C.c_int, vp, vp, vp, u64]
     lib.msm_test_batch_add_mode.argtypes = [vp, vp, vp, vp, u64, C.c_int, C.c_uint32]
     lib.msm_test_bucket_reduce.argtypes = [vp, vp, i32, C.c_uint32, C.c_int, C.c_int, vp, C.POINTER(C.c_float)]
+    # the bucket finish and reduction on crafted buckets: a new test symbol under ABI 8
+    if not hasattr(lib, "msm_test_bucket_sums"):
+        raise ImportError(f"{LIB_PATH} predates msm_test_bucket_sums: rebuild it (`make`)")
+    lib.msm_test_bucket_sums.argtypes = [vp, vp, u64, vp, vp, i32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, vp, vp]
     for name in EXPORTS:
         if name not in ("msm_ctx_destroy", "msm_last_error", "msm_abi_version", "msm_abi_struct_bytes"):
             getattr(lib, name).restype = C.c_int

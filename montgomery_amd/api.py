@@ -939,6 +939,25 @@ class MsmContext:
         self._check(self._lib.msm_test_bucket_reduce(self._h, buf, K, L, mode, c0, out, C.byref(ms)))
         return bytes(out), float(ms.value)
 
+    def test_bucket_sums(self, pool: BytesLike, off, elems, K: int, L: int, merged: bool = False, stride: int = 0, tc: int = 0,
+                         want_perm: bool = False):
+        """The bucket finish and the bucket reduction of the pipeline on crafted buckets (msm_test_bucket_sums, msm_hip.h): `pool`
+        = affine wire points, bucket l of window k = the pool points elems[off[k L + l - 1] : off[k L + l]] (uint32 arrays).
+        Returns K x 144 bytes (X || Y || Z per slot); with want_perm also the K L bucket indices in the order the finish took them."""
+        import numpy as np
+
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        elems = np.ascontiguousarray(elems, dtype=np.uint32)
+        pb = 2 * self.coord_bytes
+        if len(pool) == 0 or len(pool) % pb or len(off) != K * L + 1 or len(elems) != int(off[-1]):
+            raise MsmError(_lib.MSM_ERR_ARG, f"expected whole {pb}-byte pool points, {K * L + 1} offsets and off[-1] elements")
+        buf = (C.c_uint8 * len(pool)).from_buffer_copy(bytes(pool))
+        out = (C.c_uint8 * (144 * K))()
+        perm = np.empty(K * L, dtype=np.uint32) if want_perm else None
+        self._check(self._lib.msm_test_bucket_sums(self._h, buf, len(pool) // pb, off.ctypes.data, elems.ctypes.data if len(elems) else None,
+                                                   K, L, int(bool(merged)), stride, tc, out, perm.ctypes.data if want_perm else None))
+        return (bytes(out), perm) if want_perm else bytes(out)
+
     def test_batch_add(self, g: BytesLike, h: BytesLike) -> bytes:
         n = len(g) // (2 * self.coord_bytes)
         bg = (C.c_uint8 * len(g)).from_buffer_copy(bytes(g))

@@ -520,7 +520,8 @@ void fe6_to_bytes(uint8_t* out, const msm_host::Fe6& a);
 void device_coord_to_wire(const msm_host::Field6& F, const msm_host::Fe6& k_to_host, const uint32_t* w, int nw, uint8_t* out);
 void plane_element_to_wire(const msm_ctx* ctx, const uint32_t* planes, uint64_t cap, uint64_t e, uint8_t* out_xy);
 void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint64_t fin_cap, const uint32_t* off_fin,
-                    const uint32_t* bucket_proj, uint32_t L, int kc, uint32_t* h_partials_out, bool merged = false, int stride = 0);
+                    const uint32_t* bucket_proj, uint32_t L, int kc, uint32_t* h_partials_out, bool merged = false, int stride = 0,
+                    uint32_t tc_force = 0);
 // The host tail: what happens to window sums between the bucket reduction and the caller.  A slot is ctx->sum_words() words;
 // `words` are K slots in a row.  These read the context's curve constants only, so any number of host threads may call them.
 void sum_set_identity(const msm_ctx* ctx, uint32_t* slot);
@@ -577,6 +578,11 @@ struct TreeOut {
 // (0 on window tables: every group reads them from table 0)
 void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl, int kc, uint64_t row_off, const SortOut& so,
                              GroupStats& st, TreeOut& to);
+// bytes of w.bucket_proj for nb buckets: a projective (Edwards: extended) point of raw limbs each
+inline size_t bucket_proj_bytes(const msm_ctx* ctx, uint64_t nb) { return nb * (ctx->is_te() ? 4 * te::TL : 3 * NL) * 4; }
+// the last step of accumulate_window_group, which the operator test msm_test_bucket_sums runs on buckets of its own (msm_tree.hip)
+const uint32_t* finish_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint64_t fin_cap, const uint32_t* off_fin,
+                               uint64_t nb, const uint32_t** perm_out = nullptr);
 void sort_kernel_attributes();   // dynamic-LDS limits of the sort kernels (once per process and device)
 
 // ---- msm_tables.hip ---------------------------------------------------------------------------------------------

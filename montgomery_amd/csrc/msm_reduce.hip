@@ -52,8 +52,11 @@ static void host_to_partial(const msm_ctx*, const msm_host::Proj6& P, uint32_t* 
 // sums come as projective points from k_bucket_finish (`bucket_proj`) or as the first element of every bucket in the tree
 // buffer (`fin`, `off_fin`).  Runs on w.stream, records w.ev[4] behind its last kernel and returns when the sums are on the host.
 // stride: bits a window advances by (Plan::c); 0 = log2(L) + 1, the plain plan's c.
+// tc_force: buckets per lane in place of the rule below, a power of two in 2 .. 32 -- the values the rule can give; 0: the rule
+// (the operator test msm_test_bucket_sums reaches every one of them at small sizes with it; the pipeline never passes it).
 void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint64_t fin_cap, const uint32_t* off_fin,
-                    const uint32_t* bucket_proj, uint32_t L, int kc, uint32_t* h_partials_out, bool merged, int stride) {
+                    const uint32_t* bucket_proj, uint32_t L, int kc, uint32_t* h_partials_out, bool merged, int stride,
+                    uint32_t tc_force) {
   hipStream_t s = w.stream;
   const bool te = ctx->is_te();
   const uint64_t nb = (uint64_t)kc * L;
@@ -64,6 +67,7 @@ void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint6
   const uint32_t tc_cap = nb >= (1ull << 22) ? 32 : 16;
   while (TC < tc_cap && nb / TC > 65536) TC *= 2;
   MSM_KNOB(TC, "MSM_TC", 1);
+  if (tc_force) TC = tc_force;
   TC = std::min<uint32_t>(TC, L);
   uint32_t nchunks = (L + TC - 1) / TC;
   // bit-sliced weighting (Weierstrass path, enough chunks to matter, TC a power of two)

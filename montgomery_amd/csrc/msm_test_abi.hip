@@ -380,6 +380,92 @@ int msm_test_bucket_reduce(msm_ctx* ctx, const uint8_t* buckets, int32_t K, uint
   } MSM_CATCH_ALL(ctx)
 }
 
+int msm_test_bucket_sums(msm_ctx* ctx, const uint8_t* pool, uint64_t n_pool, const uint32_t* off, const uint32_t* elems, int32_t K,
+                         uint32_t L, int merged, int stride, uint32_t tc, uint8_t* sums_out, uint32_t* perm_out) {
+  if (!ctx || !pool || !off || !sums_out || n_pool == 0 || K <= 0 || L == 0 || (L & (L - 1)) || stride < 0)
+    return fail(ctx, MSM_ERR_ARG, "msm_test_bucket_sums: bad argument");
+  if (tc && (tc < 2 || tc > 32 || (tc & (tc - 1)))) return fail(ctx, MSM_ERR_ARG, "msm_test_bucket_sums: tc must be 0 or a power of two in 2 .. 32");
+  const uint64_t nb = (uint64_t)K * L;
+  // the reduction hands the host up to log2(L) sums per window through the pinned buffer of a workspace (128 * 20 slots)
+  if (nb >= (1ull << 31) || (uint64_t)K * (ceil_log2_u64(L) + 1) > 128 * 20)
+    return fail(ctx, MSM_ERR_ARG, "msm_test_bucket_sums: too many buckets or windows");
+  const uint64_t n_el = off[nb];
+  if (off[0] != 0 || (n_el && !elems) || n_el >= (1ull << 31)) return fail(ctx, MSM_ERR_ARG, "msm_test_bucket_sums: bad offsets");
+  for (uint64_t b = 0; b < nb; b++)
+    if (off[b] > off[b + 1]) return fail(ctx, MSM_ERR_ARG, "msm_test_bucket_sums: offsets must ascend");
+  for (uint64_t e = 0; e < n_el; e++)
+    if (elems[e] >= n_pool) return fail(ctx, MSM_ERR_ARG, "msm_test_bucket_sums: element %llu names no pool point", (unsigned long long)e);
+  try {
+    HIPCHK(hipSetDevice(ctx->device));
+    msm_ctx::Workspace& w = ctx->ws[0];
+    hipStream_t s = w.stream;
+    const bool te = ctx->is_te();
+    const uint64_t cap = n_el + 2 * 257 * 512 + 256;   // plane capacity: idle lanes read (and ignore) past the end
+    const size_t pb = 2 * ctx->coord_bytes();          // wire point
+    const size_t elem_bytes = te ? 128 : pb;           // tree node: extended (X, Y, Z, T), or affine (x, y)
+    ScopedDevBuf wire, rows, planes, d_off, slots;
+    ctx->ensure(planes, cap * elem_bytes);
+    ctx->ensure(d_off, (nb + 1) * 4);
+    HIPCHK(hipMemsetAsync(planes.p, 0, cap * elem_bytes, s));
+    HIPCHK(hipMemsetAsync(ctx->errflag.p, 0, 4, s));
+    HIPCHK(hipMemcpyAsync(d_off.p, off, (nb + 1) * 4, hipMemcpyHostToDevice, s));
+    std::vector<uint8_t> h_wire;     // (both live until the stream has been waited for)
+    std::vector<uint32_t> h_slots;
+    if (n_el && te) {
+      // the pool as point rows; element e = pool[elems[e]] + the absent operand, through one gather round of the tree
+      ctx->ensure(wire, n_pool * pb);
+      ctx->ensure(rows, n_pool * te::TE_ROW_WORDS * 4);
+      ctx->ensure(slots, 2 * n_el * 4);
+      h_slots.resize(2 * n_el);
+      for (uint64_t e = 0; e < n_el; e++) { h_slots[2 * e] = elems[e] << 1; h_slots[2 * e + 1] = SLOT_EMPTY; }
+      HIPCHK(hipMemcpyAsync(wire.p, pool, n_pool * pb, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(slots.p, h_slots.data(), h_slots.size() * 4, hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(te::k_te_points_from_wire, dim3((uint32_t)((n_pool + 255) / 256)), dim3(256), 0, s, (uint32_t*)rows.p,
+                         (const uint32_t*)wire.p, n_pool, 0, (uint32_t*)ctx->errflag.p);
+      BatchArgs a{};
+      a.points = (const uint32_t*)rows.p;
+      a.slots = (const uint32_t*)slots.p;
+      a.out = (uint4*)planes.p;
+      a.out_cap = cap;
+      a.n_out = n_el;
+      a.steps = 1;
+      hipLaunchKernelGGL(te::k_te_add<MODE_GATHER>, dim3((uint32_t)((n_el + 255) / 256)), dim3(256), 0, s, a);
+    } else if (n_el) {
+      // element e = wire point pool[elems[e]] -> row e -> element e of the planes
+      h_wire.resize(n_el * pb);
+      for (uint64_t e = 0; e < n_el; e++) memcpy(&h_wire[e * pb], pool + (size_t)elems[e] * pb, pb);
+      ctx->ensure(wire, n_el * pb);
+      ctx->ensure(rows, n_el * ROW_WORDS * 4);
+      HIPCHK(hipMemcpyAsync(wire.p, h_wire.data(), n_el * pb, hipMemcpyHostToDevice, s));
+      W_LAUNCH(ctx, k_points_from_wire, dim3((uint32_t)((n_el + 255) / 256)), dim3(256), 0, s, (uint32_t*)rows.p,
+               (const uint32_t*)wire.p, n_el, 0, (uint32_t*)ctx->errflag.p);
+      ROWS_TO_PLANES(ctx, dim3((uint32_t)((n_el + 255) / 256)), dim3(256), 0, s, (uint4*)planes.p, cap, (const uint32_t*)rows.p,
+                     (uint32_t)n_el);
+    }
+    // the pipeline's own finish, over bucket sums that start out as garbage: a bucket the finish skips cannot come out right.
+    // No entries at all: as in the pipeline, the reduction reads the (empty) buckets of the tree buffer instead.
+    const uint32_t* bucket_proj = nullptr;
+    const uint32_t* perm = nullptr;
+    if (n_el) {
+      ctx->ensure(w.bucket_proj, bucket_proj_bytes(ctx, nb));
+      HIPCHK(hipMemsetAsync(w.bucket_proj.p, 0x2A, bucket_proj_bytes(ctx, nb), s));
+      bucket_proj = finish_buckets(ctx, w, (const uint4*)planes.p, cap, (const uint32_t*)d_off.p, nb, &perm);
+    }
+    if (perm_out) {
+      if (perm) HIPCHK(hipMemcpyAsync(perm_out, perm, nb * 4, hipMemcpyDeviceToHost, s));
+      else for (uint64_t b = 0; b < nb; b++) perm_out[b] = (uint32_t)b;   // no ordering: the buckets are taken as they lie
+    }
+    const int sw = ctx->sum_words();
+    std::vector<uint32_t> parts((size_t)K * sw, 0);
+    reduce_buckets(ctx, w, (const uint4*)planes.p, cap, (const uint32_t*)d_off.p, bucket_proj, L, K, parts.data(), merged != 0, stride, tc);
+    HIPCHK(hipMemcpyAsync(w.h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (w.h_info[0] & 1) return fail(ctx, MSM_ERR_POINT, "msm_test_bucket_sums: coordinate >= p");
+    for (int k = 0; k < K; k++) sum_to_wire(ctx, &parts[(size_t)k * sw], sums_out + (size_t)k * SUM_WIRE_BYTES);
+    return MSM_OK;
+  } MSM_CATCH_ALL(ctx)
+}
+
 int msm_test_batch_add_mode(msm_ctx* ctx, const uint8_t* g, const uint8_t* h, uint8_t* out, uint64_t n, int mode, uint32_t steps) {
   if (!ctx || !g || !h || !out || n == 0 || steps == 0) return fail(ctx, MSM_ERR_ARG, "msm_test_batch_add_mode: bad argument");
   if (ctx->is_te() || (mode != MODE_REGULAR && mode != MODE_SEARCH))

@@ -8,6 +8,37 @@ using namespace msmi;
 
 namespace msmi {
 
+// The end of the accumulation: one lane per bucket sums what the tree left of it (k_bucket_finish / k_te_bucket_finish) into
+// w.bucket_proj, a projective (Edwards: extended) point per bucket, which is returned.  fin, off_fin: the tree buffer and the nb + 1
+// offsets of its buckets.  Queued on w.stream.  perm_out: where the buckets were ordered first (nb >= 4096), that order -- nb
+// words on the device, perm[j] = the j-th bucket in descending order of its element count -- else nullptr.
+const uint32_t* finish_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint64_t fin_cap, const uint32_t* off_fin,
+                               uint64_t nb, const uint32_t** perm_out) {
+  hipStream_t s = w.stream;
+  const bool te = ctx->is_te();
+  ctx->ensure(w.bucket_proj, bucket_proj_bytes(ctx, nb));
+  // lanes of a wave should have equal trip counts: order the buckets by what they still hold
+  const uint32_t* perm = nullptr;
+  if (nb >= 4096) {
+    ctx->ensure(w.blk_tab2, (nb + 2 * FINISH_BINS) * 4);
+    uint32_t* hist = (uint32_t*)w.blk_tab2.p;
+    HIPCHK(hipMemsetAsync(hist, 0, 2 * FINISH_BINS * 4, s));
+    const uint32_t fgrid = (uint32_t)((nb + FINISH_THREADS - 1) / FINISH_THREADS);
+    hipLaunchKernelGGL(k_finish_hist, dim3(fgrid), dim3(FINISH_THREADS), 0, s, off_fin, (uint32_t)nb, hist);
+    hipLaunchKernelGGL(k_finish_perm, dim3(fgrid), dim3(FINISH_THREADS), 0, s, off_fin, (uint32_t)nb,
+                       (const uint32_t*)hist, hist + FINISH_BINS, hist + 2 * FINISH_BINS);
+    perm = hist + 2 * FINISH_BINS;
+  }
+  if (te)
+    hipLaunchKernelGGL(te::k_te_bucket_finish, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, (uint32_t*)w.bucket_proj.p,
+                       fin, fin_cap, off_fin, (uint32_t)nb, perm);
+  else
+    W_LAUNCH(ctx, k_bucket_finish, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, (uint32_t*)w.bucket_proj.p, fin,
+                       fin_cap, off_fin, (uint32_t)nb, perm);
+  if (perm_out) *perm_out = perm;
+  return (const uint32_t*)w.bucket_proj.p;
+}
+
 // queues the tree on w.stream behind whatever is there; records w.ev[6] behind round 1 and w.ev[3] behind the last kernel
 void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl, int kc, uint64_t row_off, const SortOut& so,
                              GroupStats& st, TreeOut& to) {
@@ -152,28 +183,7 @@ void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl
   }
   st.rounds += round;
   const uint32_t* bucket_proj = nullptr;
-  if (use_finish && total_slots > 0) {
-    ctx->ensure(w.bucket_proj, nb * (te ? 4 * te::TL : 3 * NL) * 4);
-    // lanes of a wave should have equal trip counts: order the buckets by what they still hold
-    const uint32_t* perm = nullptr;
-    if (nb >= 4096) {
-      ctx->ensure(w.blk_tab2, (nb + 2 * FINISH_BINS) * 4);
-      uint32_t* hist = (uint32_t*)w.blk_tab2.p;
-      HIPCHK(hipMemsetAsync(hist, 0, 2 * FINISH_BINS * 4, s));
-      const uint32_t fgrid = (uint32_t)((nb + FINISH_THREADS - 1) / FINISH_THREADS);
-      hipLaunchKernelGGL(k_finish_hist, dim3(fgrid), dim3(FINISH_THREADS), 0, s, off_fin, (uint32_t)nb, hist);
-      hipLaunchKernelGGL(k_finish_perm, dim3(fgrid), dim3(FINISH_THREADS), 0, s, off_fin, (uint32_t)nb,
-                         (const uint32_t*)hist, hist + FINISH_BINS, hist + 2 * FINISH_BINS);
-      perm = hist + 2 * FINISH_BINS;
-    }
-    if (te)
-      hipLaunchKernelGGL(te::k_te_bucket_finish, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, (uint32_t*)w.bucket_proj.p,
-                         fin, fin_cap, off_fin, (uint32_t)nb, perm);
-    else
-      W_LAUNCH(ctx, k_bucket_finish, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, (uint32_t*)w.bucket_proj.p, fin,
-                         fin_cap, off_fin, (uint32_t)nb, perm);
-    bucket_proj = (const uint32_t*)w.bucket_proj.p;
-  }
+  if (use_finish && total_slots > 0) bucket_proj = finish_buckets(ctx, w, fin, fin_cap, off_fin, nb);
   if (total_slots == 0) HIPCHK(hipEventRecord(w.ev[6], s));
   HIPCHK(hipEventRecord(w.ev[3], s));
   to.fin = fin;
