@@ -531,6 +531,22 @@ int msm_test_bucket_reduce(msm_ctx* ctx, const uint8_t* buckets, int32_t K, uint
  * from 63 up alike -- or 0, 1, 2, ... where it did not order them (fewer than 4096 buckets, or no element at all). */
 int msm_test_bucket_sums(msm_ctx* ctx, const uint8_t* pool, uint64_t n_pool, const uint32_t* off, const uint32_t* elems, int32_t K,
                          uint32_t L, int merged, int stride, uint32_t tc, uint8_t* sums_out, uint32_t* perm_out);
+/* The sort path of a window group -- which of the forms of the sort and of round 1 of the accumulation tree it took:
+ *   ONE_LEVEL  a window's counters fit the LDS and the input is small
+ *   RADIX      the radix split (an input whose largest bucket is `heavy` still takes the one-level scatter as its last pass)
+ *   SLOTS      the bin split, round 1 over bucket-ordered padded slots (k_bin_slots), results as planes
+ *   PAIRS      the bin split, round 1 over the tile-ordered pairs of k_bin_pairs, results as 64-byte element records that
+ *              round 2 reads back ("pair form") */
+enum { MSM_SORT_ONE_LEVEL = 0, MSM_SORT_RADIX = 1, MSM_SORT_SLOTS = 2, MSM_SORT_PAIRS = 3 };
+/* The pair form is taken by big windows (c >= 18, buckets deep enough for two index-free rounds) over MORE than 2^log2_rows
+ * rows of the point table or of the window tables a group reads.  The default, 23, is a measured break-even; this entry moves
+ * it for the context, so that tests reach the pair form -- through the pipeline's own host code -- at sizes of a few seconds.
+ * log2_rows: 1 .. 40, or 0 to restore the default.  Results do not depend on it.  Refused on a device-list context. */
+int msm_test_set_chunk_rows_log(msm_ctx* ctx, int32_t log2_rows);
+/* The sort paths (MSM_SORT_*) of the window groups of the last msm_run, msm_run_narrow, msm_run_indexed(_narrow), msm_run_placed
+ * or msm_window_sums on this context, one per group in the order of the call's schedule; none (count 0) after a call that failed or a fused batch: writes
+ * min(count, cap) of them to `out` (may be NULL with cap = 0) and returns the count, or -1 for a null or device-list context. */
+int msm_test_last_sort_paths(msm_ctx* ctx, int32_t* out, int cap);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,7 @@ CURVE_VESTA = 6
 CURVES_32_BYTE = (CURVE_ED_ON_BLS12_377, CURVE_PALLAS, CURVE_BN254_G1, CURVE_GRUMPKIN, CURVE_VESTA)   # 9 limbs / 8 words
 ABI_VERSION = 8   # MSM_ABI_VERSION of the include/msm_hip.h this binding was written against
 N_PHASES = 8
+SORT_PATH_NAMES = ("one_level", "radix", "slots", "pairs")   # MSM_SORT_* of include/msm_hip.h
 PHASE_NAMES = ("total", "upload", "digits", "sort", "accumulate", "reduce", "final", "accumulate_round1")
 
 POINTS_UNCOMPRESSED, POINTS_COMPRESSED = 0, 1
@@ -47,7 +48,7 @@ EXPORTS = (
     "msm_run_indexed", "msm_run_indexed_narrow",
     "msm_points_lincomb", "msm_pointset_size",
     "msm_device_download", "msm_scalars_lincomb", "msm_scalars_mul", "msm_scalars_inner", "msm_scalars_powers",
-    "msm_test_bucket_sums",
+    "msm_test_bucket_sums", "msm_test_set_chunk_rows_log", "msm_test_last_sort_paths",
 )
 
 
@@ -211,6 +212,11 @@ def load() -> C.CDLL:
     if not hasattr(lib, "msm_test_bucket_sums"):
         raise ImportError(f"{LIB_PATH} predates msm_test_bucket_sums: rebuild it (`make`)")
     lib.msm_test_bucket_sums.argtypes = [vp, vp, u64, vp, vp, i32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, vp, vp]
+    # the pair-form threshold and the sort-path report: new test symbols under ABI 8
+    if not hasattr(lib, "msm_test_last_sort_paths"):
+        raise ImportError(f"{LIB_PATH} predates msm_test_last_sort_paths: rebuild it (`make`)")
+    lib.msm_test_set_chunk_rows_log.argtypes = [vp, i32]
+    lib.msm_test_last_sort_paths.argtypes = [vp, C.POINTER(i32), C.c_int]
     for name in EXPORTS:
         if name not in ("msm_ctx_destroy", "msm_last_error", "msm_abi_version", "msm_abi_struct_bytes"):
             getattr(lib, name).restype = C.c_int

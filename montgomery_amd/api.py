@@ -958,6 +958,23 @@ class MsmContext:
                                                    K, L, int(bool(merged)), stride, tc, out, perm.ctypes.data if want_perm else None))
         return (bytes(out), perm) if want_perm else bytes(out)
 
+    def test_set_chunk_rows_log(self, log2_rows: int = 0) -> None:
+        """Round 1 of big windows takes the pair form above 2^log2_rows table rows (msm_test_set_chunk_rows_log, msm_hip.h);
+        0 restores the default of 23."""
+        self._check(self._lib.msm_test_set_chunk_rows_log(self._h, log2_rows))
+
+    def test_last_sort_paths(self) -> List[str]:
+        """The sort path of every window group of the last call, in schedule order: "one_level", "radix", "slots" or "pairs"
+        (msm_test_last_sort_paths, msm_hip.h)."""
+        count = self._lib.msm_test_last_sort_paths(self._h, None, 0)
+        if count < 0:
+            raise MsmError(_lib.MSM_ERR_ARG, "msm_test_last_sort_paths: not on a device-list context")
+        out = (C.c_int32 * max(count, 1))()
+        self._lib.msm_test_last_sort_paths(self._h, out, count)
+        if any(not 0 <= v < len(_lib.SORT_PATH_NAMES) for v in out[:count]):
+            raise MsmError(_lib.MSM_ERR_INTERNAL, f"msm_test_last_sort_paths: unknown sort path in {list(out[:count])}")
+        return [_lib.SORT_PATH_NAMES[v] for v in out[:count]]
+
     def test_batch_add(self, g: BytesLike, h: BytesLike) -> bytes:
         n = len(g) // (2 * self.coord_bytes)
         bg = (C.c_uint8 * len(g)).from_buffer_copy(bytes(g))

@@ -96,6 +96,7 @@ int run_fused(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, 
   HIPCHK(hipStreamSynchronize(ctx->stream));   // scalars and the error flag are in place before the group streams start
   const uint64_t p_lo = point_lo(opts);
   const bool serial = opts && opts->serial;
+  ctx->last_sort_paths.clear();   // (a fused batch is not recorded: no report of an earlier call stays behind)
   GroupStats sts[msm_ctx::N_WS];
   run_on_workspaces(ctx, n_groups, serial, [&](int slot, int g) {
     const int b0 = g * per, cnt = std::min<int>(per, (int)B - b0);

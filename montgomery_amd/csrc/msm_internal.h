@@ -287,6 +287,13 @@ struct msm_ctx {
   hipEvent_t piece_ev[MAX_PIECES][STAGE_THREADS] = {};
   uint64_t ws_budget = 0;          // bytes the per-group workspaces may take in total
   uint64_t ws_limit = 0;           // msm_set_workspace_limit: the caller's cap on ws_budget (0 = automatic)
+  // log2 of the table rows above which round 1 of a big window takes the pair form (sort_window_group, where the measurements
+  // behind the default are); only msm_test_set_chunk_rows_log moves it, so that tests reach the pair form at small sizes
+  static constexpr int CHUNK_ROWS_LOG = 23;
+  int chunk_rows_log = CHUNK_ROWS_LOG;
+  // MSM_SORT_* of every window group of the last call, in the order of its schedule; cleared when a call starts its groups and
+  // written when all of them have run, so a call that failed, or a fused batch, leaves it empty
+  std::vector<int32_t> last_sort_paths;
 
   // per-group workspace: two of them, each with its own stream, so that the memory-bound sort of one
   // window group runs under the ALU-bound accumulation of the other
@@ -550,6 +557,7 @@ struct SortOut {
   const uint32_t* round1_dest = nullptr;    // tile order: the element index every pair's sum belongs to
   uint64_t rec_y_off = 0;       // 12-word fields: where the y records of round 1's results start inside w.rows1
   bool chunked = false;         // round 1 walks tile-ordered pairs and writes element records, round 2 reads them
+  int path = MSM_SORT_ONE_LEVEL;   // the sort path taken (MSM_SORT_*, include/msm_hip.h): what msm_test_last_sort_paths reports
 };
 // Digits and slice histograms of SEVERAL window groups from one launch of the digit kernel (the two groups of a call decompose
 // the same scalars: one GLV decomposition instead of two).  sort_window_group(..., share) with share->produce set runs the digit

@@ -21,7 +21,7 @@ const uint32_t* group_scalars(const uint32_t* d_scalars_all, uint64_t p_lo, Plan
 }
 
 void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars_all, uint64_t p_lo, uint64_t n, const Plan& pl_in,
-                      int k_lo, int k_hi, uint32_t* h_partials_out, GroupStats& st, uint64_t p_off = 0, GroupDigits* share = nullptr) {
+                      int k_lo, int k_hi, uint32_t* h_partials_out, GroupStats& st, int32_t& path, uint64_t p_off = 0, GroupDigits* share = nullptr) {
   hipStream_t s = w.stream;
   Plan pl = pl_in;
   const uint32_t* d_scalars = group_scalars(d_scalars_all, p_lo, pl);   // scalar i of the call <-> resident point p_off + i
@@ -32,6 +32,7 @@ void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sca
   HIPCHK(hipEventRecord(w.ev[0], s));
   sort_window_group(ctx, w, d_scalars, n, pl, k_lo, k_hi, st, so, share);
   st.max_bucket = std::max<uint64_t>(st.max_bucket, so.max_bucket);
+  path = so.path;
   if (idx) {
     // msm_run_indexed: the payloads name positions of the group; round 1 gathers rows of the whole resident table by them, so
     // they are rewritten to name the rows of idx[position] first (one coalesced pass whatever sort path wrote them)
@@ -106,6 +107,7 @@ float run_groups(msm_ctx* ctx, const CallSetup& cs, const void* scalars, uint64_
                  std::vector<std::vector<uint32_t>>& part, GroupStats& st) {
   const std::vector<GroupSchedule::Group>& groups = cs.sch.groups;
   const int pw = ctx->sum_words();
+  ctx->last_sort_paths.clear();   // (a call that fails on its way reports nothing, not the call before it)
   HIPCHK(hipMemsetAsync(ctx->errflag.p, 0, 4, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));   // staged scalars are in place before the group streams start
   std::unique_ptr<PieceUpload> pipe;
@@ -130,13 +132,15 @@ float run_groups(msm_ctx* ctx, const CallSetup& cs, const void* scalars, uint64_
   pg.lone = cs.sch.lone;
   GroupStats sts[msm_ctx::N_WS];
   part.assign(groups.size(), {});
+  std::vector<int32_t> paths(groups.size(), -1);
   run_on_workspaces(ctx, (int)groups.size(), serial, [&](int slot, int gi) {
     const GroupSchedule::Group& g = groups[gi];
     part[gi].resize((size_t)(g.kb - g.ka) * pw);
     if (g.piece >= 0) pipe->wait_piece(g.piece, ctx->ws[slot].stream);
-    run_window_group(ctx, ctx->ws[slot], cs.d_scal, g.p_lo, g.p_n, pg, g.ka, g.kb, part[gi].data(), sts[slot], p_off,
+    run_window_group(ctx, ctx->ws[slot], cs.d_scal, g.p_lo, g.p_n, pg, g.ka, g.kb, part[gi].data(), sts[slot], paths[gi], p_off,
                      share.valid ? &share : nullptr);
   });
+  ctx->last_sort_paths = std::move(paths);
   check_scalar_flags(ctx, pl, "msm_run_narrow");
   float upload_ms = -1;
   if (pipe) upload_ms = pipe->finish();   // joins the staging threads; their last copy is done

@@ -14,7 +14,10 @@ int fail(msm_ctx* ctx, int code, const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(buf, sizeof buf, fmt, ap);
   va_end(ap);
-  if (ctx) ctx->err = buf;
+  if (ctx) {
+    ctx->err = buf;
+    ctx->last_sort_paths.clear();   // (msm_test_last_sort_paths: a failed call reports no paths, not those of the call before it)
+  }
   return code;
 }
 

@@ -194,7 +194,7 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
     // from more than 2^23 rows of 256 bytes = 2 GB (measured, tools/chunk_plain.py on the round-5 tuning build: at
     // 2^23 rows -- 2^23 points, or 2^20 on seven window tables -- the plain slot form is 2.5 % ahead: 20.15 against 20.64 ms,
     // 3.23 / 3.32; at 2^23.8 rows level; at 2^24 rows the tile order wins by 10 %: 38.6 against 43.0)
-    const int chunk_rows_log = 23;
+    const int chunk_rows_log = ctx->chunk_rows_log;   // (23 unless a test has moved it)
     const uint64_t table_rows = pl.tables ? (uint64_t)kc_d * n : n;
     const bool want_chunks = bin_split && !te && pl.c >= 18 && table_rows > (1ull << chunk_rows_log);
     // (round 2 must be an index-free round to read the element records round 1 then writes: logG >= 2)
@@ -418,6 +418,7 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
   so.round1_dest = round1_dest;
   so.rec_y_off = rec_y_off;
   so.chunked = chunked;
+  so.path = chunked ? MSM_SORT_PAIRS : bin_split ? MSM_SORT_SLOTS : radix ? MSM_SORT_RADIX : MSM_SORT_ONE_LEVEL;
 }
 
 }  // namespace msmi

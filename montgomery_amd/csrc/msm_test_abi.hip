@@ -525,6 +525,21 @@ int msm_test_batch_add_mode(msm_ctx* ctx, const uint8_t* g, const uint8_t* h, ui
   } MSM_CATCH_ALL(ctx)
 }
 
+int msm_test_set_chunk_rows_log(msm_ctx* ctx, int32_t log2_rows) {
+  if (!ctx) return MSM_ERR_ARG;
+  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "msm_test_set_chunk_rows_log: not on a device-list context");
+  if (log2_rows < 0 || log2_rows > 40) return fail(ctx, MSM_ERR_ARG, "msm_test_set_chunk_rows_log: log2_rows must be 0 (default) or 1 .. 40");
+  ctx->chunk_rows_log = log2_rows ? log2_rows : msm_ctx::CHUNK_ROWS_LOG;
+  return MSM_OK;
+}
+
+int msm_test_last_sort_paths(msm_ctx* ctx, int32_t* out, int cap) {
+  if (!ctx || !ctx->children.empty() || cap < 0 || (cap && !out)) return -1;
+  const int count = (int)ctx->last_sort_paths.size();
+  for (int i = 0; i < count && i < cap; i++) out[i] = ctx->last_sort_paths[i];
+  return count;
+}
+
 int msm_generate_points(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) {
   if (!ctx) return MSM_ERR_ARG;
   if (ctx->children.empty()) return generate_points_one(ctx, n, seed, a_out);

@@ -67,10 +67,12 @@ class Plan:
         self.L_log = c if self.fold else c - 1
         self.halves = 1 if (cv.te or narrow_bits) else 2            # crafted digit strings per scalar
         self.per_point = 1 if cv.te else 2                          # entries per point and window (two_n_d / n)
-        self.value_bits = narrow_bits or (TE_SCALAR_BITS if cv.te else HALF_BITS[curve])
-        assert self.value_bits > c * (self.K - 1) + 2, "the crafted values do not reach the top window"
-        self.top_max = 1 << (self.value_bits - c * (self.K - 1))    # top digits 1 .. top_max (top_max: with a negative digit below)
-        assert self.top_max <= (1 << (c - 1))
+        # (a curve without a measured HALF_BITS has the plan arithmetic and the sort's cuts only: no crafted scalars)
+        self.value_bits = narrow_bits or (TE_SCALAR_BITS if cv.te else HALF_BITS.get(curve))
+        if self.value_bits is not None:
+            assert self.value_bits > c * (self.K - 1) + 2, "the crafted values do not reach the top window"
+            self.top_max = 1 << (self.value_bits - c * (self.K - 1))    # top digits 1 .. top_max (top_max: with a negative digit below)
+            assert self.top_max <= (1 << (c - 1))
 
     def eff_bits(self, k, tables=False):
         """Bits the bucket indices of window k really have (msm_sort.hip, the loop that fills WinSplit)."""
@@ -92,9 +94,11 @@ class Geometry:
     (`fits_lds` .. `radix`, `will_chunk`), the split of every window's bucket index into coarse and fine bits
     (`abk = eff <= ab_big ? eff : max(ab_big, eff - BS_MAX_FB)`, `ws.fb = eff - abk`; the radix split: 7 fine bits), the bins of
     the group V = kc * hb, and `part_len = max(2^16, roundup(2 * n_entries / V, BP_TILE))` with BP_TILE = 4096.
-    tables: the kc_d digit windows are one merged window of kc_d * two_n_d entries."""
+    tables: the kc_d digit windows are one merged window of kc_d * two_n_d entries.
+    chunk_rows: the table rows above which round 1 takes the pair form -- 2^23 unless a test has moved the context's threshold
+    (msm_test_set_chunk_rows_log).  mean, logG: the mean bucket the padding granule is sized from, and log2 of that granule."""
 
-    def __init__(self, plan, n, k_lo, k_hi, tables=False):
+    def __init__(self, plan, n, k_lo, k_hi, tables=False, chunk_rows=1 << 23):
         kc_d = k_hi - k_lo
         two_n_d = plan.per_point * n
         self.n_entries = kc_d * two_n_d
@@ -123,8 +127,9 @@ class Geometry:
         logG = 1
         while logG < 10 and (1 << (logG + 1)) * left <= mean:
             logG += 1
-        rows = kc_d * n if tables else n
-        pairs = bin_split and (not plan.te) and plan.c >= 18 and rows > (1 << 23) and logG >= 2
+        self.mean, self.logG = mean, logG
+        self.rows = rows = kc_d * n if tables else n
+        pairs = bin_split and (not plan.te) and plan.c >= 18 and rows > chunk_rows and logG >= 2
         self.path = "pairs" if pairs else "slots" if bin_split else "radix" if radix else "one_level"
 
 
@@ -324,7 +329,9 @@ def craft(name, plan, n, classes, seed, pool=4096, tables=False):
             free = ~planted[:, :, k] & ~lone_rows[:, None]
             hit = free & (d != 0) & np.isin((np.abs(d) - 1) >> fb[k], barr)
             if lone_rows.any():
-                hit |= free & np.isin(np.abs(d), np.abs(d[lone_rows]))
+                # (on window tables the windows of a group share their buckets: the lone digits of all of them count)
+                glo, ghi = [g for g in groups if g[0] == first_of[k]][0]
+                hit |= free & np.isin(np.abs(d), np.abs(digits[lone_rows, :, glo:ghi]))
             if not hit.any():
                 break
             d[hit] = draw(k, int(hit.sum()))
@@ -383,11 +390,11 @@ def full_bin(plan, n, window=None, b=None, seed=1, pool=4096, tables=False):
     return craft("full_bin", plan, n, [cl], seed, max(pool, m + 1024), tables)
 
 
-def exact_edges(plan, n, window=None, seed=2, pool=4096, bins=None):
+def exact_edges(plan, n, window=None, seed=2, pool=4096, bins=None, tables=False):
     """Four bins of one window hold exactly 2 * part_len, part_len + 1, 2 * part_len - 1 and part_len records.  With an
     endomorphism the entries of the second and fourth are entries of the first and third, through their other half (one half
     per point would not fit four such bins into 2^18 points).  bins: the four bins, else four around the middle one."""
-    window, b0, fb, part_len = _target(plan, n, window, None)
+    window, b0, fb, part_len = _target(plan, n, window, None, tables)
     bs = bins or [b0, b0 + 1, b0 + 3, b0 + 4]
     NB = 1 << fb
     m = max(NB, 64)
@@ -401,8 +408,8 @@ def exact_edges(plan, n, window=None, seed=2, pool=4096, bins=None):
         classes = [pair(sizes[0], sizes[1], bs[0], bs[1]), pair(sizes[2], sizes[3], bs[2], bs[3])]
     else:
         classes = [Class(m, [Plant(window, bb, offs, _alt_neg(m))], counts=split_counts(sz, m)) for sz, bb in zip(sizes, bs)]
-    cr = craft("exact_edges", plan, n, classes, seed, pool)
-    assert [cr.bins[(window, bb)] for bb in bs] == sizes
+    cr = craft("exact_edges", plan, n, classes, seed, pool, tables)
+    assert [cr.bins[(cr.windows_of(window)[0], bb)] for bb in bs] == sizes
     return cr
 
 
@@ -452,22 +459,23 @@ def neighbours(plan, n, seed=4, pool=4096, tables=False):
     return craft("neighbours", plan, n, classes, seed, pool, tables)
 
 
-def _four_buckets(plan, n, window, b):
-    window, b, fb, part_len = _target(plan, n, window, b)
+def _four_buckets(plan, n, window, b, tables=False):
+    window, b, fb, part_len = _target(plan, n, window, b, tables)
     NB = 1 << fb
     assert NB >= 8
     return window, b, part_len, np.array([0, NB // 3, NB // 2 + 1, NB - 1])
 
 
-def alternating(plan, n, window=None, b=None, seed=5, pool=4096):
+def alternating(plan, n, window=None, b=None, seed=5, pool=4096, tables=False):
     """A heavy bin over four buckets A B C D in three parts and a bit.  In point order a full part is (A B C D) x (part_len / 4 - 1)
     and then B D B D: part_len / 4 - 1 entries of A and of C, part_len / 4 + 1 of B and of D -- EVERY part holds an odd count of
-    every bucket.  The short last part is A B D."""
-    window, b, part_len, offs = _four_buckets(plan, n, window, b)
+    every bucket.  The short last part is A B D.  (On window tables the bin holds no record of the group's other windows: the
+    fill stays out of it in all of them.)"""
+    window, b, part_len, offs = _four_buckets(plan, n, window, b, tables)
     part = np.concatenate([np.tile(np.arange(4), part_len // 4 - 1), np.array([1, 3, 1, 3])])
     seq = np.concatenate([part, part, part, np.array([0, 1, 3])])
     cl = Class(4, [Plant(window, b, offs, neg=[False, True, False, True])], seq=seq)
-    return craft("alternating", plan, n, [cl], seed, pool)
+    return craft("alternating", plan, n, [cl], seed, pool, tables)
 
 
 def runs(plan, n, window=None, b=None, seed=6, pool=4096):
@@ -571,4 +579,296 @@ INDEXED_CASE = Case("full_bin", c=21, n=1 << 18, seed=11)
 # bucket shards (g, 2) of a 21-bit plan cut every window's 2^20 buckets at 2^19 = the start of bin 512
 SHARD_CASES = [Case("full_bin", c=21, n=1 << 18, b=300), Case("exact_edges", c=21, n=1 << 18, bins=(510, 511, 512, 513))]
 BN254_CASE = Case("full_bin", curve="bn254", c=21, n=1 << 18)
-ALL_CASES = SLOT_CASES + PAIR_CASES + TABLES_CASES + RADIX_CASES + ED_CASES + [NARROW_CASE, INDEXED_CASE] + SHARD_CASES + [BN254_CASE]
+
+# ---------------------------------------------------------------------------------------------- the pair form at small sizes
+# tests/test_gpu_pair_form.py lowers the context's row threshold (msm_test_set_chunk_rows_log) to 2^PAIR_ROWS_LOG rows; what is
+# left of `will_chunk` in msm_sort.hip is c >= 18 and logG >= 2.  logG >= 2 means 4 * per_bucket_left <= mean, and
+# per_bucket_left is 8 below a mean of 64: mean >= 32.  The mean is floor(entries of the (merged) window / 2^(c-1)) -- a folded
+# plan fills L / 2 = 2^(c-1) of its 2^c buckets, an unfolded one has L = 2^(c-1) -- and a window holds 2 n entries on the plain
+# path (both GLV halves; no_glv and narrow calls keep the second, empty, half), 2 n kc_d on window tables that merge kc_d windows:
+#     plain   n >= 2^(c+3)                    c = 18: 2^21, c = 21: 2^24, c = 22: 2^25
+#     tables  n kc_d >= 2^(c+3); below 2^21 points one group of all K windows, from 2^21 two groups and the smaller one has
+#             floor(K / 2) windows            c = 18: K = 7: ceil(2^21 / 7) = 299 594, K = 8: 2^18
+#                                             c = 21: K = 6 or 7, smaller group 3: ceil(2^24 / 3) = 5 592 406
+#                                             c = 22: K = 6, groups 3 + 3: ceil(2^25 / 3) = 11 184 811
+PAIR_ROWS_LOG = 10
+PAIR_MIN_PLAIN = {18: 1 << 21, 21: 1 << 24, 22: 1 << 25}
+PAIR_MIN_TABLES = {(18, 7): 299594, (18, 8): 1 << 18, (21, 6): 5592406, (21, 7): 5592406, (22, 6): 11184811}
+
+
+def sort_paths(plan, n, tables=False, chunk_rows=1 << 23):
+    """The predicted path of every window group of a call, in schedule order."""
+    return [Geometry(plan, n, lo, hi, tables, chunk_rows).path for lo, hi in plan.window_groups(n, tables)]
+
+
+# c = 21 in the pair form: six windows as two merged windows of three, with an odd entry per part
+PAIR21_N = PAIR_MIN_TABLES[(21, 6)]
+PAIR21_CASES = [Case(d, c=21, n=PAIR21_N, tables=True, pool=16384) for d in ("exact_edges", "alternating")]
+ALL_CASES = (SLOT_CASES + PAIR_CASES + TABLES_CASES + RADIX_CASES + ED_CASES + [NARROW_CASE, INDEXED_CASE] + SHARD_CASES + [BN254_CASE]
+             + PAIR21_CASES)
+
+
+# ---------------------------------------------------------------------------------------------- degenerate pairs in the pair form
+# A layout is the roles of m points that share ONE scalar no other point has a digit in common with (a `lone` pool entry of
+# count m): every non-zero digit of that scalar is a bucket of exactly these m entries, in point order.  Roles: a capital letter
+# is an ordinary point of the set, "-X" its negative, "O" the identity row, "T" the point of order 2 (BLS12-377, calls without
+# the endomorphism only).  In the pair form a bucket's entries pair up in that order in round 1 -- an odd one out with nothing,
+# pads behind it -- and its round-1 elements, which start at an even element index, pair up in round 2.
+DEGENERATE_LAYOUTS = {
+    "PPPP": ("P", "P", "P", "P"),            # round 1: two doublings; round 2: a doubling of two equal records
+    "PQPQ": ("P", "Q", "P", "Q"),            # round 2: equal sums
+    "PQ-P-Q": ("P", "Q", "-P", "-Q"),        # round 2: opposite sums, a cancellation read from records
+    "P-PQR": ("P", "-P", "Q", "R"),          # round 1 writes an identity record; round 2 copies B through the second fetch
+    "QRP-P": ("Q", "R", "P", "-P"),          # round 2 copies A
+    "OPQO": ("O", "P", "Q", "O"),            # identity rows of the point set as first and as second operand
+    "PQRSU": ("P", "Q", "R", "S", "U"),      # a fifth element: paired with nothing, then with the sum of a pair of pads
+}
+TORSION_LAYOUTS = {
+    "TTPQ": ("T", "T", "P", "Q"),            # T + T: equal points with y = 0, the identity and not a doubling
+    "PTQT": ("P", "T", "Q", "T"),            # generic additions with T; round 2 adds (P + T) + (Q + T)
+}
+# The pairs of ONE bucket of every layout at logG = 2, as {(round, kind): count} of pair_kinds, written down by hand: m entries
+# pair up in order in round 1 (five entries own 8 slots: the fifth is paired with nothing and a pair of pads follows), the
+# round-1 elements pair up in round 2.
+LAYOUT_PAIRS = {
+    "PPPP": {(1, "double"): 2, (2, "double"): 1},
+    "PQPQ": {(1, "generic"): 2, (2, "double"): 1},
+    "PQ-P-Q": {(1, "generic"): 2, (2, "cancel"): 1},
+    "P-PQR": {(1, "cancel"): 1, (1, "generic"): 1, (2, "copy_b"): 1},
+    "QRP-P": {(1, "generic"): 1, (1, "cancel"): 1, (2, "copy_a_identity"): 1},
+    "OPQO": {(1, "copy_b"): 1, (1, "copy_a_identity"): 1, (2, "generic"): 1},
+    "PQRSU": {(1, "generic"): 2, (1, "copy_a_absent"): 1, (1, "zero"): 1, (2, "generic"): 1, (2, "copy_a_identity"): 1},
+    "TTPQ": {(1, "cancel"): 1, (1, "generic"): 1, (2, "copy_b"): 1},
+    "PTQT": {(1, "generic"): 2, (2, "generic"): 1},
+}
+# ... and of the bucket that degenerate_pairs_in_parts spreads over two parts, m entries in each: the parts pair up on their own,
+# so a layout of four gives the pairs above twice in both rounds; of five, each part leaves its fifth entry paired with nothing,
+# the six elements need no pad and round 2 adds (P + Q) + (R + S), U + (P' + Q'), (R' + S') + U'.
+LAYOUT_PAIRS_TWO_PARTS = {name: {k: 2 * v for k, v in pairs.items()} for name, pairs in LAYOUT_PAIRS.items() if name != "PQRSU"}
+LAYOUT_PAIRS_TWO_PARTS["PQRSU"] = {(1, "generic"): 4, (1, "copy_a_absent"): 2, (2, "generic"): 3}
+
+
+def check_layout_pairs(dp, kinds):
+    """Every bucket of every lone scalar holds exactly the pairs written down for its layout (the planted bucket of
+    degenerate_pairs_in_parts: those of two parts)."""
+    planted = getattr(dp, "planted", {})
+    for j, (name, _) in enumerate(dp.groups):
+        assert kinds[j], name
+        for l, cnt in kinds[j]:
+            cnt = dict(cnt)
+            parts = cnt.pop("parts")
+            two = planted.get(j) == l
+            assert parts == (2 if two else 1), (name, l, parts)
+            assert cnt == (LAYOUT_PAIRS_TWO_PARTS if two else LAYOUT_PAIRS)[name], (name, l, cnt)
+        assert j not in planted or planted[j] in [l for l, _ in kinds[j]]
+
+
+class DegeneratePairs:
+    """cr: the Crafted input; groups: [(layout name, [point index of every role, ascending])]; edits: [(point index, source
+    point index or None, sign, torsion?)] -- row dst becomes sign * row src, the identity (src None) or T."""
+
+    def __init__(self, cr, groups, layouts):
+        self.cr, self.groups, self.layouts = cr, groups, layouts
+        self.edits = []
+        for name, pos in groups:
+            first = {}
+            for role, at in zip(layouts[name], pos):
+                letter = role.lstrip("-")
+                if letter == "O":
+                    self.edits.append((at, None, 1, False))
+                elif letter == "T":
+                    self.edits.append((at, None, 1, True))
+                elif letter in first:
+                    self.edits.append((at, first[letter], -1 if role[0] == "-" else 1, False))
+                else:
+                    assert role[0] != "-"
+                    first[letter] = at
+
+    def values(self, logs, q):
+        """{point index: (discrete log, torsion bit)} of every point of a group, after the edits; logs: index -> a_i."""
+        out = {at: (logs(at) % q, 0) for _, pos in self.groups for at in pos}
+        for at, src, sign, tors in self.edits:
+            out[at] = (0, 1) if tors else (0, 0) if src is None else (sign * logs(src) % q, 0)
+        return out
+
+
+def _lone_buckets_ok(cr, n_lone, bucket_sets, planted=None):
+    """No bucket of a lone scalar is shared: not with another lone scalar, not with a second digit of the same one, not with any
+    other pool entry that has points (craft keeps the uniform fill out, not the classes).  planted: {lone row: (magnitude, windows)}
+    -- the one bucket a row fills on purpose from several windows of a merged window; its bin holds no other digit of a lone row."""
+    mags = np.abs(cr.digits)
+    live = cr.counts > 0
+    for lo, hi in bucket_sets:
+        lone = mags[:n_lone, :, lo:hi]
+        vals = lone[lone > 0]
+        uniq, cnt = np.unique(vals, return_counts=True)
+        want = {}
+        for row, (mag, windows) in (planted or {}).items():
+            k_in = [k for k in windows if lo <= k < hi]
+            if k_in:
+                want[mag] = len(k_in)
+                fb = cr.fb[lo]
+                others = lone[row][lone[row] != mag]
+                if (((others[others > 0] - 1) >> fb) == ((mag - 1) >> fb)).any():
+                    return False
+        if any(int(c) != want.get(int(u), 1) for u, c in zip(uniq, cnt)):
+            return False
+        rest = mags[n_lone:, :, lo:hi][live[n_lone:]]
+        if np.isin(rest, uniq).any():
+            return False
+    if planted:      # no stray digit of another lone row in a planted bin either
+        for lo, hi in bucket_sets:
+            fb = cr.fb[lo]
+            bins = {(mag - 1) >> fb for mag, windows in planted.values() if any(lo <= k < hi for k in windows)}
+            lone = mags[:n_lone, :, lo:hi]
+            stray = (lone > 0) & np.isin((lone - 1) >> fb, list(bins)) & ~np.isin(lone, [m for m, _ in planted.values()])
+            if stray.any():
+                return False
+    return True
+
+
+def degenerate_pairs(plan, n, seed=21, pool=4096, reps=2, tables=False, layouts=None):
+    """Every layout `reps` times among uniform fill: one lone pool entry per group, its points anywhere in the point order."""
+    layouts = DEGENERATE_LAYOUTS if layouts is None else layouts
+    names = [name for _ in range(reps) for name in layouts]
+    classes = [Class(1, [], counts=[len(layouts[name])], lone=True) for name in names]
+    bucket_sets = plan.window_groups(n, True) if tables else [(k, k + 1) for k in range(plan.K)]
+    for attempt in range(32):
+        # (craft keeps the fill out of the lone scalars' buckets, not the lone scalars out of each other's: draw until they are)
+        cr = craft("degenerate_pairs", plan, n, classes, seed + 1000 * attempt, pool, tables)
+        if _lone_buckets_ok(cr, len(names), bucket_sets):
+            break
+    else:
+        raise AssertionError("no draw without a shared bucket among the lone scalars")
+    groups = [(name, np.nonzero(cr.order == j)[0].tolist()) for j, name in enumerate(names)]
+    assert all(len(pos) == len(layouts[name]) for name, pos in groups)
+    return DegeneratePairs(cr, groups, layouts)
+
+
+HEAVY_WINDOWS = (1, 4)      # the digit windows of the merged window in which a lone scalar of degenerate_pairs_in_parts has its bucket
+
+
+def degenerate_pairs_in_parts(plan, n, seed=22, pool=4096, reps=2, layouts=None):
+    """The layouts inside a MULTI-PART bin of a merged window (window tables, one group of all K windows).  A heavy class of 256
+    pool entries has every digit -- all K windows, both halves -- in one bin b, over the lower half of its buckets: 2 K records
+    per point, 2.5 part_len records in all, so the bin is cut into three parts, the cuts falling in windows 2 and 5 (a bin's
+    records are ordered by digit window, then point, then half).  Every lone scalar has one bucket of the upper half of bin b as
+    its digit in window 1 AND in window 4 (first half): the merged bucket holds the m entries of window 1 in part 0 and the m
+    entries of window 4, which read the rows 2^(3c) further up the tables, in part 1.  The parts pair up on their own: a bucket of
+    five entries leaves its fifth paired with nothing at the end of BOTH parts, and part 1 starts its pairs at part_pair_off and
+    its elements at the sub row of k_part_scan.  pair_kinds walks exactly that."""
+    layouts = DEGENERATE_LAYOUTS if layouts is None else layouts
+    K, c = plan.K, plan.c
+    assert plan.halves == 2 and plan.window_groups(n, True) == [(0, K)] and max(HEAVY_WINDOWS) < K - 1
+    window, b, fb, part_len = _target(plan, n, 0, None, True)
+    NB = 1 << fb
+    names = [name for _ in range(reps) for name in layouts]
+    assert len(names) <= NB // 2
+    classes, planted = [], {}
+    for j, name in enumerate(names):
+        off = NB // 2 + j
+        classes.append(Class(1, [Plant(k, b, [off]) for k in HEAVY_WINDOWS], counts=[len(layouts[name])], lone=True))
+        planted[j] = ((b << fb) + off + 1, HEAVY_WINDOWS)
+    m = 256
+    heavy_points = -(-(5 * part_len // 2) // (2 * K))
+    plants = [Plant(k, b, (np.arange(m) * 5 + 3 * k + h) % (NB // 2), half=h) for k in range(K) for h in range(2)]
+    classes.append(Class(m, plants, counts=split_counts(heavy_points, m)))
+    for attempt in range(32):
+        cr = craft("degenerate_pairs_in_parts", plan, n, classes, seed + 1000 * attempt, pool, True)
+        if _lone_buckets_ok(cr, len(names), [(0, K)], planted):
+            break
+    else:
+        raise AssertionError("no draw without a shared bucket among the lone scalars")
+    assert 2 * part_len < cr.bins[(0, b)] <= 3 * part_len
+    groups = [(name, np.nonzero(cr.order == j)[0].tolist()) for j, name in enumerate(names)]
+    dp = DegeneratePairs(cr, groups, layouts)
+    dp.planted = {j: mag for j, (mag, _) in planted.items()}
+    return dp
+
+
+ABSENT = None
+
+
+def combine(A, B, q):
+    """(kind, sum) of one pair of the tree as k_batch_add classifies it (ba_denominator, batch_add.h); an operand is ABSENT (an
+    empty slot) or (l, t) = l G + t T with T of order 2, (0, 0) the identity."""
+    inf_a, inf_b = A is ABSENT or A == (0, 0), B is ABSENT or B == (0, 0)
+    if inf_a and inf_b:
+        return "zero", (0, 0)
+    if inf_b:
+        return ("copy_a_absent" if B is ABSENT else "copy_a_identity"), A
+    if inf_a:
+        return "copy_b", B
+    if A == B:                                   # equal points: a doubling unless y = 0, which only T has (2 l = 0 mod q: l = 0)
+        return ("cancel", (0, 0)) if A == (0, 1) else ("double", (2 * A[0] % q, 0))
+    if A[1] == B[1] and (A[0] + B[0]) % q == 0:  # opposite points (-T = T)
+        return "cancel", (0, 0)
+    return "generic", ((A[0] + B[0]) % q, A[1] ^ B[1])
+
+
+def _bin_record_index(cr, lo, hi, fb, b):
+    """The records of bin b of the (merged) window [lo, hi) in record order -- by digit window, point, half -- as sorted linear
+    indices ((window - lo) * n + point) * halves + half."""
+    stack = np.stack([np.abs(cr.digits[:, :, k])[cr.order] for k in range(lo, hi)])
+    return np.flatnonzero(((stack > 0) & (((stack - 1) >> fb) == b)).ravel())
+
+
+def pair_kinds(dp, values, logG, glv=True):
+    """Walks the buckets of the lone scalars of `dp` the way the pair form does and counts the pairs of every kind:
+    {group index: [Counter((round, kind)) per bucket, ascending by bucket]}.  A bucket of a lone scalar holds entries of its group
+    alone (asserted), ordered by digit window (window tables), point, half; entry = sign * lambda^half * 2^(c (window - first of the
+    group)) * the point.  A bin of more than part_len records is cut into parts of part_len records (sort_kernels.h, "Parts of heavy
+    bins"): round 1 pairs a bucket's entries in order INSIDE each part, the odd one out of a part with nothing, and fills up to
+    roundup(2 * elements, 2^logG) / 2 elements with pairs of pads; round 2 pairs the elements."""
+    from collections import Counter
+
+    cr, pl = dp.cr, dp.cr.plan
+    q, lam, c, n, H = pl.cv.q, pl.cv.B.lam, pl.c, dp.cr.n, dp.cr.plan.halves
+    groups = pl.window_groups(cr.n, True) if cr.tables else [(k, k + 1) for k in range(pl.K)]
+    hists = cr.stats()[0]
+    mags = np.abs(cr.digits)
+    live = cr.counts > 0
+    bin_index = {}
+    out = {}
+    for j, (name, pos) in enumerate(dp.groups):
+        per_bucket = []
+        for gi, (lo, hi) in enumerate(groups):
+            for l in sorted({int(m) for m in mags[j, :, lo:hi].ravel() if m}):
+                owners = np.argwhere((mags[:, :, lo:hi] == l) & live[:, None, None])
+                assert {int(o[0]) for o in owners} == {j}, (name, l, owners)       # no other scalar touches the bucket
+                hist = hists[gi] if cr.tables else hists[lo]
+                fb, part_len = cr.fb[lo], cr.part_len[lo]
+                b = (l - 1) >> fb
+                multi = int(hist[1 + (b << fb):1 + ((b + 1) << fb)].sum()) > part_len
+                if multi and (lo, b) not in bin_index:
+                    bin_index[(lo, b)] = _bin_record_index(cr, lo, hi, fb, b)
+                entries = []
+                for _, h, kk in owners:
+                    d = int(cr.digits[j, h, lo + kk])
+                    w = (-1 if d < 0 else 1) * (lam if h else 1) * (1 << (c * int(kk)))
+                    for at in pos:
+                        v = values[at]
+                        assert not (v[1] and (glv or kk)), "T only where a scalar's digits are not split and the tables are not used"
+                        key = (int(kk) * n + at) * H + int(h)
+                        part = int(np.searchsorted(bin_index[(lo, b)], key)) // part_len if multi else 0
+                        entries.append((key, part, (v[0] * w % q, v[1])))
+                entries.sort()
+                assert len(entries) == int(hist[l])
+                cnt = Counter()
+                elements = []
+                for part in sorted({p for _, p, _ in entries}):
+                    mine = [v for _, p, v in entries if p == part]
+                    for e in range(0, len(mine), 2):
+                        kind, s = combine(mine[e], mine[e + 1] if e + 1 < len(mine) else ABSENT, q)
+                        cnt[(1, kind)] += 1
+                        elements.append(s)
+                G = 1 << logG
+                for _ in range((-2 * len(elements) % G) // 2):
+                    cnt[(1, "zero")] += 1
+                    elements.append((0, 0))
+                for e in range(0, len(elements), 2):
+                    cnt[(2, combine(elements[e], elements[e + 1], q)[0])] += 1
+                cnt["parts"] = len({p for _, p, _ in entries})
+                per_bucket.append((l, cnt))
+        out[j] = per_bucket
+    return out

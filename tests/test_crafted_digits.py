@@ -208,3 +208,120 @@ def test_shard_ranges_cut_at_a_bin_boundary():
     whole = cr.stats()
     parts = [cr.stats(keep=D.shard_ranges(pl, g, 2)) for g in range(2)]
     assert parts[0][2] + parts[1][2] == whole[2] and max(parts[0][1], parts[1][1]) == whole[1]
+
+
+# ---------------------------------------------------------------------------------------------- the pair form at small sizes
+
+ALL_W = ("bls377", "bls381", "pallas", "bn254", "grumpkin", "vesta")
+
+
+def test_geometry_takes_the_row_threshold():
+    """The default is msm_sort.hip's 2^23 rows; a lowered threshold leaves c >= 18 and logG >= 2 as the conditions."""
+    p18, p21 = D.Plan("bls377", 18), D.Plan("bls377", 21)
+    for n in (1 << 21, D.PAIR_N):
+        assert D.sort_paths(p18, n) == D.sort_paths(p18, n, chunk_rows=1 << 23)
+    assert D.sort_paths(p18, 1 << 21) == ["slots"] and D.sort_paths(p18, 1 << 21, chunk_rows=1 << D.PAIR_ROWS_LOG) == ["pairs"]
+    assert D.sort_paths(p18, 1 << 21, chunk_rows=1 << 21) == ["slots"]           # rows must EXCEED the threshold
+    assert D.sort_paths(p18, (1 << 21) + 1, chunk_rows=1 << 21) == ["pairs"]
+    assert D.sort_paths(D.Plan("bls377", 16), 1 << 21, chunk_rows=1 << D.PAIR_ROWS_LOG) == ["radix"]      # c < 18: never
+    assert D.sort_paths(D.Plan("ed377", 21), 1 << 23, chunk_rows=1 << D.PAIR_ROWS_LOG) == ["slots", "slots"]   # nor the Edwards curve
+    g = D.Geometry(p21, 1 << 24, 0, 3)
+    assert (g.mean, g.logG, g.rows) == (32, 2, 1 << 24)
+    g = D.Geometry(p18, 1 << 21, 0, 7)
+    assert (g.mean, g.logG, g.part_len, g.V) == (32, 2, 1 << 16, 7 << 10)
+
+
+@pytest.mark.parametrize("curve", ALL_W)
+def test_smallest_pair_form_sizes(curve):
+    """PAIR_MIN_PLAIN and PAIR_MIN_TABLES, derived by hand in tests/crafted_digits.py, against Geometry under the lowered
+    threshold: at the size every window group takes the pair form, one point less and a group's mean bucket is 31 -- logG = 1,
+    the slot form.  K per curve: b = 126 (BLS12-377, BN254, Grumpkin) or 127 bits after the endomorphism split."""
+    rows = 1 << D.PAIR_ROWS_LOG
+    K18 = {"bls377": 7, "bn254": 7, "grumpkin": 7, "bls381": 8, "pallas": 8, "vesta": 8}[curve]
+    K21 = {"bls377": 6, "bn254": 6, "grumpkin": 6, "bls381": 7, "pallas": 7, "vesta": 7}[curve]
+    for c, K in ((18, K18), (21, K21), (22, 6)):
+        pl = D.Plan(curve, c)
+        assert pl.K == K, (curve, c)
+        n = D.PAIR_MIN_PLAIN[c]
+        assert n == 1 << (c + 3)
+        assert set(D.sort_paths(pl, n, False, rows)) == {"pairs"} and set(D.sort_paths(pl, n - 1, False, rows)) == {"slots"}
+        assert all(D.Geometry(pl, n, lo, hi, False, rows).mean == 32 for lo, hi in pl.window_groups(n))
+        assert all(D.Geometry(pl, n - 1, lo, hi, False, rows).logG == 1 for lo, hi in pl.window_groups(n - 1))
+        n = D.PAIR_MIN_TABLES[(c, K)]
+        groups = pl.window_groups(n, True)
+        small = min(hi - lo for lo, hi in groups)
+        assert len(groups) == (1 if n < (1 << 21) else 2) and small == (K if len(groups) == 1 else K // 2)
+        assert n == -(-(1 << (c + 3)) // small)
+        assert set(D.sort_paths(pl, n, True, rows)) == {"pairs"}, (curve, c)
+        assert "slots" in D.sort_paths(pl, n - 1, True, rows), (curve, c)
+        assert min(D.Geometry(pl, n - 1, lo, hi, True, rows).mean for lo, hi in pl.window_groups(n - 1, True)) == 31
+    # at the default threshold the 18-bit sizes take the slot form; the 21- and 22-bit ones have more than 2^23 rows anyway (the
+    # GPU tests reach THEIR slot form by raising the threshold)
+    pl = D.Plan(curve, 18)
+    assert set(D.sort_paths(pl, 1 << 21)) == {"slots"} and set(D.sort_paths(pl, D.PAIR_MIN_TABLES[(18, K18)], True)) == {"slots"}
+    assert set(D.sort_paths(D.Plan(curve, 21), D.PAIR_MIN_TABLES[(21, K21)], True)) == {"pairs"}
+    assert set(D.sort_paths(D.Plan(curve, 21), D.PAIR_MIN_TABLES[(21, K21)], True, 1 << 40)) == {"slots"}
+
+
+def test_the_tables_cases_mix_both_forms():
+    """Two window groups of one call in different forms: on window tables the groups of a seven-window plan merge four and
+    three windows, and a threshold between 3 n and 4 n rows -- the default one at TABLES_N -- gives the first the pair form and
+    the second the slot form.  The plain path cannot: its groups all see n rows."""
+    p18 = D.Plan("bls377", 18)
+    assert p18.window_groups(D.TABLES_N, True) == [(0, 4), (4, 7)] and 3 * D.TABLES_N <= (1 << 23) < 4 * D.TABLES_N
+    assert D.sort_paths(p18, D.TABLES_N, True) == ["pairs", "slots"]
+    assert D.sort_paths(p18, D.TABLES_N, True, 1 << D.PAIR_ROWS_LOG) == ["pairs", "pairs"]
+    assert len(set(D.sort_paths(p18, D.PAIR_N, False, 1 << 22))) == 1
+
+
+def _layout_case(curve, tables, narrow_bits=0, layouts=None):
+    pl = D.Plan(curve, 18, narrow_bits)
+    n = D.PAIR_MIN_TABLES[(18, pl.K)] if tables else D.PAIR_MIN_PLAIN[18]
+    if tables == "parts":
+        return D.degenerate_pairs_in_parts(pl, n, layouts=layouts)
+    return D.degenerate_pairs(pl, n, tables=tables, layouts=layouts)
+
+
+@pytest.mark.parametrize("curve,tables,narrow_bits", [("bls377", False, 0), ("bn254", False, 0), ("bls377", True, 0), ("bn254", True, 0),
+                                                      ("bls377", "parts", 0), ("bn254", "parts", 0), ("bls377", False, D.NARROW_BITS)])
+def test_degenerate_layouts_produce_their_pairs(curve, tables, narrow_bits):
+    """Every layout, by the bucket walk of the pair form (pair_kinds): EVERY bucket of its lone scalar holds exactly the pairs
+    written down by hand for the layout, kind by kind and round by round (LAYOUT_PAIRS) -- and the bucket that "parts" spreads
+    over two parts of a multi-part bin those of LAYOUT_PAIRS_TWO_PARTS, with an entry paired with nothing at the end of both
+    parts; the lone scalars are below q and come back from the decomposition and the recoding."""
+    layouts = dict(D.DEGENERATE_LAYOUTS, **D.TORSION_LAYOUTS) if narrow_bits else None
+    dp = _layout_case(curve, tables, narrow_bits, layouts)
+    tables = bool(tables)
+    cr, pl = dp.cr, dp.cr.plan
+    cv = pl.cv
+    geo = [D.Geometry(pl, cr.n, lo, hi, tables, 1 << D.PAIR_ROWS_LOG) for lo, hi in pl.window_groups(cr.n, tables)]
+    assert {g.path for g in geo} == {"pairs"} and {g.logG for g in geo} == {2}
+    for j in range(len(dp.groups)):
+        s, hv = cr.pool_scalars()[j], cr.halves()[j]
+        assert 0 <= s < cv.q
+        if pl.halves == 2:
+            assert O.glv_decompose(s, cv.glv) == (hv[0], hv[1], False, False)
+        for hf in range(pl.halves):
+            assert [(l, neg and l != 0) for l, neg in O.signed_digits(hv[hf], pl.c, pl.K)] == [(abs(e), e < 0) for e in cr.digits[j][hf].tolist()]
+    logs = {at: 1000003 * (at + 1) + 7 for _, pos in dp.groups for at in pos}       # stand-ins for the a_i: distinct, non-zero
+    kinds = D.pair_kinds(dp, dp.values(logs.__getitem__, cv.q), 2, glv=not narrow_bits)
+    for name, pos in dp.groups:
+        assert pos == sorted(pos) and len(set(pos)) == len(pos)
+    D.check_layout_pairs(dp, kinds)
+    # a scalar has a bucket per non-zero digit: 2 K of them with the endomorphism (the planted one counts for two digits), K without
+    digits = pl.halves * pl.K
+    assert all(digits - 2 <= len(kinds[j]) + (j in getattr(dp, "planted", {})) <= digits for j in kinds)
+    if hasattr(dp, "planted"):
+        (w, b), records = max(cr.bins.items(), key=lambda kv: kv[1])
+        assert len(dp.planted) == len(dp.groups) and 2 * cr.part_len[0] < records <= 3 * cr.part_len[0]
+
+
+def test_combine_is_the_kernels_case_table():
+    q = 101
+    assert D.combine(D.ABSENT, D.ABSENT, q) == ("zero", (0, 0)) and D.combine((0, 0), D.ABSENT, q)[0] == "zero"
+    assert D.combine((5, 0), D.ABSENT, q) == ("copy_a_absent", (5, 0)) and D.combine((5, 0), (0, 0), q) == ("copy_a_identity", (5, 0))
+    assert D.combine((0, 0), (7, 0), q) == ("copy_b", (7, 0))
+    assert D.combine((5, 0), (5, 0), q) == ("double", (10, 0)) and D.combine((5, 0), (96, 0), q) == ("cancel", (0, 0))
+    assert D.combine((0, 1), (0, 1), q) == ("cancel", (0, 0))                   # T + T: y = 0
+    assert D.combine((5, 1), (5, 1), q) == ("double", (10, 0))                  # (P + T) doubled: 2 T = O
+    assert D.combine((5, 1), (96, 1), q) == ("cancel", (0, 0)) and D.combine((5, 1), (96, 0), q) == ("generic", (0, 1))

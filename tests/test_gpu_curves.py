@@ -235,17 +235,21 @@ def test_msm_large_known_discrete_logs(cv, lg):
 
 @pytest.mark.parametrize("c", [20, 22])
 def test_big_windows_chunk_ordered_round1(cv, c):
-    """2^23 points with windows of 2^19 / 2^21 buckets: the three-pass split, round 1 walking its pairs chunk by chunk of
-    the row table and leaving element records (one 64-byte record [x | y] per element on the 8-word field of Pallas, an x and
-    a y record on the 12-word field of BLS12-381), round 2 reading them back -- against the known discrete logs."""
+    """2^23 + 4096 points -- more than the 2^23 rows from which round 1 may take the pair form -- with windows of 2^19 / 2^21
+    buckets: the three-pass split at size.  c = 20 (mean bucket 32, logG = 2) takes the pair form: round 1 walks its pairs tile
+    by tile and leaves element records (one 64-byte record [x | y] per element on the 8-word field of Pallas, an x and a y record
+    on the 12-word field of BLS12-381), round 2 reads them back.  c = 22 (mean bucket 8, logG = 1) takes the slot form at this
+    size; its pair form is tests/test_gpu_pair_form.py's.  Both are asserted from the library's report, the result against the
+    known discrete logs."""
     from oracle import c_oracle
 
     ctx, B = cv.ctx, cv.B
-    n = 1 << 23
+    n = (1 << 23) + 4096
     a = ctx.generate_points(n, seed=777 + c, want_scalars=True, raw=True)
     dev, s = ctx.generate_scalars(n, seed=888 + c, to_host=True, raw=True)
     res, info = ctx.run_device(dev, n, c=c)
     assert info["c"] == c
+    assert set(ctx.test_last_sort_paths()) == {"pairs" if c == 20 else "slots"}, (ctx.test_last_sort_paths(), info)
     k = c_oracle.dot_mod(a, s, n, B.q)
     assert res.as_tuple() == O.aff_scale(k, (B.gx, B.gy), B.p), info
     res16, _ = ctx.run_device(dev, n)

@@ -508,13 +508,16 @@ def test_large_windows_three_pass_sort(gpu_ctx):
 
 @pytest.mark.parametrize("c", [19, 20, 22])
 def test_big_windows_chunk_ordered_round1(gpu_ctx, c_oracle, c):
-    """2^23 points (a 2 GB row table) with windows of 2^18 .. 2^21 buckets: the three-pass split at size, round 1 walking
-    its pairs chunk by chunk of the table (k_chunk_order) and leaving element rows, round 2 reading them back.  The result
-    must be the group element of the known discrete logs, whatever the window size."""
-    n = 1 << 23
+    """2^23 + 4096 points (more than the 2^23 rows, 2 GB, from which round 1 may take the pair form) with windows of 2^18 .. 2^21
+    buckets: the three-pass split at size.  c = 19 and c = 20 (mean bucket 64 and 32: logG >= 2) take the pair form -- round 1
+    walks the tile-ordered pairs of k_bin_pairs and leaves element records, round 2 reads them back --, c = 22 (mean bucket 8)
+    the slot form; asserted from the library's report.  The result must be the group element of the known discrete logs,
+    whatever the window size."""
+    n = (1 << 23) + 4096
     a = gpu_ctx.generate_points(n, seed=2323 + c, want_scalars=True, raw=True)
     dev, s = gpu_ctx.generate_scalars(n, seed=3232 + c, to_host=True, raw=True)
     res, info = gpu_ctx.run_device(dev, n, c=c)
+    assert set(gpu_ctx.test_last_sort_paths()) == {"slots" if c == 22 else "pairs"}, (gpu_ctx.test_last_sort_paths(), info)
     k = c_oracle.dot_mod(a, s, n, C.q)
     assert info["c"] == c
     assert res.as_tuple() == O.aff_scale(k, (C.gx, C.gy), P_MOD), info
@@ -522,6 +525,7 @@ def test_big_windows_chunk_ordered_round1(gpu_ctx, c_oracle, c):
     assert res16.as_tuple() == res.as_tuple()
     if c == 20:   # msmProjective's window structure (whole 253-bit scalars, no endomorphism: K = 13) through the same path
         resp, infop = gpu_ctx.run_device(dev, n, c=c, no_glv=True)
+        assert set(gpu_ctx.test_last_sort_paths()) == {"pairs"}
         assert infop["K"] == 13 and resp.as_tuple() == res.as_tuple()
 
 

@@ -42,7 +42,8 @@ def test_skewed_scalars_small(gpu_ctx, c_oracle, lg, c, kind):
 @pytest.mark.parametrize("lg,kind", [(23, "one"), (24, "one"), (24, "prover")])
 def test_skewed_scalars_through_the_tile_ordered_round(gpu_ctx, c_oracle, lg, kind):
     """2^23: seven 18-bit windows (padded slots); 2^24: six 21-bit windows, the pairs of round 1 emitted by the parts of the
-    one heavy bin of every window (k_bin_pairs), 24 tail rounds behind them."""
+    one heavy bin of every window (k_bin_pairs), 24 tail rounds behind them; at 2^24 a 22-bit plan (mean bucket 16) is back in the
+    slot form.  The forms are asserted from the library's report."""
     n = 1 << lg
     a = gpu_ctx.generate_points(n, seed=950 + lg, want_scalars=True, raw=True)
     s = workloads.scalars(kind, n, seed=lg)
@@ -51,11 +52,13 @@ def test_skewed_scalars_through_the_tile_ordered_round(gpu_ctx, c_oracle, lg, ki
     try:
         gpu_ctx.device_upload(dev, s.tobytes())
         res, info = gpu_ctx.run_device(dev, n, no_tables=True)
+        assert (info["c"], set(gpu_ctx.test_last_sort_paths())) == ((18, {"slots"}) if lg == 23 else (21, {"pairs"})), info
         assert res.as_tuple() == exp, (lg, kind, info)
         if kind == "one":
             assert info["max_bucket"] >= n, info      # every entry of a half scalar's window in one bucket
         if lg == 24:
             res22, i22 = gpu_ctx.run_device(dev, n, c=22)
+            assert set(gpu_ctx.test_last_sort_paths()) == {"slots"}, i22
             assert res22.as_tuple() == exp, (lg, kind, i22)
     finally:
         gpu_ctx.device_free(dev)

@@ -12,7 +12,7 @@ either side of its one-level fallback and with one busy coarse bin.  Every case 
   4. info["c"], info["K"], info["tables"].
 
 The shapes are the smallest that reach each path, derived from msm_sort.hip (crafted_digits.Geometry restates it, and every
-test asserts the path it means to take).  The pair form needs more than 2^23 table rows AND logG >= 2: at 2^23 + 4096 points
+test asserts the path it means to take, and that the library reports the same: msm_test_last_sort_paths).  The pair form needs more than 2^23 table rows AND logG >= 2: at 2^23 + 4096 points
 the mean bucket of a 21-bit plan is 16 (logG = 1, slot form), so the pair-form cases run seven 18-bit windows there.
 run_batch is fused into the one-level sort only (msm_batch.hip refuses any other path), so it has no case here.
 Needs an MI355X: `-m gpu`."""
@@ -85,6 +85,12 @@ def paths(cr):
     return [D.Geometry(cr.plan, cr.n, lo, hi, cr.tables).path for lo, hi in cr.plan.window_groups(cr.n, cr.tables)]
 
 
+def took(ctx, cr):
+    """The prediction against the library's own report of the call just made (msm_test_last_sort_paths)."""
+    got = ctx.test_last_sort_paths()
+    assert got == paths(cr), (cr.name, got, paths(cr))
+
+
 # ---------------------------------------------------------------------------------------------- bin split, slot form
 
 @pytest.mark.parametrize("cs", D.SLOT_CASES, ids=ids(D.SLOT_CASES))
@@ -95,6 +101,7 @@ def test_bin_split_slot_form(gpu_ctx, c_oracle, cs):
     a = points(gpu_ctx, cs.n)
     s = cr.scalars()
     res, info = gpu_ctx.run(s.tobytes(), c=cs.c, no_tables=True)
+    took(gpu_ctx, cr)
     assert res.as_tuple() == expected_point(c_oracle, CURVE_TABLE["bls377"], a, s, cs.n), (cs.id, info)
     check_info(cr, info, cs.c)
 
@@ -119,6 +126,7 @@ def test_bin_split_pair_form(gpu_ctx, c_oracle, big, cs):
     s = cr.scalars()
     gpu_ctx.device_upload(big, as_c(s))
     res, info = gpu_ctx.run_device(big, cs.n, c=cs.c, no_tables=True)
+    took(gpu_ctx, cr)
     assert res.as_tuple() == expected_point(c_oracle, CURVE_TABLE["bls377"], a, s, cs.n), (cs.id, info)
     check_info(cr, info, cs.c)
 
@@ -135,6 +143,7 @@ def test_bin_split_on_window_tables(gpu_ctx, c_oracle, big, cs):
     gpu_ctx.device_upload(big, as_c(s))
     gpu_ctx.precompute(cs.n)
     res, info = gpu_ctx.run_device(big, cs.n)
+    took(gpu_ctx, cr)
     assert res.as_tuple() == expected_point(c_oracle, CURVE_TABLE["bls377"], a, s, cs.n), (cs.id, info)
     check_info(cr, info, cs.c, tables=True)
 
@@ -151,6 +160,7 @@ def test_radix_split_and_its_fallbacks(gpu_ctx, c_oracle, cs):
     a = points(gpu_ctx, cs.n)
     s = cr.scalars()
     res, info = gpu_ctx.run(s.tobytes(), c=cs.c, no_tables=True)
+    took(gpu_ctx, cr)
     assert res.as_tuple() == expected_point(c_oracle, CURVE_TABLE["bls377"], a, s, cs.n), (cs.id, info)
     check_info(cr, info, cs.c)
     if cs.dist == "radix_edge":
@@ -179,6 +189,7 @@ def test_edwards_digits_pack_directly(ed_ctx, c_oracle, cs):
     a = points(ed_ctx, cs.n, seed=1701)
     s = cr.scalars()
     res, info = ed_ctx.run(s.tobytes(), c=cs.c, no_tables=True)
+    took(ed_ctx, cr)
     assert (res.x, res.y) == expected_point(c_oracle, CURVE_TABLE["ed377"], a, s, cs.n), (cs.id, info)
     check_info(cr, info, cs.c)
 
@@ -190,6 +201,7 @@ def test_narrow_scalars(gpu_ctx, c_oracle):
     assert paths(cr) == ["slots"]
     a = points(gpu_ctx, cs.n)
     res, info = gpu_ctx.run_narrow(cr.scalars(16).tobytes(), bits=cs.narrow_bits, signed=False, c=cs.c, width=16)
+    took(gpu_ctx, cr)
     assert res.as_tuple() == expected_point(c_oracle, CURVE_TABLE["bls377"], a, cr.scalars(), cs.n), info
     check_info(cr, info, cs.c)
 
@@ -204,6 +216,7 @@ def test_indexed_over_a_strict_subset(gpu_ctx, c_oracle):
     s = cr.scalars()
     a_sel = np.ascontiguousarray(np.frombuffer(a, dtype=np.uint8).reshape(N, 32)[idx])
     res, info = gpu_ctx.msm_indexed(s, idx, c=cs.c)
+    took(gpu_ctx, cr)
     assert res.as_tuple() == expected_point(c_oracle, CURVE_TABLE["bls377"], as_c(a_sel), s, cs.n), info
     check_info(cr, info, cs.c)
 
@@ -240,6 +253,7 @@ def test_bn254_nine_limb_digits(c_oracle):
         a = ctx.generate_points(cs.n, seed=1702, want_scalars=True, raw=True)
         s = cr.scalars()
         res, info = ctx.run(s.tobytes(), c=cs.c, no_tables=True)
+        took(ctx, cr)
         assert res.as_tuple() == expected_point(c_oracle, cv, a, s, cs.n), info
         check_info(cr, info, cs.c)
     finally:

@@ -109,8 +109,9 @@ def test_two_contexts_from_two_threads():
 
 def test_degenerate_inputs_through_the_big_window_paths():
     """2^23 copies of one point, then P and -P alternating, at c = 22: every pair of the tree is a doubling or a cancellation,
-    and it goes through the three-pass sort, the chunk-ordered round 1 and the element records.  Expected: (sum of the signed
-    scalars) P."""
+    and it goes through the three-pass sort and the bucket-ordered slot form of round 1 (2^23 rows are not MORE than 2^23, and a
+    mean bucket of 8 is too shallow for the pair form at any size: asserted from the library's report).  Degenerate pairs in
+    the pair form and its element records are tests/test_gpu_pair_form.py's.  Expected: (sum of the signed scalars) P."""
     import numpy as np
 
     from montgomery_amd.api import MsmContext
@@ -133,6 +134,7 @@ def test_degenerate_inputs_through_the_big_window_paths():
             ctx.set_points(O.points_to_bytes(pts, 48) * (n // 2))
             k = scalar_sum(signs) % C.q
             res, info = ctx.run(sc.tobytes(), c=22)
+            assert set(ctx.test_last_sort_paths()) == {"slots"}, info
             assert info["c"] == 22 and res.as_tuple() == (O.aff_scale(k, P, C.p) if k else None), info
     finally:
         ctx.close()
