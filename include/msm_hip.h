@@ -509,7 +509,7 @@ int msm_test_batch_add_mode(msm_ctx* ctx, const uint8_t* g, const uint8_t* h, ui
 /* Bucket reduction alone (Weierstrass curves): buckets = K x L affine points (x || y, 48-byte LE; (0, 0) = empty bucket),
  * bucket l of window k at index k L + l - 1; L a power of two.  Writes P_k = sum_l l B_(k,l) as K x 144 bytes (X || Y || Z)
  * and the device time of the reduction in *ms_out.
- *   mode 0: as the MSM does it -- projective row / triangle sums per chunk of buckets and bit-sliced weights
+ *   mode 0: as the MSM does it -- bucket finish, then projective row / triangle sums per chunk of buckets and bit-sliced weights
  *           (reduceBucketsColumnProjective, src/msm-batched-affine.ts:556-583);
  *   mode 1: the all-affine reduction of the reference's single-thread MSM (reduceBucketsAffine,
  *           src/msm-batched-affine-single-thread.ts:522-667, doc/zprize22.md:317-358) out of in-place batched-affine
@@ -528,7 +528,7 @@ int msm_test_bucket_reduce(msm_ctx* ctx, const uint8_t* buckets, int32_t K, uint
  *   tc     buckets per lane of the reduction: 0 = the library's rule, else a power of two in 2 .. 32
  * Writes K x 144 bytes (X || Y || Z; Z = 0: the identity of a Weierstrass curve), without merged P_k = sum_l l B_(k,l).
  * perm_out (may be NULL): K L words, the order in which the finish took the buckets -- descending by element count, counts
- * from 63 up alike -- or 0, 1, 2, ... where it did not order them (fewer than 4096 buckets, or no element at all). */
+ * from 63 up alike -- or 0, 1, 2, ... where it did not order them (fewer than 4096 buckets). */
 int msm_test_bucket_sums(msm_ctx* ctx, const uint8_t* pool, uint64_t n_pool, const uint32_t* off, const uint32_t* elems, int32_t K,
                          uint32_t L, int merged, int stride, uint32_t tc, uint8_t* sums_out, uint32_t* perm_out);
 /* The sort path of a window group -- which of the forms of the sort and of round 1 of the accumulation tree it took:

@@ -15,11 +15,9 @@
   X(msm::k_batch_add<CV MSM_COMMA msm::MODE_REGULAR>, (msm::BatchArgs))                                                  \
   X(msm::k_batch_add<CV MSM_COMMA msm::MODE_SEARCH>, (msm::BatchArgs))                                                   \
   X(msm::k_bucket_finish<CV>, (uint32_t*, const uint4*, uint64_t, const uint32_t*, uint32_t, const uint32_t*))                     \
-  X(msm::k_bucket_reduce<CV>, (uint32_t*, uint32_t*, const uint4*, uint64_t, const uint32_t*, const uint32_t*, uint32_t, \
-                               uint32_t, uint32_t, uint32_t))                                                            \
+  X(msm::k_bucket_reduce<CV>, (uint32_t*, uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t))           \
   X(msm::k_window_sum<CV>, (uint32_t*, const uint32_t*, uint32_t))                                                       \
-  X(msm::k_column_tree<CV>, (uint32_t*, const uint32_t*, uint32_t, uint32_t))                                            \
-  X(msm::k_bit_tree<CV>, (uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, int, int, uint32_t))          \
+  X(msm::k_bit_tree<CV>, (uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, int, uint32_t))               \
   X(msm::k_test_fp<CV>, (uint32_t*, const uint32_t*, const uint32_t*, uint32_t, int))                                    \
   X(msm::k_test_batch_inverse<CV>, (uint32_t*, const uint32_t*, uint32_t, uint32_t))                                     \
   X(msm::k_test_glv<CV>, (uint32_t*, const uint32_t*, uint32_t))                                                         \

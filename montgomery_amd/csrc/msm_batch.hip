@@ -62,7 +62,7 @@ void run_batch_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl_in, con
   TreeOut to;
   accumulate_window_group(ctx, w, pl, kc, p_lo, so, st, to);
   // unmerged: a merged reduction would fold the windows of different elements into one slot
-  reduce_buckets(ctx, w, to.fin, to.fin_cap, to.off_fin, to.bucket_proj, pl.L, kc, part, false, pl.c);
+  reduce_buckets(ctx, w, to.bucket_proj, pl.L, kc, part, false, pl.c);
   add_group_times(w, st);
 }
 

@@ -2,8 +2,9 @@
 //   msm_plan.hip      window size, plan, launch geometry, workspace budget model, the schedule of a call's window groups
 //                     (group_schedule: pure arithmetic, tested on the CPU by tests/test_group_schedule.py), error helpers
 //   msm_sort.hip      digits + counting sort of one window group (driver of sort_kernels.h)
-//   msm_tree.hip      accumulation tree of one window group (driver of k_batch_add / k_te_add) + k_bucket_finish
-//   msm_reduce.hip    bucket reduction, and the host tail over window sums (sum, Horner, to-affine, wire form, combine)
+//   msm_tree.hip      accumulation tree of one window group (driver of k_batch_add / k_te_add), always ended by k_bucket_finish
+//   msm_reduce.hip    bucket reduction over the finished bucket sums, and the host tail over window sums (sum, Horner, to-affine,
+//                     wire form, combine): one implementation over the two host point kinds (Weierstrass / Edwards)
 //   msm_upload.hip    staged and pipelined host -> device transfers
 //   msm_pipeline.hip  runs a schedule: window groups on two streams, their sums added back; multi-device fan-out, call statistics,
 //                     and the begin / finish every full-MSM entry point shares (call_begin, call_finish)
@@ -53,6 +54,7 @@
 // Policy knobs -- the six thresholds that are re-measured when a plan changes (MSM_GROUPS, MSM_MAX_STEPS, MSM_PBL, MSM_TC,
 // MSM_FINISH_MAX, MSM_TAIL_MIN) -- are environment variables ONLY in builds made with -DMSM_TUNING (make ab EXTRA=-DMSM_TUNING,
 // tools/knob_sweep.sh); the product never reads the environment.  The knobs of closed experiments left in round 6.
+// MSM_TC is rounded down to a power of two where it is read (reduce_buckets): a window is cut into 2^nbits chunks.
 #ifdef MSM_TUNING
 #define MSM_KNOB(var, name, lo) do { if (const char* _e = getenv(name)) var = std::max<long long>((lo), atoll(_e)); } while (0)
 #define MSM_KNOB_SET(name) (getenv(name) != nullptr)
@@ -526,9 +528,9 @@ void fe6_to_bytes(uint8_t* out, const msm_host::Fe6& a);
 // context's k_dev_to_host (F = hc.F) or k_te_to_host (F = hte.F)
 void device_coord_to_wire(const msm_host::Field6& F, const msm_host::Fe6& k_to_host, const uint32_t* w, int nw, uint8_t* out);
 void plane_element_to_wire(const msm_ctx* ctx, const uint32_t* planes, uint64_t cap, uint64_t e, uint8_t* out_xy);
-void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4* fin, uint64_t fin_cap, const uint32_t* off_fin,
-                    const uint32_t* bucket_proj, uint32_t L, int kc, uint32_t* h_partials_out, bool merged = false, int stride = 0,
-                    uint32_t tc_force = 0);
+// P_k = sum_l l B_(k,l) of kc windows of L buckets (a power of two) over the bucket sums of finish_buckets -> kc slots on the host
+void reduce_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* bucket_proj, uint32_t L, int kc, uint32_t* h_partials_out,
+                    bool merged = false, int stride = 0, uint32_t tc_force = 0);
 // The host tail: what happens to window sums between the bucket reduction and the caller.  A slot is ctx->sum_words() words;
 // `words` are K slots in a row.  These read the context's curve constants only, so any number of host threads may call them.
 void sum_set_identity(const msm_ctx* ctx, uint32_t* slot);
@@ -577,10 +579,7 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
                        GroupStats& st, SortOut& so, GroupDigits* share = nullptr);
 // what the tree leaves behind for the bucket reduction
 struct TreeOut {
-  const uint4* fin = nullptr;   // tree buffer holding what is left of every bucket
-  uint64_t fin_cap = 0;
-  const uint32_t* off_fin = nullptr;
-  const uint32_t* bucket_proj = nullptr;   // bucket sums from k_bucket_finish (projective / extended)
+  const uint32_t* bucket_proj = nullptr;   // one bucket sum per bucket from k_bucket_finish (projective / extended, raw limbs)
 };
 // kc: windows of the group as the tree sees them (1 on window tables); row_off: first row of the point table the payloads count from
 // (0 on window tables: every group reads them from table 0)

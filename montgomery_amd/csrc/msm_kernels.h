@@ -438,7 +438,8 @@ __global__ void __launch_bounds__(256) k_digits_batch(uint32_t* dig, BatchScalar
 }
 
 // ---------------------------------------------------------------------------------------------
-// projective points in raw limb form (3 x 13 words) between the reduction kernels
+// projective points in raw limb form (3 x 13 words) between the reduction kernels: what k_bucket_finish writes and
+// tools/ubench_bt.hip reads (the reduction kernels go through ProjPT below)
 // ---------------------------------------------------------------------------------------------
 
 template <class F>
@@ -447,24 +448,8 @@ MSM_DEV void proj_store(uint32_t* dst, const Proj<F>& P) {
 #pragma unroll
   for (int l = 0; l < NL; l++) { dst[l] = P.X.l[l]; dst[NL + l] = P.Y.l[l]; dst[2 * NL + l] = P.Z.l[l]; }
 }
-template <class F>
-MSM_DEV void proj_load(Proj<F>& P, const uint32_t* src) {
-  constexpr int NL = F::NL;
-#pragma unroll
-  for (int l = 0; l < NL; l++) { P.X.l[l] = src[l]; P.Y.l[l] = src[NL + l]; P.Z.l[l] = src[2 * NL + l]; }
-}
 
 // "planar" form for arrays that consecutive lanes walk together: word w of element j at base[w * stride + j]
-template <class F>
-MSM_DEV void proj_store_planar(uint32_t* base, uint64_t stride, uint64_t j, const Proj<F>& P) {
-  constexpr int NL = F::NL;
-#pragma unroll
-  for (int l = 0; l < NL; l++) {
-    base[(uint64_t)l * stride + j] = P.X.l[l];
-    base[(uint64_t)(NL + l) * stride + j] = P.Y.l[l];
-    base[(uint64_t)(2 * NL + l) * stride + j] = P.Z.l[l];
-  }
-}
 template <class F>
 MSM_DEV void proj_load_planar(Proj<F>& P, const uint32_t* base, uint64_t stride, uint64_t j) {
   constexpr int NL = F::NL;
@@ -516,208 +501,24 @@ __global__ void __launch_bounds__(256) k_bucket_finish(uint32_t* bucket_proj, co
   proj_store(bucket_proj + (uint64_t)b * (3 * NL), acc);
 }
 
-// rows != nullptr: "bit-sliced" mode -- the chunk's plain sum is written to rows[id] and its local triangle to
-// columns[id]; the weight (lstart - 1) = ch * TC is applied later through per-bit sums (k_bit_tree) instead of a
-// double-and-add chain in every lane.
-// bucket_proj != nullptr: bucket sums come from k_bucket_finish (projective, one per bucket) instead of the tree buffer
-template <class CV>
-__global__ void __launch_bounds__(64) k_bucket_reduce(uint32_t* columns, uint32_t* rows, const uint4* fin, uint64_t fin_cap,
-                                                       const uint32_t* off_fin, const uint32_t* bucket_proj, uint32_t L,
-                                                       uint32_t TC, uint32_t nchunks, uint32_t k_cnt) {
-  using F = typename CV::F;
-  constexpr int NL = F::NL, NW = F::NW, NP = F::NW / 4;
-  uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= nchunks * k_cnt) return;
-  uint32_t kk = id / nchunks, ch = id - kk * nchunks;
-  uint32_t lstart = ch * TC + 1;                       // bucket indices l are 1-based
-  uint32_t lend = min(lstart + TC - 1, L);
-  Proj<F> row, tri;
-  proj_set_zero<F>(row);
-  proj_set_zero<F>(tri);
-#pragma unroll 1
-  for (uint32_t l = lend; l >= lstart; l--) {
-    uint64_t b = (uint64_t)kk * L + (l - 1);
-    Proj<F> Q;
-    if (bucket_proj) {
-      proj_load(Q, bucket_proj + b * (3 * NL));
-      proj_add<F>(row, row, Q);
-    } else {
-      // every element the tree left in this bucket goes straight into the running row sum (mixed additions): no separate
-      // pass that first sums each bucket on its own, and one full addition per bucket less
-      const uint32_t o0 = off_fin[b], o1 = off_fin[b + 1];
-      uint32_t nx[NW], ny[NW];
-      if (o0 < o1) {
-        load_planes3(nx, fin, fin_cap, 0, o0);
-        load_planes3(ny, fin, fin_cap, NP, o0);
-      }
-#pragma unroll 1
-      for (uint32_t o = o0; o < o1; o++) {
-        const bool qinf = nx[NW - 1] == INF_WORD;
-        fe_unpack<F>(Q.X, nx);
-        fe_unpack<F>(Q.Y, ny);
-        if (o + 1 < o1) {   // the next element's words are in flight during the addition
-          load_planes3(nx, fin, fin_cap, 0, o + 1);
-          load_planes3(ny, fin, fin_cap, NP, o + 1);
-        }
-        proj_add_mixed<F>(row, row, Q, qinf);
-      }
-    }
-    proj_add<F>(tri, tri, row);
-  }
-  if (rows) {   // per window a [39][nchunks] matrix each: lanes (= consecutive chunks) write and k_bit_tree reads coalesced
-    proj_store_planar(rows + (uint64_t)kk * (3 * NL) * nchunks, nchunks, ch, row);
-    proj_store_planar(columns + (uint64_t)kk * (3 * NL) * nchunks, nchunks, ch, tri);
-    return;
-  }
-  uint32_t ls = lstart - 1;
-  if (ls) {
-#pragma unroll 1
-    while (true) {
-      if (ls & 1) proj_add<F>(tri, tri, row);
-      ls >>= 1;
-      if (ls == 0) break;
-      proj_double<F>(row, row);
-    }
-  }
-  proj_store(columns + (uint64_t)id * (3 * NL), tri);
-}
-
 // ---------------------------------------------------------------------------------------------
-// k_window_sum: P_k = sum of the window's columns; one workgroup per window
-// output: 3 x 12 packed canonical Montgomery words (X, Y, Z) per window
+// The bucket reduction P_k = sum_l l B_(k,l) over the bucket sums of k_bucket_finish, for both kinds of point: every stage is
+// one body over a point-kind policy PT, and a kernel per kind around it with its own __shared__ array.  What a kind of point
+// offers: the point P, its W raw words between the reduction kernels (word w = limb w of the point as it sits in registers),
+// the identity, the group addition and doubling, and the packed window sum of PW words the host reads.
+// ProjPT<F>: projective points of a Weierstrass curve; TePT (te_kernels.h): extended points of the Edwards curve.
 // ---------------------------------------------------------------------------------------------
 
-constexpr int WS_THREADS = 256;
-
-template <class CV>
-__global__ void __launch_bounds__(WS_THREADS) k_window_sum(uint32_t* partials, const uint32_t* columns, uint32_t nchunks) {
-  using F = typename CV::F;
-  constexpr int NL = F::NL, NW = F::NW, NP = F::NW / 4;
-  __shared__ uint32_t lds[3 * NL * WS_THREADS];
-  const uint32_t kk = blockIdx.x, tid = threadIdx.x;
-  Proj<F> acc;
-  proj_set_zero<F>(acc);
-#pragma unroll 1
-  for (uint32_t j = tid; j < nchunks; j += WS_THREADS) {
-    Proj<F> Q;
-    proj_load(Q, columns + ((uint64_t)kk * nchunks + j) * (3 * NL));
-    proj_add<F>(acc, acc, Q);
-  }
-#pragma unroll 1
-  for (uint32_t s = WS_THREADS / 2; s >= 1; s >>= 1) {
-    if (tid >= s && tid < 2 * s) {
-#pragma unroll
-      for (int l = 0; l < NL; l++) {
-        lds[(l)*WS_THREADS + tid] = acc.X.l[l];
-        lds[(NL + l) * WS_THREADS + tid] = acc.Y.l[l];
-        lds[(2 * NL + l) * WS_THREADS + tid] = acc.Z.l[l];
-      }
-    }
-    __syncthreads();
-    if (tid < s) {
-      Proj<F> Q;
-#pragma unroll
-      for (int l = 0; l < NL; l++) {
-        Q.X.l[l] = lds[(l)*WS_THREADS + tid + s];
-        Q.Y.l[l] = lds[(NL + l) * WS_THREADS + tid + s];
-        Q.Z.l[l] = lds[(2 * NL + l) * WS_THREADS + tid + s];
-      }
-      proj_add<F>(acc, acc, Q);
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    fe_reduce_2p<F>(acc.X);
-    fe_reduce_2p<F>(acc.Y);
-    fe_reduce_2p<F>(acc.Z);
-    uint32_t* dst = partials + (uint64_t)kk * PART_WORDS;
-    uint32_t w[NW];
-#pragma unroll
-    for (int j = 0; j < PART_WORDS; j++) dst[j] = 0;
-    fe_pack<F>(w, acc.X);
-#pragma unroll
-    for (int j = 0; j < NW; j++) dst[j] = w[j];
-    fe_pack<F>(w, acc.Y);
-#pragma unroll
-    for (int j = 0; j < NW; j++) dst[12 + j] = w[j];
-    fe_pack<F>(w, acc.Z);
-#pragma unroll
-    for (int j = 0; j < NW; j++) dst[24 + j] = w[j];
-  }
-}
-
-// first stage of the window sum when a window has many chunk columns: block (b, kk) tree-sums columns
-// [b * per_block, (b + 1) * per_block) of window kk into one raw projective point, so that no lane adds more
-// than a couple of columns serially (the sum of 8192 columns drops from 40 dependent additions to ~18)
-template <class CV>
-__global__ void __launch_bounds__(WS_THREADS) k_column_tree(uint32_t* out, const uint32_t* columns, uint32_t nchunks,
-                                                            uint32_t per_block) {
-  using F = typename CV::F;
-  constexpr int NL = F::NL, NW = F::NW, NP = F::NW / 4;
-  __shared__ uint32_t lds[3 * NL * WS_THREADS];
-  const uint32_t b = blockIdx.x, kk = blockIdx.y, tid = threadIdx.x, nblk = gridDim.x;
-  const uint32_t beg = b * per_block, end = min(beg + per_block, nchunks);
-  Proj<F> acc;
-  proj_set_zero<F>(acc);
-#pragma unroll 1
-  for (uint32_t j = beg + tid; j < end; j += WS_THREADS) {
-    Proj<F> Q;
-    proj_load(Q, columns + ((uint64_t)kk * nchunks + j) * (3 * NL));
-    proj_add<F>(acc, acc, Q);
-  }
-#pragma unroll 1
-  for (uint32_t s = WS_THREADS / 2; s >= 1; s >>= 1) {
-    if (tid >= s && tid < 2 * s) {
-#pragma unroll
-      for (int l = 0; l < NL; l++) {
-        lds[(l)*WS_THREADS + tid] = acc.X.l[l];
-        lds[(NL + l) * WS_THREADS + tid] = acc.Y.l[l];
-        lds[(2 * NL + l) * WS_THREADS + tid] = acc.Z.l[l];
-      }
-    }
-    __syncthreads();
-    if (tid < s) {
-      Proj<F> Q;
-#pragma unroll
-      for (int l = 0; l < NL; l++) {
-        Q.X.l[l] = lds[(l)*WS_THREADS + tid + s];
-        Q.Y.l[l] = lds[(NL + l) * WS_THREADS + tid + s];
-        Q.Z.l[l] = lds[(2 * NL + l) * WS_THREADS + tid + s];
-      }
-      proj_add<F>(acc, acc, Q);
-    }
-    __syncthreads();
-  }
-  if (tid == 0) proj_store(out + ((uint64_t)kk * nblk + b) * (3 * NL), acc);
-}
-
-// Bit-sliced weighting of the chunk sums:  sum_ch (ch * TC) * row_ch = TC * sum_b 2^b * S_b  with
-// S_b = sum of row_ch over the chunks whose index has bit b set.  Wave (blk, y, kk) sums, for window kk,
-//   y <  nbits : its share of the n_in / 2 rows whose chunk index has bit y set (enumerated directly),
-//   y == nbits : its share of the n_in local triangles (columns), unmasked.
-// masked = 0 is the second stage: plain sums of the first stage's [kk][y][n_in] block results.
-// The K * (nbits + 1) results go to the host, which applies the 2^b weights with nbits doublings per window --
-// one chain per window instead of one per lane (the reference applies the same weight by double-and-add per
-// chunk, src/msm-batched-affine.ts:574-580).
-//
-// One wave per block: every lane adds a few elements serially, then the lane sums are folded through LDS in
-// log2 steps.  A projective addition is ~7000 dependent VALU instructions (15 us for a lone wave), so what
-// matters is the number of additions in sequence, not their count: ~8 + 6 here, then log2(n_in) in the second stage.
-constexpr int BT_THREADS = 64;
-
-// amdgpu_waves_per_eu(1, 1): one wave per SIMD.  The work is a chain of dependent additions per wave; a second wave on
-// the same SIMD halves the speed of both, and the dispatcher fills a SIMD before it moves to the next one (measured:
-// 40 us per addition in sequence with two resident waves against 19 us alone).
-// What a kind of point must offer the bit tree: raw words (limb w of the point as it sits in registers), the group addition,
-// and the packed window sum the host reads.
 template <class F>
 struct ProjPT {
   using P = Proj<F>;
-  static constexpr int W = 3 * F::NL;     // raw words per point between the reduction kernels
-  static constexpr int PW = PART_WORDS;   // words of a packed window sum
+  static constexpr int W = 3 * F::NL;
+  static constexpr int PW = PART_WORDS;
   static MSM_DEV void zero(P& p) { proj_set_zero<F>(p); }
   static MSM_DEV void add(P& r, const P& a, const P& b) { proj_add<F>(r, a, b); }
+  static MSM_DEV void dbl(P& r, const P& a) { proj_double<F>(r, a); }
   static MSM_DEV uint32_t& word(P& p, int w) { return w < F::NL ? p.X.l[w] : w < 2 * F::NL ? p.Y.l[w - F::NL] : p.Z.l[w - 2 * F::NL]; }
+  // 3 x 12 packed canonical Montgomery words (X, Y, Z)
   static MSM_DEV void pack(uint32_t* dst, P& acc) {
     constexpr int NW = F::NW;
     fe_reduce_2p<F>(acc.X);
@@ -738,161 +539,210 @@ struct ProjPT {
   }
 };
 
-// the body of k_bit_tree / k_te_bit_tree (see above); one wave per block
+// a point as W raw words in a row ...
 template <class PT>
-MSM_DEV void bit_tree_body(uint32_t* out, const uint32_t* rows, const uint32_t* tris, uint32_t n_in, uint32_t nbits, int masked,
-                           int pack_out, uint32_t nblk_out, uint32_t* lds) {
+MSM_DEV void pt_load(typename PT::P& p, const uint32_t* src) {
+#pragma unroll
+  for (int w = 0; w < PT::W; w++) PT::word(p, w) = src[w];
+}
+template <class PT>
+MSM_DEV void pt_store(uint32_t* dst, typename PT::P& p) {
+#pragma unroll
+  for (int w = 0; w < PT::W; w++) dst[w] = PT::word(p, w);
+}
+// ... and in the planar form of arrays that consecutive lanes walk together
+template <class PT>
+MSM_DEV void pt_load_planar(typename PT::P& p, const uint32_t* base, uint64_t stride, uint64_t j) {
+#pragma unroll
+  for (int w = 0; w < PT::W; w++) PT::word(p, w) = base[(uint64_t)w * stride + j];
+}
+template <class PT>
+MSM_DEV void pt_store_planar(uint32_t* base, uint64_t stride, uint64_t j, typename PT::P& p) {
+#pragma unroll
+  for (int w = 0; w < PT::W; w++) base[(uint64_t)w * stride + j] = PT::word(p, w);
+}
+
+// k_bucket_reduce / k_te_bucket_reduce (normalizeBucketsStorage + reduceBucketsColumnProjective; Edwards: reduceBucketsChunk,
+// src/msm-basic.ts:180-211): lane (kk, ch) walks the TC buckets of chunk ch of window kk from the top; `row` is the running
+// sum of the bucket sums, `tri` the sum of the running sums = sum_l (l - lstart + 1) B_l, the chunk's local triangle.
+// rows == nullptr: the lane applies the weight (lstart - 1) = ch * TC to `row` by double-and-add and writes the chunk's
+// column to columns[id].
+// rows != nullptr: "bit-sliced" mode -- the chunk's plain sum is written to rows and its local triangle to columns, both
+// planar ([window][word][chunk]: lanes = consecutive chunks write and k_bit_tree reads coalesced); the weight is applied
+// later through per-bit sums (k_bit_tree) instead of a double-and-add chain in every lane.
+template <class PT>
+MSM_DEV void bucket_reduce_body(uint32_t* columns, uint32_t* rows, const uint32_t* bucket_sums, uint32_t L, uint32_t TC,
+                                uint32_t nchunks, uint32_t k_cnt) {
   using P = typename PT::P;
   constexpr int W = PT::W;
-  // First stage (masked): grid.x enumerates, per window, nbits masked sums of nblk_out / 2 blocks each and then the
-  // triangle sum of nblk_out blocks -- the masked sums have half as many elements, so every wave of the launch has
-  // the same number of additions in sequence.  Second stage (masked == 2): grid (1, nbits + 1, kc).
-  uint32_t blk = blockIdx.x, y = blockIdx.y, nblk = gridDim.x;
-  const uint32_t kk = blockIdx.z, tid = threadIdx.x;
-  if (masked >= 3) {
-    // Two-dimensional form (round 6).  The masked sums above add every row to half of the nbits sums: nchunks * nbits / 2
-    // additions.  With the chunk index cut as ch = hi * M_lo + lo,  sum_ch ch * row_ch = M_lo * sum_hi hi * A_hi + sum_lo lo * B_lo
-    // with A_hi = sum_lo row (a run of M_lo rows) and B_lo = sum_hi row (a column of M_hi rows): 2 * nchunks additions, and the
-    // bit-sliced weighting then runs over the M_hi + M_lo sums only -- S_b = masked sum over B for the low bits, over A for the
-    // high ones: the same nbits + 1 results, so the host tail is unchanged.
-    //   masked == 3: grid (M_hi + M_lo + nblk_out, 1, kc): block -> A_hi | B_lo | a share of the local triangles; raw points to
-    //                out[kk][M_hi + M_lo + nblk_out]
-    //   masked == 4: grid (1, nbits + 1, kc) over those (`rows` = the first stage's output): y < h0: bit y of lo over B;
-    //                y < nbits: bit y - h0 of hi over A; y == nbits: the nblk_out triangle shares
-    const uint32_t h1 = nbits / 2, h0 = nbits - h1, M_lo = 1u << h0, M_hi = 1u << h1, per_kk = M_hi + M_lo + nblk_out;
-    uint32_t count, kind;   // kind 0: A run, 1: B column, 2: triangle share (first stage); 3: masked over stage-1 slots, 4: plain over slots
-    uint32_t a0 = 0, a1 = 0;
-    if (masked == 3) {
-      if (blk < M_hi) { kind = 0; count = M_lo; a0 = blk * M_lo; }
-      else if (blk < M_hi + M_lo) { kind = 1; count = M_hi; a0 = blk - M_hi; }
-      else {
-        kind = 2;
-        const uint32_t t = blk - M_hi - M_lo, span = (n_in + nblk_out - 1) / nblk_out;
-        a0 = min(t * span, n_in);
-        count = min(a0 + span, n_in) - a0;
-      }
-    } else {
-      if (y < h0) { kind = 3; count = M_lo >> 1; a0 = M_hi; a1 = y; }
-      else if (y < nbits) { kind = 3; count = M_hi >> 1; a0 = 0; a1 = y - h0; }
-      else { kind = 4; count = nblk_out; a0 = M_hi + M_lo; }
-    }
-    uint32_t m = 1;
-    while (m < count && m < BT_THREADS) m <<= 1;
-    const uint32_t gl = tid & (m - 1);
-    P acc;
-    PT::zero(acc);
+  uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= nchunks * k_cnt) return;
+  uint32_t kk = id / nchunks, ch = id - kk * nchunks;
+  uint32_t lstart = ch * TC + 1;                       // bucket indices l are 1-based
+  uint32_t lend = min(lstart + TC - 1, L);
+  P row, tri;
+  PT::zero(row);
+  PT::zero(tri);
 #pragma unroll 1
-    for (uint32_t i = gl; i < count; i += m) {
-      P Q;
-      if (kind <= 2) {
-        const uint32_t j = kind == 1 ? i * M_lo + a0 : a0 + i;
-        const uint32_t* pl = (kind == 2 ? tris : rows) + (uint64_t)kk * W * n_in;
-#pragma unroll
-        for (int w = 0; w < W; w++) PT::word(Q, w) = pl[(uint64_t)w * n_in + j];
-      } else {
-        const uint32_t j = kind == 3 ? ((((i >> a1) << 1) | 1u) << a1) | (i & ((1u << a1) - 1u)) : i;
-        const uint32_t* pp = rows + ((uint64_t)kk * per_kk + a0 + j) * W;
-#pragma unroll
-        for (int w = 0; w < W; w++) PT::word(Q, w) = pp[w];
-      }
-      PT::add(acc, acc, Q);
-    }
-#pragma unroll 1
-    for (uint32_t s = m >> 1; s >= 1; s >>= 1) {
-#pragma unroll
-      for (int w = 0; w < W; w++) lds[w * BT_THREADS + tid] = PT::word(acc, w);
-      __syncthreads();
-      const uint32_t partner = (tid & ~(m - 1)) | ((gl + s) & (m - 1));
-      P Q;
-#pragma unroll
-      for (int w = 0; w < W; w++) PT::word(Q, w) = lds[w * BT_THREADS + partner];
-      __syncthreads();
-      PT::add(acc, acc, Q);
-    }
-    if (tid == 0) {
-      if (masked == 3) {
-        uint32_t* o = out + ((uint64_t)kk * per_kk + blk) * W;
-#pragma unroll
-        for (int w = 0; w < W; w++) o[w] = PT::word(acc, w);
-      } else {
-        PT::pack(out + ((uint64_t)kk * (nbits + 1) + y) * PT::PW, acc);
-      }
-    }
+  for (uint32_t l = lend; l >= lstart; l--) {
+    P Q;
+    pt_load<PT>(Q, bucket_sums + ((uint64_t)kk * L + (l - 1)) * W);
+    PT::add(row, row, Q);
+    PT::add(tri, tri, row);
+  }
+  if (rows) {
+    pt_store_planar<PT>(rows + (uint64_t)kk * W * nchunks, nchunks, ch, row);
+    pt_store_planar<PT>(columns + (uint64_t)kk * W * nchunks, nchunks, ch, tri);
     return;
   }
-  if (masked == 1) {
-    const uint32_t half = nblk_out >> 1;
-    if (blk < nbits * half) { y = blk / half; blk -= y * half; nblk = half; }
-    else { blk -= nbits * half; y = nbits; nblk = nblk_out; }
+  uint32_t ls = lstart - 1;
+  if (ls) {
+#pragma unroll 1
+    while (true) {
+      if (ls & 1) PT::add(tri, tri, row);
+      ls >>= 1;
+      if (ls == 0) break;
+      PT::dbl(row, row);
+    }
   }
-  // masked == 1: first stage.  masked == 2: second stage over the first stage's block sums -- a masked sum filled only the
-  // first half of its nblk_out slots (the rest is never written, never read: all-zero words are the identity of a projective
-  // point but not of an extended Edwards one).  masked == 0: plain sums of n_in points.
-  const bool sel = masked == 1 && y < nbits;         // n_in = 2^nbits on the masked stage
-  const uint32_t count = (sel || (masked == 2 && y < nbits)) ? n_in >> 1 : n_in;
-  if (masked == 2) masked = 0;
-  const uint32_t span = (count + nblk - 1) / nblk;
-  const uint32_t beg = min(blk * span, count), end = min(beg + span, count);
-  // first stage: planar arrays [kk][W][n_in] written by the bucket-reduce kernel; second stage: [kk][y][n_in] points of W words
-  const uint64_t base = ((uint64_t)kk * (nbits + 1) + y) * n_in;
-  const uint32_t* src = (masked && y == nbits) ? tris : rows;
-  // Every lane takes part in every addition: a wave whose EXEC mask is down to a few lanes runs this arithmetic
-  // up to 3.5x slower per instruction when the chip is busy (tools/ubench_exec.hip), so the usual halving tree --
-  // 32, 16, ... 1 active lanes -- is the worst shape.  Instead the lanes form groups of m = min(64, 2^ceil(log2 n))
-  // lanes, each group sums all n elements of the block (64 / m groups do the same work redundantly), and the fold is
-  // a cyclic all-reduce inside the group: after log2 m steps every lane holds the total.
-  const uint32_t n_el = end - beg;
+  pt_store<PT>(columns + (uint64_t)id * W, tri);
+}
+
+template <class CV>
+__global__ void __launch_bounds__(64) k_bucket_reduce(uint32_t* columns, uint32_t* rows, const uint32_t* bucket_proj, uint32_t L,
+                                                       uint32_t TC, uint32_t nchunks, uint32_t k_cnt) {
+  bucket_reduce_body<ProjPT<typename CV::F>>(columns, rows, bucket_proj, L, TC, nchunks, k_cnt);
+}
+
+// k_window_sum / k_te_window_sum: P_k = sum of the window's columns (the partition sums, :312-319); one workgroup per
+// window, the packed sum to partials[kk]
+constexpr int WS_THREADS = 256;
+
+template <class PT>
+MSM_DEV void window_sum_body(uint32_t* partials, const uint32_t* columns, uint32_t nchunks, uint32_t* lds) {
+  using P = typename PT::P;
+  constexpr int W = PT::W;
+  const uint32_t kk = blockIdx.x, tid = threadIdx.x;
+  P acc;
+  PT::zero(acc);
+#pragma unroll 1
+  for (uint32_t j = tid; j < nchunks; j += WS_THREADS) {
+    P Q;
+    pt_load<PT>(Q, columns + ((uint64_t)kk * nchunks + j) * W);
+    PT::add(acc, acc, Q);
+  }
+#pragma unroll 1
+  for (uint32_t s = WS_THREADS / 2; s >= 1; s >>= 1) {
+    if (tid >= s && tid < 2 * s) pt_store_planar<PT>(lds, WS_THREADS, tid, acc);
+    __syncthreads();
+    if (tid < s) {
+      P Q;
+      pt_load_planar<PT>(Q, lds, WS_THREADS, tid + s);
+      PT::add(acc, acc, Q);
+    }
+    __syncthreads();
+  }
+  if (tid == 0) PT::pack(partials + (uint64_t)kk * PT::PW, acc);
+}
+
+template <class CV>
+__global__ void __launch_bounds__(WS_THREADS) k_window_sum(uint32_t* partials, const uint32_t* columns, uint32_t nchunks) {
+  __shared__ uint32_t lds[ProjPT<typename CV::F>::W * WS_THREADS];
+  window_sum_body<ProjPT<typename CV::F>>(partials, columns, nchunks, lds);
+}
+
+// Bit-sliced weighting of the chunk sums:  sum_ch (ch * TC) * row_ch = TC * sum_b 2^b * S_b  with S_b = sum of row_ch over
+// the chunks whose index has bit b set; a window has nchunks = 2^nbits chunks, nbits >= 6 (reduce_buckets).  The nbits sums
+// S_b and the sum of the local triangles go to the host, which applies the 2^b weights with nbits doublings per window -- one
+// chain per window instead of one per lane (the reference applies the same weight by double-and-add per chunk,
+// src/msm-batched-affine.ts:574-580).
+//
+// Adding every row to half of the nbits sums would take nchunks * nbits / 2 additions.  With the chunk index cut as
+// ch = hi * M_lo + lo,  sum_ch ch * row_ch = M_lo * sum_hi hi * A_hi + sum_lo lo * B_lo  with A_hi = sum_lo row (a run of M_lo
+// rows) and B_lo = sum_hi row (a column of M_hi rows): 2 * nchunks additions, and the bit-sliced weighting then runs over the
+// M_hi + M_lo sums only -- S_b = masked sum over B for the low bits, over A for the high ones.
+//   stage 0: grid (M_hi + M_lo + nblk_out, 1, kc): block -> A_hi | B_lo | a share of the n_in local triangles; raw points to
+//            out[kk][M_hi + M_lo + nblk_out]
+//   stage 1: grid (1, nbits + 1, kc) over those (`rows` = the first stage's output): y < h0: bit y of lo over B;
+//            y < nbits: bit y - h0 of hi over A; y == nbits: the nblk_out triangle shares; packed sums to out[kk][nbits + 1]
+//
+// One wave per block: every lane adds a few elements serially, then the lane sums are folded through LDS in log2 steps.  A
+// projective addition is ~7000 dependent VALU instructions (15 us for a lone wave), so what matters is the number of
+// additions in sequence, not their count.
+// Every lane takes part in every addition: a wave whose EXEC mask is down to a few lanes runs this arithmetic up to 3.5x
+// slower per instruction when the chip is busy (tools/ubench_exec.hip), so the usual halving tree -- 32, 16, ... 1 active
+// lanes -- is the worst shape.  Instead the lanes form groups of m = min(64, 2^ceil(log2 count)) lanes, each group sums all
+// elements of the block (64 / m groups do the same work redundantly), and the fold is a cyclic all-reduce inside the group:
+// after log2 m steps every lane holds the total.
+constexpr int BT_THREADS = 64;
+
+template <class PT>
+MSM_DEV void bit_tree_body(uint32_t* out, const uint32_t* rows, const uint32_t* tris, uint32_t n_in, uint32_t nbits, int stage,
+                           uint32_t nblk_out, uint32_t* lds) {
+  using P = typename PT::P;
+  constexpr int W = PT::W;
+  const uint32_t blk = blockIdx.x, y = blockIdx.y, kk = blockIdx.z, tid = threadIdx.x;
+  const uint32_t h1 = nbits / 2, h0 = nbits - h1, M_lo = 1u << h0, M_hi = 1u << h1, per_kk = M_hi + M_lo + nblk_out;
+  uint32_t count, kind;   // kind 0: A run, 1: B column, 2: triangle share (stage 0); 3: masked over stage-0 slots, 4: plain over slots
+  uint32_t a0 = 0, a1 = 0;
+  if (stage == 0) {
+    if (blk < M_hi) { kind = 0; count = M_lo; a0 = blk * M_lo; }
+    else if (blk < M_hi + M_lo) { kind = 1; count = M_hi; a0 = blk - M_hi; }
+    else {
+      kind = 2;
+      const uint32_t t = blk - M_hi - M_lo, span = (n_in + nblk_out - 1) / nblk_out;
+      a0 = min(t * span, n_in);
+      count = min(a0 + span, n_in) - a0;
+    }
+  } else {
+    if (y < h0) { kind = 3; count = M_lo >> 1; a0 = M_hi; a1 = y; }
+    else if (y < nbits) { kind = 3; count = M_hi >> 1; a0 = 0; a1 = y - h0; }
+    else { kind = 4; count = nblk_out; a0 = M_hi + M_lo; }
+  }
   uint32_t m = 1;
-  while (m < n_el && m < BT_THREADS) m <<= 1;
+  while (m < count && m < BT_THREADS) m <<= 1;
   const uint32_t gl = tid & (m - 1);
   P acc;
   PT::zero(acc);
 #pragma unroll 1
-  for (uint32_t i = beg + gl; i < end; i += m) {
-    // i-th index with bit y set: insert a one at bit position y
-    const uint32_t j = sel ? ((((i >> y) << 1) | 1u) << y) | (i & ((1u << y) - 1u)) : i;
+  for (uint32_t i = gl; i < count; i += m) {
     P Q;
-    if (masked) {
-      const uint32_t* pl = src + (uint64_t)kk * W * n_in;
-#pragma unroll
-      for (int w = 0; w < W; w++) PT::word(Q, w) = pl[(uint64_t)w * n_in + j];
+    if (kind <= 2) {
+      const uint32_t j = kind == 1 ? i * M_lo + a0 : a0 + i;
+      pt_load_planar<PT>(Q, (kind == 2 ? tris : rows) + (uint64_t)kk * W * n_in, n_in, j);
     } else {
-      const uint32_t* pp = src + (base + j) * W;
-#pragma unroll
-      for (int w = 0; w < W; w++) PT::word(Q, w) = pp[w];
+      // i-th index with bit a1 set: insert a one at bit position a1
+      const uint32_t j = kind == 3 ? ((((i >> a1) << 1) | 1u) << a1) | (i & ((1u << a1) - 1u)) : i;
+      pt_load<PT>(Q, rows + ((uint64_t)kk * per_kk + a0 + j) * W);
     }
     PT::add(acc, acc, Q);
   }
 #pragma unroll 1
   for (uint32_t s = m >> 1; s >= 1; s >>= 1) {
-#pragma unroll
-    for (int w = 0; w < W; w++) lds[w * BT_THREADS + tid] = PT::word(acc, w);
+    pt_store_planar<PT>(lds, BT_THREADS, tid, acc);
     __syncthreads();
     const uint32_t partner = (tid & ~(m - 1)) | ((gl + s) & (m - 1));
     P Q;
-#pragma unroll
-    for (int w = 0; w < W; w++) PT::word(Q, w) = lds[w * BT_THREADS + partner];
+    pt_load_planar<PT>(Q, lds, BT_THREADS, partner);
     __syncthreads();
     PT::add(acc, acc, Q);
   }
   if (tid == 0) {
-    const uint64_t o = ((uint64_t)kk * (nbits + 1) + y) * nblk_out + blk;
-    if (!pack_out) {
-#pragma unroll
-      for (int w = 0; w < W; w++) out[o * W + w] = PT::word(acc, w);
-    } else {
-      PT::pack(out + o * PT::PW, acc);
-    }
+    if (stage == 0) pt_store<PT>(out + ((uint64_t)kk * per_kk + blk) * W, acc);
+    else PT::pack(out + ((uint64_t)kk * (nbits + 1) + y) * PT::PW, acc);
   }
 }
 
+// amdgpu_waves_per_eu(1, 1): one wave per SIMD.  The work is a chain of dependent additions per wave; a second wave on
+// the same SIMD halves the speed of both, and the dispatcher fills a SIMD before it moves to the next one (measured:
+// 40 us per addition in sequence with two resident waves against 19 us alone).
 template <class CV>
 __global__ void __launch_bounds__(BT_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) k_bit_tree(uint32_t* out, const uint32_t* rows, const uint32_t* tris,
-                                                         uint32_t n_in, uint32_t nbits, int masked, int pack_out,
-                                                         uint32_t nblk_out) {
+                                                         uint32_t n_in, uint32_t nbits, int stage, uint32_t nblk_out) {
   __shared__ uint32_t lds[ProjPT<typename CV::F>::W * BT_THREADS];
-  bit_tree_body<ProjPT<typename CV::F>>(out, rows, tris, n_in, nbits, masked, pack_out, nblk_out, lds);
+  bit_tree_body<ProjPT<typename CV::F>>(out, rows, tris, n_in, nbits, stage, nblk_out, lds);
 }
+
 
 // ---------------------------------------------------------------------------------------------
 // test kernels: element-wise field / curve / GLV operations for parity tests against the oracle

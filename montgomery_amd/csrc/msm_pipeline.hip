@@ -47,11 +47,11 @@ void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sca
     // already.  It goes into the group's first slot, identities into the others.
     if (kc > pl.tab_T) throw MsmFail{MSM_ERR_INTERNAL, "a window group on window tables with more windows than tables"};
     accumulate_window_group(ctx, w, pl, 1, 0, so, st, to);
-    reduce_buckets(ctx, w, to.fin, to.fin_cap, to.off_fin, to.bucket_proj, pl.L, 1, h_partials_out, pl.merged, pl.c);
+    reduce_buckets(ctx, w, to.bucket_proj, pl.L, 1, h_partials_out, pl.merged, pl.c);
     for (int kk = 1; kk < kc; kk++) sum_set_identity(ctx, h_partials_out + (size_t)kk * ctx->sum_words());
   } else {
     accumulate_window_group(ctx, w, pl, kc, p_lo, so, st, to);
-    reduce_buckets(ctx, w, to.fin, to.fin_cap, to.off_fin, to.bucket_proj, pl.L, kc, h_partials_out, pl.merged, pl.c);
+    reduce_buckets(ctx, w, to.bucket_proj, pl.L, kc, h_partials_out, pl.merged, pl.c);
   }
   add_group_times(w, st);
 }

@@ -275,8 +275,8 @@ int msm_test_bucket_reduce(msm_ctx* ctx, const uint8_t* buckets, int32_t K, uint
       for (uint64_t b = 0; b <= nb; b++) off[b] = (uint32_t)b;
       ctx->ensure(desc, (nb + 1) * 4);
       HIPCHK(hipMemcpyAsync(desc.p, off.data(), (nb + 1) * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipEventRecord(w.ev[3], s));
-      reduce_buckets(ctx, w, (const uint4*)planes.p, cap, (const uint32_t*)desc.p, nullptr, L, K, parts.data());
+      HIPCHK(hipEventRecord(w.ev[3], s));   // in front of the finish: *ms_out spans affine buckets to window sums
+      reduce_buckets(ctx, w, finish_buckets(ctx, w, (const uint4*)planes.p, cap, (const uint32_t*)desc.p, nb), L, K, parts.data());
       HIPCHK(hipEventElapsedTime(&ms, w.ev[3], w.ev[4]));
     } else {
       // The rounds of reduceBucketsAffine as (first operand, second operand) element lists; the sum replaces the first.
@@ -442,22 +442,18 @@ int msm_test_bucket_sums(msm_ctx* ctx, const uint8_t* pool, uint64_t n_pool, con
       ROWS_TO_PLANES(ctx, dim3((uint32_t)((n_el + 255) / 256)), dim3(256), 0, s, (uint4*)planes.p, cap, (const uint32_t*)rows.p,
                      (uint32_t)n_el);
     }
-    // the pipeline's own finish, over bucket sums that start out as garbage: a bucket the finish skips cannot come out right.
-    // No entries at all: as in the pipeline, the reduction reads the (empty) buckets of the tree buffer instead.
-    const uint32_t* bucket_proj = nullptr;
+    // the pipeline's own finish, over bucket sums that start out as garbage: a bucket the finish skips cannot come out right
     const uint32_t* perm = nullptr;
-    if (n_el) {
-      ctx->ensure(w.bucket_proj, bucket_proj_bytes(ctx, nb));
-      HIPCHK(hipMemsetAsync(w.bucket_proj.p, 0x2A, bucket_proj_bytes(ctx, nb), s));
-      bucket_proj = finish_buckets(ctx, w, (const uint4*)planes.p, cap, (const uint32_t*)d_off.p, nb, &perm);
-    }
+    ctx->ensure(w.bucket_proj, bucket_proj_bytes(ctx, nb));
+    HIPCHK(hipMemsetAsync(w.bucket_proj.p, 0x2A, bucket_proj_bytes(ctx, nb), s));
+    const uint32_t* bucket_proj = finish_buckets(ctx, w, (const uint4*)planes.p, cap, (const uint32_t*)d_off.p, nb, &perm);
     if (perm_out) {
       if (perm) HIPCHK(hipMemcpyAsync(perm_out, perm, nb * 4, hipMemcpyDeviceToHost, s));
       else for (uint64_t b = 0; b < nb; b++) perm_out[b] = (uint32_t)b;   // no ordering: the buckets are taken as they lie
     }
     const int sw = ctx->sum_words();
     std::vector<uint32_t> parts((size_t)K * sw, 0);
-    reduce_buckets(ctx, w, (const uint4*)planes.p, cap, (const uint32_t*)d_off.p, bucket_proj, L, K, parts.data(), merged != 0, stride, tc);
+    reduce_buckets(ctx, w, bucket_proj, L, K, parts.data(), merged != 0, stride, tc);
     HIPCHK(hipMemcpyAsync(w.h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (w.h_info[0] & 1) return fail(ctx, MSM_ERR_POINT, "msm_test_bucket_sums: coordinate >= p");

@@ -66,17 +66,13 @@ void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl
   // bucket cheaper (2^26, c = 22: 154.3 -> 150.8 ms; profiles/r04_experiments.txt item 8)
   uint32_t tail_min_pairs = pl.c >= 18 ? 1u << 23 : 1u << 21;
   MSM_KNOB(tail_min_pairs, "MSM_TAIL_MIN", 1);
-  const bool use_finish = true;
-  int r_stop = RT;
-  if (use_finish) {
-    // a tail round is worth its launch + inversion latency (~0.25 ms) only while it still has a few million pairs;
-    // below that, and once no bucket holds more than FINISH_MAX elements, k_bucket_finish takes over
-    uint32_t cap_elems = (max_bucket + (1u << logG) - 1) >> logG;   // largest bucket after the regular rounds
-    r_stop = 0;
-    while (r_stop < RT &&
-           (((cap_elems + (1u << r_stop) - 1) >> r_stop) > FINISH_MAX || w.h_info[3 + r_stop + 1] >= tail_min_pairs))
-      r_stop++;
-  }
+  // a tail round is worth its launch + inversion latency (~0.25 ms) only while it still has a few million pairs;
+  // below that, and once no bucket holds more than FINISH_MAX elements, k_bucket_finish takes over
+  const uint32_t cap_elems = (max_bucket + (1u << logG) - 1) >> logG;   // largest bucket after the regular rounds
+  int r_stop = 0;
+  while (r_stop < RT &&
+         (((cap_elems + (1u << r_stop) - 1) >> r_stop) > FINISH_MAX || w.h_info[3 + r_stop + 1] >= tail_min_pairs))
+    r_stop++;
   // outputs alternate between two buffers: size each for the largest round it receives
   uint64_t capA = 1, capB = 1;
   {
@@ -107,7 +103,6 @@ void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl
   int round = 0;
   const uint4* fin = buf[0];
   uint64_t fin_cap = cap[0];
-  const uint32_t* off_fin = (const uint32_t*)w.tail_off.p;
   if (total_slots > 0) {
     for (uint32_t r = 1; r <= logG; r++) {
       uint64_t n_out = n_in / 2;
@@ -179,17 +174,12 @@ void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl
       cur ^= 1;
       round++;
     }
-    off_fin = (const uint32_t*)w.tail_off.p + (uint64_t)r_stop * (nb + 1);
   }
   st.rounds += round;
-  const uint32_t* bucket_proj = nullptr;
-  if (use_finish && total_slots > 0) bucket_proj = finish_buckets(ctx, w, fin, fin_cap, off_fin, nb);
   if (total_slots == 0) HIPCHK(hipEventRecord(w.ev[6], s));
+  // (a group without entries has r_stop = 0 and all-equal offsets: every bucket sum comes out as the identity)
+  to.bucket_proj = finish_buckets(ctx, w, fin, fin_cap, (const uint32_t*)w.tail_off.p + (uint64_t)r_stop * (nb + 1), nb);
   HIPCHK(hipEventRecord(w.ev[3], s));
-  to.fin = fin;
-  to.fin_cap = fin_cap;
-  to.off_fin = off_fin;
-  to.bucket_proj = bucket_proj;
 }
 
 }  // namespace msmi

@@ -444,17 +444,13 @@ __global__ void __launch_bounds__(256) k_te_gen_points(uint32_t* wire_out, const
 #endif
 
 // ---------------------------------------------------------------------------------------------
-// k_te_bucket_reduce / k_te_window_sum: reduceBucketsChunk (src/msm-basic.ts:180-211) per chunk of TC
-// buckets, then the per-window sum of the chunk columns
+// k_te_bucket_finish, then k_te_bucket_reduce / k_te_window_sum / k_te_bit_tree: the bodies of msm_kernels.h (reduceBucketsChunk,
+// src/msm-basic.ts:180-211, per chunk of TC buckets, then the per-window sum of the chunk columns) over TePT
 // ---------------------------------------------------------------------------------------------
 
 MSM_DEV void ext_store_raw(uint32_t* dst, const Ext& P) {
 #pragma unroll
   for (int l = 0; l < TL; l++) { dst[l] = P.X.l[l]; dst[TL + l] = P.Y.l[l]; dst[2 * TL + l] = P.Z.l[l]; dst[3 * TL + l] = P.T.l[l]; }
-}
-MSM_DEV void ext_load_raw(Ext& P, const uint32_t* src) {
-#pragma unroll
-  for (int l = 0; l < TL; l++) { P.X.l[l] = src[l]; P.Y.l[l] = src[TL + l]; P.Z.l[l] = src[2 * TL + l]; P.T.l[l] = src[3 * TL + l]; }
 }
 
 // k_te_bucket_finish: the unified addition needs no inversion, so the tree exists only for parallelism; once every
@@ -482,74 +478,16 @@ __global__ void __launch_bounds__(256) k_te_bucket_finish(uint32_t* bucket_ext, 
 }
 #endif
 
-// rows != nullptr: bit-sliced mode, as k_bucket_reduce (msm_kernels.h) -- the chunk's plain sum goes to rows, its local
-// triangle to columns, both planar ([window][word][chunk]); the weight ch * TC is applied through per-bit sums (k_te_bit_tree)
-__global__ void __launch_bounds__(64) k_te_bucket_reduce(uint32_t* columns, uint32_t* rows, const uint4* fin, uint64_t fin_cap,
-                                                          const uint32_t* off_fin, const uint32_t* bucket_ext, uint32_t L, uint32_t TC,
-                                                          uint32_t nchunks, uint32_t k_cnt)
-#ifndef MSM_TE_TU
-    ;
-#else
-{
-  uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= nchunks * k_cnt) return;
-  uint32_t kk = id / nchunks, ch = id - kk * nchunks;
-  uint32_t lstart = ch * TC + 1;
-  uint32_t lend = min(lstart + TC - 1, L);
-  Ext row, tri;
-  te_set_identity(row);
-  te_set_identity(tri);
-#pragma unroll 1
-  for (uint32_t l = lend; l >= lstart; l--) {
-    uint64_t b = (uint64_t)kk * L + (l - 1);
-    if (bucket_ext) {   // bucket sums from k_te_bucket_finish (the identity for an empty bucket)
-      Ext Q;
-      ext_load_raw(Q, bucket_ext + b * (4 * TL));
-      te_add(row, row, Q);
-    } else {
-      uint32_t o0 = off_fin[b], o1 = off_fin[b + 1];
-      if (o1 > o0) {
-        Ext Q;
-        load_ext(Q, fin, fin_cap, o0);
-        te_add(row, row, Q);
-      }
-    }
-    te_add(tri, tri, row);
-  }
-  if (rows) {
-    uint32_t* rp = rows + (uint64_t)kk * (4 * TL) * nchunks;
-    uint32_t* cp = columns + (uint64_t)kk * (4 * TL) * nchunks;
-#pragma unroll
-    for (int l = 0; l < TL; l++) {
-      rp[(uint64_t)l * nchunks + ch] = row.X.l[l]; rp[(uint64_t)(TL + l) * nchunks + ch] = row.Y.l[l];
-      rp[(uint64_t)(2 * TL + l) * nchunks + ch] = row.Z.l[l]; rp[(uint64_t)(3 * TL + l) * nchunks + ch] = row.T.l[l];
-      cp[(uint64_t)l * nchunks + ch] = tri.X.l[l]; cp[(uint64_t)(TL + l) * nchunks + ch] = tri.Y.l[l];
-      cp[(uint64_t)(2 * TL + l) * nchunks + ch] = tri.Z.l[l]; cp[(uint64_t)(3 * TL + l) * nchunks + ch] = tri.T.l[l];
-    }
-    return;
-  }
-  uint32_t ls = lstart - 1;
-  if (ls) {
-#pragma unroll 1
-    while (true) {
-      if (ls & 1) te_add(tri, tri, row);
-      ls >>= 1;
-      if (ls == 0) break;
-      te_add(row, row, row);   // doubling = unified add, src/curve-twisted-edwards.ts:215-217
-    }
-  }
-  ext_store_raw(columns + (uint64_t)id * (4 * TL), tri);
-}
-#endif
-
-// the bit tree of msm_kernels.h over extended Edwards points (X, Y, Z, T: 4 x 9 limbs; packed sums: 4 x 8 words)
+// the bucket reduction of msm_kernels.h over extended Edwards points (X, Y, Z, T: 4 x 9 limbs; packed sums: 4 x 8 words)
 struct TePT {
   using P = Ext;
   static constexpr int W = 4 * TL;
   static constexpr int PW = 32;
   static MSM_DEV void zero(P& p) { te_set_identity(p); }
   static MSM_DEV void add(P& r, const P& a, const P& b) { te_add(r, a, b); }
+  static MSM_DEV void dbl(P& r, const P& a) { te_add(r, a, a); }   // doubling = unified add, src/curve-twisted-edwards.ts:215-217
   static MSM_DEV uint32_t& word(P& p, int w) { return w < TL ? p.X.l[w] : w < 2 * TL ? p.Y.l[w - TL] : w < 3 * TL ? p.Z.l[w - 2 * TL] : p.T.l[w - 3 * TL]; }
+  // 4 x 8 packed words (X, Y, Z, T), Montgomery form, values < 2p
   static MSM_DEV void pack(uint32_t* dst, P& acc) {
     uint32_t w[TW];
     fe_pack<FT>(w, acc.X);
@@ -567,79 +505,38 @@ struct TePT {
   }
 };
 
+__global__ void __launch_bounds__(64) k_te_bucket_reduce(uint32_t* columns, uint32_t* rows, const uint32_t* bucket_ext, uint32_t L,
+                                                          uint32_t TC, uint32_t nchunks, uint32_t k_cnt)
+#ifndef MSM_TE_TU
+    ;
+#else
+{
+  bucket_reduce_body<TePT>(columns, rows, bucket_ext, L, TC, nchunks, k_cnt);
+}
+#endif
+
+__global__ void __launch_bounds__(WS_THREADS) k_te_window_sum(uint32_t* partials, const uint32_t* columns, uint32_t nchunks)
+#ifndef MSM_TE_TU
+    ;
+#else
+{
+  __shared__ uint32_t lds[TePT::W * WS_THREADS];
+  window_sum_body<TePT>(partials, columns, nchunks, lds);
+}
+#endif
+
 __global__ void __launch_bounds__(BT_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) k_te_bit_tree(uint32_t* out, const uint32_t* rows,
-                                                         const uint32_t* tris, uint32_t n_in, uint32_t nbits, int masked,
-                                                         int pack_out, uint32_t nblk_out)
+                                                         const uint32_t* tris, uint32_t n_in, uint32_t nbits, int stage,
+                                                         uint32_t nblk_out)
 #ifndef MSM_TE_TU
     ;
 #else
 {
   __shared__ uint32_t lds[TePT::W * BT_THREADS];
-  bit_tree_body<TePT>(out, rows, tris, n_in, nbits, masked, pack_out, nblk_out, lds);
+  bit_tree_body<TePT>(out, rows, tris, n_in, nbits, stage, nblk_out, lds);
 }
 #endif
 
-constexpr int TE_WS_THREADS = 256;
-
-// output: 4 x 8 packed words (X, Y, Z, T), Montgomery form, values < 2p
-__global__ void __launch_bounds__(TE_WS_THREADS) k_te_window_sum(uint32_t* partials, const uint32_t* columns, uint32_t nchunks)
-#ifndef MSM_TE_TU
-    ;
-#else
-{
-  __shared__ uint32_t lds[4 * TL * TE_WS_THREADS];
-  const uint32_t kk = blockIdx.x, tid = threadIdx.x;
-  Ext acc;
-  te_set_identity(acc);
-#pragma unroll 1
-  for (uint32_t j = tid; j < nchunks; j += TE_WS_THREADS) {
-    Ext Q;
-    ext_load_raw(Q, columns + ((uint64_t)kk * nchunks + j) * (4 * TL));
-    te_add(acc, acc, Q);
-  }
-#pragma unroll 1
-  for (uint32_t s = TE_WS_THREADS / 2; s >= 1; s >>= 1) {
-    if (tid >= s && tid < 2 * s) {
-#pragma unroll
-      for (int l = 0; l < TL; l++) {
-        lds[(l)*TE_WS_THREADS + tid] = acc.X.l[l];
-        lds[(TL + l) * TE_WS_THREADS + tid] = acc.Y.l[l];
-        lds[(2 * TL + l) * TE_WS_THREADS + tid] = acc.Z.l[l];
-        lds[(3 * TL + l) * TE_WS_THREADS + tid] = acc.T.l[l];
-      }
-    }
-    __syncthreads();
-    if (tid < s) {
-      Ext Q;
-#pragma unroll
-      for (int l = 0; l < TL; l++) {
-        Q.X.l[l] = lds[(l)*TE_WS_THREADS + tid + s];
-        Q.Y.l[l] = lds[(TL + l) * TE_WS_THREADS + tid + s];
-        Q.Z.l[l] = lds[(2 * TL + l) * TE_WS_THREADS + tid + s];
-        Q.T.l[l] = lds[(3 * TL + l) * TE_WS_THREADS + tid + s];
-      }
-      te_add(acc, acc, Q);
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    uint32_t* dst = partials + (uint64_t)kk * 32;
-    uint32_t w[TW];
-    fe_pack<FT>(w, acc.X);
-#pragma unroll
-    for (int j = 0; j < TW; j++) dst[j] = w[j];
-    fe_pack<FT>(w, acc.Y);
-#pragma unroll
-    for (int j = 0; j < TW; j++) dst[8 + j] = w[j];
-    fe_pack<FT>(w, acc.Z);
-#pragma unroll
-    for (int j = 0; j < TW; j++) dst[16 + j] = w[j];
-    fe_pack<FT>(w, acc.T);
-#pragma unroll
-    for (int j = 0; j < TW; j++) dst[24 + j] = w[j];
-  }
-}
-#endif
 
 // element-wise base-field operators for parity tests (same op codes as k_test_fp)
 __global__ void __launch_bounds__(256) k_te_test_fp(uint32_t* out, const uint32_t* a, const uint32_t* b, uint32_t n, int op)

@@ -61,7 +61,7 @@ def run(ctx_of, cr, merged=False, stride=0, tc=0):
     K, L = cr.K, cr.L
     raw, perm = ctx_of(cr.curve).test_bucket_sums(cr.pool_wire(), cr.off, cr.elems, K, L, merged=merged, stride=stride, tc=tc, want_perm=True)
     perm = perm.astype(np.int64)
-    if K * L >= FINISH_ORDER_FROM and len(cr.elems):
+    if K * L >= FINISH_ORDER_FROM:
         # a permutation of the buckets, in descending order of their element counts (counts from 63 up share the last bin)
         assert (np.sort(perm) == np.arange(K * L)).all()
         keys = np.minimum(cr.counts[perm], B.FINISH_BINS - 1)

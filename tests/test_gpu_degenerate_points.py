@@ -343,6 +343,23 @@ def test_torsion_points_in_run_narrow(name, fmt):
         assert cs.key(res) == exp, (c, info)
 
 
+# ---------------------------------------------------------------------------------------------- no entry at all
+
+@pytest.mark.parametrize("name", ["bls377", "pallas", "ed377"])
+def test_all_zero_scalars(name):
+    """A whole MSM whose window groups have no entry: every bucket sum is the identity the finish writes (from 4096 buckets on
+    behind its ordering pass), and the reduction over them -- bit-sliced at the default window -- gives the identity.  On the
+    plain path and on window tables (which exist from 4096 points)."""
+    cs, n = case(name), 4096
+    cs.load_raw(list(D.pool(name)[0]) * (n // D.POOL))
+    sb = bytes(32 * n)
+    res, info = cs.ctx.run(sb, no_tables=True)
+    assert not info["tables"] and cs.key(res) == cs.cv.zero, info
+    assert cs.ctx.precompute(n)[2] > 0
+    res, info = cs.ctx.run(sb)
+    assert info["tables"] and cs.key(res) == cs.cv.zero, info
+
+
 # ---------------------------------------------------------------------------------------------- one larger shape
 
 @pytest.mark.parametrize("name", ["bls381", "bn254", "vesta"])
