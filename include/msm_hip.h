@@ -547,6 +547,33 @@ int msm_test_set_chunk_rows_log(msm_ctx* ctx, int32_t log2_rows);
  * or msm_window_sums on this context, one per group in the order of the call's schedule; none (count 0) after a call that failed or a fused batch: writes
  * min(count, cap) of them to `out` (may be NULL with cap = 0) and returns the count, or -1 for a null or device-list context. */
 int msm_test_last_sort_paths(msm_ctx* ctx, int32_t* out, int cap);
+/* The first step of every MSM alone: the window digits of a call's scalars, from the digit kernel the call would launch
+ * (k_digits, k_te_digits, k_digits_narrow<W>, k_te_digits_narrow<W>; B >= 2: their _batch forms), through the pipeline's own
+ * launch code and geometry, and nothing behind it -- nothing sorts the digits, so a wrong one is a wrong word in digits_out and
+ * never a bucket index.  Needs no resident points.
+ *   scalars   B host arrays of n_array scalars each; the call's scalars are the elements [first, first + n) (what a range of
+ *             the points of a bigger call sees: a narrow range may start inside the dword a lane loads)
+ *   width_bytes, bits, is_signed   the narrow format of msm_run_narrow, bits resolved the same way; width_bytes = 0: 32-byte
+ *             scalars (bits and is_signed are then ignored)
+ *   opts      c, no_glv, strict, bucket_shard, bucket_shards as msm_window_sums reads them.  A narrow call and a batch refuse
+ *             shard options as msm_run_narrow and msm_run_batch do (MSM_ERR_ARG): bucket shards, and k_lo / k_hi of opts, which
+ *             a call of 32-byte scalars does not read
+ *   k_lo, k_hi   the windows [k_lo, k_hi) of the plan's K; 0, 0 = all
+ *   B >= 2    the fused batch of msm_run_batch(_narrow): host elements staged 16 bytes apart as there; opts->c must be set,
+ *             first = 0, n_array = n, all windows, no shard; at most 16 elements, 64 narrow ones.  Unlike the real call, which
+ *             fuses only under the one-level sort, any window the plan accepts is run, a folded plan included.
+ * digits_out = NULL: only the plan is made and reported (c_out, K_out, fold_out), from which a caller sizes digits_out.
+ * digits_out: (k_hi - k_lo) rows of 2 n words (Ed-on-BLS12-377: n words) -- on a Weierstrass curve word 2 i is the digit of
+ * scalar i (with the endomorphism: of its first half), word 2 i + 1 that of the second half or 0; a word is magnitude |
+ * sign << 31, 0 = no entry.  B >= 2: B K rows, row b K + k = window k of element b.
+ * c_out, K_out, fold_out (may be NULL): the plan; fold = the top window is c + 1 bits wide (msm_plan).
+ * Returns MSM_ERR_ARG where the real call refuses the plan or the format.  Otherwise MSM_OK with the digits, and in
+ * *flags_rc_out what the real call returns for the error word the kernel left: MSM_OK, MSM_ERR_SCALAR (a scalar >= q under
+ * opts->strict, a narrow value outside its range -- such a value counts as 0) or MSM_ERR_INTERNAL (a folded top window had to
+ * be clamped). */
+int msm_test_digits(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, uint64_t n_array, uint64_t first,
+                    int32_t width_bytes, int32_t bits, int32_t is_signed, const msm_opts* opts, int32_t k_lo, int32_t k_hi,
+                    uint32_t* digits_out, int32_t* c_out, int32_t* K_out, int32_t* fold_out, int32_t* flags_rc_out);
 
 #ifdef __cplusplus
 }

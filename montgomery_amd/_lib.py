@@ -48,7 +48,7 @@ EXPORTS = (
     "msm_run_indexed", "msm_run_indexed_narrow",
     "msm_points_lincomb", "msm_pointset_size",
     "msm_device_download", "msm_scalars_lincomb", "msm_scalars_mul", "msm_scalars_inner", "msm_scalars_powers",
-    "msm_test_bucket_sums", "msm_test_set_chunk_rows_log", "msm_test_last_sort_paths",
+    "msm_test_bucket_sums", "msm_test_set_chunk_rows_log", "msm_test_last_sort_paths", "msm_test_digits",
 )
 
 
@@ -217,6 +217,11 @@ def load() -> C.CDLL:
         raise ImportError(f"{LIB_PATH} predates msm_test_last_sort_paths: rebuild it (`make`)")
     lib.msm_test_set_chunk_rows_log.argtypes = [vp, i32]
     lib.msm_test_last_sort_paths.argtypes = [vp, C.POINTER(i32), C.c_int]
+    # the digit kernels alone: a new test symbol under ABI 8
+    if not hasattr(lib, "msm_test_digits"):
+        raise ImportError(f"{LIB_PATH} predates msm_test_digits: rebuild it (`make`)")
+    lib.msm_test_digits.argtypes = [vp, C.POINTER(vp), C.c_uint32, u64, u64, u64, i32, i32, i32, C.POINTER(MsmOpts), i32, i32, vp,
+                                    C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     for name in EXPORTS:
         if name not in ("msm_ctx_destroy", "msm_last_error", "msm_abi_version", "msm_abi_struct_bytes"):
             getattr(lib, name).restype = C.c_int

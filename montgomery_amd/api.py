@@ -975,6 +975,39 @@ class MsmContext:
             raise MsmError(_lib.MSM_ERR_INTERNAL, f"msm_test_last_sort_paths: unknown sort path in {list(out[:count])}")
         return [_lib.SORT_PATH_NAMES[v] for v in out[:count]]
 
+    def test_digits(self, scalars, n: Optional[int] = None, first: int = 0, width: int = 0, bits: int = 0, signed: bool = False,
+                    c: int = 0, no_glv: bool = False, strict: bool = False, bucket_shard: int = 0, bucket_shards: int = 0,
+                    k_lo: int = 0, k_hi: int = 0) -> dict:
+        """The window digits of a call's scalars from the digit kernel alone (msm_test_digits, msm_hip.h).  scalars: one uint8
+        array of whole scalars (32 bytes each, or `width` bytes of the narrow format (width, bits, signed)), or a list of B >= 2
+        such arrays for the fused batch.  The call's scalars are the elements [first, first + n) of the array (n: the rest).
+        Returns {"rc": what the real call makes of the kernel's error word, "c", "K", "fold", "words": uint32 array of shape
+        (windows, 2 n) -- Ed-on-BLS12-377: (windows, n); a batch: (B, K, ...)}; raises MsmError where the plan is refused."""
+        import numpy as np
+
+        batch = isinstance(scalars, (list, tuple))
+        wb = width or 32
+        arrs = [np.ascontiguousarray(np.frombuffer(bytes(a), dtype=np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8).reshape(-1)
+                for a in (scalars if batch else [scalars])]
+        if not arrs or any(len(a) != len(arrs[0]) or len(a) % wb for a in arrs):
+            raise MsmError(_lib.MSM_ERR_ARG, f"expected arrays of whole {wb}-byte scalars, all of one length")
+        n_array = len(arrs[0]) // wb
+        if n is None:
+            n = n_array - first
+        if n <= 0 or first < 0 or first + n > n_array:
+            raise MsmError(_lib.MSM_ERR_ARG, f"scalars [{first}, {first} + {n}) of an array of {n_array}")
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        opts = MsmOpts(c=c or 0, no_glv=int(no_glv), strict=int(strict), bucket_shard=bucket_shard, bucket_shards=bucket_shards)
+        per = 1 if self.curve == _lib.CURVE_ED_ON_BLS12_377 else 2
+        cc, K, fold, frc = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        args = (self._h, ptrs, len(arrs), n, n_array, first, width, bits, int(bool(signed)), C.byref(opts), k_lo, k_hi)
+        # the plan first (no output buffer: nothing runs), then a buffer of exactly its rows
+        self._check(self._lib.msm_test_digits(*args, None, C.byref(cc), C.byref(K), C.byref(fold), None))
+        rows = k_hi - k_lo if (k_lo or k_hi) else K.value
+        out = np.empty((len(arrs), rows, per * n) if batch else (rows, per * n), dtype=np.uint32)
+        self._check(self._lib.msm_test_digits(*args, out.ctypes.data, C.byref(cc), C.byref(K), C.byref(fold), C.byref(frc)))
+        return {"rc": frc.value, "c": cc.value, "K": K.value, "fold": bool(fold.value), "words": out}
+
     def test_batch_add(self, g: BytesLike, h: BytesLike) -> bytes:
         n = len(g) // (2 * self.coord_bytes)
         bg = (C.c_uint8 * len(g)).from_buffer_copy(bytes(g))

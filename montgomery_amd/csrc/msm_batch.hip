@@ -22,6 +22,33 @@ int pick_window_batch(bool te, uint64_t n, uint32_t B, int glv_max_bits) {
   return pick_window(te, n, glv_max_bits);
 }
 
+std::vector<const uint32_t*> stage_batch_scalars(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device,
+                                                 const Plan& pl) {
+  std::vector<const uint32_t*> sc(B);
+  if (on_device) {
+    for (uint32_t b = 0; b < B; b++) sc[b] = (const uint32_t*)scalars[b];
+  } else {
+    // (narrow elements, msm_run_batch_narrow: n x width bytes each, every element on a 16-byte boundary)
+    const size_t el_bytes = (size_t)n * (pl.nar.width ? pl.nar.width : 32), el_stride = (el_bytes + 15) & ~(size_t)15;
+    ctx->ensure(ctx->scal, (size_t)B * el_stride);
+    for (uint32_t b = 0; b < B; b++) {
+      sc[b] = (const uint32_t*)((const char*)ctx->scal.p + (size_t)b * el_stride);
+      upload_staged(ctx, (void*)sc[b], scalars[b], el_bytes);
+    }
+  }
+  return sc;
+}
+
+void bind_batch_scalars(Plan& pl, NarrowBatchScalars& nbs, const std::vector<const uint32_t*>& sc, int b0, int cnt) {
+  pl.batch = cnt;
+  if (pl.nar.width) {
+    for (int j = 0; j < cnt; j++) nbs.p[j] = sc[b0 + j];
+    pl.nar.nb = &nbs;
+  } else {
+    for (int j = 0; j < cnt; j++) pl.batch_sc.p[j] = sc[b0 + j];
+  }
+}
+
 }  // namespace msmi
 
 namespace {
@@ -44,15 +71,9 @@ bool fuse(const msm_ctx* ctx, uint64_t n, uint32_t B, const Plan& pl) {
 void run_batch_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl_in, const std::vector<const uint32_t*>& sc, int b0, int cnt,
                      uint64_t n, uint64_t p_lo, bool lone, uint32_t* part, GroupStats& st) {
   Plan pl = pl_in;
-  pl.batch = cnt;
   pl.lone = lone;
   NarrowBatchScalars nbs{};   // (narrow elements: up to NARROW_BATCH_MAX pointers, k_digits_narrow_batch)
-  if (pl.nar.width) {
-    for (int j = 0; j < cnt; j++) nbs.p[j] = sc[b0 + j];
-    pl.nar.nb = &nbs;
-  } else {
-    for (int j = 0; j < cnt; j++) pl.batch_sc.p[j] = sc[b0 + j];
-  }
+  bind_batch_scalars(pl, nbs, sc, b0, cnt);
   const int kc = cnt * pl.K;
   SortOut so;
   HIPCHK(hipEventRecord(w.ev[0], w.stream));
@@ -70,18 +91,7 @@ int run_fused(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, 
               msm_result* out) {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipEventRecord(ctx->ev[8], ctx->stream));
-  std::vector<const uint32_t*> sc(B);
-  if (on_device) {
-    for (uint32_t b = 0; b < B; b++) sc[b] = (const uint32_t*)scalars[b];
-  } else {
-    // (narrow elements, msm_run_batch_narrow: n x width bytes each, every element on a 16-byte boundary)
-    const size_t el_bytes = (size_t)n * (pl.nar.width ? pl.nar.width : 32), el_stride = (el_bytes + 15) & ~(size_t)15;
-    ctx->ensure(ctx->scal, (size_t)B * el_stride);
-    for (uint32_t b = 0; b < B; b++) {
-      sc[b] = (const uint32_t*)((const char*)ctx->scal.p + (size_t)b * el_stride);
-      upload_staged(ctx, (void*)sc[b], scalars[b], el_bytes);
-    }
-  }
+  const std::vector<const uint32_t*> sc = stage_batch_scalars(ctx, scalars, B, n, on_device, pl);
   HIPCHK(hipEventRecord(ctx->ev[9], ctx->stream));
   // groups of whole elements: at most 128 windows, BATCH_MAX elements, and what the workspace budget gives one group
   const uint64_t budget = ctx->ws_limit ? ctx->ws_limit : ctx->ws_budget;

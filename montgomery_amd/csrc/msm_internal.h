@@ -567,6 +567,8 @@ struct SortOut {
 // a group's own call then takes its part of the arrays (bin split only) instead of slicing the scalars again.
 struct GroupDigits {
   bool produce = false;
+  bool any_path = false;          // produce on every sort path and for a fused batch, not the bin split alone: the digits are all the
+                                  // caller wants (msm_test_digits; no consumer takes them -- `hist` is null off the bin split)
   int k_lo = 0;                   // first window of the arrays
   const uint32_t* dig = nullptr;  // [windows][entries per window]
   uint32_t* hist = nullptr;       // [windows][sortB][hb]
@@ -726,6 +728,9 @@ int window_sums_impl(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
 int any_window_sums(msm_ctx* ctx, const void* scalars, uint64_t n, int on_device, const msm_opts* opts, int k_lo, int k_hi,
                     const Plan& pl, std::vector<uint32_t>& words, msm_result* stats, const void* const* placed = nullptr);
 
+// the scalars of the points [p_lo, ...) of a call: 32-byte scalars are addressed; narrow ones (msm_run_narrow) keep the call's
+// array and count from `first`, which the digit kernel resolves (a range may start inside the dword a lane loads)
+const uint32_t* group_scalars(const uint32_t* d_scalars_all, uint64_t p_lo, Plan& pl);
 // The two-stream runner of a call: job(slot, i) for i = 0 .. n_jobs - 1, each on one of the context's two workspaces (slot), the
 // second worker on the context's helper thread unless `serial`.  Whatever a job throws is re-raised only after both workers have
 // stopped and both group streams are idle.
@@ -775,6 +780,13 @@ int on_all_devices(msm_ctx* ctx, F f) {
 
 // ---- msm_batch.hip ----------------------------------------------------------------------------------------------
 int pick_window_batch(bool te, uint64_t n, uint32_t B, int glv_max_bits);
+// The scalars of the B elements of a fused batch on the device: device pointers as they are; host arrays uploaded into
+// ctx->scal one behind the other, every element on a 16-byte boundary (narrow elements: n x width bytes each).
+std::vector<const uint32_t*> stage_batch_scalars(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, int on_device,
+                                                 const Plan& pl);
+// pl becomes the plan of the fused group of elements [b0, b0 + cnt) of `sc`: Plan::batch, and their scalars in the form the
+// _batch digit kernels take as an argument (narrow elements: in nbs, which must outlive the launch)
+void bind_batch_scalars(Plan& pl, NarrowBatchScalars& nbs, const std::vector<const uint32_t*>& sc, int b0, int cnt);
 
 // ---- msm_narrow.hip ---------------------------------------------------------------------------------------------
 // checks the format and the options of a narrow call (MSM_ERR_ARG with a message) and resolves it: bits = 0 -> all the width gives
@@ -786,6 +798,9 @@ int narrow_scalars_ok(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devi
 // The array the pipeline gets for the device scalars `dev` of a narrow call: rounded down to the alignment of a lane's load, with
 // nar.first = where the first scalar sits in it (only the 1- and 2-byte formats can start inside a lane's dword)
 const char* narrow_lane_base(const char* dev, int32_t width_bytes, Plan::Narrow& nar);
+// the scalars of a narrow call on the device: host scalars are uploaded whole before the run (timed as *up_ms), device scalars
+// stay where they are
+const char* stage_narrow(msm_ctx* ctx, const void* scalars, size_t bytes, int on_device, float* up_ms);
 
 // ---- msm_indexed.hip --------------------------------------------------------------------------------------------
 // Queues on `s` the pass that rewrites the n_slots payloads the sort left for round 1 -- (entry << 1) | sign, entry counting the

@@ -47,10 +47,6 @@ const char* narrow_lane_base(const char* dev, int32_t width_bytes, Plan::Narrow&
   return dev - off;
 }
 
-}  // namespace msmi
-
-namespace {
-
 // Host scalars are uploaded whole before the run (2 - 32 x smaller than the wide form), timed as up_ms; device scalars stay where
 // they are.  Returns the device array.
 const char* stage_narrow(msm_ctx* ctx, const void* scalars, size_t bytes, int on_device, float* up_ms) {
@@ -64,7 +60,7 @@ const char* stage_narrow(msm_ctx* ctx, const void* scalars, size_t bytes, int on
   return (const char*)ctx->scal.p;
 }
 
-}  // namespace
+}  // namespace msmi
 
 extern "C" {
 

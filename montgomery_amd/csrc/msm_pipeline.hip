@@ -12,14 +12,6 @@ namespace {
 // Partition sums P_k for windows [k_lo, k_hi) over the points [p_lo, p_lo + n) -> slot k - k_lo of h_partials_out
 // scalars: device pointer, n x 8 words.
 // On window tables every group reads table j = 2^(c j) P for its window k_lo + j: its sum is relative to its OWN first window.
-// the scalars of the points [p_lo, ...) of a call: 32-byte scalars are addressed; narrow ones (msm_run_narrow) keep the call's
-// array and count from `first`, which the digit kernel resolves (a range may start inside the dword a lane loads)
-const uint32_t* group_scalars(const uint32_t* d_scalars_all, uint64_t p_lo, Plan& pl) {
-  if (!pl.nar.width) return d_scalars_all + p_lo * 8;
-  pl.nar.first += p_lo;
-  return d_scalars_all;
-}
-
 void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars_all, uint64_t p_lo, uint64_t n, const Plan& pl_in,
                       int k_lo, int k_hi, uint32_t* h_partials_out, GroupStats& st, int32_t& path, uint64_t p_off = 0, GroupDigits* share = nullptr) {
   hipStream_t s = w.stream;
@@ -214,6 +206,12 @@ int window_sums_once(msm_ctx* ctx, const void* scalars, uint64_t n, int on_devic
 }  // namespace
 
 namespace msmi {
+
+const uint32_t* group_scalars(const uint32_t* d_scalars_all, uint64_t p_lo, Plan& pl) {
+  if (!pl.nar.width) return d_scalars_all + p_lo * 8;
+  pl.nar.first += p_lo;
+  return d_scalars_all;
+}
 
 void run_on_workspaces(msm_ctx* ctx, int n_jobs, bool serial, const std::function<void(int slot, int index)>& job) {
   std::atomic<int> next{0};

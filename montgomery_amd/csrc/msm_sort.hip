@@ -31,7 +31,7 @@ void sort_kernel_attributes() {
 // k_digits / k_te_digits write -- digits and, for the bin split, the slice histograms -- or, for a fused batch, their _batch
 // forms.  A lane of the 1- and 2-byte formats takes 4 / 2 scalars, so a block of the plain launch covers 256 lanes' worth.
 static void narrow_digits(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars, uint64_t n, const Plan& pl, int k_lo, int kc_d,
-                          bool bin_split, bool radix, uint32_t sortB, uint64_t pps, uint32_t hb, const WinSplit& ws) {
+                          bool bin_split, bool radix, uint32_t sortB, uint64_t pps, uint32_t hb, const WinSplit& ws, bool digits_only) {
   hipStream_t s = w.stream;
   const bool te = ctx->is_te();
   const int W = pl.nar.width, per_lane = W == 1 ? 4 : W == 2 ? 2 : 1;
@@ -39,7 +39,7 @@ static void narrow_digits(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d
   uint32_t* err = (uint32_t*)ctx->errflag.p;
   const int fold = pl.fold ? 1 : 0;
   if (pl.batch) {
-    if (bin_split || radix || k_lo != 0 || kc_d != pl.batch * pl.K || !pl.nar.nb) throw MsmFail{MSM_ERR_INTERNAL, "a batch group outside the one-level sort"};
+    if (((bin_split || radix) && !digits_only) || k_lo != 0 || kc_d != pl.batch * pl.K || !pl.nar.nb) throw MsmFail{MSM_ERR_INTERNAL, "a batch group outside the one-level sort"};
     const uint32_t grid = (uint32_t)(((n + per_lane - 1) / per_lane + 255) / 256);
 #define MSM_NARROW_LAUNCH_B(WW)                                                                                               \
   if (W == WW) {                                                                                                              \
@@ -76,6 +76,7 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
                        GroupStats& st, SortOut& so, GroupDigits* share) {
   hipStream_t s = w.stream;
   const bool produce = share && share->produce;              // digits of all groups' windows, nothing else
+  const bool digits_only = produce && share->any_path;       // ... whatever the sort path: nothing sorts them (msm_test_digits)
   const bool consume = share && !share->produce && share->valid;
   const int kc_d = k_hi - k_lo;             // windows the digit kernel slices
   const uint32_t L = pl.L;
@@ -129,7 +130,9 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
   const bool radix = !bin_split && want_radix && cbits > (int)RX_FINE_BITS && cbits - (int)RX_FINE_BITS <= 8;
   WinSplit ws{};
   uint32_t hb = 1, nbmax = 1;   // bin split: coarse bins per window (stride of the bin tables), most buckets of one bin
-  if (bin_split) {
+  // (the digits of a fused batch alone -- msm_test_digits -- need no cuts: the _batch kernels count nothing, whatever the windows)
+  const bool cuts = !(digits_only && pl.batch);
+  if (bin_split && cuts) {
     if (kc > 16) throw MsmFail{MSM_ERR_INTERNAL, "more than 16 windows in a group of a window size above 16"};
     for (int kk = 0; kk < kc; kk++) {
       // bits the digits of this window really have: the top window of a scalar is usually short (msm_kernels.h, WinSplit)
@@ -146,7 +149,7 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
       hb = std::max(hb, 1u << abk);
       nbmax = std::max(nbmax, 1u << (eff - abk));
     }
-  } else if (radix) {
+  } else if (radix && cuts) {
     if (kc > 16) throw MsmFail{MSM_ERR_INTERNAL, "more than 16 windows in a radix-split group"};
     for (int kk = 0; kk < kc; kk++) { ws.ab[kk] = (uint8_t)(cbits - (int)RX_FINE_BITS); ws.fb[kk] = (uint8_t)RX_FINE_BITS; }
   }
@@ -200,7 +203,7 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
     // (round 2 must be an index-free round to read the element records round 1 then writes: logG >= 2)
     will_chunk = bin_split && want_chunks && !te && logG >= 2;
   }
-  if (produce && !bin_split) return;   // (only the bin split takes its histograms from the digit kernel)
+  if (produce && !bin_split && !digits_only) return;   // (only the bin split takes its histograms from the digit kernel)
   if (produce) ctx->ensure(w.dig, n_entries * 4);
   if (share && !share->produce && !bin_split) throw MsmFail{MSM_ERR_INTERNAL, "shared digits for a group that does not take the bin split"};
   // where this group's digits and slice histograms are: its own buffers, or its part of the producer's
@@ -211,11 +214,11 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
   HIPCHK(hipEventRecord(w.ev[0], s));
   if (pl.nar.width) {
     // msm_run_narrow: the same digit array (and, for the bin split, the same slice histograms) from k_digits_narrow
-    if (!consume) narrow_digits(ctx, w, d_scalars, n, pl, k_lo, kc_d, bin_split, radix, sortB, pps, hb, ws);
+    if (!consume) narrow_digits(ctx, w, d_scalars, n, pl, k_lo, kc_d, bin_split, radix, sortB, pps, hb, ws, digits_only);
   } else if (pl.batch) {
     // msm_run_batch: the kc_d windows are the K windows of pl.batch elements (virtual windows), one thread per point.  A fused
     // batch is sized to take the one-level sort (msm_batch.hip), which needs no slice histograms from the digit kernel.
-    if (bin_split || radix || k_lo != 0 || kc_d != pl.batch * pl.K) throw MsmFail{MSM_ERR_INTERNAL, "a batch group outside the one-level sort"};
+    if (((bin_split || radix) && !digits_only) || k_lo != 0 || kc_d != pl.batch * pl.K) throw MsmFail{MSM_ERR_INTERNAL, "a batch group outside the one-level sort"};
     const uint32_t grid = (uint32_t)((n + 255) / 256);
     if (te)
       hipLaunchKernelGGL(te::k_te_digits_batch, dim3(grid), dim3(256), 0, s, (uint32_t*)w.dig.p, pl.batch_sc, (uint32_t)pl.batch,

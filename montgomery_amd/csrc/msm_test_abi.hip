@@ -536,6 +536,79 @@ int msm_test_last_sort_paths(msm_ctx* ctx, int32_t* out, int cap) {
   return count;
 }
 
+int msm_test_digits(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, uint64_t n_array, uint64_t first,
+                    int32_t width_bytes, int32_t bits, int32_t is_signed, const msm_opts* opts, int32_t k_lo, int32_t k_hi,
+                    uint32_t* digits_out, int32_t* c_out, int32_t* K_out, int32_t* fold_out, int32_t* flags_rc_out) {
+  if (!ctx || !scalars || (digits_out && !flags_rc_out) || B == 0 || n == 0 || (n >> 32))
+    return fail(ctx, MSM_ERR_ARG, "msm_test_digits: null argument, no element or n outside 1 .. 2^32 - 1");
+  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "msm_test_digits: not on a device-list context");
+  for (uint32_t b = 0; b < B; b++)
+    if (!scalars[b]) return fail(ctx, MSM_ERR_ARG, "msm_test_digits: no scalars for element %u", b);
+  if (first + n > n_array || (n_array >> 32)) return fail(ctx, MSM_ERR_ARG, "msm_test_digits: [first, first + n) lies outside the array");
+  // the plan, as msm_window_sums / msm_run_narrow / msm_run_batch(_narrow) make it
+  Plan pl;
+  Plan::Narrow nar;
+  if (width_bytes) {
+    if (int rc = narrow_format(ctx, width_bytes, bits, is_signed, opts, "msm_test_digits", nar)) return rc;
+  }
+  if (make_plan(ctx, n, opts, pl, false, width_bytes ? nar.fmt.bits : 0)) return fail(ctx, MSM_ERR_ARG, "msm_test_digits: bad window size");
+  pl.nar = nar;
+  if (k_lo == 0 && k_hi == 0) k_hi = pl.K;
+  if (k_lo < 0 || k_hi > pl.K || k_lo >= k_hi) return fail(ctx, MSM_ERR_ARG, "msm_test_digits: bad window range [%d, %d) of %d", k_lo, k_hi, pl.K);
+  if (B > 1) {
+    // a fused batch: whole elements from their first scalar, all windows, no shard (the _batch kernels know none of these)
+    if (int rc = refuse_shard_opts(ctx, opts, "msm_test_digits", "a batch")) return rc;
+    if (!opts || opts->c <= 0) return fail(ctx, MSM_ERR_ARG, "msm_test_digits: a batch needs its window (msm_opts.c)");
+    if (first || n_array != n || k_lo != 0 || k_hi != pl.K || B > (uint32_t)(width_bytes ? NARROW_BATCH_MAX : BATCH_MAX))
+      return fail(ctx, MSM_ERR_ARG, "msm_test_digits: a batch takes whole arrays, all windows and at most %d elements",
+                  width_bytes ? NARROW_BATCH_MAX : BATCH_MAX);
+  }
+  if (c_out) *c_out = pl.c;
+  if (K_out) *K_out = pl.K;
+  if (fold_out) *fold_out = pl.fold ? 1 : 0;
+  if (!digits_out) return MSM_OK;   // the plan alone: what the caller sizes digits_out from
+  *flags_rc_out = MSM_OK;
+  try {
+    HIPCHK(hipSetDevice(ctx->device));
+    msm_ctx::Workspace& w = ctx->ws[0];
+    // the scalars where the real calls put them
+    const uint32_t* d_scal = nullptr;
+    NarrowBatchScalars nbs{};
+    int kc = k_hi - k_lo;
+    if (B > 1) {
+      bind_batch_scalars(pl, nbs, stage_batch_scalars(ctx, scalars, B, n, 0, pl), 0, (int)B);
+      k_hi = kc = (int)B * pl.K;   // virtual windows b K + k
+    } else if (width_bytes) {
+      float up_ms = 0;
+      const char* dev = narrow_lane_base(stage_narrow(ctx, scalars[0], (size_t)n_array * width_bytes, 0, &up_ms), width_bytes, pl.nar);
+      d_scal = group_scalars((const uint32_t*)dev, first, pl);
+    } else {
+      stage_scalars(ctx, scalars[0], n_array, 0, &d_scal);
+      d_scal = group_scalars(d_scal, first, pl);
+    }
+    HIPCHK(hipMemsetAsync(ctx->errflag.p, 0, 4, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // scalars and the error flag are in place before the group stream starts
+    // the digit launch of sort_window_group, and nothing behind it
+    GroupDigits dg;
+    dg.produce = dg.any_path = true;
+    dg.ready = ctx->ev_dig[1];
+    GroupStats st;
+    SortOut none;
+    sort_window_group(ctx, w, d_scal, n, pl, k_lo, k_hi, st, none, &dg);
+    if (!dg.valid) throw MsmFail{MSM_ERR_INTERNAL, "msm_test_digits: the digit kernel was not launched"};
+    HIPCHK(hipGetLastError());
+    const uint64_t words = (uint64_t)kc * (ctx->is_te() ? n : 2 * n);
+    HIPCHK(hipMemcpyAsync(digits_out, dg.dig, words * 4, hipMemcpyDeviceToHost, w.stream));
+    HIPCHK(hipStreamSynchronize(w.stream));
+    try {
+      check_scalar_flags(ctx, pl, "msm_test_digits");
+    } catch (const MsmFail& f) {
+      *flags_rc_out = fail(ctx, f.code, "%s", f.msg.c_str());
+    }
+    return MSM_OK;
+  } MSM_CATCH_ALL(ctx)
+}
+
 int msm_generate_points(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) {
   if (!ctx) return MSM_ERR_ARG;
   if (ctx->children.empty()) return generate_points_one(ctx, n, seed, a_out);
