@@ -286,6 +286,45 @@ int msm_scalars_inner(msm_ctx* ctx, const void* a, const void* b, uint64_t n, ui
 /* dst[i] = s * x^i mod q, i < n */
 int msm_scalars_powers(msm_ctx* ctx, void* dst, const uint8_t* s /* 32 B LE */, const uint8_t* x /* 32 B LE */, uint64_t n);
 
+/* The resident number-theoretic transform over the same vectors: polynomials in evaluation form (PLONK / Halo2 columns, KZG,
+ * Groth16's quotient) go to coefficients and back, on a domain or on a coset of it, without leaving the device; an msm_run over
+ * dst needs no extra step.  A binding detects the feature by the presence of msm_scalars_ntt.  The reference has no counterpart.
+ * B transforms of n = 2^log2n elements each, vectors back to back (vector b at element offset b n):
+ *   forward:  dst[k] = sum_j a[j] (shift omega^k)^j  -- the polynomial with coefficients a on the coset shift <omega>
+ *   inverse:  the exact inverse map (evaluations on that coset -> coefficients; the factors n^-1 and shift^-j included)
+ *   natural order in and out, both directions.
+ * Vectors: everything msm_scalars_* says above holds -- plain 32-byte little-endian integers, any value below 2^256 counts as
+ *   its residue, every element written is canonical, 16-byte alignment at any 32-byte offset inside an allocation.  Single-device
+ *   contexts only.  The call returns when the result is in place (it synchronises the context's stream) and touches no point set,
+ *   window table or range-table candidate.
+ * Aliasing: dst may be exactly a, or disjoint from it, over the whole B n range; a partial overlap is MSM_ERR_ARG.
+ * omega: 32 bytes little-endian, a primitive n-th root of unity mod q of the caller's convention (arkworks, halo2), or NULL for
+ *   the library's (msm_scalars_root_of_unity).  The host checks omega^(n/2) = q - 1 for n >= 2 -- which is "primitive n-th root" --
+ *   and fails with MSM_ERR_ARG and a message about the order otherwise; a value >= q is MSM_ERR_SCALAR; for n = 1 omega is ignored.
+ * shift: 32 bytes little-endian in [1, q), or NULL for 1.  0 is MSM_ERR_ARG (the inverse needs shift^-1), a value >= q is
+ *   MSM_ERR_SCALAR.  The host computes shift^-1 and n^-1 once per call.  A forward transform without a shift multiplies nothing
+ *   for it.
+ * Limits: log2n above msm_scalars_ntt_max_log2n, B == 0 and B n >= 2^30 are MSM_ERR_ARG.  The two-adicity of q - 1 is 47 for
+ *   BLS12-377, 32 for BLS12-381, Pallas and Vesta, 28 for BN254 and 1 for Grumpkin and Ed-on-BLS12-377: the last two accept
+ *   log2n <= 1 and refuse the rest, which is the correct answer for those fields.
+ * Errors: null pointers, misaligned pointers, a device-list context and the limits above: MSM_ERR_ARG.  All checks run before
+ *   anything is written; a failed call leaves the context usable.
+ * Device memory beyond the caller's vectors, owned by the context and freed with it (each grows to the largest call, plus 1/16):
+ *   twiddle cache   64 (2^h + 2^(log2n - h) + 2^(g - 1)) bytes, h = log2n for log2n <= 10 and ceil(log2n / 2) above, g = min(log2n, 10):
+ *                   two-level tables of omega and omega^-1 (3.0 MiB at 2^29, 1 MiB at 2^26).  It holds the tables of one
+ *                   (log2n, omega) at a time; a second call with the same pair builds nothing.
+ *   shift table     32 (2^h + 2^(log2n - h)) bytes, calls with a shift other than 1 only, rebuilt by each of them
+ *   scratch vector  32 B n bytes when the transform takes more than one pass (log2n > 9), else none */
+int msm_scalars_ntt(msm_ctx* ctx, void* dst, const void* a, uint32_t log2n, uint32_t B,
+                    const uint8_t* omega /* 32 B LE, NULL = the library's root */,
+                    const uint8_t* shift /* 32 B LE, NULL = 1 */, int inverse);
+/* the library's primitive 2^log2n-th root of unity mod q: g^((q-1)/2^log2n), g = the smallest positive quadratic non-residue
+ * (11 for BLS12-377, 3 for Grumpkin, 5 for the other five), so root(k)^2 = root(k - 1).  log2n above the two-adicity of q - 1:
+ * MSM_ERR_ARG.  No device work. */
+int msm_scalars_root_of_unity(const msm_ctx* ctx, uint32_t log2n, uint8_t* out /* 32 B LE */);
+/* the largest log2n msm_scalars_ntt accepts on this context: min(two-adicity of q - 1, 29) */
+int msm_scalars_ntt_max_log2n(const msm_ctx* ctx, uint32_t* out);
+
 /* Device memory the working buffers of one call may take (digits, sort records, tree nodes: the reference sizes them per call
  * in wasm memory, src/msm-batched-affine.ts:96-130).  0 = automatic: 85 % of what the device has free when a big call starts.
  * Windows run in as many groups as fit, and a window whose buffers would not fit at all runs over ranges of the points, one
@@ -547,6 +586,15 @@ int msm_test_set_chunk_rows_log(msm_ctx* ctx, int32_t log2_rows);
  * or msm_window_sums on this context, one per group in the order of the call's schedule; none (count 0) after a call that failed or a fused batch: writes
  * min(count, cap) of them to `out` (may be NULL with cap = 0) and returns the count, or -1 for a null or device-list context. */
 int msm_test_last_sort_paths(msm_ctx* ctx, int32_t* out, int cap);
+/* msm_scalars_ntt cuts its log2n stages into ceil(log2n / tile_log) passes of at most tile_log stages, one launch each.  This
+ * entry moves tile_log for the context, so that tests reach plans of several passes, ragged ones included, at n <= 2^12 through
+ * the library's own host code.  tile_log: 1 .. 10 (the kernel's maximum), or 0 to restore the default (9).  Results do not depend
+ * on it.  Refused on a device-list context. */
+int msm_test_set_ntt_tile_log(msm_ctx* ctx, int32_t tile_log);
+/* The stages per pass of the last msm_scalars_ntt on this context, in the order the passes ran; none (count 0) after a call that
+ * failed or a transform of one element: writes min(count, cap) of them to `stages_out` (may be NULL with cap = 0) and returns
+ * the count, or -1 for a null or device-list context. */
+int msm_test_last_ntt_plan(msm_ctx* ctx, int32_t* stages_out, int cap);
 /* The first step of every MSM alone: the window digits of a call's scalars, from the digit kernel the call would launch
  * (k_digits, k_te_digits, k_digits_narrow<W>, k_te_digits_narrow<W>; B >= 2: their _batch forms), through the pipeline's own
  * launch code and geometry, and nothing behind it -- nothing sorts the digits, so a wrong one is a wrong word in digits_out and

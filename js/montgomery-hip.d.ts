@@ -63,6 +63,12 @@ export interface Parallel {
   scalarsInner(ptrA: ScalarPtr, ptrB: ScalarPtr, N: number, options?: { aLo?: number; bLo?: number }): bigint;
   /** a new scalar pointer holding s * x^i, i < N (msm_scalars_powers); s: default 1 */
   scalarsPowers(x: bigint | number | Uint8Array, N: number, s?: bigint | number | Uint8Array): ScalarPtr;
+  /** dstPtr = the NTT of `batch` vectors of 2^log2n scalars at the start of ptr, natural order in and out (msm_scalars_ntt);
+   *  forward: dst[k] = sum_j a[j] (shift omega^k)^j, inverse: the exact inverse map; dstPtr may be ptr */
+  scalarsNtt(dstPtr: ScalarPtr, ptr: ScalarPtr, log2n: number, options?: { inverse?: boolean; omega?: bigint | number | Uint8Array;
+    shift?: bigint | number | Uint8Array; batch?: number }): ScalarPtr;
+  /** the library's primitive 2^log2n-th root of unity mod the group order (msm_scalars_root_of_unity) */
+  scalarsRootOfUnity(log2n: number): bigint;
   /** in-place fold: v[i] <- a * v[i] + b * v[i + n/2], i < n/2 (n even); the pointer then holds n/2 scalars */
   foldScalars(scalarPtr: ScalarPtr, a: bigint | number | Uint8Array, b: bigint | number | Uint8Array): ScalarPtr;
   /** the first N scalars behind a pointer (default: all) as N x 32 bytes on the host (msm_device_download) */

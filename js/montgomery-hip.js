@@ -243,6 +243,21 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       hip.scalarsPowers(ctx, ptr.dev, 0, scalarBuffer(s === undefined || s === null ? 1 : s, "s"), scalarBuffer(x, "x"), N);
       return firstOf(ptr);
     },
+    // The resident NTT (msm_scalars_ntt): dstPtr = the transform of the `batch` vectors of 2^log2n scalars at the start of ptr,
+    // natural order in and out.  forward: dst[k] = sum_j a[j] (shift omega^k)^j; inverse: the exact inverse map.
+    // options: {inverse, omega, shift, batch} -- omega: a primitive 2^log2n-th root of unity (default: scalarsRootOfUnity(log2n)),
+    // shift: in [1, order) (default 1), both BigInt / number or 32 bytes.  dstPtr may be ptr.
+    scalarsNtt(dstPtr, ptr, log2n, options) {
+      const o = options || {}, batch = o.batch === undefined ? 1 : o.batch;
+      const count = batch * 2 ** log2n;
+      needScalars(ptr, count, "scalarsNtt");
+      roomFor(dstPtr, count);
+      const opt = (v, what) => (v === undefined || v === null ? null : scalarBuffer(v, what));
+      hip.scalarsNtt(ctx, dstPtr.dev, 0, ptr.dev, 0, log2n, batch, opt(o.omega, "omega"), opt(o.shift, "shift"), !!o.inverse);
+      return dstPtr;
+    },
+    // the library's primitive 2^log2n-th root of unity mod the group order, as a BigInt (msm_scalars_root_of_unity)
+    scalarsRootOfUnity(log2n) { return leBytesToBigint(hip.scalarsRootOfUnity(ctx, log2n)); },
     // the in-place fold of an inner-product argument: v[i] <- a * v[i] + b * v[i + n/2], i < n/2; the pointer then holds n/2 scalars
     foldScalars(scalarPtr, a, b) {
       const n = scalarPtr.n;

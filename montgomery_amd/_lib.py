@@ -49,6 +49,7 @@ EXPORTS = (
     "msm_points_lincomb", "msm_pointset_size",
     "msm_device_download", "msm_scalars_lincomb", "msm_scalars_mul", "msm_scalars_inner", "msm_scalars_powers",
     "msm_test_bucket_sums", "msm_test_set_chunk_rows_log", "msm_test_last_sort_paths", "msm_test_digits",
+    "msm_scalars_ntt", "msm_scalars_root_of_unity", "msm_scalars_ntt_max_log2n", "msm_test_set_ntt_tile_log", "msm_test_last_ntt_plan",
 )
 
 
@@ -222,6 +223,14 @@ def load() -> C.CDLL:
         raise ImportError(f"{LIB_PATH} predates msm_test_digits: rebuild it (`make`)")
     lib.msm_test_digits.argtypes = [vp, C.POINTER(vp), C.c_uint32, u64, u64, u64, i32, i32, i32, C.POINTER(MsmOpts), i32, i32, vp,
                                     C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    # the resident NTT over scalar vectors, with its test surface: new symbols under ABI 8 as well
+    if not hasattr(lib, "msm_scalars_ntt"):
+        raise ImportError(f"{LIB_PATH} predates msm_scalars_ntt: rebuild it (`make`)")
+    lib.msm_scalars_ntt.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int]
+    lib.msm_scalars_root_of_unity.argtypes = [vp, C.c_uint32, vp]
+    lib.msm_scalars_ntt_max_log2n.argtypes = [vp, C.POINTER(C.c_uint32)]
+    lib.msm_test_set_ntt_tile_log.argtypes = [vp, i32]
+    lib.msm_test_last_ntt_plan.argtypes = [vp, C.POINTER(i32), C.c_int]
     for name in EXPORTS:
         if name not in ("msm_ctx_destroy", "msm_last_error", "msm_abi_version", "msm_abi_struct_bytes"):
             getattr(lib, name).restype = C.c_int

@@ -797,6 +797,29 @@ class MsmContext:
         """dst[i] = s * x^i mod q, i < n (msm_scalars_powers)."""
         self._check(self._lib.msm_scalars_powers(self._h, C.c_void_p(dst), self._scalar_buf(s, "s"), self._scalar_buf(x, "x"), n))
 
+    def scalars_ntt(self, dst: int, a: int, log2n: int, inverse: bool = False, omega=None, shift=None, batch: int = 1) -> None:
+        """`batch` transforms of n = 2^log2n scalars each, vectors back to back, natural order in and out (msm_scalars_ntt).
+        forward: dst[k] = sum_j a[j] (shift omega^k)^j; inverse: the exact inverse map (n^-1 and shift^-j included).
+        omega: a primitive n-th root of unity < q (int or 32 bytes), None = scalars_root_of_unity(log2n); shift: in [1, q),
+        None = 1.  dst may be a itself or disjoint from it."""
+        om = None if omega is None else self._scalar_buf(omega, "omega")
+        sh = None if shift is None else self._scalar_buf(shift, "shift")
+        self._check(self._lib.msm_scalars_ntt(self._h, C.c_void_p(dst), C.c_void_p(a), log2n, batch, om, sh, int(bool(inverse))))
+
+    def scalars_root_of_unity(self, log2n: int) -> int:
+        """The library's primitive 2^log2n-th root of unity mod q as an int: g^((q-1)/2^log2n), g the smallest non-residue."""
+        out = (C.c_uint8 * 32)()
+        rc = self._lib.msm_scalars_root_of_unity(self._h, log2n, out)
+        if rc:
+            raise MsmError(rc, f"scalars_root_of_unity: q - 1 has no factor 2^{log2n}")
+        return int.from_bytes(bytes(out), "little")
+
+    def scalars_ntt_max_log2n(self) -> int:
+        """The largest log2n scalars_ntt accepts on this context: min(two-adicity of q - 1, 29)."""
+        out = C.c_uint32(0)
+        self._check(self._lib.msm_scalars_ntt_max_log2n(self._h, C.byref(out)))
+        return int(out.value)
+
     def fold_scalars(self, dev_ptr: int, n: int, lo_scalar, hi_scalar) -> int:
         """The in-place fold of the n scalars at dev_ptr: v[i] <- lo_scalar * v[i] + hi_scalar * v[i + n/2], i < n/2 (n even); the
         upper half stays as it was.  The scalar fold of an inner-product argument beside fold_points.  Returns n/2."""
@@ -1313,6 +1336,21 @@ class _Parallel:
         ptr = ScalarPtr(self._ctx, size=32 * N)
         self._ctx.scalars_powers(self._scalar_dev(ptr, N, "scalarsPowers", alloc=True), x, N, s)
         return ptr
+
+    def scalarsNtt(self, dstPtr: ScalarPtr, ptr: ScalarPtr, log2n: int, options: Optional[Dict] = None) -> ScalarPtr:
+        """dstPtr = the transform of the `batch` vectors of 2^log2n scalars at the start of ptr (MsmContext.scalars_ntt).
+        options: {"inverse", "omega", "shift", "batch"}.  dstPtr may be ptr."""
+        options = options or {}
+        batch = int(options.get("batch", 1))
+        count = batch << log2n
+        a = self._scalar_dev(ptr, count, "scalarsNtt")
+        d = self._scalar_dev(dstPtr, count, "scalarsNtt", alloc=True)
+        self._ctx.scalars_ntt(d, a, log2n, bool(options.get("inverse", False)), options.get("omega"), options.get("shift"), batch)
+        return dstPtr
+
+    def scalarsRootOfUnity(self, log2n: int) -> int:
+        """The library's primitive 2^log2n-th root of unity mod q (MsmContext.scalars_root_of_unity)."""
+        return self._ctx.scalars_root_of_unity(log2n)
 
     def foldScalars(self, scalarPtr: ScalarPtr, a, b) -> ScalarPtr:
         """The in-place fold of the scalars behind scalarPtr: v[i] <- a * v[i] + b * v[i + n/2]; the pointer then holds n/2

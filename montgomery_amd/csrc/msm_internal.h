@@ -296,6 +296,14 @@ struct msm_ctx {
   // MSM_SORT_* of every window group of the last call, in the order of its schedule; cleared when a call starts its groups and
   // written when all of them have run, so a call that failed, or a fused batch, leaves it empty
   std::vector<int32_t> last_sort_paths;
+  // msm_scalars_ntt (msm_ntt.hip): the twiddle tables of one (log2n, omega) at a time, both directions; the two-level table of the
+  // shift of the last coset call; the vector that the passes before the last work in.  Freed with the context.
+  msmi::DevBuf ntt_tw, ntt_shift, ntt_scratch;
+  int ntt_tw_log2n = -1;           // -1: no tables
+  uint8_t ntt_tw_omega[32] = {};   // the root the tables are of, 32 bytes little-endian
+  bool ntt_tw_library = false;     // ... and it is the library's root of that size (a call without omega then computes no root)
+  int ntt_tile_log = 0;            // msm_test_set_ntt_tile_log: stages a pass may have; 0 = ntt::DEFAULT_TILE_LOG
+  std::vector<int32_t> last_ntt_plan;   // stages per pass of the last msm_scalars_ntt (msm_test_last_ntt_plan); empty after a refusal
 
   // per-group workspace: two of them, each with its own stream, so that the memory-bound sort of one
   // window group runs under the ALU-bound accumulation of the other

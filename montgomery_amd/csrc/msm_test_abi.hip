@@ -536,6 +536,21 @@ int msm_test_last_sort_paths(msm_ctx* ctx, int32_t* out, int cap) {
   return count;
 }
 
+int msm_test_set_ntt_tile_log(msm_ctx* ctx, int32_t tile_log) {
+  if (!ctx) return MSM_ERR_ARG;
+  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "msm_test_set_ntt_tile_log: not on a device-list context");
+  if (tile_log < 0 || tile_log > 10) return fail(ctx, MSM_ERR_ARG, "msm_test_set_ntt_tile_log: tile_log must be 0 (default) or 1 .. 10");
+  ctx->ntt_tile_log = tile_log;
+  return MSM_OK;
+}
+
+int msm_test_last_ntt_plan(msm_ctx* ctx, int32_t* stages_out, int cap) {
+  if (!ctx || !ctx->children.empty() || cap < 0 || (cap && !stages_out)) return -1;
+  const int count = (int)ctx->last_ntt_plan.size();
+  for (int i = 0; i < count && i < cap; i++) stages_out[i] = ctx->last_ntt_plan[i];
+  return count;
+}
+
 int msm_test_digits(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, uint64_t n_array, uint64_t first,
                     int32_t width_bytes, int32_t bits, int32_t is_signed, const msm_opts* opts, int32_t k_lo, int32_t k_hi,
                     uint32_t* digits_out, int32_t* c_out, int32_t* K_out, int32_t* fold_out, int32_t* flags_rc_out) {

@@ -27,6 +27,8 @@
 //          deviceDownload(h, dbuf, byteOffset, bytes) -> Buffer, scalarsLincomb(h, dst, dstOff, Buffer x, a, aOff, Buffer y | null,
 //          b | null, bOff, n): dst[i] = x a[i] + y b[i] mod q, scalarsMul(h, dst, dstOff, a, aOff, b, bOff, n),
 //          scalarsInner(h, a, aOff, b, bOff, n) -> Buffer of 32 bytes, scalarsPowers(h, dst, dstOff, Buffer s, Buffer x, n),
+//          scalarsNtt(h, dst, dstOff, a, aOff, log2n, batch, Buffer omega | null, Buffer shift | null, inverse) (msm_scalars_ntt),
+//          scalarsRootOfUnity(h, log2n) -> Buffer of 32 bytes, scalarsNttMaxLog2n(h) -> number,
 //          plan(h, n, c) -> {c, K}, generatePoints(h, n, seed) -> n, generateScalars(h, n, seed[, dbuf]) -> Buffer | n
 //          the fine operator table of the reference's wasm exports (src/field-msm.ts:86-123,190-243, src/scalar-glv.ts:41-51,105-128)
 //          over Buffers instead of wasm pointers: fieldOp(h, op, a, b) -> Buffer (msm_test_fp: multiply / square / add / subtract /
@@ -1012,6 +1014,71 @@ static napi_value ScalarsPowers(napi_env env, napi_callback_info info) {
   if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsPowers");
   return NULL;
 }
+// the resident NTT (msm_scalars_ntt): B vectors of 2^log2n elements back to back from (buffer, offset); omega, shift: Buffer | null
+static napi_value ScalarsNtt(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value argv[10];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 10) {
+    napi_throw_type_error(env, NULL, "scalarsNtt(ctx, dst, dstOff, a, aOff, log2n, batch, omega, shift, inverse)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  uint32_t log2n = 0, batch = 0;
+  bool inverse = false;
+  NAPI_OK(napi_get_value_uint32(env, argv[5], &log2n));
+  NAPI_OK(napi_get_value_uint32(env, argv[6], &batch));
+  NAPI_OK(napi_get_value_bool(env, argv[9], &inverse));
+  if (log2n > 31) {
+    napi_throw_range_error(env, NULL, "scalarsNtt: log2n must be below 32");
+    return NULL;
+  }
+  const int64_t n = (int64_t)batch << log2n;
+  uint8_t *dst = NULL, *a = NULL;
+  const uint8_t *omega = NULL, *shift = NULL;
+  if (!vec_arg(env, h, argv[1], argv[2], n, "scalarsNtt", &dst) || !vec_arg(env, h, argv[3], argv[4], n, "scalarsNtt", &a)) return NULL;
+  if (!is_nullish(env, argv[7]) && !host_scalar_arg(env, argv[7], &omega)) return NULL;
+  if (!is_nullish(env, argv[8]) && !host_scalar_arg(env, argv[8], &shift)) return NULL;
+  int rc = msm_scalars_ntt(h->ctx, dst, a, log2n, batch, omega, shift, inverse ? 1 : 0);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsNtt");
+  return NULL;
+}
+// scalarsRootOfUnity(ctx, log2n) -> Buffer of 32 bytes; scalarsNttMaxLog2n(ctx) -> number
+static napi_value ScalarsRootOfUnity(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) {
+    napi_throw_type_error(env, NULL, "scalarsRootOfUnity(ctx, log2n)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  uint32_t log2n = 0;
+  NAPI_OK(napi_get_value_uint32(env, argv[1], &log2n));
+  napi_value out;
+  void* po = NULL;
+  NAPI_OK(napi_create_buffer(env, 32, &po, &out));
+  if (msm_scalars_root_of_unity(h->ctx, log2n, (uint8_t*)po) != MSM_OK) {
+    napi_throw_range_error(env, NULL, "scalarsRootOfUnity: the group order minus one has no such power of two as a factor");
+    return NULL;
+  }
+  return out;
+}
+static napi_value ScalarsNttMaxLog2n(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  js_ctx* h = argc ? get_handle(env, argv[0]) : NULL;
+  if (!h) return NULL;
+  uint32_t top = 0;
+  int rc = msm_scalars_ntt_max_log2n(h->ctx, &top);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsNttMaxLog2n");
+  napi_value out;
+  NAPI_OK(napi_create_uint32(env, top, &out));
+  return out;
+}
 
 /* ---- the fine operator table: element-wise field / GLV / curve operators over Buffers -------------------------------- */
 
@@ -1152,6 +1219,7 @@ NAPI_MODULE_INIT() {
       {"pointsLincomb", PointsLincomb}, {"pointsetSize", PointsetSize},
       {"deviceDownload", DeviceDownload}, {"scalarsLincomb", ScalarsLincomb}, {"scalarsMul", ScalarsMul},
       {"scalarsInner", ScalarsInner}, {"scalarsPowers", ScalarsPowers},
+      {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity}, {"scalarsNttMaxLog2n", ScalarsNttMaxLog2n},
       {"fieldOp", FieldOp}, {"batchInverse", BatchInverse}, {"glvDecompose", GlvDecompose}, {"batchAdd", BatchAdd}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
     napi_value f;
