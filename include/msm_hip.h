@@ -622,6 +622,36 @@ int msm_test_last_ntt_plan(msm_ctx* ctx, int32_t* stages_out, int cap);
 int msm_test_digits(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64_t n, uint64_t n_array, uint64_t first,
                     int32_t width_bytes, int32_t bits, int32_t is_signed, const msm_opts* opts, int32_t k_lo, int32_t k_hi,
                     uint32_t* digits_out, int32_t* c_out, int32_t* K_out, int32_t* fold_out, int32_t* flags_rc_out);
+/* The stage between "sorted" and "finished" on buckets of the caller, all curves: the scans behind the sort (k_bucket_max,
+ * k_pscan_partial / _top / _final), the host's round plan and every round of the accumulation tree in their real order on the
+ * real buffers (accumulate_window_group itself: gather round 1 over padded slots, regular rounds, k_tail_desc and the search
+ * rounds, the bucket finish), then the bucket reduction.  Runs on workspace 0; the resident points are not touched.
+ *   pool, off, elems, K, L   as msm_test_bucket_sums (L = 1 allowed)
+ *   flags  one byte per element, or NULL: bit 0 negates the point, bit 1 takes the beta x line of its row (the endomorphism
+ *          image, of discrete log lambda d).  Every Weierstrass curve of this library carries that line; the Edwards curve has
+ *          none and refuses bit 1.
+ *   c      selects the threshold class only: FINISH_MAX and the smallest tail round worth a launch, as the tree derives them
+ *          from the plan's window (c >= 18 or below); 1 .. 24
+ *   logG   buckets are padded to multiples of 2^logG slots and take logG regular rounds; 1 .. 10, what the sort can ask for
+ *   reported_max   0: k_bucket_max finds the largest bucket.  Otherwise a value >= the largest bucket that stands in its place,
+ *          as the count pass of the pair form over-reports it: RT grows, the sums do not change.
+ * Writes K x 144 bytes to sums_out (X || Y || Z as msm_test_bucket_sums, never merged) and the plan that ran:
+ *   plan_out      8 words: RT, r_stop (tail rounds run), total padded slots, the largest bucket as reported, rounds and n_pairs
+ *                 as msm_result counts them, launched rounds, 0
+ *   cursor_out    (may be NULL) K L + 1 words: the slot every bucket starts at, [K L] = the total
+ *   tail_off_out  (may be NULL) min(RT + 1, tail_tables_cap) tables of K L + 1 words: table r = offsets of the elements every
+ *                 bucket holds after r tail rounds
+ *   round_log_out (may be NULL with round_log_cap = 0) per launched round, at most round_log_cap: mode (0 gather, 1 regular,
+ *                 2 search), n_out, steps (pairs per lane)
+ * The slots are written on the host from the device's cursor.  Scans whose total or cursor would leave the padded slots end the
+ * call with MSM_ERR_INTERNAL before any round runs (plan_out[0], [2], [3] and the two tables are written by then).
+ * MSM_ERR_ARG, the context staying usable: a device-list context, offsets that do not start at 0 or do not ascend, an element
+ * outside the pool, a flag the curve has no line for, logG or c outside their range, reported_max below the largest bucket,
+ * 2^31 padded slots or more, and the sizes msm_test_bucket_sums refuses. */
+int msm_test_tree_sums(msm_ctx* ctx, const uint8_t* pool, uint64_t n_pool, const uint32_t* off, const uint32_t* elems,
+                       const uint8_t* flags, int32_t K, uint32_t L, int32_t c, uint32_t logG, uint32_t reported_max, uint8_t* sums_out,
+                       uint64_t* plan_out, uint32_t* cursor_out, uint32_t* tail_off_out, uint32_t tail_tables_cap,
+                       uint64_t* round_log_out, uint32_t round_log_cap);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,7 @@ EXPORTS = (
     "msm_device_download", "msm_scalars_lincomb", "msm_scalars_mul", "msm_scalars_inner", "msm_scalars_powers",
     "msm_test_bucket_sums", "msm_test_set_chunk_rows_log", "msm_test_last_sort_paths", "msm_test_digits",
     "msm_scalars_ntt", "msm_scalars_root_of_unity", "msm_scalars_ntt_max_log2n", "msm_test_set_ntt_tile_log", "msm_test_last_ntt_plan",
+    "msm_test_tree_sums",
 )
 
 
@@ -231,6 +232,11 @@ def load() -> C.CDLL:
     lib.msm_scalars_ntt_max_log2n.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.msm_test_set_ntt_tile_log.argtypes = [vp, i32]
     lib.msm_test_last_ntt_plan.argtypes = [vp, C.POINTER(i32), C.c_int]
+    # the scans, the round plan and the tree rounds on crafted buckets: a new test symbol under ABI 8
+    if not hasattr(lib, "msm_test_tree_sums"):
+        raise ImportError(f"{LIB_PATH} predates msm_test_tree_sums: rebuild it (`make`)")
+    lib.msm_test_tree_sums.argtypes = [vp, vp, u64, vp, vp, vp, i32, C.c_uint32, i32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32,
+                                       vp, C.c_uint32]
     for name in EXPORTS:
         if name not in ("msm_ctx_destroy", "msm_last_error", "msm_abi_version", "msm_abi_struct_bytes"):
             getattr(lib, name).restype = C.c_int

@@ -981,6 +981,44 @@ class MsmContext:
                                                    K, L, int(bool(merged)), stride, tc, out, perm.ctypes.data if want_perm else None))
         return (bytes(out), perm) if want_perm else bytes(out)
 
+    TREE_MODES = ("gather", "regular", "search")
+
+    def test_tree_sums(self, pool: BytesLike, off, elems, K: int, L: int, c: int, logG: int, flags=None, reported_max: int = 0,
+                       tail_tables: int = 0, want_cursor: bool = True) -> dict:
+        """The scans behind the sort, the round plan and every round of the accumulation tree on crafted buckets, then the bucket
+        reduction (msm_test_tree_sums, msm_hip.h).  pool, off, elems, K, L as test_bucket_sums; flags: one uint8 per element
+        (bit 0 negate, bit 1 the beta x line) or None; c picks the threshold class, logG the padding granule; reported_max
+        stands in for the largest bucket (0: the device finds it).  tail_tables: how many tail_off tables to bring back.
+        Returns {"sums": K x 144 bytes, "RT", "r_stop", "total_slots", "max_bucket", "rounds", "n_pairs", "cursor": uint32
+        [K L + 1] or None, "tail_off": uint32 [min(RT + 1, tail_tables), K L + 1], "log": [(mode name, n_out, steps), ...]}."""
+        import numpy as np
+
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        elems = np.ascontiguousarray(elems, dtype=np.uint32)
+        pb = 2 * self.coord_bytes
+        if len(pool) == 0 or len(pool) % pb or len(off) != K * L + 1 or len(elems) != int(off[-1]):
+            raise MsmError(_lib.MSM_ERR_ARG, f"expected whole {pb}-byte pool points, {K * L + 1} offsets and off[-1] elements")
+        if flags is not None:
+            flags = np.ascontiguousarray(flags, dtype=np.uint8)
+            if len(flags) != len(elems):
+                raise MsmError(_lib.MSM_ERR_ARG, "expected one flag byte per element")
+        buf = (C.c_uint8 * len(pool)).from_buffer_copy(bytes(pool))
+        out = (C.c_uint8 * (144 * K))()
+        plan = np.zeros(8, dtype=np.uint64)
+        cursor = np.zeros(K * L + 1, dtype=np.uint32) if want_cursor else None
+        tail = np.zeros((max(tail_tables, 0), K * L + 1), dtype=np.uint32)
+        LOG_CAP = 48   # logG <= 10 regular and RT <= 32 tail rounds
+        log = np.zeros((LOG_CAP, 3), dtype=np.uint64)
+        self._check(self._lib.msm_test_tree_sums(
+            self._h, buf, len(pool) // pb, off.ctypes.data, elems.ctypes.data if len(elems) else None,
+            flags.ctypes.data if flags is not None and len(flags) else None, K, L, c, logG, reported_max, out, plan.ctypes.data,
+            cursor.ctypes.data if want_cursor else None, tail.ctypes.data if tail_tables > 0 else None, max(tail_tables, 0),
+            log.ctypes.data, LOG_CAP))
+        RT, r_stop, total_slots, max_bucket, rounds, n_pairs, n_log = (int(v) for v in plan[:7])
+        return {"sums": bytes(out), "RT": RT, "r_stop": r_stop, "total_slots": total_slots, "max_bucket": max_bucket, "rounds": rounds,
+                "n_pairs": n_pairs, "cursor": cursor, "tail_off": tail[:min(RT + 1, max(tail_tables, 0))],
+                "log": [(self.TREE_MODES[int(m)], int(n), int(s)) for m, n, s in log[:min(n_log, LOG_CAP)]]}
+
     def test_set_chunk_rows_log(self, log2_rows: int = 0) -> None:
         """Round 1 of big windows takes the pair form above 2^log2_rows table rows (msm_test_set_chunk_rows_log, msm_hip.h);
         0 restores the default of 23."""

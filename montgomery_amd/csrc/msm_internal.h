@@ -587,14 +587,37 @@ struct GroupDigits {
 };
 void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars, uint64_t n, const Plan& pl, int k_lo, int k_hi,
                        GroupStats& st, SortOut& so, GroupDigits* share = nullptr);
+// The scans behind the sort, which sort_window_group and the operator test msm_test_tree_sums both run: the nb bucket sizes in
+// w.counts -> w.cursor (padded slot offsets, nb + 1 words), w.tail_off (RT + 1 tables of nb + 1 words) and the totals in w.info.
+// find_max: clears w.info and looks for the largest bucket first (k_bucket_max); otherwise info[1] holds it already, or a bound
+// on it.  Queued on w.stream; records w.ev[7] behind the last scan.
+void scan_bucket_sizes(msm_ctx* ctx, msm_ctx::Workspace& w, uint64_t nb, uint32_t logG, bool find_max);
+// the ONE read-back of w.info behind the scans, on w.side while w.stream goes on: the launch geometry of the tree
+struct ScanTotals {
+  uint64_t total_slots = 0;
+  uint32_t max_bucket = 0;
+  int RT = 0;                 // tail rounds the largest bucket would need: 2^RT >= ceil(max_bucket / 2^logG)
+  uint64_t algo_pairs = 0;    // sum over the non-empty buckets of (size - 1)
+};
+ScanTotals read_scan_totals(msm_ctx::Workspace& w, uint32_t logG);
 // what the tree leaves behind for the bucket reduction
 struct TreeOut {
   const uint32_t* bucket_proj = nullptr;   // one bucket sum per bucket from k_bucket_finish (projective / extended, raw limbs)
 };
+// the round plan as it ran, for msm_test_tree_sums (normal calls pass no log)
+struct TreeLog {
+  int r_stop = 0;             // tail rounds run
+  struct Round {
+    int mode;                 // MODE_GATHER / MODE_REGULAR / MODE_SEARCH
+    uint64_t n_out;
+    uint32_t steps;
+  };
+  std::vector<Round> rounds;  // one per launched round, in launch order
+};
 // kc: windows of the group as the tree sees them (1 on window tables); row_off: first row of the point table the payloads count from
 // (0 on window tables: every group reads them from table 0)
 void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl, int kc, uint64_t row_off, const SortOut& so,
-                             GroupStats& st, TreeOut& to);
+                             GroupStats& st, TreeOut& to, TreeLog* log = nullptr);
 // bytes of w.bucket_proj for nb buckets: a projective (Edwards: extended) point of raw limbs each
 inline size_t bucket_proj_bytes(const msm_ctx* ctx, uint64_t nb) { return nb * (ctx->is_te() ? 4 * te::TL : 3 * NL) * 4; }
 // the last step of accumulate_window_group, which the operator test msm_test_bucket_sums runs on buckets of its own (msm_tree.hip)

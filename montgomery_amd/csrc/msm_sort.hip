@@ -69,6 +69,40 @@ static void narrow_digits(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d
 #undef MSM_NARROW_LAUNCH
 }
 
+// largest bucket -> number of tail rounds RT, then the multi-block scan of RT + 2 quantities.  The scan kernels take RT
+// from the device (pscan_nq), so ONE read-back behind them brings the largest bucket and the totals together.
+void scan_bucket_sizes(msm_ctx* ctx, msm_ctx::Workspace& w, uint64_t nb, uint32_t logG, bool find_max) {
+  hipStream_t s = w.stream;
+  if (find_max) {
+    HIPCHK(hipMemsetAsync(w.info.p, 0, 64 * 4, s));
+    hipLaunchKernelGGL(k_bucket_max, dim3((uint32_t)std::min<uint64_t>(1024, (nb + 255) / 256)), dim3(256), 0, s,
+                       (const uint32_t*)w.counts.p, (uint32_t)nb, (uint32_t*)w.info.p);
+  }
+  const uint32_t nblocks = (uint32_t)((nb + PS_SPAN - 1) / PS_SPAN);
+  ctx->ensure(w.scan_partial, (size_t)PS_MAX_NQ * nblocks * 4);
+  hipLaunchKernelGGL(k_pscan_partial, dim3(nblocks), dim3(PS_BLOCK), 0, s, (const uint32_t*)w.counts.p, (uint32_t)nb, logG,
+                     (const uint32_t*)w.info.p, (uint32_t*)w.scan_partial.p, nblocks);
+  hipLaunchKernelGGL(k_pscan_top, dim3(1), dim3(SCAN_THREADS), 0, s, (uint32_t*)w.scan_partial.p, nblocks, logG,
+                     (uint32_t*)w.info.p);
+  hipLaunchKernelGGL(k_pscan_final, dim3(nblocks), dim3(PS_BLOCK), 0, s, (const uint32_t*)w.counts.p, (uint32_t)nb, logG,
+                     (const uint32_t*)w.scan_partial.p, nblocks, (uint32_t*)w.cursor.p, (uint32_t*)w.tail_off.p,
+                     (const uint32_t*)w.info.p);
+  HIPCHK(hipEventRecord(w.ev[7], s));
+}
+
+ScanTotals read_scan_totals(msm_ctx::Workspace& w, uint32_t logG) {
+  ScanTotals t;
+  HIPCHK(hipStreamWaitEvent(w.side, w.ev[7], 0));
+  HIPCHK(hipMemcpyAsync(w.h_info, w.info.p, 64 * 4, hipMemcpyDeviceToHost, w.side));
+  HIPCHK(hipStreamSynchronize(w.side));
+  t.total_slots = w.h_info[0];
+  t.max_bucket = w.h_info[1];
+  t.algo_pairs = (uint64_t)w.h_info[INFO_ALGO_PAIRS] | ((uint64_t)w.h_info[INFO_ALGO_PAIRS + 1] << 32);
+  const uint32_t capmax = (t.max_bucket + (1u << logG) - 1) >> logG;
+  while (t.RT < 32 && (1u << t.RT) < capmax) t.RT++;
+  return t;
+}
+
 // windows [k_lo, k_hi) over n points whose scalars start at d_scalars (n x 8 words); queues everything on w.stream, records
 // w.ev[0] (start), w.ev[1] (digits done), w.ev[2] (sort done) and returns after ONE read-back (largest bucket, scan totals ->
 // w.h_info: the launch geometry of the tree)
@@ -300,28 +334,8 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
                        (const uint32_t*)d_extra_first, (const uint32_t*)d_mp_first, hb, L, nbmax, ws, (uint32_t*)w.info.p,
                        will_chunk ? 1u : 0u);
   }
-  int RT = 0;
-  uint64_t total_slots = 0;
-  uint32_t max_bucket = 0;
-  {
-    // largest bucket -> number of tail rounds RT, then the multi-block scan of RT + 2 quantities.  The scan kernels take RT
-    // from the device (pscan_nq), so ONE read-back behind them brings the largest bucket and the totals together.
-    if (!bin_split) {
-      HIPCHK(hipMemsetAsync(w.info.p, 0, 64 * 4, s));
-      hipLaunchKernelGGL(k_bucket_max, dim3((uint32_t)std::min<uint64_t>(1024, (nb + 255) / 256)), dim3(256), 0, s,
-                         (const uint32_t*)w.counts.p, (uint32_t)nb, (uint32_t*)w.info.p);
-    }
-    const uint32_t nblocks = (uint32_t)((nb + PS_SPAN - 1) / PS_SPAN);
-    ctx->ensure(w.scan_partial, (size_t)PS_MAX_NQ * nblocks * 4);
-    hipLaunchKernelGGL(k_pscan_partial, dim3(nblocks), dim3(PS_BLOCK), 0, s, (const uint32_t*)w.counts.p, (uint32_t)nb, logG,
-                       (const uint32_t*)w.info.p, (uint32_t*)w.scan_partial.p, nblocks);
-    hipLaunchKernelGGL(k_pscan_top, dim3(1), dim3(SCAN_THREADS), 0, s, (uint32_t*)w.scan_partial.p, nblocks, logG,
-                       (uint32_t*)w.info.p);
-    hipLaunchKernelGGL(k_pscan_final, dim3(nblocks), dim3(PS_BLOCK), 0, s, (const uint32_t*)w.counts.p, (uint32_t)nb, logG,
-                       (const uint32_t*)w.scan_partial.p, nblocks, (uint32_t*)w.cursor.p, (uint32_t*)w.tail_off.p,
-                       (const uint32_t*)w.info.p);
-    HIPCHK(hipEventRecord(w.ev[7], s));
-  }
+  // (the bin split's count pass has left the largest bucket in `info`; the other paths look for it here)
+  scan_bucket_sizes(ctx, w, nb, logG, !bin_split);
   // Big windows over a big table: round 1 walks the pairs in the order the last pass of the sort emits them -- tile by tile of
   // a bin's records, which are in point order -- and writes every sum to the element index that comes with the pair, as
   // 64-byte records that round 2 reads back (batch_add.h).  Needed once the 128 slots of a wave span more than ~1 GB of
@@ -361,16 +375,11 @@ void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_sc
     }
   };
   if (bin_split) launch_bin_pass(slots_bound);
-  {
-    HIPCHK(hipStreamWaitEvent(w.side, w.ev[7], 0));
-    HIPCHK(hipMemcpyAsync(w.h_info, w.info.p, 64 * 4, hipMemcpyDeviceToHost, w.side));
-    HIPCHK(hipStreamSynchronize(w.side));
-    total_slots = w.h_info[0];
-    max_bucket = w.h_info[1];
-    st.n_pairs_algo += (uint64_t)w.h_info[INFO_ALGO_PAIRS] | ((uint64_t)w.h_info[INFO_ALGO_PAIRS + 1] << 32);
-    const uint32_t capmax = (max_bucket + (1u << logG) - 1) >> logG;
-    while (RT < 32 && (1u << RT) < capmax) RT++;
-  }
+  const ScanTotals tot = read_scan_totals(w, logG);
+  const int RT = tot.RT;
+  const uint64_t total_slots = tot.total_slots;
+  const uint32_t max_bucket = tot.max_bucket;
+  st.n_pairs_algo += tot.algo_pairs;
   st.max_bucket = std::max<uint64_t>(st.max_bucket, max_bucket);
   if (total_slots > slots_bound) throw MsmFail{MSM_ERR_INTERNAL, "the padded slots exceed their bound"};
   if (bin_split && chunked && total_slots < 2) {   // (no entry at all: the plain slot form handles the empty tree)

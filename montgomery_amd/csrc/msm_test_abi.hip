@@ -462,6 +462,145 @@ int msm_test_bucket_sums(msm_ctx* ctx, const uint8_t* pool, uint64_t n_pool, con
   } MSM_CATCH_ALL(ctx)
 }
 
+int msm_test_tree_sums(msm_ctx* ctx, const uint8_t* pool, uint64_t n_pool, const uint32_t* off, const uint32_t* elems,
+                       const uint8_t* flags, int32_t K, uint32_t L, int32_t c, uint32_t logG, uint32_t reported_max, uint8_t* sums_out,
+                       uint64_t* plan_out, uint32_t* cursor_out, uint32_t* tail_off_out, uint32_t tail_tables_cap,
+                       uint64_t* round_log_out, uint32_t round_log_cap) {
+  if (!ctx || !pool || !off || !sums_out || !plan_out || n_pool == 0 || K <= 0 || L == 0 || (L & (L - 1)) || (round_log_cap && !round_log_out))
+    return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: bad argument");
+  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: not on a device-list context");
+  if (c < 1 || c > 24) return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: c must be in 1 .. 24");
+  if (logG < 1 || logG > 10) return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: logG must be in 1 .. 10");
+  const uint64_t nb = (uint64_t)K * L;
+  if (nb >= (1ull << 31) || (uint64_t)K * (ceil_log2_u64(L) + 1) > 128 * 20)
+    return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: too many buckets or windows");
+  const uint64_t n_el = off[nb];
+  if (off[0] != 0 || (n_el && !elems) || n_el >= (1ull << 31)) return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: bad offsets");
+  const bool te = ctx->is_te();
+  const uint32_t G = 1u << logG;
+  uint32_t true_max = 0;
+  uint64_t padded = 0;   // the slots the scans owe: every bucket rounded up to a multiple of G
+  for (uint64_t b = 0; b < nb; b++) {
+    if (off[b] > off[b + 1]) return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: offsets must ascend");
+    const uint32_t cnt = off[b + 1] - off[b];
+    true_max = std::max(true_max, cnt);
+    padded += ((uint64_t)cnt + G - 1) / G * G;
+  }
+  if (padded >= (1ull << 31)) return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: too many padded slots");
+  if (reported_max && reported_max < true_max)
+    return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: reported_max %u lies below the largest bucket, %u", reported_max, true_max);
+  for (uint64_t e = 0; e < n_el; e++) {
+    if (elems[e] >= n_pool) return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: element %llu names no pool point", (unsigned long long)e);
+    if (flags && (flags[e] > 3 || (te && (flags[e] & 2))))
+      return fail(ctx, MSM_ERR_ARG, "msm_test_tree_sums: element %llu: flags are bit 0 (negate) and, on the Weierstrass curves, bit 1 (beta x)",
+                  (unsigned long long)e);
+  }
+  try {
+    HIPCHK(hipSetDevice(ctx->device));
+    msm_ctx::Workspace& w = ctx->ws[0];
+    hipStream_t s = w.stream;
+    const size_t pb = 2 * ctx->coord_bytes();   // wire point
+    // 1. the pool as point rows of its own (the resident set stays as it is), the bucket sizes where the sort leaves them
+    ScopedDevBuf wire, rows;
+    ctx->ensure(wire, n_pool * pb);
+    ctx->ensure(rows, n_pool * ctx->row_words() * 4);
+    ctx->ensure(w.counts, nb * 4);
+    ctx->ensure(w.cursor, (nb + 1) * 4);
+    ctx->ensure(w.tail_off, (size_t)34 * (nb + 1) * 4);
+    ctx->ensure(w.info, 64 * 4);
+    std::vector<uint32_t> h_counts(nb);
+    for (uint64_t b = 0; b < nb; b++) h_counts[b] = off[b + 1] - off[b];
+    HIPCHK(hipMemsetAsync(ctx->errflag.p, 0, 4, s));
+    HIPCHK(hipMemcpyAsync(wire.p, pool, n_pool * pb, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.counts.p, h_counts.data(), nb * 4, hipMemcpyHostToDevice, s));
+    if (te)
+      hipLaunchKernelGGL(te::k_te_points_from_wire, dim3((uint32_t)((n_pool + 255) / 256)), dim3(256), 0, s, (uint32_t*)rows.p,
+                         (const uint32_t*)wire.p, n_pool, 0, (uint32_t*)ctx->errflag.p);
+    else
+      W_LAUNCH(ctx, k_points_from_wire, dim3((uint32_t)((n_pool + 255) / 256)), dim3(256), 0, s, (uint32_t*)rows.p,
+               (const uint32_t*)wire.p, n_pool, 0, (uint32_t*)ctx->errflag.p);
+    // 2. the pipeline's scans; a reported maximum stands in `info` where the count pass of the bin split leaves its own
+    if (reported_max) {
+      std::vector<uint32_t> h_info(64, 0);
+      h_info[1] = reported_max;
+      HIPCHK(hipMemcpyAsync(w.info.p, h_info.data(), 64 * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipStreamSynchronize(s));   // (h_info leaves the scope)
+    }
+    scan_bucket_sizes(ctx, w, nb, logG, reported_max == 0);
+    const ScanTotals tot = read_scan_totals(w, logG);
+    // 3. the padded slots from the device's cursor
+    std::vector<uint32_t> h_cursor(nb + 1);
+    HIPCHK(hipMemcpyAsync(h_cursor.data(), w.cursor.p, (nb + 1) * 4, hipMemcpyDeviceToHost, s));
+    const uint32_t tables = std::min<uint32_t>((uint32_t)tot.RT + 1, tail_tables_cap);
+    if (tail_off_out && tables)
+      HIPCHK(hipMemcpyAsync(tail_off_out, w.tail_off.p, (size_t)tables * (nb + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (cursor_out) memcpy(cursor_out, h_cursor.data(), (nb + 1) * 4);
+    plan_out[0] = (uint64_t)tot.RT;
+    plan_out[2] = tot.total_slots;
+    plan_out[3] = tot.max_bucket;
+    plan_out[1] = plan_out[4] = plan_out[5] = plan_out[6] = plan_out[7] = 0;
+    // (slots are written, and the tree sized, from what the device reports: a cursor that would leave them is a finding of its own)
+    if (tot.total_slots != padded || h_cursor[nb] != padded)
+      throw MsmFail{MSM_ERR_INTERNAL, "msm_test_tree_sums: the scans report " + std::to_string(tot.total_slots) + " padded slots, the buckets need " + std::to_string(padded)};
+    for (uint64_t b = 0; b < nb; b++)
+      if ((uint64_t)h_cursor[b] + h_counts[b] > padded)
+        throw MsmFail{MSM_ERR_INTERNAL, "msm_test_tree_sums: the cursor of bucket " + std::to_string(b) + " leaves the padded slots"};
+    std::vector<uint32_t> h_slots(std::max<uint64_t>(padded, 2), SLOT_EMPTY);
+    for (uint64_t b = 0; b < nb; b++)
+      for (uint32_t i = 0; i < h_counts[b]; i++) {
+        const uint64_t e = (uint64_t)off[b] + i;
+        const uint32_t f = flags ? flags[e] : 0u;
+        // the payloads k_batch_add<MODE_GATHER> / k_te_add<MODE_GATHER> decode: (entry << 1) | negate, entry = 2 row + line, or the row
+        const uint32_t entry = te ? elems[e] : 2 * elems[e] + ((f >> 1) & 1u);
+        h_slots[h_cursor[b] + i] = (entry << 1) | (f & 1u);
+      }
+    ctx->ensure(w.slots, h_slots.size() * 4);
+    HIPCHK(hipMemcpyAsync(w.slots.p, h_slots.data(), h_slots.size() * 4, hipMemcpyHostToDevice, s));
+    // 4. what the sort leaves for its tree, 5. the tree itself
+    SortOut so;
+    so.logG = logG;
+    so.RT = tot.RT;
+    so.total_slots = tot.total_slots;
+    so.max_bucket = tot.max_bucket;
+    so.round1_slots = (const uint32_t*)w.slots.p;
+    Plan pl{};
+    pl.c = c;
+    pl.K = K;
+    pl.L = L;
+    pl.L_log = (int)ceil_log2_u64(L);
+    pl.no_glv = false;
+    pl.tables = true;   // (the payloads count the rows of a buffer of the plan's own)
+    pl.tab_rows = (const uint32_t*)rows.p;
+    pl.tab_n = n_pool;
+    ctx->ensure(w.bucket_proj, bucket_proj_bytes(ctx, nb));
+    HIPCHK(hipMemsetAsync(w.bucket_proj.p, 0x2A, bucket_proj_bytes(ctx, nb), s));   // a bucket the finish skips cannot come out right
+    GroupStats st;
+    TreeOut to;
+    TreeLog log;
+    accumulate_window_group(ctx, w, pl, K, 0, so, st, to, &log);
+    // 6. the bucket reduction
+    const int sw = ctx->sum_words();
+    std::vector<uint32_t> parts((size_t)K * sw, 0);
+    reduce_buckets(ctx, w, to.bucket_proj, L, K, parts.data());
+    HIPCHK(hipMemcpyAsync(w.h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    if (w.h_info[0] & 1) return fail(ctx, MSM_ERR_POINT, "msm_test_tree_sums: coordinate >= p");
+    plan_out[1] = (uint64_t)log.r_stop;
+    plan_out[4] = (uint64_t)st.rounds;
+    plan_out[5] = st.n_pairs;
+    plan_out[6] = log.rounds.size();
+    for (size_t i = 0; i < log.rounds.size() && i < round_log_cap; i++) {
+      round_log_out[3 * i] = (uint64_t)log.rounds[i].mode;
+      round_log_out[3 * i + 1] = log.rounds[i].n_out;
+      round_log_out[3 * i + 2] = log.rounds[i].steps;
+    }
+    for (int k = 0; k < K; k++) sum_to_wire(ctx, &parts[(size_t)k * sw], sums_out + (size_t)k * SUM_WIRE_BYTES);
+    return MSM_OK;
+  } MSM_CATCH_ALL(ctx)
+}
+
 int msm_test_batch_add_mode(msm_ctx* ctx, const uint8_t* g, const uint8_t* h, uint8_t* out, uint64_t n, int mode, uint32_t steps) {
   if (!ctx || !g || !h || !out || n == 0 || steps == 0) return fail(ctx, MSM_ERR_ARG, "msm_test_batch_add_mode: bad argument");
   if (ctx->is_te() || (mode != MODE_REGULAR && mode != MODE_SEARCH))

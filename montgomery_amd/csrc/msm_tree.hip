@@ -41,7 +41,7 @@ const uint32_t* finish_buckets(msm_ctx* ctx, msm_ctx::Workspace& w, const uint4*
 
 // queues the tree on w.stream behind whatever is there; records w.ev[6] behind round 1 and w.ev[3] behind the last kernel
 void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl, int kc, uint64_t row_off, const SortOut& so,
-                             GroupStats& st, TreeOut& to) {
+                             GroupStats& st, TreeOut& to, TreeLog* log) {
   hipStream_t s = w.stream;
   const bool lone = pl.lone;
   const bool te = ctx->is_te();
@@ -73,6 +73,7 @@ void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl
   while (r_stop < RT &&
          (((cap_elems + (1u << r_stop) - 1) >> r_stop) > FINISH_MAX || w.h_info[3 + r_stop + 1] >= tail_min_pairs))
     r_stop++;
+  if (log) log->r_stop = r_stop;
   // outputs alternate between two buffers: size each for the largest round it receives
   uint64_t capA = 1, capB = 1;
   {
@@ -128,6 +129,7 @@ void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl
       if (rows_in) { a.points = (const uint32_t*)w.rows1.p; a.slots = nullptr; }
       if (rows_out) a.out_y_off = rec_y_off;                      // 12-word fields: x records, then y records (batch_add.h)
       if (rows_in && ctx->nw() == 12) a.y_off = rec_y_off;
+      if (log) log->rounds.push_back({r == 1 || rows_in ? MODE_GATHER : MODE_REGULAR, n_out, g.steps});
       if (r == 1 || rows_in) {
         if (te) hipLaunchKernelGGL(te::k_te_add<MODE_GATHER>, dim3(g.grid), dim3(256), 0, s, a);
         else W_LAUNCH_MODE(ctx, k_batch_add, MODE_GATHER, dim3(g.grid), dim3(256), 0, s, a);
@@ -165,6 +167,7 @@ void accumulate_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const Plan& pl
         hipLaunchKernelGGL(k_tail_desc, dim3((uint32_t)((n_out + 255) / 256)), dim3(256), 0, s, (uint32_t*)w.desc.p, off_in,
                            off_out, (uint32_t)nb, (uint32_t)n_out);
         a.desc = (const uint32_t*)w.desc.p;
+        if (log) log->rounds.push_back({MODE_SEARCH, n_out, g.steps});
         if (te) hipLaunchKernelGGL(te::k_te_add<MODE_SEARCH>, dim3(g.grid), dim3(256), 0, s, a);
         else W_LAUNCH_MODE(ctx, k_batch_add, MODE_SEARCH, dim3(g.grid), dim3(256), 0, s, a);
       }

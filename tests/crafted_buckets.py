@@ -9,6 +9,8 @@ negatives, the identity, small multiples of G -- and, as off / elems, the pool i
 sums follow from the discrete logs alone, one scaling of G per window whatever L is: Crafted.expected, Crafted.expected_group.
 The named fill patterns at the end build the inputs of tests/test_gpu_bucket_sums.py (msm_test_bucket_sums, include/msm_hip.h);
 tests/test_crafted_buckets.py proves them against the oracle's point arithmetic on the CPU first.
+A Crafted may also carry one flag byte per element (negate, beta x line), and the tree_* patterns at the very end choose bucket
+SIZES for the accumulation tree: the inputs of tests/test_gpu_tree.py (msm_test_tree_sums).
 """
 import functools
 import os
@@ -53,7 +55,7 @@ def neg_index(j):
 class Crafted:
     """K windows of L buckets over a pool: bucket l (1-based) of window k holds the pool points elems[off[k L + l - 1] : off[k L + l]]."""
 
-    def __init__(self, name, curve, K, L, counts, elems, extra=()):
+    def __init__(self, name, curve, K, L, counts, elems, extra=(), flags=None):
         cv = CURVE_TABLE[curve]
         pts, logs = base_pool(curve)
         self.name, self.curve, self.cv, self.K, self.L = name, curve, cv, K, L
@@ -64,6 +66,10 @@ class Crafted:
         self.off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint32)
         self.elems = np.asarray(elems, dtype=np.uint32)
         assert self.elems.shape == (int(self.off[-1]),) and (len(self.elems) == 0 or int(self.elems.max()) < len(self.points))
+        # per element, for the entries that take them (msm_test_tree_sums): bit 0 negates the point, bit 1 takes the beta x line of
+        # its row -- the element then stands for -d, lambda d or -lambda d
+        self.flags = None if flags is None else np.asarray(flags, dtype=np.uint8)
+        assert self.flags is None or (self.flags.shape == self.elems.shape and int(self.flags.max(initial=0)) <= (1 if cv.te else 3))
 
     @property
     def counts(self):
@@ -83,9 +89,12 @@ class Crafted:
         K, L, q = self.K, self.L, self.cv.q
         weight = np.repeat(np.tile(np.arange(1, L + 1, dtype=np.int64), K), self.counts)      # l of every element
         window = np.repeat(np.repeat(np.arange(K, dtype=np.int64), L), self.counts)
-        per_point = np.zeros((K, len(self.points)), dtype=np.int64)                            # sum of l per (window, pool point): < 2^63
-        np.add.at(per_point, (window, self.elems.astype(np.int64)), weight)
-        return [sum(int(w) * d for w, d in zip(per_point[k].tolist(), self.logs)) % q for k in range(K)]
+        kind = np.zeros(len(self.elems), dtype=np.int64) if self.flags is None else self.flags.astype(np.int64)
+        per_point = np.zeros((K, 4, len(self.points)), dtype=np.int64)                         # sum of l per (window, flags, pool point): < 2^63
+        np.add.at(per_point, (window, kind, self.elems.astype(np.int64)), weight)
+        factor = (1, -1) if self.cv.te else (1, -1, self.cv.B.lam, -self.cv.B.lam)             # what the flags make of a log
+        return [sum(f * sum(int(w) * d for w, d in zip(per_point[k, i].tolist(), self.logs) if w) for i, f in enumerate(factor)) % q
+                for k in range(K)]
 
     def expected(self):
         """[k] -> P_k as an affine result (the identity: None, or (0, 1) on the Edwards curve)"""
@@ -244,3 +253,132 @@ PATTERNS = {f.__name__: f for f in (random, one_point, all_empty, one_window_emp
 @functools.lru_cache(maxsize=64)
 def make(pattern, curve, K, L, tc=2):
     return PATTERNS[pattern](curve, K, L, tc)
+
+
+# ---------------------------------------------------------------------------------------------- the fill patterns of the tree
+# For msm_test_tree_sums (tests/test_gpu_tree.py): what matters here is how many entries every bucket holds.  F = FINISH_MAX of
+# the window class (32 below c = 18, 64 from it), G = 2^logG the padding granule: a bucket of n entries holds ceil(n / G)
+# elements behind the regular rounds, and tail rounds run while the largest holds more than F.  flags: also give every element
+# random payload bits (negate; on the Weierstrass curves the beta x line too).
+
+def _tree(name, curve, K, L, counts, elems=None, flags=False, seed=0):
+    """a Crafted over the counts; elems = None: any pool point per entry"""
+    counts = np.asarray(counts, dtype=np.int64)
+    rng = _rng(name, curve, K, L, seed)
+    n = int(counts.sum())
+    if elems is None:
+        elems = rng.integers(0, POOL, size=n)
+    fl = rng.integers(0, 2 if CURVE_TABLE[curve].te else 4, size=n).astype(np.uint8) if flags else None
+    return Crafted(name, curve, K, L, counts, elems, flags=fl)
+
+
+def tree_threshold(curve, deep, flags=False, bucket=64 + 37):
+    """K = 2, L = 64: one bucket of `deep` entries among buckets of 0 to 3 (A: deep = F G, F G + 1, 2 F G, 2 F G + 1)"""
+    counts = _rng("tree_threshold", curve, 2, 64, deep).integers(0, 4, size=128)
+    counts[bucket] = deep
+    return _tree("tree_threshold", curve, 2, 64, counts, flags=flags, seed=deep)
+
+
+def tree_every_size(curve, top, reverse=False, flags=False):
+    """K = 1: the buckets hold 0, 1, 2, ..., top entries in this order (or in reverse), the rest of the window is empty
+    (B: top = 4 F G + G, so every tail level meets every small size, the odd ones with their missing second operand)"""
+    L = 1 << (top + 1).bit_length()
+    counts = np.zeros(L, dtype=np.int64)
+    counts[:top + 1] = np.arange(top + 1)[::-1] if reverse else np.arange(top + 1)
+    return _tree("tree_every_size", curve, 1, L, counts, flags=flags, seed=top + int(reverse))
+
+
+TREE_BLOCK = 256       # outputs per block of k_tail_desc
+TREE_EMPTY_RUN = 300   # empty buckets in a row: more than a block has lanes
+
+
+def tree_desc_blocks(curve, extra=0):
+    """C, at logG = 1 (a bucket of n entries holds ceil(n / 2) elements behind the regular round and ceil(n / 4) outputs in the
+    first tail round), K = 1, L = 2048:
+        300 empty buckets | A: 1024 entries = 256 outputs, so the next bucket starts a block | 300 empty buckets, which that block
+        boundary falls into | D: 4400 entries = 1100 outputs, three whole blocks and more inside one bucket | 100 buckets of 1 to 3 |
+        single entries until the first tail round has 256 k + `extra` outputs | empty to the end (more than 300)"""
+    L, run = 2048, TREE_EMPTY_RUN
+    rng = _rng("tree_desc_blocks", curve, 1, L, extra)
+    counts = np.zeros(L, dtype=np.int64)
+    counts[run] = 4 * TREE_BLOCK
+    d = 2 * run + 1
+    counts[d] = 4400
+    counts[d + 1:d + 101] = rng.integers(1, 4, size=100)
+    outputs = int(((counts + 3) // 4).sum())
+    fill = (extra - outputs) % TREE_BLOCK
+    counts[d + 101:d + 101 + fill] = 1
+    assert d + 101 + fill + run <= L
+    return _tree("tree_desc_blocks", curve, 1, L, counts, seed=extra)
+
+
+def tree_one_bucket(curve, deep):
+    """K = 1, L = 1: the whole group is one deep bucket"""
+    return _tree("tree_one_bucket", curve, 1, 1, [deep], seed=deep)
+
+
+def tree_last_deep(curve, deep):
+    """K = 1, L = 64: buckets of 0 to 3, the last one alone is deep"""
+    counts = _rng("tree_last_deep", curve, 1, 64, deep).integers(0, 4, size=64)
+    counts[-1] = deep
+    return _tree("tree_last_deep", curve, 1, 64, counts, seed=deep)
+
+
+TREE_SCAN_SPAN, TREE_SCAN_ITEMS = 4096, 4     # buckets per block and per lane of the scans (PS_SPAN, PS_ITEMS)
+
+
+def tree_scan_blocks(curve, K, L, deep=65):
+    """D: buckets of 0 to 3; deep buckets (deep, deep + 1, ... entries) at the first and last bucket of every block of 4096 buckets
+    and at each of the four buckets of one lane (lane 77 of block 0)"""
+    nb = K * L
+    counts = _rng("tree_scan_blocks", curve, K, L, deep).integers(0, 4, size=nb)
+    at = sorted({b for b0 in range(0, nb, TREE_SCAN_SPAN) for b in (b0, min(b0 + TREE_SCAN_SPAN, nb) - 1)}
+                | {77 * TREE_SCAN_ITEMS + j for j in range(TREE_SCAN_ITEMS)})
+    counts[at] = deep + np.arange(len(at))
+    return _tree("tree_scan_blocks", curve, K, L, counts, seed=deep)
+
+
+def tree_sparse(curve, K, L, every=4 * TREE_SCAN_SPAN, deep=70):
+    """D, the second trip of k_pscan_top: one bucket of 1 to 3 entries every `every` buckets and in the last bucket, all else empty;
+    two deep buckets, one in the first scan block and one behind the 1024 scan blocks of the first trip"""
+    nb = K * L
+    counts = np.zeros(nb, dtype=np.int64)
+    at = np.concatenate([np.arange(every // 2, nb, every), [nb - 1]])
+    counts[at] = _rng("tree_sparse", curve, K, L, deep).integers(1, 4, size=len(at))
+    counts[5] = deep
+    counts[min(nb - 2, 1024 * TREE_SCAN_SPAN + TREE_SCAN_SPAN + 3)] = deep + 1
+    return _tree("tree_sparse", curve, K, L, counts, seed=deep)
+
+
+def tree_steps(curve, L=1 << 18, filled=150_000, per=4, deep=1001):
+    """E: `filled` buckets of `per` entries and one deep bucket of an odd size: rounds of a few hundred thousand outputs"""
+    counts = np.zeros(L, dtype=np.int64)
+    counts[:filled] = per
+    counts[filled + 7] = deep
+    return _tree("tree_steps", curve, 1, L, counts, seed=deep)
+
+
+def tree_equal(curve, nb, per, odd_one=0):
+    """F: nb buckets of `per` entries each; odd_one: the size of bucket 1000 instead"""
+    counts = np.full(nb, per, dtype=np.int64)
+    if odd_one:
+        counts[1000] = odd_one
+    return _tree("tree_equal", curve, 1, nb, counts, elems=np.resize(np.arange(2 * N_RANDOM), int(counts.sum())), seed=odd_one)
+
+
+def tree_degenerate(curve, n=1024):
+    """H, K = 1, L = 8, n a power of two: bucket 1 holds n copies of one point (a doubling in every round), 2: P, -P, P, -P, ...
+    (round 1 cancels, identities from then on), 3: P, P, -P, -P, ... (round 2 cancels), 4: a point and the pool's identity row in
+    turn, 5: identity rows alone, 6: three entries, 7 and 8: empty"""
+    P = 3
+    i = np.arange(n)
+    buckets = [np.full(n, P), np.where(i % 2 == 0, P, neg_index(P)), np.where(i % 4 < 2, P, neg_index(P)),
+               np.where(i % 2 == 0, i // 2 % N_RANDOM, IDENT), np.full(n, IDENT), np.array([1, 2, IDENT]), i[:0], i[:0]]
+    return _tree("tree_degenerate", curve, 1, 8, [len(b) for b in buckets], elems=np.concatenate(buckets))
+
+
+def tree_few(curve, entries):
+    """J, K = 2, L = 8: nothing, one entry in all, or two entries in one bucket"""
+    counts = np.zeros(16, dtype=np.int64)
+    counts[11] = entries
+    return _tree("tree_few", curve, 2, 8, counts, elems=[4, 9][:entries])

@@ -109,3 +109,72 @@ def test_patterns_fill_the_buckets_they_promise(curve):
         elif kind == 2 and el:
             assert el[0] == el[len(el) // 2] == el[-1] == B.IDENT
     assert {c for c, k in seen if k == 0} == {c for c, k in seen if k == 1} == set(B.DEEP_COUNTS)
+
+
+# ---------------------------------------------------------------------------------------------- flags and the tree's patterns
+
+def direct_sums_flagged(cr):
+    """direct_sums with the payload bits applied to every element: bit 0 negates the point, bit 1 takes (beta x, y)"""
+    cv = cr.cv
+    out = []
+    for k in range(cr.K):
+        acc = cv.zero
+        for l in range(1, cr.L + 1):
+            b = k * cr.L + l - 1
+            bsum = cv.zero
+            for e in range(int(cr.off[b]), int(cr.off[b + 1])):
+                P, f = cr.points[int(cr.elems[e])], int(cr.flags[e])
+                if f & 2 and P is not None:
+                    P = (cv.B.beta * P[0] % cv.p, P[1])
+                if f & 1 and P != cv.zero:
+                    P = cv.neg(P)
+                bsum = cv.add(bsum, P)
+            acc = cv.add(acc, cv.scale(l, bsum))
+        out.append(acc)
+    return out
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_flagged_elements_stand_for_the_logs_they_claim(curve):
+    cv = CURVE_TABLE[curve]
+    if not cv.te:
+        G = (cv.B.gx, cv.B.gy)
+        assert (cv.B.beta * G[0] % cv.p, G[1]) == cv.scale_g(cv.B.lam)       # the beta x line of a row is lambda times its point
+    cr = B.tree_threshold(curve, 9, flags=True, bucket=5)
+    assert cr.flags is not None and set(cr.flags.tolist()) == ({0, 1} if cv.te else {0, 1, 2, 3})
+    small = B.Crafted("flagged", curve, K, L, cr.counts[:K * L], cr.elems[:int(cr.off[K * L])], flags=cr.flags[:int(cr.off[K * L])])
+    assert small.expected() == direct_sums_flagged(small)
+    plain = B.Crafted("plain", curve, K, L, small.counts, small.elems, flags=np.zeros(len(small.elems), dtype=np.uint8))
+    assert plain.expected() == direct_sums(plain) == B.Crafted("plain", curve, K, L, small.counts, small.elems).expected()
+
+
+def test_tree_patterns_fill_the_buckets_they_promise():
+    curve = "bls377"
+    cr = B.tree_threshold(curve, 65)
+    assert (cr.K, cr.L) == (2, 64) and cr.counts.max() == 65 and np.sort(cr.counts)[-2] <= 3 and cr.flags is None
+    cr = B.tree_every_size(curve, 258)
+    assert cr.L == 512 and cr.counts[:259].tolist() == list(range(259)) and cr.counts[259:].sum() == 0
+    assert B.tree_every_size(curve, 258, reverse=True).counts[:259].tolist() == list(range(258, -1, -1))
+    for extra in (0, 1):
+        cr = B.tree_desc_blocks(curve, extra)
+        out = (cr.counts + 3) // 4                                           # outputs of the first tail round at logG = 1
+        start = np.concatenate([[0], np.cumsum(out)])
+        run, d = B.TREE_EMPTY_RUN, 2 * B.TREE_EMPTY_RUN + 1
+        assert int(start[-1]) % B.TREE_BLOCK == extra
+        assert cr.counts[:run].sum() == 0 and cr.counts[-run:].sum() == 0 and cr.counts[run + 1:d].sum() == 0
+        assert start[run + 1] == start[d] == B.TREE_BLOCK                    # D starts a block, behind a run of empty buckets
+        assert out[d] >= 4 * B.TREE_BLOCK and start[d + 1] - start[d] == out[d]
+    cr = B.tree_scan_blocks(curve, 3, 2048)
+    deep = np.nonzero(cr.counts >= 65)[0].tolist()
+    assert deep == [0, 308, 309, 310, 311, 4095, 4096, 6143] and len(set(cr.counts[deep].tolist())) == len(deep)
+    cr = B.tree_sparse(curve, 2, 1 << 14, every=1 << 10)
+    assert np.count_nonzero(cr.counts) == 32 + 1 + 2 and cr.counts[-1] > 0 and np.sort(cr.counts)[-2:].tolist() == [70, 71]
+    cr = B.tree_degenerate(curve, 128)
+    P = 3
+    assert cr.bucket(0, 1) == [P] * 128 and cr.bucket(0, 2)[:4] == [P, B.neg_index(P)] * 2 and cr.bucket(0, 3)[:4] == [P, P, B.neg_index(P), B.neg_index(P)]
+    assert cr.bucket(0, 4)[1::2] == [B.IDENT] * 64 and B.IDENT not in cr.bucket(0, 4)[0::2] and cr.bucket(0, 5) == [B.IDENT] * 128
+    d = cr.logs[P]
+    assert cr.window_logs()[0] == (128 * d + sum(cr.logs[j] for j in cr.bucket(0, 4)) * 4 + sum(cr.logs[j] for j in cr.bucket(0, 6)) * 6) % cr.cv.q
+    assert [int(B.tree_few(curve, n).counts.sum()) for n in (0, 1, 2)] == [0, 1, 2]
+    cr = B.tree_equal(curve, 1 << 10, 64, odd_one=0)
+    assert (cr.counts == 64).all() and B.IDENT not in cr.elems
