@@ -289,7 +289,7 @@ struct msm_ctx {
   hipEvent_t piece_ev[MAX_PIECES][STAGE_THREADS] = {};
   uint64_t ws_budget = 0;          // bytes the per-group workspaces may take in total
   uint64_t ws_limit = 0;           // msm_set_workspace_limit: the caller's cap on ws_budget (0 = automatic)
-  // log2 of the table rows above which round 1 of a big window takes the pair form (sort_window_group, where the measurements
+  // log2 of the table rows above which round 1 of a big window takes the pair form (sort_geometry, where the measurements
   // behind the default are); only msm_test_set_chunk_rows_log moves it, so that tests reach the pair form at small sizes
   static constexpr int CHUNK_ROWS_LOG = 23;
   int chunk_rows_log = CHUNK_ROWS_LOG;
@@ -476,6 +476,13 @@ inline int window_groups_wanted(bool te, uint64_t n, bool tables, int nwin) {
 // measured (round 5, with one ds_add per key as the ranking: tools/sortpath_sweep.sh): the split wins from 2^21 entries per
 // window -- 2^20 points: sort 0.31 against 0.36 ms, 2^21: 0.51 / 0.85; 2^19: level, below: the one-level sort (2^16 0.11 / 0.14)
 inline uint64_t one_level_entry_limit(bool te) { return te ? 1ull << 22 : 1ull << 21; }
+// a window's counters fit the LDS of the one-level and radix sorts (c <= 16)
+inline bool window_fits_lds(const Plan& pl) { return (size_t)pl.L * 4 <= 128 * 1024; }
+// May a window of `entries` entries under this plan leave the one-level sort for one that describes its windows in a WinSplit
+// of 16 entries?  The ONE statement of the rule: group_schedule caps such a group at 16 windows, sort_geometry picks the path.
+inline bool leaves_one_level(bool te, const Plan& pl, uint64_t entries) {
+  return !window_fits_lds(pl) || (pl.L_log > (int)RX_FINE_BITS && entries >= one_level_entry_limit(te));
+}
 
 struct GroupStats {
   uint64_t n_pairs = 0;
@@ -569,24 +576,78 @@ struct SortOut {
   bool chunked = false;         // round 1 walks tile-ordered pairs and writes element records, round 2 reads them
   int path = MSM_SORT_ONE_LEVEL;   // the sort path taken (MSM_SORT_*, include/msm_hip.h): what msm_test_last_sort_paths reports
 };
-// Digits and slice histograms of SEVERAL window groups from one launch of the digit kernel (the two groups of a call decompose
-// the same scalars: one GLV decomposition instead of two).  sort_window_group(..., share) with share->produce set runs the digit
-// kernel over [k_lo, k_hi) -- all groups' windows -- into w's buffers, fills the rest of `share`, records `ready` and returns;
-// a group's own call then takes its part of the arrays (bin split only) instead of slicing the scalars again.
+// The geometry of the sort of windows [k_lo, k_hi) over n points: every size, cut and path choice sort_window_group acts on,
+// from sort_geometry (msm_plan.hip) -- plain arithmetic like group_schedule, checked on the CPU by tests/test_sort_geometry.py.
+struct SortGeometry {
+  int kc_d = 0, kc = 0;            // windows the digit kernel slices; windows behind it (on window tables ONE: the digit array
+  uint64_t two_n_d = 0, two_n = 0; //   [kc_d][two_n_d] read as one run of entries); entries per digit window / per window
+  uint64_t n_entries = 0, nb = 0;  // entries and buckets of the group
+  uint64_t mean = 1;               // mean bucket population the padding granule is sized from
+  uint32_t logG = 1;               // buckets are padded to multiples of 2^logG slots
+  // the path as intended before the read-back: neither flag = the one-level sort; pairs: the bin split ends in the pair form
+  // (k_bin_pairs) and round 1 walks tile-ordered pairs, otherwise in bucket-ordered slots (k_bin_slots)
+  bool bin_split = false, radix = false, pairs = false;
+  WinSplit ws{};                   // coarse and fine bits of every window (bin split, radix split)
+  uint32_t hb = 1;                 // bin split: coarse bins per window of THIS group's windows; V counts with it
+  uint32_t hb_stride = 1;          // ... and the stride of the bin tables and slice histograms: hb, unless the group consumes the
+                                   // digits of a producer that sliced wider windows too (sort_window_group takes the producer's)
+  uint32_t nbmax = 1;              // bin split: most buckets of one bin
+  uint32_t Hn = 1;                 // radix split: coarse bins = blocks of its last pass per window
+  uint32_t V = 0;                  // bins of the group
+  uint32_t sortB = 1;              // slices: block (b, kk) of the histogram and of the first pass owns entries
+  uint64_t pps = 0, chunk = 0;     //   [b * chunk, (b + 1) * chunk) of window kk; pps: points per slice
+  uint32_t per_block = 1;          // bin split: consecutive slices one block of pass A takes
+  uint32_t part_len = 0, part_grid = 0;   // bin split: records per part of a heavy bin; blocks of the count and last passes
+  uint64_t parts_extra = 0;        // pair form: slots the parts of heavy bins may add
+  uint64_t slots_bound = 0;        // bound of the padded slots, known before the read-back
+  // bin split: every window's digits span all L = 2^cbits buckets at the tables' stride (else `counts` is cleared first)
+  bool spans_all(int cbits) const {
+    bool all = true;
+    for (int kk = 0; kk < kc; kk++) all &= (1u << ws.ab[kk]) == hb_stride && (int)ws.ab[kk] + (int)ws.fb[kk] == cbits;
+    return all;
+  }
+  // the geometry of digits that nothing sorts (msm_test_digits of a fused batch): the digit array and no cuts
+  static SortGeometry digits_alone(int kc_d, uint64_t two_n_d) {
+    SortGeometry g;
+    g.kc_d = g.kc = kc_d;
+    g.two_n_d = g.two_n = two_n_d;
+    g.n_entries = (uint64_t)kc_d * two_n_d;
+    return g;
+  }
+};
+// Reads ctx->is_te(), n_cu and chunk_rows_log; no HIP call, no allocation, no write to the context.  Throws MsmFail for a group
+// the sorts cannot describe (more than 16 windows off the one-level sort, a window too wide for the bin split).
+SortGeometry sort_geometry(const msm_ctx* ctx, uint64_t n, const Plan& pl, int k_lo, int k_hi);
+// The two decisions that wait for the read-back (max_bucket, total_slots).
+// Radix split: its last pass gives one block to a coarse bin, and a bucket that holds far more than a bin's share of the entries
+// (one scalar repeated: a whole window in one bucket) would make one block walk them all.  The histogram is the one-level
+// sort's, so such an input takes the one-level scatter instead, which splits the ENTRIES across the blocks (its partial-line
+// writes do not matter when most payloads go to a few long runs): one scalar repeated at 2^20 points, sort phase 1.39 -> 0.4x ms.
+inline bool radix_bucket_too_heavy(const SortGeometry& g, uint32_t max_bucket) {
+  return max_bucket >= (1u << 16) && (uint64_t)max_bucket * g.Hn >= 16 * g.two_n;
+}
+// Pair form: no entry at all -- the plain slot form handles the empty tree.
+inline bool pair_form_tree_empty(uint64_t total_slots) { return total_slots < 2; }
+
+// Digits and slice histograms that are already there: written by launch_group_digits, for the group itself or -- the two groups
+// of a call decompose the same scalars: one GLV decomposition instead of two -- for SEVERAL window groups at once, each of which
+// then takes its part of the arrays (bin split only) instead of slicing the scalars again.
 struct GroupDigits {
-  bool produce = false;
-  bool any_path = false;          // produce on every sort path and for a fused batch, not the bin split alone: the digits are all the
-                                  // caller wants (msm_test_digits; no consumer takes them -- `hist` is null off the bin split)
   int k_lo = 0;                   // first window of the arrays
   const uint32_t* dig = nullptr;  // [windows][entries per window]
-  uint32_t* hist = nullptr;       // [windows][sortB][hb]
+  uint32_t* hist = nullptr;       // [windows][sortB][hb]; null off the bin split
   uint32_t hb = 0, sortB = 0;
   uint64_t pps = 0, chunk = 0;
-  hipEvent_t ready = nullptr;     // behind the digit kernel, on the producing workspace's stream
-  bool valid = false;             // the producer found the bin split applicable and has run
+  hipEvent_t ready = nullptr;     // behind the digit kernel, on the producing workspace's stream (null: not recorded)
+  bool valid = false;
 };
+// The digit launch of windows [k_lo, k_lo + g.kc_d) on w.stream, into w.dig and (bin split) w.block_hist, which it sizes: the
+// wide kernels, those of a narrow call, or the _batch forms of a fused batch, as the plan says.  Records `ready` behind it if given.
+GroupDigits launch_group_digits(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars, uint64_t n, const Plan& pl, int k_lo,
+                                const SortGeometry& g, hipEvent_t ready = nullptr);
+// share: digits of this group's windows that a launch over several groups has left (valid); the group takes its part
 void sort_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars, uint64_t n, const Plan& pl, int k_lo, int k_hi,
-                       GroupStats& st, SortOut& so, GroupDigits* share = nullptr);
+                       GroupStats& st, SortOut& so, const GroupDigits* share = nullptr);
 // The scans behind the sort, which sort_window_group and the operator test msm_test_tree_sums both run: the nb bucket sizes in
 // w.counts -> w.cursor (padded slot offsets, nb + 1 words), w.tail_off (RT + 1 tables of nb + 1 words) and the totals in w.info.
 // find_max: clears w.info and looks for the largest bucket first (k_bucket_max); otherwise info[1] holds it already, or a bound

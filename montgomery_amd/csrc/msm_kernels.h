@@ -279,35 +279,63 @@ inline uint64_t pack_fine_bits(const WinSplit& ws) {
   for (int kk = 0; kk < 16; kk++) v |= (uint64_t)(ws.fb[kk] & 15u) << (4 * kk);
   return v;
 }
+// The frame of the slice histogram around a digit kernel's loop: the block's `cells` = k_cnt * hb LDS counters zeroed (nullptr:
+// the launch wants no histogram), and after the loop written to their row of slice_hist.
+__device__ __forceinline__ uint32_t* slice_hist_begin(const uint32_t* slice_hist, uint32_t cells) {
+  extern __shared__ uint32_t lds_dig_hist[];
+  if (!slice_hist) return nullptr;
+  for (uint32_t j = threadIdx.x; j < cells; j += blockDim.x) lds_dig_hist[j] = 0;
+  __syncthreads();
+  return lds_dig_hist;
+}
+__device__ __forceinline__ void slice_hist_end(uint32_t* slice_hist, const uint32_t* lds_hist, uint32_t cells, uint32_t hb) {
+  if (!lds_hist) return;
+  __syncthreads();
+  for (uint32_t j = threadIdx.x; j < cells; j += blockDim.x) {
+    const uint32_t kk = j / hb, h = j - kk * hb;
+    slice_hist[((uint64_t)kk * gridDim.x + blockIdx.x) * hb + h] = lds_hist[j];
+  }
+}
+// s = the 32-byte scalar at src.  Inputs are specified < q (src/curve-random.ts:151-194); larger values are reduced mod q -- the
+// group element is the same, MAX_SUB subtractions suffice (2^256 < 16 q on the Weierstrass curves, < 56 q on the Edwards one)
+// -- unless the caller asked for strict checking (msm_opts.strict), in which case the call fails with MSM_ERR_SCALAR.
+// k_te_digits and k_te_digits_batch call it; k_digits and k_digits_batch spell the same five lines out, because behind the call
+// their BN254 instances were allocated two more VGPRs than the kernels they replace.
+template <int MAX_SUB>
+__device__ __forceinline__ void load_scalar_mod_q(uint32_t (&s)[8], const uint32_t* src, const uint32_t (&q)[8], int strict, uint32_t* err) {
+  load_words12<8>(s, src);
+  if (words8_ge(s, q)) {
+    if (strict) atomicOr(err, 4u);
+    for (int it = 0; it < MAX_SUB && words8_ge(s, q); it++) bn_addsub<8, 8>(s, q, true);
+  }
+}
+// One step of the signed-window recoding, L = 2^(c-1): `raw` = the window's c bits plus `carry` from the window below; a digit
+// above L becomes 2 L - l with a carry into the next window.  A folded top window (Plan::fold: raw = c + 1 bits) is not
+// recoded -- at most 2^c, it cannot carry out; its value stays within its 2^c buckets only while the scalar (the GLV half) stays
+// below its bound, so a larger one sets `over` (the caller flags err bit 8: MSM_ERR_INTERNAL) and is clamped to the last bucket.
+MSM_DEV uint32_t window_step(uint32_t raw, uint32_t& carry, uint32_t L, bool folded_top, bool& over) {
+  uint32_t l = raw + carry;
+  if (!folded_top && l > L) { l = 2 * L - l; carry = 1; } else { carry = 0; }
+  if (folded_top) { over |= l > 2 * L; l = l > 2 * L ? 2 * L : l; }
+  return l;
+}
 
 template <class CV>
 __global__ void __launch_bounds__(1024) k_digits(uint32_t* dig, const uint32_t* scalars, uint32_t n, int c, int k_total,
                                                 int k_lo, int k_cnt, int glv_flags, int strict, uint32_t* err, uint32_t pps,
                                                 uint32_t* slice_hist, uint32_t hb, uint64_t fbp, uint32_t b_lo, uint32_t b_n, uint32_t bt_lo,
                                                 uint32_t bt_n) {
-  extern __shared__ uint32_t lds_dig_hist[];
-  uint32_t* lds_hist = slice_hist ? lds_dig_hist : nullptr;
-  if (lds_hist) {
-    for (uint32_t j = threadIdx.x; j < (uint32_t)k_cnt * hb; j += blockDim.x) lds_hist[j] = 0;
-    __syncthreads();
-  }
+  uint32_t* lds_hist = slice_hist_begin(slice_hist, (uint32_t)k_cnt * hb);
   const int glv = glv_flags & 1;
   const bool fold = glv_flags & 2;
   const uint64_t p_end = min((uint64_t)(blockIdx.x + 1) * pps, (uint64_t)n);
   for (uint64_t i64 = (uint64_t)blockIdx.x * pps + threadIdx.x; i64 < p_end; i64 += blockDim.x) {
   const uint32_t i = (uint32_t)i64;
-  uint32_t s[8];
-  {
-    const uint4* p4 = reinterpret_cast<const uint4*>(scalars + (uint64_t)i * 8);
-    uint4 a = p4[0], b = p4[1];
-    s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w; s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
-  }
-  uint32_t q[8];
+  uint32_t s[8], q[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) q[j] = CV::G::Q[j];
-  // inputs are specified < q (src/curve-random.ts:151-194).  Larger values are reduced mod q -- the group element is the
-  // same -- unless the caller asked for strict checking (msm_opts.strict), in which case the call fails with MSM_ERR_SCALAR
-  if (words8_ge(s, q)) {
+  load_words12<8>(s, scalars + (uint64_t)i * 8);
+  if (words8_ge(s, q)) {   // (load_scalar_mod_q<16>, spelt out: see there)
     if (strict) atomicOr(err, 4u);
     for (int it = 0; it < 16 && words8_ge(s, q); it++) bn_addsub<8, 8>(s, q, true);
   }
@@ -320,9 +348,9 @@ __global__ void __launch_bounds__(1024) k_digits(uint32_t* dig, const uint32_t* 
     uint32_t carry = 0;
     for (int k = 0; k < k_total; k++) {
       const bool top = fold && k == k_total - 1;
-      uint32_t l = bn_take_bits<8>(s, top ? c + 1 : c) + carry;
-      if (!top && l > L) { l = 2 * L - l; carry = 1; } else { carry = 0; }
-      if (top && l > 2 * L) { atomicOr(err, 8u); l = 2 * L; }   // (see below: a folded top window must stay within its buckets)
+      bool over = false;
+      uint32_t l = window_step(bn_take_bits<8>(s, top ? c + 1 : c), carry, L, top, over);
+      if (over) atomicOr(err, 8u);
       uint32_t sgn = carry;
       if (l - 1 - (k == k_total - 1 ? bt_lo : b_lo) >= (k == k_total - 1 ? bt_n : b_n)) { l = 0; sgn = 0; }
       int kk = k - k_lo;
@@ -340,14 +368,10 @@ __global__ void __launch_bounds__(1024) k_digits(uint32_t* dig, const uint32_t* 
   uint32_t carry0 = 0, carry1 = 0;
   for (int k = 0; k < k_total; k++) {
     const bool top = fold && k == k_total - 1;
-    uint32_t l0 = bn_take_bits<4>(h[0].mag, top ? c + 1 : c) + carry0;
-    uint32_t l1 = bn_take_bits<4>(h[1].mag, top ? c + 1 : c) + carry1;
-    if (!top && l0 > L) { l0 = 2 * L - l0; carry0 = 1; } else { carry0 = 0; }
-    if (!top && l1 > L) { l1 = 2 * L - l1; carry1 = 1; } else { carry1 = 0; }
-    // the folded top window is not recoded: its value stays within its 2^c buckets only while the GLV halves stay below
-    // 2^glv_max_bits -- a half that ever exceeded the bound would index past the window's buckets, so it is flagged (the call
-    // fails with MSM_ERR_INTERNAL) and clamped instead
-    if (top && (l0 > 2 * L || l1 > 2 * L)) { atomicOr(err, 8u); l0 = min(l0, 2 * L); l1 = min(l1, 2 * L); }
+    bool over = false;
+    const uint32_t l0 = window_step(bn_take_bits<4>(h[0].mag, top ? c + 1 : c), carry0, L, top, over);
+    const uint32_t l1 = window_step(bn_take_bits<4>(h[1].mag, top ? c + 1 : c), carry1, L, top, over);
+    if (over) atomicOr(err, 8u);
     const int kk = k - k_lo;
     if (kk >= 0 && kk < k_cnt) {
       uint32_t neg0 = carry0 ^ (h[0].neg ? 1u : 0u), neg1 = carry1 ^ (h[1].neg ? 1u : 0u);
@@ -361,13 +385,7 @@ __global__ void __launch_bounds__(1024) k_digits(uint32_t* dig, const uint32_t* 
     }
   }
   }
-  if (lds_hist) {
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < (uint32_t)k_cnt * hb; j += blockDim.x) {
-      const uint32_t kk = j / hb, h = j - kk * hb;
-      slice_hist[((uint64_t)kk * gridDim.x + blockIdx.x) * hb + h] = lds_hist[j];
-    }
-  }
+  slice_hist_end(slice_hist, lds_hist, (uint32_t)k_cnt * hb, hb);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -400,12 +418,8 @@ __global__ void __launch_bounds__(256) k_digits_batch(uint32_t* dig, BatchScalar
 #pragma unroll 1
   for (uint32_t b = 0; b < b_cnt; b++) {
     uint32_t s[8];
-    {
-      const uint4* p4 = reinterpret_cast<const uint4*>(sc.p[b] + (uint64_t)i * 8);
-      uint4 x = p4[0], y = p4[1];
-      s[0] = x.x; s[1] = x.y; s[2] = x.z; s[3] = x.w; s[4] = y.x; s[5] = y.y; s[6] = y.z; s[7] = y.w;
-    }
-    if (words8_ge(s, q)) {   // as k_digits: reduced mod q, or refused under msm_opts.strict
+    load_words12<8>(s, sc.p[b] + (uint64_t)i * 8);
+    if (words8_ge(s, q)) {   // (load_scalar_mod_q<16>, spelt out: see there)
       if (strict) atomicOr(err, 4u);
       for (int it = 0; it < 16 && words8_ge(s, q); it++) bn_addsub<8, 8>(s, q, true);
     }
@@ -414,9 +428,9 @@ __global__ void __launch_bounds__(256) k_digits_batch(uint32_t* dig, BatchScalar
       uint32_t carry = 0;
       for (int k = 0; k < k_total; k++) {
         const bool top = fold && k == k_total - 1;
-        uint32_t l = bn_take_bits<8>(s, top ? c + 1 : c) + carry;
-        if (!top && l > L) { l = 2 * L - l; carry = 1; } else { carry = 0; }
-        if (top && l > 2 * L) { atomicOr(err, 8u); l = 2 * L; }
+        bool over = false;
+        const uint32_t l = window_step(bn_take_bits<8>(s, top ? c + 1 : c), carry, L, top, over);
+        if (over) atomicOr(err, 8u);
         *reinterpret_cast<uint2*>(db + (uint64_t)k * two_n) = make_uint2(l | ((l ? carry : 0u) << 31), 0u);
       }
       continue;
@@ -426,11 +440,10 @@ __global__ void __launch_bounds__(256) k_digits_batch(uint32_t* dig, BatchScalar
     uint32_t carry0 = 0, carry1 = 0;
     for (int k = 0; k < k_total; k++) {
       const bool top = fold && k == k_total - 1;
-      uint32_t l0 = bn_take_bits<4>(h[0].mag, top ? c + 1 : c) + carry0;
-      uint32_t l1 = bn_take_bits<4>(h[1].mag, top ? c + 1 : c) + carry1;
-      if (!top && l0 > L) { l0 = 2 * L - l0; carry0 = 1; } else { carry0 = 0; }
-      if (!top && l1 > L) { l1 = 2 * L - l1; carry1 = 1; } else { carry1 = 0; }
-      if (top && (l0 > 2 * L || l1 > 2 * L)) { atomicOr(err, 8u); l0 = min(l0, 2 * L); l1 = min(l1, 2 * L); }
+      bool over = false;
+      const uint32_t l0 = window_step(bn_take_bits<4>(h[0].mag, top ? c + 1 : c), carry0, L, top, over);
+      const uint32_t l1 = window_step(bn_take_bits<4>(h[1].mag, top ? c + 1 : c), carry1, L, top, over);
+      if (over) atomicOr(err, 8u);
       const uint32_t neg0 = l0 ? carry0 ^ (h[0].neg ? 1u : 0u) : 0u, neg1 = l1 ? carry1 ^ (h[1].neg ? 1u : 0u) : 0u;
       *reinterpret_cast<uint2*>(db + (uint64_t)k * two_n) = make_uint2(l0 | (neg0 << 31), l1 | (neg1 << 31));
     }

@@ -13,7 +13,7 @@ namespace {
 // scalars: device pointer, n x 8 words.
 // On window tables every group reads table j = 2^(c j) P for its window k_lo + j: its sum is relative to its OWN first window.
 void run_window_group(msm_ctx* ctx, msm_ctx::Workspace& w, const uint32_t* d_scalars_all, uint64_t p_lo, uint64_t n, const Plan& pl_in,
-                      int k_lo, int k_hi, uint32_t* h_partials_out, GroupStats& st, int32_t& path, uint64_t p_off = 0, GroupDigits* share = nullptr) {
+                      int k_lo, int k_hi, uint32_t* h_partials_out, GroupStats& st, int32_t& path, uint64_t p_off = 0, const GroupDigits* share = nullptr) {
   hipStream_t s = w.stream;
   Plan pl = pl_in;
   const uint32_t* d_scalars = group_scalars(d_scalars_all, p_lo, pl);   // scalar i of the call <-> resident point p_off + i
@@ -110,15 +110,12 @@ float run_groups(msm_ctx* ctx, const CallSetup& cs, const void* scalars, uint64_
   }
   GroupDigits share;
   if (cs.sch.share_digits) {
-    share.produce = true;
-    share.ready = ctx->ev_dig[1];
-    SortOut none;
-    GroupStats gs;
+    // one digit launch over both groups' windows, on the first workspace (only the bin split takes its histograms from there)
     HIPCHK(hipEventRecord(ctx->ev_dig[0], ctx->ws[0].stream));
     Plan pd = pl;
     const uint32_t* d_grp = group_scalars(cs.d_scal, groups[0].p_lo, pd);
-    sort_window_group(ctx, ctx->ws[0], d_grp, groups[0].p_n, pd, groups[0].ka, groups[1].kb, gs, none, &share);
-    share.produce = false;
+    const SortGeometry g = sort_geometry(ctx, groups[0].p_n, pd, groups[0].ka, groups[1].kb);
+    if (g.bin_split) share = launch_group_digits(ctx, ctx->ws[0], d_grp, groups[0].p_n, pd, groups[0].ka, g, ctx->ev_dig[1]);
   }
   Plan pg = pl;
   pg.lone = cs.sch.lone;

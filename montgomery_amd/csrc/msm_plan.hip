@@ -273,14 +273,9 @@ GroupSchedule group_schedule(const msm_ctx* ctx, uint64_t n, uint64_t p_off, int
   // may take one of them holds at most 16 windows (msmProjective with a small explicit window: K = 17 .. 29 at c = 15 .. 9)
   // (the one-level sort of small inputs -- a window's counters fit the LDS and fewer than 2^22 entries per window -- has no
   // such table: Ed-on-BLS12-377 at 2^20 keeps its 18 windows in one group)
-  {
-    const uint64_t entries = te ? n : 2 * n;
-    const bool fits_lds = ((size_t)pl.L * 4 <= 128 * 1024);
-    if (pl.c - 1 > (int)RX_FINE_BITS && (!fits_lds || entries >= one_level_entry_limit(te))) wpg = std::min(wpg, 16);
-    // (on window tables the merged window of a group may take the bin split whatever a single digit window would have taken,
-    // and the digit kernel describes the fine bits of at most 16 windows: pack_fine_bits)
-    if (pl.tables) wpg = std::min(wpg, 16);
-  }
+  // (on window tables the merged window of a group may take the bin split whatever a single digit window would have taken,
+  // and the digit kernel describes the fine bits of at most 16 windows: pack_fine_bits)
+  if (leaves_one_level(te, pl, te ? n : 2 * n) || pl.tables) wpg = std::min(wpg, 16);
   const int nwin = k_hi - k_lo;
   int want_groups = window_groups_wanted(te, n, pl.tables, nwin);
   MSM_KNOB(want_groups, "MSM_GROUPS", 1);
@@ -337,6 +332,107 @@ GroupSchedule group_schedule(const msm_ctx* ctx, uint64_t n, uint64_t p_off, int
   // the exclusive timing of the roofline) -- walks its pairs in four short batches instead of one long one (round_geom)
   sc.lone = (groups.size() == 1 && (groups[0].kb - groups[0].ka == 1 || sc.tables)) || serial;
   return sc;
+}
+
+SortGeometry sort_geometry(const msm_ctx* ctx, uint64_t n, const Plan& pl, int k_lo, int k_hi) {
+  SortGeometry g;
+  const bool te = ctx->is_te();
+  const uint32_t L = pl.L;
+  const int cbits = pl.L_log;   // bits of a bucket index
+  g.kc_d = k_hi - k_lo;
+  g.two_n_d = te ? n : 2 * n;   // entries per digit window: both GLV halves, or the plain scalar
+  g.n_entries = (uint64_t)g.kc_d * g.two_n_d;
+  // On window tables the kc_d digit windows of the group are ONE window for everything behind the digit kernel: the digit
+  // array [kc_d][two_n_d] read as one run of entries, entry j = (window, point, half) naming row j of the tables.
+  g.kc = pl.tables ? 1 : g.kc_d;
+  g.two_n = pl.tables ? g.n_entries : g.two_n_d;
+  g.nb = (uint64_t)g.kc * L;
+
+  // padding granule G = 2^g: about 1/8 of the mean bucket population (pads cost G/2 slots per bucket; what is
+  // left after g regular rounds, ~8 elements per bucket, is finished without inversions by k_bucket_finish)
+  // Bigger buckets leave more: pads are identity pairs that occupy a lane for nothing (mean / (2 * left) of all slots), and
+  // k_bucket_finish is cheap next to them.  Measured (profiles/r04_experiments.txt items 6 and 14, best `left` per mean bucket):
+  // 64 entries 8 with 16-bit windows (2^20: 3.89 against 3.93 ms) but 16 with the big ones (2^25: 81.5 -> 79.9);
+  // 128 .. 256: 16 (2^21 6.92 -> 6.88, 2^22 12.45 -> 12.17, Ed-377 2^20 2.64 -> 2.59, 2^26 145.7 -> 142.5, 2^27 304.9 -> 301.8);
+  // from 512: 32 (2^23 22.65 -> 22.18, 2^26 at c = 16 152.7 -> 152.1); 32 entries: 8 (2^24: 16 costs 8 %).
+  g.mean = std::max<uint64_t>(1, g.two_n / (pl.fold ? L / 2 : L));   // (a folded plan's lower windows fill half their buckets)
+  // (on window tables at 2^20 points, mean 112 at c = 18: 8 -- a third regular round -- 3.37 against 3.41 ms)
+  uint64_t per_bucket_left = g.mean >= 512 ? 32 : (g.mean >= 128 || (g.mean >= 64 && pl.c >= 18 && !pl.tables)) ? 16 : 8;
+  MSM_KNOB(per_bucket_left, "MSM_PBL", 1);
+  while (g.logG < 10 && (1ull << (g.logG + 1)) * per_bucket_left <= g.mean) g.logG++;
+
+  // Sort path: LDS-privatised histogram / ranking, every pass staged through the LDS so that a wave store is a full segment
+  // (sort_kernels.h; a direct scatter sends each 4-byte payload to a line of its own: round 1 wrote 7.7x the algorithmic bytes).
+  //   one level  : a window's counters fit the LDS (c <= 16) and the input is small
+  //   radix split: c <= 16, big inputs -- 2^(c-8) coarse bins x 128 buckets, two passes over pairs of 4-byte arrays
+  //   bin split  : c > 16 (up to c = 24, the largest window make_plan accepts) -- coarse bins x up to 2^12 buckets, two passes
+  //                over 8-byte records, the histogram of the first fused into the digit kernel, the second emitting the pairs
+  //                of round 1 in an order that keeps its row gathers local
+  // (the merged window of a run on window tables has kc = 1: the radix split would give its last pass one block per coarse bin,
+  // 2^(c-8) of them for the whole chip -- the bin split cuts it into 2^10 bins whatever the window is)
+  g.bin_split = !window_fits_lds(pl) || (pl.tables && g.two_n >= (1ull << 22));
+  g.radix = !g.bin_split && leaves_one_level(te, pl, g.two_n);   // (counters that fit the LDS: at most 2^8 coarse bins)
+  if ((g.bin_split || g.radix) && g.kc > 16)
+    throw MsmFail{MSM_ERR_INTERNAL, g.bin_split ? "more than 16 windows in a group of a window size above 16" : "more than 16 windows in a radix-split group"};
+  for (int kk = 0; kk < g.kc && g.bin_split; kk++) {
+    // bits the digits of this window really have: the top window of a scalar is usually short (msm_kernels.h, WinSplit)
+    // (a window below the top one holds signed digits of magnitude <= 2^(c - 1); the top one what is left of the scalar)
+    const bool top = (k_lo + kk) % pl.K == pl.K - 1;   // (window k of its element in a batch: msm_run_batch)
+    const int eff = pl.tables ? cbits : std::max(1, top ? std::min(cbits, pl.bits - (k_lo + kk) * pl.c) : std::min(cbits, pl.c - 1));
+    // up to 10 bits: pass A sorts the window outright; else 2^10 coarse bins (16-entry runs of a 16 k tile), 2^11 if the
+    // fine part would otherwise exceed 2^12 buckets per bin
+    const int ab_big = 10;
+    const int abk = eff <= ab_big ? eff : std::max(ab_big, eff - (int)BS_MAX_FB);
+    if (abk > (int)BS_MAX_AB) throw MsmFail{MSM_ERR_INTERNAL, "window too wide for the bin split"};
+    g.ws.ab[kk] = (uint8_t)abk;
+    g.ws.fb[kk] = (uint8_t)(eff - abk);
+    g.hb = std::max(g.hb, 1u << abk);
+    g.nbmax = std::max(g.nbmax, 1u << (eff - abk));
+  }
+  for (int kk = 0; kk < g.kc && g.radix; kk++) { g.ws.ab[kk] = (uint8_t)(cbits - (int)RX_FINE_BITS); g.ws.fb[kk] = (uint8_t)RX_FINE_BITS; }
+  g.hb_stride = g.hb;
+  if (g.radix) g.Hn = 1u << (cbits - (int)RX_FINE_BITS);
+  g.V = (uint32_t)g.kc * (g.bin_split ? g.hb : g.Hn);
+  g.chunk = g.two_n;
+  g.pps = n;
+  if (g.bin_split) {
+    // the digit kernel histograms ALL windows of the group over its slice of the points: four slices per CU, one slice per
+    // 4 096 points at least; the digit kernel wants a few blocks per CU whatever kc_d is, k_slice_scan walks the kc_d * sortB
+    // rows of the merged window with 32 lanes per column
+    g.sortB = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)4 * ctx->n_cu, n / 4096));
+    // (pass A names an entry by its offset inside the slice in BS_SPAN_LOG bits: from 2^27 points the slices multiply instead of growing)
+    const uint64_t max_pps = (1ull << BS_SPAN_LOG) / (te ? 1 : 2);
+    g.sortB = (uint32_t)std::max<uint64_t>(g.sortB, (n + max_pps - 1) / max_pps);
+    g.pps = (n + g.sortB - 1) / g.sortB;
+    g.chunk = (te ? 1 : 2) * g.pps;
+    // a block of pass A takes as many consecutive slices of the digit kernel as make two tiles
+    g.per_block = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(g.sortB, std::max<uint64_t>(1, (1ull << BS_SPAN_LOG) / g.chunk)),
+                                               std::max<uint64_t>(1, (2 * (uint64_t)BS_TILE + g.chunk - 1) / g.chunk));
+    // heavy bins are cut into parts of part_len records, one block each (sort_kernels.h, "Parts of heavy bins"): twice the mean
+    // bin, so that uniform digits never see one; a multiple of the tile of pass B.  The table comes out of k_vscan.
+    g.part_len = (uint32_t)std::max<uint64_t>(1u << 16, ((2 * g.n_entries / g.V + BP_TILE - 1) / BP_TILE) * BP_TILE);
+    g.part_grid = g.V + g.V / 2 + 1;
+    // Big windows over a big table take the pair form: from more than 2^23 rows of 256 bytes = 2 GB (measured,
+    // tools/chunk_plain.py on the round-5 tuning build: at 2^23 rows -- 2^23 points, or 2^20 on seven window tables -- the plain
+    // slot form is 2.5 % ahead: 20.15 against 20.64 ms, 3.23 / 3.32; at 2^23.8 rows level; at 2^24 rows the tile order wins by
+    // 10 %: 38.6 against 43.0).  chunk_rows_log: 23 unless a test has moved it.
+    // (round 2 must be an index-free round to read the element records round 1 then writes: logG >= 2)
+    const uint64_t table_rows = pl.tables ? (uint64_t)g.kc_d * n : n;
+    g.pairs = !te && pl.c >= 18 && table_rows > (1ull << ctx->chunk_rows_log) && g.logG >= 2;
+  } else {
+    // big inputs: finer slices also keep the round-1 gathers of neighbouring lanes inside one Infinity-Cache-sized
+    // range of point rows (measured: 193 -> 183 ms at 2^26); small inputs: fewer, larger blocks (less fixed cost)
+    const uint64_t mult = g.two_n >= (1ull << 27) ? 8 : g.two_n >= (1ull << 24) ? 4 : 2;   // measured 2^21 .. 2^26
+    const uint64_t want = std::max<uint64_t>(1, (mult * ctx->n_cu + g.kc - 1) / g.kc);
+    g.sortB = (uint32_t)std::min<uint64_t>(want, std::max<uint64_t>(1, g.two_n / 8192));
+    g.chunk = (g.two_n + g.sortB - 1) / g.sortB;
+  }
+  // The padded slots have a bound -- every non-empty bucket pads by less than G -- which lets the bin split's last pass start
+  // before the totals are read back.  (the parts of a heavy bin pair their entries up on their own: a bucket gains at most one
+  // slot per part that holds an odd number of its entries -- sort_kernels.h, "Parts of heavy bins")
+  g.parts_extra = g.pairs ? std::min<uint64_t>(g.n_entries, (uint64_t)g.V * g.nbmax) : 0;
+  g.slots_bound = g.n_entries + g.parts_extra + (((uint64_t)1 << g.logG) - 1) * std::min<uint64_t>(g.nb, g.n_entries);
+  return g;
 }
 
 }  // namespace msmi

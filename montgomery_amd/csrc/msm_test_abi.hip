@@ -742,16 +742,12 @@ int msm_test_digits(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64
     }
     HIPCHK(hipMemsetAsync(ctx->errflag.p, 0, 4, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));   // scalars and the error flag are in place before the group stream starts
-    // the digit launch of sort_window_group, and nothing behind it
-    GroupDigits dg;
-    dg.produce = dg.any_path = true;
-    dg.ready = ctx->ev_dig[1];
-    GroupStats st;
-    SortOut none;
-    sort_window_group(ctx, w, d_scal, n, pl, k_lo, k_hi, st, none, &dg);
-    if (!dg.valid) throw MsmFail{MSM_ERR_INTERNAL, "msm_test_digits: the digit kernel was not launched"};
+    // the digit launch of sort_window_group under the group's sort geometry, and nothing behind it
+    // (the digits of a fused batch need no cuts: the _batch kernels count nothing, whatever the windows)
+    const uint64_t two_n_d = ctx->is_te() ? n : 2 * n, words = (uint64_t)kc * two_n_d;
+    const SortGeometry g = B > 1 ? SortGeometry::digits_alone(kc, two_n_d) : sort_geometry(ctx, n, pl, k_lo, k_hi);
+    const GroupDigits dg = launch_group_digits(ctx, w, d_scal, n, pl, k_lo, g);
     HIPCHK(hipGetLastError());
-    const uint64_t words = (uint64_t)kc * (ctx->is_te() ? n : 2 * n);
     HIPCHK(hipMemcpyAsync(digits_out, dg.dig, words * 4, hipMemcpyDeviceToHost, w.stream));
     HIPCHK(hipStreamSynchronize(w.stream));
     try {

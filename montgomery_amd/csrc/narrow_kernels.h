@@ -141,9 +141,9 @@ MSM_DEV void narrow_emit(uint32_t* dig, uint64_t stride, uint64_t i, uint32_t (&
   uint32_t carry = 0;
   for (int k = 0; k < k_total; k++) {
     const bool top = fold && k == k_total - 1;
-    uint32_t l = bn_take_bits<5>(m, top ? c + 1 : c) + carry;
-    if (!top && l > L) { l = 2 * L - l; carry = 1; } else { carry = 0; }
-    if (top && l > 2 * L) { atomicOr(err, 8u); l = 2 * L; }
+    bool over = false;
+    const uint32_t l = window_step(bn_take_bits<5>(m, top ? c + 1 : c), carry, L, top, over);
+    if (over) atomicOr(err, 8u);
     const uint32_t sgn = l ? carry ^ neg : 0u;
     const int kk = k - k_lo;
     if (kk >= 0 && kk < k_cnt) {
@@ -160,13 +160,8 @@ MSM_DEV void narrow_emit(uint32_t* dig, uint64_t stride, uint64_t i, uint32_t (&
 template <int W, bool TE>
 MSM_DEV void digits_narrow(uint32_t* dig, const void* scalars, uint64_t first, uint32_t n, int c, int k_total, int k_lo, int k_cnt,
                            int fold, const NarrowFmt& f, uint32_t* err, uint32_t pps, uint32_t* slice_hist, uint32_t hb, uint64_t fbp) {
-  extern __shared__ uint32_t lds_dig_hist[];
   constexpr int PER = NarrowLane<W>::PER;
-  uint32_t* lds_hist = slice_hist ? lds_dig_hist : nullptr;
-  if (lds_hist) {
-    for (uint32_t j = threadIdx.x; j < (uint32_t)k_cnt * hb; j += blockDim.x) lds_hist[j] = 0;
-    __syncthreads();
-  }
+  uint32_t* lds_hist = slice_hist_begin(slice_hist, (uint32_t)k_cnt * hb);
   const uint64_t r_lo = (uint64_t)blockIdx.x * pps, r_hi = min(r_lo + pps, (uint64_t)n);
   const uint64_t a_lo = first + r_lo, a_hi = first + r_hi;
   const uint64_t stride = TE ? (uint64_t)n : 2ull * n;
@@ -184,13 +179,7 @@ MSM_DEV void digits_narrow(uint32_t* dig, const void* scalars, uint64_t first, u
       }
     }
   }
-  if (lds_hist) {
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < (uint32_t)k_cnt * hb; j += blockDim.x) {
-      const uint32_t kk = j / hb, h = j - kk * hb;
-      slice_hist[((uint64_t)kk * gridDim.x + blockIdx.x) * hb + h] = lds_hist[j];
-    }
-  }
+  slice_hist_end(slice_hist, lds_hist, (uint32_t)k_cnt * hb, hb);
 }
 
 // one lane per group of PER points, its scalars of the b_cnt elements one after the other; no slice histogram (a fused batch

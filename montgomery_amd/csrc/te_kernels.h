@@ -274,33 +274,19 @@ __global__ void __launch_bounds__(1024) k_te_digits(uint32_t* dig, const uint32_
 #else
 {
   // slices and the fused histogram of the coarse bins: as k_digits (msm_kernels.h)
-  extern __shared__ uint32_t lds_dig_hist[];
-  uint32_t* lds_hist = slice_hist ? lds_dig_hist : nullptr;
-  if (lds_hist) {
-    for (uint32_t j = threadIdx.x; j < (uint32_t)k_cnt * hb; j += blockDim.x) lds_hist[j] = 0;
-    __syncthreads();
-  }
+  uint32_t* lds_hist = slice_hist_begin(slice_hist, (uint32_t)k_cnt * hb);
   const uint64_t p_end = min((uint64_t)(blockIdx.x + 1) * pps, (uint64_t)n);
   for (uint64_t i64 = (uint64_t)blockIdx.x * pps + threadIdx.x; i64 < p_end; i64 += blockDim.x) {
     const uint32_t i = (uint32_t)i64;
-    uint32_t s[8];
-    {
-      const uint4* p4 = reinterpret_cast<const uint4*>(scalars + (uint64_t)i * 8);
-      uint4 a = p4[0], b = p4[1];
-      s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w; s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
-    }
-    uint32_t q[8];
+    uint32_t s[8], q[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) q[j] = FRED_Q[j];
-    if (words8_ge(s, q)) {   // scalars >= q are reduced (2^256 < 56 q), or refused under msm_opts.strict
-      if (strict) atomicOr(err, 4u);
-      for (int it = 0; it < 64 && words8_ge(s, q); it++) bn_addsub<8, 8>(s, q, true);
-    }
+    load_scalar_mod_q<64>(s, scalars + (uint64_t)i * 8, q, strict, err);
     const uint32_t L = 1u << (c - 1);
     uint32_t carry = 0;
     for (int k = 0; k < k_total; k++) {
-      uint32_t l = bn_take_bits<8>(s, c) + carry;
-      if (l > L) { l = 2 * L - l; carry = 1; } else { carry = 0; }
+      bool over = false;   // (no folded window on this curve)
+      const uint32_t l = window_step(bn_take_bits<8>(s, c), carry, L, false, over);
       int kk = k - k_lo;
       if (kk >= 0 && kk < k_cnt) {
         uint32_t e = l, sgn = carry;
@@ -310,13 +296,7 @@ __global__ void __launch_bounds__(1024) k_te_digits(uint32_t* dig, const uint32_
       }
     }
   }
-  if (lds_hist) {
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < (uint32_t)k_cnt * hb; j += blockDim.x) {
-      const uint32_t kk = j / hb, h = j - kk * hb;
-      slice_hist[((uint64_t)kk * gridDim.x + blockIdx.x) * hb + h] = lds_hist[j];
-    }
-  }
+  slice_hist_end(slice_hist, lds_hist, (uint32_t)k_cnt * hb, hb);
 }
 #endif
 
@@ -337,20 +317,12 @@ __global__ void __launch_bounds__(256) k_te_digits_batch(uint32_t* dig, BatchSca
 #pragma unroll 1
   for (uint32_t b = 0; b < b_cnt; b++) {
     uint32_t s[8];
-    {
-      const uint4* p4 = reinterpret_cast<const uint4*>(sc.p[b] + (uint64_t)i * 8);
-      uint4 x = p4[0], y = p4[1];
-      s[0] = x.x; s[1] = x.y; s[2] = x.z; s[3] = x.w; s[4] = y.x; s[5] = y.y; s[6] = y.z; s[7] = y.w;
-    }
-    if (words8_ge(s, q)) {   // as k_te_digits
-      if (strict) atomicOr(err, 4u);
-      for (int it = 0; it < 64 && words8_ge(s, q); it++) bn_addsub<8, 8>(s, q, true);
-    }
+    load_scalar_mod_q<64>(s, sc.p[b] + (uint64_t)i * 8, q, strict, err);   // as k_te_digits
     uint32_t* db = dig + (uint64_t)b * k_total * n + i;
     uint32_t carry = 0;
     for (int k = 0; k < k_total; k++) {
-      uint32_t l = bn_take_bits<8>(s, c) + carry;
-      if (l > L) { l = 2 * L - l; carry = 1; } else { carry = 0; }
+      bool over = false;
+      const uint32_t l = window_step(bn_take_bits<8>(s, c), carry, L, false, over);
       db[(uint64_t)k * n] = l | ((l ? carry : 0u) << 31);
     }
   }

@@ -90,13 +90,15 @@ class Plan:
 
 
 class Geometry:
-    """The cuts of sort_window_group for windows [k_lo, k_hi) over n points, restated once from msm_sort.hip: the sort path
+    """The cuts of sort_geometry for windows [k_lo, k_hi) over n points, restated once from msm_plan.hip: the sort path
     (`fits_lds` .. `radix`, `will_chunk`), the split of every window's bucket index into coarse and fine bits
     (`abk = eff <= ab_big ? eff : max(ab_big, eff - BS_MAX_FB)`, `ws.fb = eff - abk`; the radix split: 7 fine bits), the bins of
     the group V = kc * hb, and `part_len = max(2^16, roundup(2 * n_entries / V, BP_TILE))` with BP_TILE = 4096.
     tables: the kc_d digit windows are one merged window of kc_d * two_n_d entries.
     chunk_rows: the table rows above which round 1 takes the pair form -- 2^23 unless a test has moved the context's threshold
-    (msm_test_set_chunk_rows_log).  mean, logG: the mean bucket the padding granule is sized from, and log2 of that granule."""
+    (msm_test_set_chunk_rows_log).  mean, logG: the mean bucket the padding granule is sized from, and log2 of that granule.
+    tests/test_sort_geometry.py checks this restatement against the library's own sort_geometry (msm_plan.hip), on the CPU, over
+    both curve kinds, every window and size: the GPU tests that build their inputs from it do not find out first."""
 
     def __init__(self, plan, n, k_lo, k_hi, tables=False, chunk_rows=1 << 23):
         kc_d = k_hi - k_lo
@@ -115,7 +117,7 @@ class Geometry:
             if bin_split:
                 ab = eff if eff <= 10 else max(10, eff - 12)
             else:
-                ab = plan.L_log - 7
+                ab = max(plan.L_log - 7, 0)             # (a window of fewer than 7 bits has no coarse ones)
                 eff = plan.L_log
             self.ab.append(ab)
             self.fb.append(eff - ab)

@@ -1,6 +1,7 @@
-// Host-side unit-test shim of the window-group schedule: msmi::group_schedule of montgomery_amd/csrc/msm_plan.hip, which this file
-// is compiled together with, over a default-constructed context that has no stream and no helper thread -- only the curve, the CU
-// count and the workspace budget the schedule reads (tests/test_group_schedule.py).  No GPU is touched.
+// Host-side unit-test shim of the window-group schedule and the sort geometry: msmi::group_schedule and msmi::sort_geometry of
+// montgomery_amd/csrc/msm_plan.hip, which this file is compiled together with, over a default-constructed context that has no
+// stream and no helper thread -- only the curve, the CU count, the workspace budget and the pair-form threshold they read
+// (tests/test_group_schedule.py, tests/test_sort_geometry.py).  No GPU is touched.
 #include "msm_internal.h"
 using namespace msmi;
 
@@ -68,6 +69,39 @@ int gs_schedule(int curve, int n_cu, uint64_t ws_budget, uint64_t n, uint64_t p_
   const int32_t f[6] = {sc.wpg, sc.tables, sc.split_points, sc.piped, sc.share_digits, sc.lone};
   memcpy(flags, f, sizeof f);
   return (int)sc.groups.size();
+}
+
+// leaves_one_level for a window of the call's plan over all n points; -1 if make_plan refuses the window
+int gs_leaves_one_level(int curve, uint64_t n, int c, int no_glv) {
+  Call cl(curve, 256, 0, n, c, no_glv);
+  if (!cl.ok) return -1;
+  return leaves_one_level(cl.ctx.is_te(), cl.pl, cl.ctx.is_te() ? n : 2 * n) ? 1 : 0;
+}
+
+// sort_geometry of windows [k_lo, k_hi) over n points under the plan of window c (tables: on window tables).  f = {kc_d, kc,
+// two_n_d, two_n, n_entries, nb, mean, logG, bin_split, radix, pairs, hb, hb_stride, nbmax, Hn, V, sortB, pps, chunk, per_block,
+// part_len, part_grid, parts_extra, slots_bound, L_log, fold, K, bits}; ab, fb: 16 entries each.  Returns 1, 0 if make_plan refuses the
+// window, -1 if sort_geometry refuses the group: f[0] = its error code, msg = its text.
+int gs_sort_geometry(int curve, int n_cu, uint64_t n, int c, int no_glv, int k_lo, int k_hi, int tables, int chunk_rows_log,
+                     uint64_t* f, uint8_t* ab, uint8_t* fb, char* msg, int msg_cap) {
+  Call cl(curve, n_cu, 0, n, c, no_glv);
+  if (!cl.ok) return 0;
+  cl.pl.tables = tables != 0;
+  cl.ctx.chunk_rows_log = chunk_rows_log;
+  try {
+    const SortGeometry g = sort_geometry(&cl.ctx, n, cl.pl, k_lo, k_hi);
+    const uint64_t v[28] = {(uint64_t)g.kc_d, (uint64_t)g.kc, g.two_n_d, g.two_n, g.n_entries, g.nb, g.mean, g.logG, g.bin_split, g.radix,
+                            g.pairs, g.hb, g.hb_stride, g.nbmax, g.Hn, g.V, g.sortB, g.pps, g.chunk, g.per_block, g.part_len,
+                            g.part_grid, g.parts_extra, g.slots_bound, (uint64_t)cl.pl.L_log, cl.pl.fold, (uint64_t)cl.pl.K, (uint64_t)cl.pl.bits};
+    memcpy(f, v, sizeof v);
+    memcpy(ab, g.ws.ab, 16);
+    memcpy(fb, g.ws.fb, 16);
+    return 1;
+  } catch (const MsmFail& e) {
+    f[0] = (uint64_t)e.code;
+    snprintf(msg, (size_t)msg_cap, "%s", e.msg.c_str());
+    return -1;
+  }
 }
 
 }  // extern "C"

@@ -32,6 +32,7 @@ def lib():
     L.gs_plan.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int, i32p]
     L.gs_window_bytes.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int]
     L.gs_window_bytes.restype = C.c_uint64
+    L.gs_leaves_one_level.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int]
     L.gs_schedule.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, i32p, i32p, u64p, u64p, i32p, i32p]
     return L
@@ -53,6 +54,7 @@ class Sched:
         plan = (C.c_int32 * 2)()
         assert L.gs_plan(curve, n, c, int(no_glv), plan), (curve, n, c, no_glv)
         self.c, self.K, self.L_log = c, plan[0], plan[1]
+        self.leaves_one_level = L.gs_leaves_one_level(curve, n, c, int(no_glv)) == 1
         self.k_lo, self.k_hi = k if k is not None else (0, self.K)
         tab_T, tab_lo, tab_n = tab if tab is not None else (0, 0, 0)
         g = L.gs_schedule(curve, n_cu, budget, n, p_off, c, int(no_glv), self.k_lo, self.k_hi, tab_T, tab_lo, tab_n, int(host),
@@ -180,10 +182,7 @@ def _check(s, te, n, p_off, tab, budget, wb):
     assert (w_lo[first] == 0).all() and (w_lo[~first] == w_end[:-1][~first[1:]]).all() and (w_end[np.r_[first[1:], True]] == n).all(), tag
     assert width.max() <= 128 and width.max() <= s.wpg, tag
     # a group that may leave the one-level sort, and any group of a plan on tables: a WinSplit of 16 entries
-    entries = n if te else 2 * n
-    fits_lds = (4 << s.L_log) <= 128 * 1024
-    leaves_one_level = s.c - 1 > 7 and (not fits_lds or entries >= ((1 << 22) if te else (1 << 21)))
-    if leaves_one_level or tab is not None:
+    if s.leaves_one_level or tab is not None:          # (the library's own rule, through the shim: msm_internal.h)
         assert width.max() <= 16, tag
     if tab is not None:
         assert width.max() <= tab[0], tag           # (kept or dropped: the cap is read before the drop)
