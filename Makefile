@@ -8,7 +8,7 @@ HIPFLAGS := -O3 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unus
 BUILD := build
 CURVES := CvBls377 CvBls381 CvPallas CvBn254 CvGrumpkin CvVesta
 CURVE_OBJS := $(CURVES:%=$(BUILD)/kernels_%.o)
-HOST_TUS := msm_plan msm_sort msm_tree msm_reduce msm_upload msm_pipeline msm_batch msm_tables msm_abi msm_test_abi msm_gen msm_ingest msm_narrow msm_indexed msm_lincomb msm_scalars msm_ntt sort_kernels te_kernels narrow_kernels
+HOST_TUS := msm_plan msm_sort msm_tree msm_reduce msm_upload msm_pipeline msm_batch msm_tables msm_abi msm_test_abi msm_gen msm_ingest msm_narrow msm_indexed msm_lincomb msm_scalars msm_ntt msm_scan sort_kernels te_kernels narrow_kernels
 HOST_OBJS := $(HOST_TUS:%=$(BUILD)/%.o)
 KHDRS := $(CSRC)/msm_kernels.h $(CSRC)/batch_add.h $(CSRC)/msm_gen_kernels.h $(CSRC)/kernel_inst.h $(CSRC)/field.h $(CSRC)/packed.h $(CSRC)/curve.h \
          $(CSRC)/glv.h $(CSRC)/constants_gen.h
@@ -25,7 +25,7 @@ $(BUILD)/kernels_%.o: $(CSRC)/kernels_curve.hip $(KHDRS)
 	$(HIPCC) $(HIPFLAGS) -DMSM_CURVE_TU=$* -c $(CSRC)/kernels_curve.hip -o $@
 
 # the host pipeline is one translation unit per concern (msm_internal.h lists them); the curve-independent kernels have two of their own
-HHDRS := $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h $(CSRC)/msm_internal.h $(CSRC)/sort_kernels.h $(CSRC)/tree_kernels.h $(CSRC)/te_kernels.h $(CSRC)/narrow_kernels.h $(CSRC)/host_field.h include/msm_hip.h
+HHDRS := $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h $(CSRC)/scalar_scan.h $(CSRC)/msm_internal.h $(CSRC)/sort_kernels.h $(CSRC)/tree_kernels.h $(CSRC)/te_kernels.h $(CSRC)/narrow_kernels.h $(CSRC)/host_field.h include/msm_hip.h
 $(BUILD)/%.o: $(CSRC)/%.hip $(HHDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -45,15 +45,19 @@ HOSTTEST_LINCOMB := tests/csrc/liblincomb_host.so
 HOSTTEST_SCALARS := tests/csrc/libscalars_host.so
 HOSTTEST_SCHEDULE := tests/csrc/libschedule_host.so
 HOSTTEST_NTT := tests/csrc/libntt_host.so
+HOSTTEST_SCANS := tests/csrc/libscans_host.so
 # (every shim whose source the tests tree holds: a tests tree from before the schedule shim still builds the others)
 hosttest: $(HOSTTEST) $(HOSTTEST_CYCLES) $(HOSTTEST_LINCOMB) $(HOSTTEST_SCALARS) $(if $(wildcard tests/csrc/schedule_host.hip),$(HOSTTEST_SCHEDULE)) \
-          $(if $(wildcard tests/csrc/ntt_host.hip),$(HOSTTEST_NTT))
+          $(if $(wildcard tests/csrc/ntt_host.hip),$(HOSTTEST_NTT)) $(if $(wildcard tests/csrc/scans_host.hip),$(HOSTTEST_SCANS))
 # the window-group schedule of msm_plan.hip (group_schedule: no HIP call) over a bare context: tests/test_group_schedule.py
 $(HOSTTEST_SCHEDULE): tests/csrc/schedule_host.hip $(CSRC)/msm_plan.hip $(HHDRS)
 	$(HIPCC) -O2 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/schedule_host.hip $(CSRC)/msm_plan.hip -o $(HOSTTEST_SCHEDULE)
 # the plan, the index functions and the lane bodies of scalar_ntt.h, run lane by lane on the host: tests/test_ntt_host.py
 $(HOSTTEST_NTT): tests/csrc/ntt_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h include/msm_hip.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/ntt_host.hip -o $(HOSTTEST_NTT)
+# the plan, the combine operators and the inverse lane body of scalar_scan.h on the host: tests/test_scans_host.py
+$(HOSTTEST_SCANS): tests/csrc/scans_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_scan.h include/msm_hip.h
+	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/scans_host.hip -o $(HOSTTEST_SCANS)
 # the lane bodies of scalar_vec.h on the scalar fields of all seven curves: tests/test_scalars_host.py
 $(HOSTTEST_SCALARS): tests/csrc/scalars_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h include/msm_hip.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/scalars_host.hip -o $(HOSTTEST_SCALARS)

@@ -325,6 +325,43 @@ int msm_scalars_root_of_unity(const msm_ctx* ctx, uint32_t log2n, uint8_t* out /
 /* the largest log2n msm_scalars_ntt accepts on this context: min(two-adicity of q - 1, 29) */
 int msm_scalars_ntt_max_log2n(const msm_ctx* ctx, uint32_t* out);
 
+/* Resident scans over the same vectors: what carries a value from one element to the next.  Prefix sums and products (the grand
+ * product z[i+1] = z[i] num[i] / den[i] of a PLONK / Halo2 permutation or lookup argument, the running sum of a log-derivative
+ * lookup), the element-wise inverse they need (Montgomery's trick), and the division of a polynomial by X - z (the witness of a
+ * KZG opening, with the evaluation a(z) as its remainder), without leaving the device; an msm_run over dst needs no extra step.
+ * A binding detects the feature by the presence of msm_scalars_scan.  The reference has no counterpart.  All seven curves.
+ * Vectors: everything msm_scalars_* says above holds -- plain 32-byte little-endian integers, any value below 2^256 counts as
+ *   its residue, every element written is canonical, 16-byte alignment at any 32-byte offset inside an allocation.  n < 2^30.
+ *   n == 0 is valid and writes nothing: total_out = init, n_zero_out = 0, rem_out = 0.
+ * Host scalars: init and z are 32 bytes little-endian; a value >= q fails with MSM_ERR_SCALAR.  0 and 1 are ordinary input.
+ * Aliasing: dst may be exactly a, or disjoint from it; a partial overlap is MSM_ERR_ARG before anything is launched.
+ * Errors: null pointers with n > 0 (a null z always), misaligned pointers, a device-list context, n >= 2^30, an unknown op and
+ *   unknown flag bits: MSM_ERR_ARG.  All checks run before anything is written; a failed call leaves the context usable.
+ * Ordering: every call returns when its result is in place (it synchronises the context's stream) and touches no point set,
+ *   window table or range-table candidate.
+ * Results are the same bits whatever the tile geometry: the operators are exact.
+ * Device memory beyond the caller's vectors, owned by the context and freed with it (it grows to the largest call, plus 1/16):
+ *   tile aggregates 32 bytes per tile and level, and 32 for the total: a scan runs over tiles of 2^10 elements, the aggregates
+ *                   of more than one tile are scanned the same way, so 32 (1 + ceil(n / 2^10) + ceil(n / 2^20)) bytes
+ *                   (2.0 MiB at 2^26; none beyond the total up to 2^10 elements)
+ *   zero counts     4 ceil(n / 2^11) bytes for msm_scalars_inverse, in the same buffer */
+enum { MSM_SCAN_SUM = 0, MSM_SCAN_PRODUCT = 1 };
+enum { MSM_SCAN_EXCLUSIVE = 1 }; /* flags; every other bit is MSM_ERR_ARG */
+/* o = addition (MSM_SCAN_SUM) or multiplication (MSM_SCAN_PRODUCT) mod q
+ *   inclusive: dst[i] = init o a[0] o ... o a[i]
+ *   exclusive: dst[i] = init o a[0] o ... o a[i-1]   (dst[0] = init)
+ * *total_out (32 B LE on the host, may be NULL) = init o a[0] o ... o a[n-1]
+ * init: 32 B LE below q, NULL = the operator's neutral element (0 / 1) */
+int msm_scalars_scan(msm_ctx* ctx, void* dst, const void* a, uint64_t n, int op, uint32_t flags,
+                     const uint8_t* init, uint8_t* total_out);
+/* dst[i] = a[i]^-1 mod q.  An element whose residue is 0 gives 0 (the rule of arkworks' and halo2's batch inversion): that is
+ * 0, q, and every other multiple of q below 2^256.  *n_zero_out (may be NULL) = how many such elements there were */
+int msm_scalars_inverse(msm_ctx* ctx, void* dst, const void* a, uint64_t n, uint64_t* n_zero_out);
+/* a = the n coefficients of a polynomial, a[0] the constant term: dst[j] = q_j for j < n - 1 and dst[n-1] = 0, where
+ * a(X) = (X - z) q(X) + a(z); *rem_out (32 B LE, may be NULL) = a(z).  z: 32 B LE below q; 0 is ordinary input.
+ * n == 1: dst[0] = 0, rem = a[0] mod q */
+int msm_scalars_div_linear(msm_ctx* ctx, void* dst, const void* a, uint64_t n, const uint8_t* z, uint8_t* rem_out);
+
 /* Device memory the working buffers of one call may take (digits, sort records, tree nodes: the reference sizes them per call
  * in wasm memory, src/msm-batched-affine.ts:96-130).  0 = automatic: 85 % of what the device has free when a big call starts.
  * Windows run in as many groups as fit, and a window whose buffers would not fit at all runs over ranges of the points, one
@@ -595,6 +632,15 @@ int msm_test_set_ntt_tile_log(msm_ctx* ctx, int32_t tile_log);
  * failed or a transform of one element: writes min(count, cap) of them to `stages_out` (may be NULL with cap = 0) and returns
  * the count, or -1 for a null or device-list context. */
 int msm_test_last_ntt_plan(msm_ctx* ctx, int32_t* stages_out, int cap);
+/* msm_scalars_scan and msm_scalars_div_linear run over tiles of 2^tile_log elements and scan the tiles' aggregates the same way,
+ * level by level.  This entry moves tile_log for the context, so that tests reach plans of three levels at 65 537 elements through
+ * the library's own host code.  tile_log: 8 (one element per lane) .. 10 (the default), or 0 to restore the default.  Results do
+ * not depend on it.  Refused on a device-list context. */
+int msm_test_set_scan_tile_log(msm_ctx* ctx, int32_t tile_log);
+/* The tiles per level of the last msm_scalars_scan or msm_scalars_div_linear on this context, bottom level first (the last entry
+ * is 1); none (count 0) after a call that was refused or had n == 0: writes min(count, cap) of them to `tiles_out` (may be NULL
+ * with cap = 0) and returns the count, or -1 for a null or device-list context. */
+int msm_test_last_scan_plan(msm_ctx* ctx, int32_t* tiles_out, int cap);
 /* The first step of every MSM alone: the window digits of a call's scalars, from the digit kernel the call would launch
  * (k_digits, k_te_digits, k_digits_narrow<W>, k_te_digits_narrow<W>; B >= 2: their _batch forms), through the pipeline's own
  * launch code and geometry, and nothing behind it -- nothing sorts the digits, so a wrong one is a wrong word in digits_out and

@@ -69,6 +69,15 @@ export interface Parallel {
     shift?: bigint | number | Uint8Array; batch?: number }): ScalarPtr;
   /** the library's primitive 2^log2n-th root of unity mod the group order (msm_scalars_root_of_unity) */
   scalarsRootOfUnity(log2n: number): bigint;
+  /** dstPtr = the running sum or product mod the group order of the first N scalars of ptr (msm_scalars_scan); returns the total.
+   *  inclusive: dst[i] = init o a[0] o ... o a[i], exclusive: dst[i] = init o a[0] o ... o a[i-1]; dstPtr may be ptr */
+  scalarsScan(dstPtr: ScalarPtr, ptr: ScalarPtr, N: number, options?: { op?: "sum" | "product"; exclusive?: boolean;
+    init?: bigint | number | Uint8Array }): bigint;
+  /** dstPtr[i] = ptr[i]^-1 mod the group order, 0 where the residue is 0; returns how many of those there were (msm_scalars_inverse) */
+  scalarsInverse(dstPtr: ScalarPtr, ptr: ScalarPtr, N: number): number;
+  /** dstPtr = the quotient of the polynomial with the N coefficients of ptr by X - z, dstPtr[N-1] = 0; returns the remainder, its
+   *  value at z (msm_scalars_div_linear); dstPtr may be ptr */
+  scalarsDivLinear(dstPtr: ScalarPtr, ptr: ScalarPtr, N: number, z: bigint | number | Uint8Array): bigint;
   /** in-place fold: v[i] <- a * v[i] + b * v[i + n/2], i < n/2 (n even); the pointer then holds n/2 scalars */
   foldScalars(scalarPtr: ScalarPtr, a: bigint | number | Uint8Array, b: bigint | number | Uint8Array): ScalarPtr;
   /** the first N scalars behind a pointer (default: all) as N x 32 bytes on the host (msm_device_download) */

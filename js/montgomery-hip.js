@@ -258,6 +258,32 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
     },
     // the library's primitive 2^log2n-th root of unity mod the group order, as a BigInt (msm_scalars_root_of_unity)
     scalarsRootOfUnity(log2n) { return leBytesToBigint(hip.scalarsRootOfUnity(ctx, log2n)); },
+    // Resident scans (msm_scalars_scan): dstPtr = the running sum or product mod the group order of the first N scalars of ptr;
+    // returns the total as a BigInt.  options: {op: "sum" | "product", exclusive, init} -- inclusive: dst[i] = init o a[0] o ... o a[i],
+    // exclusive: dst[i] = init o a[0] o ... o a[i-1]; init: BigInt / number or 32 bytes below the order (default 0 / 1).
+    // dstPtr may be ptr.
+    scalarsScan(dstPtr, ptr, N, options) {
+      const o = options || {}, op = o.op === undefined ? "sum" : o.op;
+      if (op !== "sum" && op !== "product") throw new TypeError(`scalarsScan: op must be "sum" or "product", not ${op}`);
+      needScalars(ptr, N, "scalarsScan");
+      roomFor(dstPtr, N);
+      const init = o.init === undefined || o.init === null ? null : scalarBuffer(o.init, "init");
+      return leBytesToBigint(hip.scalarsScan(ctx, dstPtr.dev, 0, ptr.dev, 0, N, op === "product" ? 1 : 0, !!o.exclusive, init));
+    },
+    // dstPtr[i] = ptr[i]^-1 mod the group order, 0 where the residue is 0; returns how many of those there were
+    // (msm_scalars_inverse).  dstPtr may be ptr.
+    scalarsInverse(dstPtr, ptr, N) {
+      needScalars(ptr, N, "scalarsInverse");
+      roomFor(dstPtr, N);
+      return hip.scalarsInverse(ctx, dstPtr.dev, 0, ptr.dev, 0, N);
+    },
+    // dstPtr = the quotient of the polynomial with the N coefficients of ptr (the constant term first) by X - z, dstPtr[N-1] = 0;
+    // returns the remainder, the polynomial's value at z, as a BigInt (msm_scalars_div_linear).  dstPtr may be ptr.
+    scalarsDivLinear(dstPtr, ptr, N, z) {
+      needScalars(ptr, N, "scalarsDivLinear");
+      roomFor(dstPtr, N);
+      return leBytesToBigint(hip.scalarsDivLinear(ctx, dstPtr.dev, 0, ptr.dev, 0, N, scalarBuffer(z, "z")));
+    },
     // the in-place fold of an inner-product argument: v[i] <- a * v[i] + b * v[i + n/2], i < n/2; the pointer then holds n/2 scalars
     foldScalars(scalarPtr, a, b) {
       const n = scalarPtr.n;

@@ -30,6 +30,9 @@ POINTS_UNCOMPRESSED, POINTS_COMPRESSED = 0, 1
 VALIDATE_NONE, VALIDATE_CURVE, VALIDATE_SUBGROUP = 0, 1, 2
 NO_BAD_INDEX = (1 << 64) - 1   # *bad_index_out when every point passed
 
+SCAN_SUM, SCAN_PRODUCT = 0, 1   # op of msm_scalars_scan
+SCAN_EXCLUSIVE = 1              # its flags
+
 OP_MUL, OP_SQR, OP_ADD, OP_SUB, OP_INV, OP_TO_MONT, OP_FROM_MONT, OP_INV_FERMAT, OP_INV_KALISKI, OP_INV_WORDSLICED = range(10)
 
 # every symbol include/msm_hip.h declares
@@ -51,6 +54,7 @@ EXPORTS = (
     "msm_test_bucket_sums", "msm_test_set_chunk_rows_log", "msm_test_last_sort_paths", "msm_test_digits",
     "msm_scalars_ntt", "msm_scalars_root_of_unity", "msm_scalars_ntt_max_log2n", "msm_test_set_ntt_tile_log", "msm_test_last_ntt_plan",
     "msm_test_tree_sums",
+    "msm_scalars_scan", "msm_scalars_inverse", "msm_scalars_div_linear", "msm_test_set_scan_tile_log", "msm_test_last_scan_plan",
 )
 
 
@@ -237,6 +241,14 @@ def load() -> C.CDLL:
         raise ImportError(f"{LIB_PATH} predates msm_test_tree_sums: rebuild it (`make`)")
     lib.msm_test_tree_sums.argtypes = [vp, vp, u64, vp, vp, vp, i32, C.c_uint32, i32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32,
                                        vp, C.c_uint32]
+    # the resident scans, the batch inverse and the division by X - z, with their test surface: new symbols under ABI 8 as well
+    if not hasattr(lib, "msm_scalars_scan"):
+        raise ImportError(f"{LIB_PATH} predates msm_scalars_scan: rebuild it (`make`)")
+    lib.msm_scalars_scan.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, vp, vp]
+    lib.msm_scalars_inverse.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
+    lib.msm_scalars_div_linear.argtypes = [vp, vp, vp, u64, vp, vp]
+    lib.msm_test_set_scan_tile_log.argtypes = [vp, i32]
+    lib.msm_test_last_scan_plan.argtypes = [vp, C.POINTER(i32), C.c_int]
     for name in EXPORTS:
         if name not in ("msm_ctx_destroy", "msm_last_error", "msm_abi_version", "msm_abi_struct_bytes"):
             getattr(lib, name).restype = C.c_int

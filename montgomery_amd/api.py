@@ -820,6 +820,34 @@ class MsmContext:
         self._check(self._lib.msm_scalars_ntt_max_log2n(self._h, C.byref(out)))
         return int(out.value)
 
+    def scalars_scan(self, dst: int, a: int, n: int, op: str = "sum", exclusive: bool = False, init=None) -> int:
+        """The running sum (op "sum") or product ("product") mod q of the n scalars at a (msm_scalars_scan):
+        inclusive dst[i] = init o a[0] o ... o a[i]; exclusive dst[i] = init o a[0] o ... o a[i-1].  init: int or 32 bytes < q,
+        None = 0 / 1.  dst may be a itself or disjoint from it.  Returns the total init o a[0] o ... o a[n-1] as an int."""
+        ops = {"sum": _lib.SCAN_SUM, "product": _lib.SCAN_PRODUCT}
+        if op not in ops:
+            raise MsmError(_lib.MSM_ERR_ARG, f"scalars_scan: op must be 'sum' or 'product', not {op!r}")
+        out = (C.c_uint8 * 32)()
+        ibuf = None if init is None else self._scalar_buf(init, "init")
+        self._check(self._lib.msm_scalars_scan(self._h, C.c_void_p(dst), C.c_void_p(a), n, ops[op],
+                                               _lib.SCAN_EXCLUSIVE if exclusive else 0, ibuf, out))
+        return int.from_bytes(bytes(out), "little")
+
+    def scalars_inverse(self, dst: int, a: int, n: int) -> int:
+        """dst[i] = a[i]^-1 mod q; an element whose residue is 0 gives 0 (msm_scalars_inverse).  dst may be a itself or disjoint
+        from it.  Returns how many elements had the residue 0."""
+        zeros = C.c_uint64(0)
+        self._check(self._lib.msm_scalars_inverse(self._h, C.c_void_p(dst), C.c_void_p(a), n, C.byref(zeros)))
+        return int(zeros.value)
+
+    def scalars_div_linear(self, dst: int, a: int, n: int, z) -> int:
+        """The division of the polynomial with the n coefficients at a (a[0] the constant term) by X - z (msm_scalars_div_linear):
+        dst[j] = q_j for j < n - 1 and dst[n-1] = 0, where a(X) = (X - z) q(X) + a(z).  z: int or 32 bytes < q.  dst may be a itself
+        or disjoint from it.  Returns the remainder a(z) as an int."""
+        out = (C.c_uint8 * 32)()
+        self._check(self._lib.msm_scalars_div_linear(self._h, C.c_void_p(dst), C.c_void_p(a), n, self._scalar_buf(z, "z"), out))
+        return int.from_bytes(bytes(out), "little")
+
     def fold_scalars(self, dev_ptr: int, n: int, lo_scalar, hi_scalar) -> int:
         """The in-place fold of the n scalars at dev_ptr: v[i] <- lo_scalar * v[i] + hi_scalar * v[i + n/2], i < n/2 (n even); the
         upper half stays as it was.  The scalar fold of an inner-product argument beside fold_points.  Returns n/2."""
@@ -1389,6 +1417,26 @@ class _Parallel:
     def scalarsRootOfUnity(self, log2n: int) -> int:
         """The library's primitive 2^log2n-th root of unity mod q (MsmContext.scalars_root_of_unity)."""
         return self._ctx.scalars_root_of_unity(log2n)
+
+    def scalarsScan(self, dstPtr: ScalarPtr, ptr: ScalarPtr, N: int, options: Optional[Dict] = None) -> int:
+        """dstPtr = the running sum or product of the first N scalars of ptr (MsmContext.scalars_scan); returns the total.
+        options: {"op": "sum" | "product", "exclusive", "init"}.  dstPtr may be ptr."""
+        options = options or {}
+        a = self._scalar_dev(ptr, N, "scalarsScan")
+        d = self._scalar_dev(dstPtr, N, "scalarsScan", alloc=True)
+        return self._ctx.scalars_scan(d, a, N, options.get("op", "sum"), bool(options.get("exclusive", False)), options.get("init"))
+
+    def scalarsInverse(self, dstPtr: ScalarPtr, ptr: ScalarPtr, N: int) -> int:
+        """dstPtr[i] = ptr[i]^-1 mod q, 0 where the residue is 0; returns how many of those there were
+        (MsmContext.scalars_inverse).  dstPtr may be ptr."""
+        a = self._scalar_dev(ptr, N, "scalarsInverse")
+        return self._ctx.scalars_inverse(self._scalar_dev(dstPtr, N, "scalarsInverse", alloc=True), a, N)
+
+    def scalarsDivLinear(self, dstPtr: ScalarPtr, ptr: ScalarPtr, N: int, z) -> int:
+        """dstPtr = the quotient of the polynomial with the N coefficients of ptr by X - z, dstPtr[N-1] = 0; returns the
+        remainder, its value at z (MsmContext.scalars_div_linear).  dstPtr may be ptr."""
+        a = self._scalar_dev(ptr, N, "scalarsDivLinear")
+        return self._ctx.scalars_div_linear(self._scalar_dev(dstPtr, N, "scalarsDivLinear", alloc=True), a, N, z)
 
     def foldScalars(self, scalarPtr: ScalarPtr, a, b) -> ScalarPtr:
         """The in-place fold of the scalars behind scalarPtr: v[i] <- a * v[i] + b * v[i + n/2]; the pointer then holds n/2

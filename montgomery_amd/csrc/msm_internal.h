@@ -304,6 +304,11 @@ struct msm_ctx {
   bool ntt_tw_library = false;     // ... and it is the library's root of that size (a call without omega then computes no root)
   int ntt_tile_log = 0;            // msm_test_set_ntt_tile_log: stages a pass may have; 0 = ntt::DEFAULT_TILE_LOG
   std::vector<int32_t> last_ntt_plan;   // stages per pass of the last msm_scalars_ntt (msm_test_last_ntt_plan); empty after a refusal
+  // msm_scalars_scan / _inverse / _div_linear (msm_scan.hip): the call's total, then one 32-byte aggregate per tile and level (the
+  // inverse keeps its per-block zero counts there).  Freed with the context.
+  msmi::DevBuf scan_agg;
+  int scan_tile_log = 0;           // msm_test_set_scan_tile_log: elements per tile = 2^it; 0 = scan::DEFAULT_TILE_LOG
+  std::vector<int32_t> last_scan_plan;  // tiles per level of the last scan / div_linear (msm_test_last_scan_plan); empty after a refusal
 
   // per-group workspace: two of them, each with its own stream, so that the memory-bound sort of one
   // window group runs under the ALU-bound accumulation of the other

@@ -29,6 +29,8 @@
 //          scalarsInner(h, a, aOff, b, bOff, n) -> Buffer of 32 bytes, scalarsPowers(h, dst, dstOff, Buffer s, Buffer x, n),
 //          scalarsNtt(h, dst, dstOff, a, aOff, log2n, batch, Buffer omega | null, Buffer shift | null, inverse) (msm_scalars_ntt),
 //          scalarsRootOfUnity(h, log2n) -> Buffer of 32 bytes, scalarsNttMaxLog2n(h) -> number,
+//          scalarsScan(h, dst, dstOff, a, aOff, n, op, exclusive, Buffer init | null) -> Buffer total (msm_scalars_scan),
+//          scalarsInverse(h, dst, dstOff, a, aOff, n) -> number of zero residues, scalarsDivLinear(h, dst, dstOff, a, aOff, n, z) -> Buffer,
 //          plan(h, n, c) -> {c, K}, generatePoints(h, n, seed) -> n, generateScalars(h, n, seed[, dbuf]) -> Buffer | n
 //          the fine operator table of the reference's wasm exports (src/field-msm.ts:86-123,190-243, src/scalar-glv.ts:41-51,105-128)
 //          over Buffers instead of wasm pointers: fieldOp(h, op, a, b) -> Buffer (msm_test_fp: multiply / square / add / subtract /
@@ -1080,6 +1082,82 @@ static napi_value ScalarsNttMaxLog2n(napi_env env, napi_callback_info info) {
   return out;
 }
 
+// the resident scans (msm_scalars_scan, msm_scalars_inverse, msm_scalars_div_linear): n elements from (buffer, offset)
+// scalarsScan(ctx, dst, dstOff, a, aOff, n, op, exclusive, init: Buffer | null) -> Buffer of 32 bytes, the total
+static napi_value ScalarsScan(napi_env env, napi_callback_info info) {
+  size_t argc = 9;
+  napi_value argv[9];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 9) {
+    napi_throw_type_error(env, NULL, "scalarsScan(ctx, dst, dstOff, a, aOff, n, op, exclusive, init)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int64_t n = 0;
+  int32_t op = 0;
+  bool exclusive = false;
+  NAPI_OK(napi_get_value_int64(env, argv[5], &n));
+  NAPI_OK(napi_get_value_int32(env, argv[6], &op));
+  NAPI_OK(napi_get_value_bool(env, argv[7], &exclusive));
+  uint8_t *dst = NULL, *a = NULL;
+  const uint8_t* init = NULL;
+  if (!vec_arg(env, h, argv[1], argv[2], n, "scalarsScan", &dst) || !vec_arg(env, h, argv[3], argv[4], n, "scalarsScan", &a)) return NULL;
+  if (!is_nullish(env, argv[8]) && !host_scalar_arg(env, argv[8], &init)) return NULL;
+  napi_value out;
+  void* po = NULL;
+  NAPI_OK(napi_create_buffer(env, 32, &po, &out));
+  int rc = msm_scalars_scan(h->ctx, dst, a, (uint64_t)n, op, exclusive ? MSM_SCAN_EXCLUSIVE : 0u, init, (uint8_t*)po);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsScan");
+  return out;
+}
+// scalarsInverse(ctx, dst, dstOff, a, aOff, n) -> number of elements whose residue is 0
+static napi_value ScalarsInverse(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 6) {
+    napi_throw_type_error(env, NULL, "scalarsInverse(ctx, dst, dstOff, a, aOff, n)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int64_t n = 0;
+  NAPI_OK(napi_get_value_int64(env, argv[5], &n));
+  uint8_t *dst = NULL, *a = NULL;
+  if (!vec_arg(env, h, argv[1], argv[2], n, "scalarsInverse", &dst) || !vec_arg(env, h, argv[3], argv[4], n, "scalarsInverse", &a)) return NULL;
+  uint64_t zeros = 0;
+  int rc = msm_scalars_inverse(h->ctx, dst, a, (uint64_t)n, &zeros);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsInverse");
+  napi_value out;
+  NAPI_OK(napi_create_int64(env, (int64_t)zeros, &out));
+  return out;
+}
+// scalarsDivLinear(ctx, dst, dstOff, a, aOff, n, z: Buffer) -> Buffer of 32 bytes, the remainder
+static napi_value ScalarsDivLinear(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 7) {
+    napi_throw_type_error(env, NULL, "scalarsDivLinear(ctx, dst, dstOff, a, aOff, n, z)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int64_t n = 0;
+  NAPI_OK(napi_get_value_int64(env, argv[5], &n));
+  uint8_t *dst = NULL, *a = NULL;
+  const uint8_t* z = NULL;
+  if (!vec_arg(env, h, argv[1], argv[2], n, "scalarsDivLinear", &dst) || !vec_arg(env, h, argv[3], argv[4], n, "scalarsDivLinear", &a)) return NULL;
+  if (!host_scalar_arg(env, argv[6], &z)) return NULL;
+  napi_value out;
+  void* po = NULL;
+  NAPI_OK(napi_create_buffer(env, 32, &po, &out));
+  int rc = msm_scalars_div_linear(h->ctx, dst, a, (uint64_t)n, z, (uint8_t*)po);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsDivLinear");
+  return out;
+}
+
 /* ---- the fine operator table: element-wise field / GLV / curve operators over Buffers -------------------------------- */
 
 static int buffer_arg(napi_env env, napi_value v, uint8_t** data, size_t* len) {
@@ -1220,6 +1298,7 @@ NAPI_MODULE_INIT() {
       {"deviceDownload", DeviceDownload}, {"scalarsLincomb", ScalarsLincomb}, {"scalarsMul", ScalarsMul},
       {"scalarsInner", ScalarsInner}, {"scalarsPowers", ScalarsPowers},
       {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity}, {"scalarsNttMaxLog2n", ScalarsNttMaxLog2n},
+      {"scalarsScan", ScalarsScan}, {"scalarsInverse", ScalarsInverse}, {"scalarsDivLinear", ScalarsDivLinear},
       {"fieldOp", FieldOp}, {"batchInverse", BatchInverse}, {"glvDecompose", GlvDecompose}, {"batchAdd", BatchAdd}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
     napi_value f;
