@@ -8,7 +8,7 @@ HIPFLAGS := -O3 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unus
 BUILD := build
 CURVES := CvBls377 CvBls381 CvPallas CvBn254 CvGrumpkin CvVesta
 CURVE_OBJS := $(CURVES:%=$(BUILD)/kernels_%.o)
-HOST_TUS := msm_plan msm_sort msm_tree msm_reduce msm_upload msm_pipeline msm_batch msm_tables msm_abi msm_test_abi msm_gen msm_ingest msm_narrow msm_indexed msm_lincomb msm_scalars msm_ntt msm_scan sort_kernels te_kernels narrow_kernels
+HOST_TUS := msm_plan msm_sort msm_tree msm_reduce msm_upload msm_pipeline msm_batch msm_tables msm_abi msm_test_abi msm_gen msm_ingest msm_narrow msm_indexed msm_lincomb msm_points_mul msm_scalars msm_ntt msm_scan sort_kernels te_kernels narrow_kernels
 HOST_OBJS := $(HOST_TUS:%=$(BUILD)/%.o)
 KHDRS := $(CSRC)/msm_kernels.h $(CSRC)/batch_add.h $(CSRC)/msm_gen_kernels.h $(CSRC)/kernel_inst.h $(CSRC)/field.h $(CSRC)/packed.h $(CSRC)/curve.h \
          $(CSRC)/glv.h $(CSRC)/constants_gen.h
@@ -25,10 +25,13 @@ $(BUILD)/kernels_%.o: $(CSRC)/kernels_curve.hip $(KHDRS)
 	$(HIPCC) $(HIPFLAGS) -DMSM_CURVE_TU=$* -c $(CSRC)/kernels_curve.hip -o $@
 
 # the host pipeline is one translation unit per concern (msm_internal.h lists them); the curve-independent kernels have two of their own
-HHDRS := $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h $(CSRC)/scalar_scan.h $(CSRC)/msm_internal.h $(CSRC)/sort_kernels.h $(CSRC)/tree_kernels.h $(CSRC)/te_kernels.h $(CSRC)/narrow_kernels.h $(CSRC)/host_field.h include/msm_hip.h
+HHDRS := $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/points_mul.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h $(CSRC)/scalar_scan.h $(CSRC)/msm_internal.h $(CSRC)/sort_kernels.h $(CSRC)/tree_kernels.h $(CSRC)/te_kernels.h $(CSRC)/narrow_kernels.h $(CSRC)/host_field.h include/msm_hip.h
+# msm_points_mul: with the loop-invariant code motion of the machine passes, every constant of the row loop's body (the GLV
+# vectors, q, p, beta) is kept in a scalar register across the whole loop and up to 37 of them go to vector lanes and back
+TUFLAGS_msm_points_mul := -mllvm -disable-machine-licm
 $(BUILD)/%.o: $(CSRC)/%.hip $(HHDRS)
 	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(TUFLAGS_$*) -c $< -o $@
 
 $(LIB): $(HOST_OBJS) $(CURVE_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -pthread $(HOST_OBJS) $(CURVE_OBJS) -o $(LIB)
@@ -36,7 +39,7 @@ $(LIB): $(HOST_OBJS) $(CURVE_OBJS)
 clean:
 	rm -rf $(LIB) $(BUILD)
 
-.PHONY: all clean
+.PHONY: all clean ab ab_pmul
 
 # CPU build of the field / GLV templates for tests/test_host_field.py (no GPU needed)
 HOSTTEST := tests/csrc/libfield_host.so
@@ -46,9 +49,11 @@ HOSTTEST_SCALARS := tests/csrc/libscalars_host.so
 HOSTTEST_SCHEDULE := tests/csrc/libschedule_host.so
 HOSTTEST_NTT := tests/csrc/libntt_host.so
 HOSTTEST_SCANS := tests/csrc/libscans_host.so
+HOSTTEST_PMUL := tests/csrc/libpoints_mul_host.so
 # (every shim whose source the tests tree holds: a tests tree from before the schedule shim still builds the others)
 hosttest: $(HOSTTEST) $(HOSTTEST_CYCLES) $(HOSTTEST_LINCOMB) $(HOSTTEST_SCALARS) $(if $(wildcard tests/csrc/schedule_host.hip),$(HOSTTEST_SCHEDULE)) \
-          $(if $(wildcard tests/csrc/ntt_host.hip),$(HOSTTEST_NTT)) $(if $(wildcard tests/csrc/scans_host.hip),$(HOSTTEST_SCANS))
+          $(if $(wildcard tests/csrc/ntt_host.hip),$(HOSTTEST_NTT)) $(if $(wildcard tests/csrc/scans_host.hip),$(HOSTTEST_SCANS)) \
+          $(if $(wildcard tests/csrc/points_mul_host.hip),$(HOSTTEST_PMUL))
 # the window-group schedule of msm_plan.hip (group_schedule: no HIP call) over a bare context: tests/test_group_schedule.py
 $(HOSTTEST_SCHEDULE): tests/csrc/schedule_host.hip $(CSRC)/msm_plan.hip $(HHDRS)
 	$(HIPCC) -O2 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/schedule_host.hip $(CSRC)/msm_plan.hip -o $(HOSTTEST_SCHEDULE)
@@ -64,6 +69,9 @@ $(HOSTTEST_SCALARS): tests/csrc/scalars_host.hip $(CSRC)/field.h $(CSRC)/constan
 # the recoder and the lane bodies of points_lincomb.h on all seven curves: tests/test_points_lincomb_host.py
 $(HOSTTEST_LINCOMB): tests/csrc/lincomb_host.hip $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/te_kernels.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/lincomb_host.hip -o $(HOSTTEST_LINCOMB)
+# the recoding and the lane bodies of points_mul.h on all seven curves, at every candidate window: tests/test_points_mul_host.py
+$(HOSTTEST_PMUL): tests/csrc/points_mul_host.hip $(KHDRS) $(CSRC)/points_mul.h $(CSRC)/te_kernels.h
+	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/points_mul_host.hip -o $(HOSTTEST_PMUL)
 # the cycle curves (BN254 G1, Grumpkin, Vesta), with the square root of points_ingest.h: tests/test_cycle_curves.py
 $(HOSTTEST_CYCLES): tests/csrc/field_host_cycles.hip $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/te_kernels.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/field_host_cycles.hip -o $(HOSTTEST_CYCLES)
@@ -87,9 +95,17 @@ examples/msm_demo: examples/msm_demo.c include/msm_hip.h $(LIB)
 ab:
 	@mkdir -p ab_builds/$(NAME)
 	for c in $(CURVES); do $(HIPCC) $(HIPFLAGS) $(EXTRA) -DMSM_CURVE_TU=$$c -c $(CSRC)/kernels_curve.hip -o ab_builds/$(NAME)/kernels_$$c.o & done; \
-	for t in $(HOST_TUS); do $(HIPCC) $(HIPFLAGS) $(EXTRA) -c $(CSRC)/$$t.hip -o ab_builds/$(NAME)/$$t.o & done; wait
+	$(foreach t,$(HOST_TUS),$(HIPCC) $(HIPFLAGS) $(TUFLAGS_$(t)) $(EXTRA) -c $(CSRC)/$(t).hip -o ab_builds/$(NAME)/$(t).o & ) wait
 	$(HIPCC) --offload-arch=$(ARCH) -shared -pthread ab_builds/$(NAME)/*.o -o ab_builds/libmsm_$(NAME).so
 	rm -rf ab_builds/$(NAME)
+
+# the same for the candidates of msm_points_mul, which differ in one translation unit: make ab_pmul NAME=w5 EXTRA="-DMSM_PMUL_W=5"
+# links ab_builds/libmsm_pmul_w5.so from that unit and the in-tree objects (tools/bench_points_mul.py --libs times them)
+ab_pmul: $(LIB)
+	@mkdir -p ab_builds
+	$(HIPCC) $(HIPFLAGS) $(TUFLAGS_msm_points_mul) $(EXTRA) -c $(CSRC)/msm_points_mul.hip -o ab_builds/pmul_$(NAME).o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -pthread $(filter-out $(BUILD)/msm_points_mul.o,$(HOST_OBJS)) ab_builds/pmul_$(NAME).o $(CURVE_OBJS) -o ab_builds/libmsm_pmul_$(NAME).so
+	rm -f ab_builds/pmul_$(NAME).o
 
 # micro-benchmarks quoted in DESIGN.md (run on the GPU box; outputs are committed under profiles/)
 UBENCH := ubench_int2 ubench_inv ubench_mul2 ubench_mad3 ubench_gather ubench_carry

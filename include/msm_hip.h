@@ -72,7 +72,9 @@ enum {
  * struct sizes unchanged.  A binding detects the feature by the presence of the symbol msm_points_lincomb.
  * The resident scalar-vector operations (msm_scalars_lincomb, msm_scalars_mul, msm_scalars_inner, msm_scalars_powers) and
  * msm_device_download came the same way: five new symbols, version 8 and both struct sizes unchanged.  A binding detects the
- * feature by the presence of the symbol msm_scalars_lincomb. */
+ * feature by the presence of the symbol msm_scalars_lincomb.
+ * Per-row scalar multiplication of point sets (msm_points_mul, msm_points_mul_base) came the same way: two new symbols, version 8
+ * and both struct sizes unchanged.  A binding detects the feature by the presence of the symbol msm_points_mul. */
 #define MSM_ABI_VERSION 8
 uint32_t msm_abi_version(void);
 uint32_t msm_abi_struct_bytes(int which);
@@ -490,6 +492,41 @@ int msm_points_lincomb(msm_ctx* ctx, int32_t src_a, uint64_t a_lo, const uint8_t
 /* number of resident points of a point set (ids as msm_pointset_create returns them; 0 = the default set) */
 int msm_pointset_size(const msm_ctx* ctx, int32_t id, uint64_t* n_out);
 
+/* Per-row scalar multiplication: D[i] = s[i] * A[a_lo + i] for i < count, written as the rows [0, count) of point set `dst` --
+ * every row under its OWN scalar, where msm_points_lincomb takes one scalar for the whole set.  With the vectors of
+ * msm_scalars_powers / msm_scalars_inverse it makes a commitment key [tau^i] G, the re-weighted generators y^-i H_i of
+ * Bulletproofs, batched ElGamal / Pedersen terms r_i G and r_i P_i, or re-randomises a set row by row, without the scalars or the
+ * points leaving the device.  The contract is that of msm_points_lincomb wherever this text does not say otherwise: point-set
+ * ids, dst replaced as by msm_set_points (window tables dropped, size `count`), the current set not switched, all checks before
+ * anything is written, the call returning when the rows are in place, count == 0 valid.
+ * Scalars: `count` x 32-byte little-endian integers in host memory (on_device = 0) or in device memory aligned to 16 bytes
+ *   (on_device = 1), the vectors msm_run and msm_scalars_* read.  A value >= q is taken as its residue (msm_run's rule without
+ *   msm_opts.strict).  0 gives the identity row, q - 1 the negative of the row.
+ * Result rows are bit-identical to what msm_set_points writes for the same affine points, the beta x line included; the identity
+ *   takes the identity row (the Edwards curve: the row of (0, 1)).  Every later call works on dst: msm_run with and without the
+ *   endomorphism, msm_get_points(_ex), msm_validate_points, msm_precompute, msm_points_lincomb.
+ * In place: dst == src is allowed with a_lo == 0 (a lane reads row i and its scalar before its one store of row i; the set is
+ *   truncated to `count`) and with a_lo >= count.  Any other overlap is MSM_ERR_ARG.
+ * Points outside the prime-order subgroup: the Weierstrass path uses the endomorphism, so -- as for msm_points_lincomb -- the
+ *   result is s * P only for points of the subgroup.  A torsion row neither faults nor disturbs its neighbours.
+ * How: one lane per row on a fixed grid; the lane reduces and splits its scalar (glv_decompose), recodes both halves into signed
+ *   4-bit windows, builds the table 1 P .. 8 P of its row in a device workspace (about 200 MB on BLS12-377 for the default grid
+ *   of one round of resident blocks, whatever `count`; it counts against msm_set_workspace_limit, under which the grid shrinks
+ *   down to one block) and walks the
+ *   windows from the top: 4 doublings and two table additions per window.
+ * Errors: MSM_ERR_ARG -- an id that does not name a live set, null `scalars` with count > 0, device scalars not aligned to 16
+ *   bytes, a device-list context, count >= 2^30, a forbidden overlap.  MSM_ERR_NO_POINTS -- a source range that ends beyond its
+ *   set.  A failed call leaves every set as it was. */
+int msm_points_mul(msm_ctx* ctx, int32_t src, uint64_t a_lo, const void* scalars, int on_device, uint64_t count, int32_t dst);
+/* The same for ONE base point: D[i] = s[i] * P.  base_xy is x || y in the wire format of msm_set_points (NULL: the curve's
+ * generator); it is checked on the host -- a coordinate >= p or a point off the curve is MSM_ERR_POINT -- and the all-zero
+ * encoding is the identity, which gives `count` identity rows.  The context keeps one table of rows j 2^(10 k) P (j = 1 .. 512,
+ * k over the 13 windows of a scalar half: 1.7 MB on BLS12-377), built by the variable-base kernel itself and cached with the base's
+ * bytes: a lane then adds one table row per window and half, no doubling.  A call with another base rebuilds the table;
+ * msm_ctx_destroy frees it.  A short call (under 2^10 rows) with a base that is not cached does not build the table and runs
+ * the variable-base kernel over a broadcast row instead. */
+int msm_points_mul_base(msm_ctx* ctx, const uint8_t* base_xy, const void* scalars, int on_device, uint64_t count, int32_t dst);
+
 /* Window-sharded form for multi-GPU runs: computes the partition sums P_k for k in [k_lo, k_hi)
  * only (src/msm-batched-affine.ts:42 "P_k = sum_l l * B_(k,l)") and writes them as
  * (k_hi - k_lo) x 144 bytes: X || Y || Z homogeneous projective, 48-byte little-endian canonical
@@ -636,6 +673,17 @@ int msm_test_last_ntt_plan(msm_ctx* ctx, int32_t* stages_out, int cap);
  * level by level.  This entry moves tile_log for the context, so that tests reach plans of three levels at 65 537 elements through
  * the library's own host code.  tile_log: 8 (one element per lane) .. 10 (the default), or 0 to restore the default.  Results do
  * not depend on it.  Refused on a device-list context. */
+/* msm_points_mul runs on a fixed grid of 256-lane blocks with a grid-stride loop over the rows.  This entry sets the number of
+ * blocks for the context (0: the default, as many as stay resident at once and no more than the rows need), so that 321 rows under one block
+ * make every lane take two rows and rebuild its table slots.  Results do not depend on it.  Refused on a device-list context. */
+int msm_test_set_points_mul_grid(msm_ctx* ctx, int32_t blocks);
+/* The path of msm_points_mul_base: 0 = automatic, 1 = always the table, 2 = always the broadcast row through the variable-base
+ * kernel.  Results do not depend on it.  Refused on a device-list context. */
+int msm_test_set_points_mul_base_path(msm_ctx* ctx, int32_t path);
+/* The shape of the last msm_points_mul / msm_points_mul_base of the context, four words: blocks of the grid that wrote the rows
+ * (0: no launch), window bits, path (0 = msm_points_mul, 1 = table, 2 = broadcast) and rows of the fixed-base table used (0:
+ * none).  Writes min(4, cap) of them and returns 4, or -1 for a null or device-list context. */
+int msm_test_last_points_mul(msm_ctx* ctx, int32_t* out, int cap);
 int msm_test_set_scan_tile_log(msm_ctx* ctx, int32_t tile_log);
 /* The tiles per level of the last msm_scalars_scan or msm_scalars_div_linear on this context, bottom level first (the last entry
  * is 1); none (count 0) after a call that was refused or had n == 0: writes min(count, cap) of them to `tiles_out` (may be NULL

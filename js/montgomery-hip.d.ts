@@ -53,6 +53,14 @@ export interface Parallel {
   pointsetSize(pointPtr: PointPtr): number;
   /** in-place fold: P[i] <- a * P[i] + b * P[i + n/2], i < n/2 (n even); the pointer then holds n/2 points */
   foldPoints(pointPtr: PointPtr, a: bigint | number | Uint8Array, b: bigint | number | Uint8Array): PointPtr;
+  /** per-row scalar multiplication (msm_points_mul): dst[i] = s[i] * A[aLo + i], i < count, every row under its own scalar; scalars: a
+   *  scalar pointer (they stay on the device) or count x 32 little-endian bytes, values at or above the group order are reduced;
+   *  dstPtr may be ptrA with aLo = 0 or aLo >= count.  Returns dstPtr */
+  pointsMul(dstPtr: PointPtr, scalars: ScalarPtr | Uint8Array, ptrA: PointPtr, options?: { aLo?: number; sLo?: number; count?: number }): PointPtr;
+  /** the same for one base point (msm_points_mul_base): dst[i] = s[i] * base; base: {x, y}, x || y as wire bytes, or null for the
+   *  curve's generator.  Returns dstPtr */
+  pointsMulBase(dstPtr: PointPtr, scalars: ScalarPtr | Uint8Array, base?: { x: bigint; y: bigint } | Uint8Array | null,
+                options?: { sLo?: number; count?: number }): PointPtr;
   /** resident scalar vectors (msm_scalars_lincomb): dst[i] = x * A[aLo + i] + y * B[bLo + i] mod the group order, i < count, over
    *  scalars that stay on the device; x, y below the group order, y and ptrB null for one term; dstPtr may be a source.  Returns dstPtr */
   scalarsLincomb(dstPtr: ScalarPtr, x: bigint | number | Uint8Array, ptrA: ScalarPtr, y?: bigint | number | Uint8Array | null, ptrB?: ScalarPtr | null,

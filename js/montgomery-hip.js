@@ -204,6 +204,33 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       if (n % 2) throw new RangeError(`foldPoints: the pointer holds ${n} points, an odd number`);
       return Parallel.pointsLincomb(pointPtr, a, pointPtr, b, pointPtr, { aLo: 0, bLo: n / 2, count: n / 2 });
     },
+    // Per-row scalar multiplication (msm_points_mul; the reference has no counterpart): the points behind dstPtr become
+    // dst[i] = s[i] * A[aLo + i], i < count, every row under its own scalar.  scalars: a scalar pointer (the scalars stay on the
+    // device: what scalarsPowers or scalarsInverse wrote) or count x 32 little-endian bytes; values at or above the group order
+    // are reduced.  options: {aLo, sLo, count} (sLo: the first scalar of a scalar pointer; count: default all the scalars from sLo
+    // on).  dstPtr may be ptrA with aLo = 0 or aLo >= count.
+    pointsMul(dstPtr, scalars, ptrA, options) {
+      const o = options || {}, v = scalarVector(scalars, o, "pointsMul");
+      dstPtr.n = hip.pointsMul(ctx, ptrA.set, o.aLo || 0, v.arg, v.off, v.count, dstPtr.set);
+      return dstPtr;
+    },
+    // the same for one base point (msm_points_mul_base): dst[i] = s[i] * base.  base: {x, y} of BigInts, x || y as bytes in the
+    // wire format of pointsFromBytes, or null / undefined for the curve's generator.  options: {sLo, count}
+    pointsMulBase(dstPtr, scalars, base, options) {
+      const o = options || {}, v = scalarVector(scalars, o, "pointsMulBase");
+      let b = null;
+      if (base !== null && base !== undefined) {
+        if (ArrayBuffer.isView(base)) {
+          if (base.byteLength !== 2 * wireBytes) throw new RangeError(`pointsMulBase: the base must be ${2 * wireBytes} bytes (x || y)`);
+          b = Buffer.alloc(pointBytes);
+          for (let i = 0; i < 2; i++) Buffer.from(base.buffer, base.byteOffset, base.byteLength).copy(b, i * coordBytes, i * wireBytes, (i + 1) * wireBytes);
+        } else {
+          b = Buffer.concat([bigintToLeBytes(BigInt(base.x), coordBytes), bigintToLeBytes(BigInt(base.y), coordBytes)]);
+        }
+      }
+      dstPtr.n = hip.pointsMulBase(ctx, b, v.arg, v.off, v.count, dstPtr.set);
+      return dstPtr;
+    },
     // Resident scalar vectors (msm_scalars_*; the reference has no counterpart): arithmetic mod the group order over the scalars
     // behind scalar pointers, which stay on the device.  Host scalars x, y, s: BigInt / number or 32 bytes, below the group order
     // (a larger value throws msm error 6); elements of the vectors may be any 32-byte integers and are taken mod the order.
@@ -347,6 +374,20 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       arr = Uint32Array.from(list);
     }
     return { buf: Buffer.from(arr.buffer, arr.byteOffset, arr.byteLength), m: arr.length };
+  }
+  // the scalar vector of pointsMul / pointsMulBase -> {arg, off, count} of the addon: a scalar pointer or n x 32 bytes
+  function scalarVector(scalars, o, who) {
+    if (ArrayBuffer.isView(scalars)) {
+      if (scalars.byteLength % 32) throw new RangeError(`${who}: ${scalars.byteLength} bytes of scalars are not a multiple of 32`);
+      const n = scalars.byteLength / 32, count = o.count === undefined ? n : o.count;
+      if (count > n) throw new RangeError(`${who}: ${count} rows requested but ${n} scalars given`);
+      return { arg: Buffer.from(scalars.buffer, scalars.byteOffset, scalars.byteLength), off: 0, count };
+    }
+    if (!scalars || typeof scalars !== "object" || !("dev" in scalars)) throw new TypeError(`${who}: scalars must be a scalar pointer or bytes`);
+    const off = o.sLo || 0, count = o.count === undefined ? Math.max(scalars.n - off, 0) : o.count;
+    needScalars(scalars, off + count, who);
+    if (!count) return { arg: Buffer.alloc(0), off: 0, count };
+    return { arg: scalars.dev, off, count };
   }
   function needScalars(ptr, n, who) {
     if (n > ptr.n || (n && !ptr.dev)) throw new Error(`${who}: ${n} scalars requested but the scalar pointer holds ${ptr.dev ? ptr.n : 0}`);

@@ -55,6 +55,8 @@ EXPORTS = (
     "msm_scalars_ntt", "msm_scalars_root_of_unity", "msm_scalars_ntt_max_log2n", "msm_test_set_ntt_tile_log", "msm_test_last_ntt_plan",
     "msm_test_tree_sums",
     "msm_scalars_scan", "msm_scalars_inverse", "msm_scalars_div_linear", "msm_test_set_scan_tile_log", "msm_test_last_scan_plan",
+    "msm_points_mul", "msm_points_mul_base", "msm_test_set_points_mul_grid", "msm_test_set_points_mul_base_path",
+    "msm_test_last_points_mul",
 )
 
 
@@ -249,6 +251,14 @@ def load() -> C.CDLL:
     lib.msm_scalars_div_linear.argtypes = [vp, vp, vp, u64, vp, vp]
     lib.msm_test_set_scan_tile_log.argtypes = [vp, i32]
     lib.msm_test_last_scan_plan.argtypes = [vp, C.POINTER(i32), C.c_int]
+    # per-row scalar multiplication of point sets, with its test surface: new symbols under ABI 8 as well
+    if not hasattr(lib, "msm_points_mul"):
+        raise ImportError(f"{LIB_PATH} predates msm_points_mul: rebuild it (`make`)")
+    lib.msm_points_mul.argtypes = [vp, i32, u64, vp, C.c_int, u64, i32]
+    lib.msm_points_mul_base.argtypes = [vp, vp, vp, C.c_int, u64, i32]
+    lib.msm_test_set_points_mul_grid.argtypes = [vp, i32]
+    lib.msm_test_set_points_mul_base_path.argtypes = [vp, i32]
+    lib.msm_test_last_points_mul.argtypes = [vp, C.POINTER(i32), C.c_int]
     for name in EXPORTS:
         if name not in ("msm_ctx_destroy", "msm_last_error", "msm_abi_version", "msm_abi_struct_bytes"):
             getattr(lib, name).restype = C.c_int

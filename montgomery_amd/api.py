@@ -762,6 +762,65 @@ class MsmContext:
             raise MsmError(_lib.MSM_ERR_ARG, f"fold_points: the set holds {n} points, an odd number")
         return self.points_lincomb(sa, sb, a_lo=0, b_lo=n // 2, count=n // 2)
 
+    # -- per-row scalar multiplication (msm_points_mul, msm_points_mul_base, include/msm_hip.h) ---
+    @staticmethod
+    def _scalar_vector(scalars, count: Optional[int], who: str):
+        """(pointer argument, on_device, count, keep-alive) of a vector of 32-byte scalars: an int is a device address (count is
+        then required), anything else n x 32 host bytes (bytes, bytearray, a ctypes or numpy array), as run() takes them."""
+        if isinstance(scalars, bool) or scalars is None:
+            raise MsmError(_lib.MSM_ERR_ARG, f"{who}: scalars must be bytes, an array or a device address")
+        if count is not None and count < 0:
+            raise MsmError(_lib.MSM_ERR_ARG, f"{who}: count must not be negative")
+        if isinstance(scalars, int):
+            if count is None:
+                raise MsmError(_lib.MSM_ERR_ARG, f"{who}: a device address needs count")
+            return C.c_void_p(scalars), 1, count, None
+        if not isinstance(scalars, (bytes, bytearray, memoryview, C.Array)):
+            scalars = _as_numpy(scalars).tobytes()
+        if len(scalars) % 32:
+            raise MsmError(_lib.MSM_ERR_ARG, f"{who}: scalar buffer length {len(scalars)} is not a multiple of 32")
+        n = len(scalars) // 32
+        if count is None:
+            count = n
+        if count > n:
+            raise MsmError(_lib.MSM_ERR_ARG, f"{who}: count {count} exceeds the {n} scalars given")
+        buf = scalars if isinstance(scalars, C.Array) else (C.c_uint8 * max(len(scalars), 1)).from_buffer_copy(bytes(scalars) or b"\0")
+        return buf, 0, count, buf
+
+    def _points_written(self, idst: int, count: int) -> int:
+        self._set_sizes[idst] = count
+        if idst == self._cur_set:
+            self.n_points = count
+        return count
+
+    def points_mul(self, scalars, *, src: Optional[int] = None, a_lo: int = 0, count: Optional[int] = None,
+                   dst: Optional[int] = None) -> int:
+        """D[i] = s[i] * A[a_lo + i], i < count, as the rows [0, count) of point set `dst` (msm_points_mul): every row under its
+        own scalar.  scalars: n x 32 little-endian bytes (bytes, bytearray, an array) or a device address (16-byte aligned, e.g.
+        what scalars_powers wrote; count is then required); values >= q are reduced.  src, dst: point-set ids, default the
+        current set; count: default the number of host scalars.  dst may be src with a_lo == 0 or a_lo >= count.  Returns count."""
+        if a_lo < 0:
+            raise MsmError(_lib.MSM_ERR_ARG, "points_mul: a_lo must not be negative")
+        ptr, on_device, count, _keep = self._scalar_vector(scalars, count, "points_mul")
+        cur = self._cur_set
+        isrc, idst = cur if src is None else src, cur if dst is None else dst
+        self._check(self._lib.msm_points_mul(self._h, isrc, a_lo, ptr, on_device, count, idst))
+        return self._points_written(idst, count)
+
+    def points_mul_base(self, scalars, base=None, *, count: Optional[int] = None, dst: Optional[int] = None) -> int:
+        """D[i] = s[i] * P, i < count, as the rows [0, count) of point set `dst` (msm_points_mul_base).  base: x || y in the wire
+        format of set_points (bytes), or None for the curve's generator; the all-zero encoding is the identity.  scalars, count,
+        dst: as points_mul.  The context caches the table of the last base.  Returns count."""
+        if base is not None:
+            base = bytes(base)
+            if len(base) != 2 * self.coord_bytes:
+                raise MsmError(_lib.MSM_ERR_ARG, f"points_mul_base: the base must be {2 * self.coord_bytes} bytes (x || y)")
+        ptr, on_device, count, _keep = self._scalar_vector(scalars, count, "points_mul_base")
+        idst = self._cur_set if dst is None else dst
+        bbuf = None if base is None else (C.c_uint8 * len(base)).from_buffer_copy(base)
+        self._check(self._lib.msm_points_mul_base(self._h, bbuf, ptr, on_device, count, idst))
+        return self._points_written(idst, count)
+
     # -- resident scalar-vector operations (msm_scalars_*, include/msm_hip.h) -------------------
     def device_download(self, dev_ptr: int, nbytes: int) -> bytes:
         """`nbytes` bytes of device memory, from a buffer of device_alloc or any device address (msm_device_download)."""

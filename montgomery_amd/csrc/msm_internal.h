@@ -310,6 +310,16 @@ struct msm_ctx {
   int scan_tile_log = 0;           // msm_test_set_scan_tile_log: elements per tile = 2^it; 0 = scan::DEFAULT_TILE_LOG
   std::vector<int32_t> last_scan_plan;  // tiles per level of the last scan / div_linear (msm_test_last_scan_plan); empty after a refusal
 
+  // msm_points_mul / msm_points_mul_base (msm_points_mul.hip): the per-lane tables of the variable-base kernel's grid; the row of
+  // the fixed base and its shared table of rows, cached under the base's bytes.  Freed with the context.
+  msmi::DevBuf pmul_tbl, pmul_row, pmul_base_tbl;
+  uint8_t pmul_base_key[97] = {};   // 1 + x || y of the base the table is of (first byte 2, the rest zero: the generator)
+  bool pmul_base_cached = false;
+  int pmul_blocks_per_cu = 0;       // resident blocks of the variable-base kernel per compute unit (0: not asked yet)
+  int pmul_grid = 0;                // msm_test_set_points_mul_grid: blocks of the variable-base grid; 0 = the default
+  int pmul_base_path = 0;           // msm_test_set_points_mul_base_path: 0 auto, 1 table, 2 broadcast
+  int32_t last_pmul[4] = {};        // grid, w, path, table rows of the last call (msm_test_last_points_mul)
+
   // per-group workspace: two of them, each with its own stream, so that the memory-bound sort of one
   // window group runs under the ALU-bound accumulation of the other
   struct Workspace {

@@ -675,6 +675,28 @@ int msm_test_last_sort_paths(msm_ctx* ctx, int32_t* out, int cap) {
   return count;
 }
 
+int msm_test_set_points_mul_grid(msm_ctx* ctx, int32_t blocks) {
+  if (!ctx) return MSM_ERR_ARG;
+  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "msm_test_set_points_mul_grid: not on a device-list context");
+  if (blocks < 0 || blocks > 65536) return fail(ctx, MSM_ERR_ARG, "msm_test_set_points_mul_grid: blocks must be 0 (default) or 1 .. 65536");
+  ctx->pmul_grid = blocks;
+  return MSM_OK;
+}
+
+int msm_test_set_points_mul_base_path(msm_ctx* ctx, int32_t path) {
+  if (!ctx) return MSM_ERR_ARG;
+  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "msm_test_set_points_mul_base_path: not on a device-list context");
+  if (path < 0 || path > 2) return fail(ctx, MSM_ERR_ARG, "msm_test_set_points_mul_base_path: path must be 0 (auto), 1 (table) or 2 (broadcast)");
+  ctx->pmul_base_path = path;
+  return MSM_OK;
+}
+
+int msm_test_last_points_mul(msm_ctx* ctx, int32_t* out, int cap) {
+  if (!ctx || !ctx->children.empty() || cap < 0 || (cap && !out)) return -1;
+  for (int i = 0; i < 4 && i < cap; i++) out[i] = ctx->last_pmul[i];
+  return 4;
+}
+
 int msm_test_set_ntt_tile_log(msm_ctx* ctx, int32_t tile_log) {
   if (!ctx) return MSM_ERR_ARG;
   if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "msm_test_set_ntt_tile_log: not on a device-list context");

@@ -21,6 +21,10 @@
 //          msmIndexed(h, Buffer scalars of m x 32 bytes, Buffer indices of m x 4 bytes (uint32 LE), c, noGlv) -> as msm:
 //          sum_j scalars[j] * P[indices[j]] (msm_run_indexed); an index >= the resident count throws (msm error 1, the position
 //          in the message), msmIndexedNarrow(h, Buffer scalars, Buffer indices, width, bits, signed, c) (msm_run_indexed_narrow),
+//          pointsMul(h, src, aLo, scalars, sOff, count, dst) -> count: rows [0, count) of point set dst = s[i] * A[aLo + i]
+//          (msm_points_mul); scalars: a Buffer of >= count x 32 host bytes (sOff ignored) or a device buffer whose elements
+//          [sOff, sOff + count) are the scalars; pointsMulBase(h, Buffer base (x || y) | null, scalars, sOff, count, dst) -> count
+//          (msm_points_mul_base; null: the generator),
 //          pointsLincomb(h, srcA, aLo, Buffer a of 32 bytes, srcB (-1: no second term), bLo, Buffer b | null, count, dst) -> count:
 //          rows [0, count) of point set dst = a * A[aLo + i] + b * B[bLo + i] (msm_points_lincomb), pointsetSize(h, id) -> n,
 //          resident scalar vectors (msm_scalars_*): a vector is a device buffer and an offset in elements of 32 bytes --
@@ -904,6 +908,97 @@ static int is_nullish(napi_env env, napi_value v) {
   napi_valuetype t;
   return napi_typeof(env, v, &t) == napi_ok && (t == napi_undefined || t == napi_null);
 }
+// per-row scalar multiplication (msm_points_mul, msm_points_mul_base).  The scalars are host bytes (a Buffer holding at least
+// count x 32 of them) or the elements [sOff, sOff + count) of a device buffer
+static int scalars_arg(napi_env env, js_ctx* h, napi_value v, napi_value v_off, int64_t count, const char* what, const void** out, int* on_device) {
+  bool is_buf = false;
+  if (napi_is_buffer(env, v, &is_buf) == napi_ok && is_buf) {
+    void* p = NULL;
+    size_t len = 0;
+    if (napi_get_buffer_info(env, v, &p, &len) != napi_ok || count < 0 || (uint64_t)count * 32 > len) {
+      char buf[160];
+      snprintf(buf, sizeof buf, "%s: the Buffer holds fewer than count x 32 bytes of scalars", what);
+      napi_throw_range_error(env, NULL, buf);
+      return 0;
+    }
+    *out = p;
+    *on_device = 0;
+    return 1;
+  }
+  uint8_t* d = NULL;
+  if (!vec_arg(env, h, v, v_off, count, what, &d)) return 0;
+  *out = d;
+  *on_device = 1;
+  return 1;
+}
+static napi_value PointsMul(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 7) {
+    napi_throw_type_error(env, NULL, "pointsMul(ctx, src, aLo, scalars, sOff, count, dst)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int32_t src = 0, dst = 0;
+  int64_t a_lo = 0, count = 0;
+  NAPI_OK(napi_get_value_int32(env, argv[1], &src));
+  NAPI_OK(napi_get_value_int64(env, argv[2], &a_lo));
+  NAPI_OK(napi_get_value_int64(env, argv[5], &count));
+  NAPI_OK(napi_get_value_int32(env, argv[6], &dst));
+  if (a_lo < 0 || count < 0) {
+    napi_throw_range_error(env, NULL, "pointsMul: aLo and count must not be negative");
+    return NULL;
+  }
+  const void* sc = NULL;
+  int on_device = 0;
+  if (!scalars_arg(env, h, argv[3], argv[4], count, "pointsMul", &sc, &on_device)) return NULL;
+  int rc = msm_points_mul(h->ctx, src, (uint64_t)a_lo, sc, on_device, (uint64_t)count, dst);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "pointsMul");
+  napi_value out;
+  NAPI_OK(napi_create_int64(env, count, &out));
+  return out;
+}
+static napi_value PointsMulBase(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 6) {
+    napi_throw_type_error(env, NULL, "pointsMulBase(ctx, base, scalars, sOff, count, dst)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int32_t dst = 0;
+  int64_t count = 0;
+  NAPI_OK(napi_get_value_int64(env, argv[4], &count));
+  NAPI_OK(napi_get_value_int32(env, argv[5], &dst));
+  if (count < 0) {
+    napi_throw_range_error(env, NULL, "pointsMulBase: count must not be negative");
+    return NULL;
+  }
+  const uint8_t* base = NULL;
+  if (!is_nullish(env, argv[1])) {
+    bool is_buf = false;
+    void* p = NULL;
+    size_t len = 0;
+    if (napi_is_buffer(env, argv[1], &is_buf) != napi_ok || !is_buf || napi_get_buffer_info(env, argv[1], &p, &len) != napi_ok ||
+        (len != 64 && len != 96)) {
+      napi_throw_type_error(env, NULL, "pointsMulBase: the base is a Buffer of x || y in the curve's wire format, or null");
+      return NULL;
+    }
+    base = (const uint8_t*)p;
+  }
+  const void* sc = NULL;
+  int on_device = 0;
+  if (!scalars_arg(env, h, argv[2], argv[3], count, "pointsMulBase", &sc, &on_device)) return NULL;
+  int rc = msm_points_mul_base(h->ctx, base, sc, on_device, (uint64_t)count, dst);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "pointsMulBase");
+  napi_value out;
+  NAPI_OK(napi_create_int64(env, count, &out));
+  return out;
+}
 static napi_value DeviceDownload(napi_env env, napi_callback_info info) {
   size_t argc = 4;
   napi_value argv[4];
@@ -1295,6 +1390,7 @@ NAPI_MODULE_INIT() {
       {"msmIndexed", MsmIndexed}, {"msmIndexedNarrow", MsmIndexedNarrow},
       {"pointsetCreate", PointsetCreate}, {"pointsetSelect", PointsetSelect}, {"pointsetDestroy", PointsetDestroy},
       {"pointsLincomb", PointsLincomb}, {"pointsetSize", PointsetSize},
+      {"pointsMul", PointsMul}, {"pointsMulBase", PointsMulBase},
       {"deviceDownload", DeviceDownload}, {"scalarsLincomb", ScalarsLincomb}, {"scalarsMul", ScalarsMul},
       {"scalarsInner", ScalarsInner}, {"scalarsPowers", ScalarsPowers},
       {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity}, {"scalarsNttMaxLog2n", ScalarsNttMaxLog2n},
