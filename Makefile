@@ -25,7 +25,7 @@ $(BUILD)/kernels_%.o: $(CSRC)/kernels_curve.hip $(KHDRS)
 	$(HIPCC) $(HIPFLAGS) -DMSM_CURVE_TU=$* -c $(CSRC)/kernels_curve.hip -o $@
 
 # the host pipeline is one translation unit per concern (msm_internal.h lists them); the curve-independent kernels have two of their own
-HHDRS := $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/points_mul.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h $(CSRC)/scalar_scan.h $(CSRC)/msm_internal.h $(CSRC)/sort_kernels.h $(CSRC)/tree_kernels.h $(CSRC)/te_kernels.h $(CSRC)/narrow_kernels.h $(CSRC)/host_field.h include/msm_hip.h
+HHDRS := $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/points_mul.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h $(CSRC)/scalar_scan.h $(CSRC)/scalar_host.h $(CSRC)/msm_internal.h $(CSRC)/operator_checks.h $(CSRC)/sort_kernels.h $(CSRC)/tree_kernels.h $(CSRC)/te_kernels.h $(CSRC)/narrow_kernels.h $(CSRC)/host_field.h include/msm_hip.h
 # msm_points_mul: with the loop-invariant code motion of the machine passes, every constant of the row loop's body (the GLV
 # vectors, q, p, beta) is kept in a scalar register across the whole loop and up to 37 of them go to vector lanes and back
 TUFLAGS_msm_points_mul := -mllvm -disable-machine-licm
@@ -50,21 +50,26 @@ HOSTTEST_SCHEDULE := tests/csrc/libschedule_host.so
 HOSTTEST_NTT := tests/csrc/libntt_host.so
 HOSTTEST_SCANS := tests/csrc/libscans_host.so
 HOSTTEST_PMUL := tests/csrc/libpoints_mul_host.so
+HOSTTEST_SCALAR_HOST := tests/csrc/libscalar_host_host.so
 # (every shim whose source the tests tree holds: a tests tree from before the schedule shim still builds the others)
 hosttest: $(HOSTTEST) $(HOSTTEST_CYCLES) $(HOSTTEST_LINCOMB) $(HOSTTEST_SCALARS) $(if $(wildcard tests/csrc/schedule_host.hip),$(HOSTTEST_SCHEDULE)) \
           $(if $(wildcard tests/csrc/ntt_host.hip),$(HOSTTEST_NTT)) $(if $(wildcard tests/csrc/scans_host.hip),$(HOSTTEST_SCANS)) \
-          $(if $(wildcard tests/csrc/points_mul_host.hip),$(HOSTTEST_PMUL))
+          $(if $(wildcard tests/csrc/points_mul_host.hip),$(HOSTTEST_PMUL)) $(if $(wildcard tests/csrc/scalar_host_host.hip),$(HOSTTEST_SCALAR_HOST))
+# scalar_host.h on all seven scalar fields and the range and row rules of operator_checks.h, whose refusals go through the fail() of
+# msm_plan.hip over a bare context: tests/test_scalar_host.py
+$(HOSTTEST_SCALAR_HOST): tests/csrc/scalar_host_host.hip $(CSRC)/msm_plan.hip $(HHDRS)
+	$(HIPCC) -O2 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/scalar_host_host.hip $(CSRC)/msm_plan.hip -o $(HOSTTEST_SCALAR_HOST)
 # the window-group schedule of msm_plan.hip (group_schedule: no HIP call) over a bare context: tests/test_group_schedule.py
 $(HOSTTEST_SCHEDULE): tests/csrc/schedule_host.hip $(CSRC)/msm_plan.hip $(HHDRS)
 	$(HIPCC) -O2 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/schedule_host.hip $(CSRC)/msm_plan.hip -o $(HOSTTEST_SCHEDULE)
 # the plan, the index functions and the lane bodies of scalar_ntt.h, run lane by lane on the host: tests/test_ntt_host.py
-$(HOSTTEST_NTT): tests/csrc/ntt_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h include/msm_hip.h
+$(HOSTTEST_NTT): tests/csrc/ntt_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h $(CSRC)/scalar_ntt.h include/msm_hip.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/ntt_host.hip -o $(HOSTTEST_NTT)
 # the plan, the combine operators and the inverse lane body of scalar_scan.h on the host: tests/test_scans_host.py
-$(HOSTTEST_SCANS): tests/csrc/scans_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_scan.h include/msm_hip.h
+$(HOSTTEST_SCANS): tests/csrc/scans_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h $(CSRC)/scalar_scan.h include/msm_hip.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/scans_host.hip -o $(HOSTTEST_SCANS)
 # the lane bodies of scalar_vec.h on the scalar fields of all seven curves: tests/test_scalars_host.py
-$(HOSTTEST_SCALARS): tests/csrc/scalars_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h include/msm_hip.h
+$(HOSTTEST_SCALARS): tests/csrc/scalars_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h include/msm_hip.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/scalars_host.hip -o $(HOSTTEST_SCALARS)
 # the recoder and the lane bodies of points_lincomb.h on all seven curves: tests/test_points_lincomb_host.py
 $(HOSTTEST_LINCOMB): tests/csrc/lincomb_host.hip $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/te_kernels.h

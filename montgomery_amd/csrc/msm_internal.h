@@ -21,6 +21,8 @@
 //                     kernels of points_lincomb.h
 //   msm_scalars.hip   msm_scalars_lincomb, _mul, _inner, _powers (vectors of scalars in device memory, mod the group order) and
 //                     msm_device_download, with the kernels of scalar_vec.h
+// The operators over resident vectors and point sets (msm_scalars, msm_ntt, msm_scan, msm_lincomb, msm_points_mul) take their
+// argument checks from operator_checks.h and the host side of the scalar field from scalar_host.h.
 // Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip, te_kernels.hip and narrow_kernels.hip; host TUs see
 // declarations.
 // Orchestration follows `createMsm().msm` (reference src/msm-batched-affine.ts:69-340); the per-thread SPMD phases separated
@@ -391,6 +393,13 @@ inline void for_scalar_field(int curve, Fn&& fn) {
 #undef MSM_DISPATCH_CASE
     default: throw msmi::HipFail{hipErrorInvalidValue, "scalar-field kernel launch for an unknown curve id", __LINE__, __FILE__};
   }
+}
+// the same for a body that may refuse the call: fn(field struct) returns the status, and so does this
+template <class Fn>
+inline int with_scalar_field(const msm_ctx* ctx, Fn&& fn) {
+  int rc = MSM_OK;
+  for_scalar_field(ctx->curve, [&](auto f) { rc = fn(f); });
+  return rc;
 }
 #define W_LAUNCH(ctx, KERNEL, ...) \
   for_weierstrass_curve((ctx)->curve, [&](auto cv_) { hipLaunchKernelGGL((KERNEL<decltype(cv_)>), __VA_ARGS__); })

@@ -2,9 +2,11 @@
 // the one entry point that PRODUCES resident points from resident points (the generator fold of an inner-product argument,
 // scaling, element-wise sums, negation).  The host recodes (a, b) into a program once (points_lincomb.h), copies it to the
 // device and launches one lane per output point; a copy (a = 1, no second term) moves rows without a kernel.
+// The checks of the sets and their rows are those of operator_checks.h, the scalars are read by scalar_host.h.
 // Every check runs before anything is written; msm_pointset_size reports what a set holds.
-#include "msm_internal.h"
+#include "operator_checks.h"
 #include "points_lincomb.h"
+#include "scalar_host.h"
 
 using namespace msm;
 using namespace msmi;
@@ -12,17 +14,6 @@ using namespace msmi;
 namespace {
 
 const char* const WHO = "msm_points_lincomb";
-
-bool live_set(const msm_ctx* ctx, int32_t id) {
-  return id >= 0 && id < (int)ctx->sets.size() && (id == 0 || ctx->sets[id].live);
-}
-
-void scalar_words(uint32_t (&w)[8], const uint8_t* s) {
-  for (int j = 0; j < 8; j++) w[j] = (uint32_t)s[4 * j] | ((uint32_t)s[4 * j + 1] << 8) | ((uint32_t)s[4 * j + 2] << 16) | ((uint32_t)s[4 * j + 3] << 24);
-}
-
-// a source range inside dst: the rows [0, count) themselves (lane i reads and writes row i only) or rows at and above `count`
-bool overlap_ok(uint64_t lo, uint64_t count) { return count == 0 || lo == 0 || lo >= count; }
 
 void make_program(const msm_ctx* ctx, lincomb::Program& P, const uint32_t* a, const uint32_t* b) {
   if (ctx->is_te()) {
@@ -39,7 +30,7 @@ extern "C" {
 int msm_pointset_size(const msm_ctx* ctx, int32_t id, uint64_t* n_out) {
   msm_ctx* c = const_cast<msm_ctx*>(ctx);
   if (!ctx || !n_out) return fail(c, MSM_ERR_ARG, "msm_pointset_size: null argument");
-  if (!live_set(ctx, id)) return fail(c, MSM_ERR_ARG, "msm_pointset_size: no point set %d", (int)id);
+  if (int rc = live_set_ok(c, "msm_pointset_size", id)) return rc;
   *n_out = ctx->sets[id].n;
   return MSM_OK;
 }
@@ -47,34 +38,31 @@ int msm_pointset_size(const msm_ctx* ctx, int32_t id, uint64_t* n_out) {
 int msm_points_lincomb(msm_ctx* ctx, int32_t src_a, uint64_t a_lo, const uint8_t* a, int32_t src_b, uint64_t b_lo, const uint8_t* b,
                        uint64_t count, int32_t dst) {
   if (!ctx || !a || (src_b >= 0 && !b)) return fail(ctx, MSM_ERR_ARG, "%s: null argument", WHO);
-  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "%s: runs on single-device contexts only", WHO);
-  if (count >= (1ull << 30)) return fail(ctx, MSM_ERR_ARG, "%s: count must be < 2^30", WHO);
+  if (int rc = vectors_ok(ctx, WHO, count, {}, "count")) return rc;
   for (int32_t id : {src_a, dst})
-    if (!live_set(ctx, id)) return fail(ctx, MSM_ERR_ARG, "%s: no point set %d", WHO, (int)id);
-  if (src_b >= 0 && !live_set(ctx, src_b)) return fail(ctx, MSM_ERR_ARG, "%s: no point set %d", WHO, (int)src_b);
-  const uint32_t* q = curve_info(ctx->curve).q;
+    if (int rc = live_set_ok(ctx, WHO, id)) return rc;
+  if (src_b >= 0)
+    if (int rc = live_set_ok(ctx, WHO, src_b)) return rc;
   uint32_t aw[8], bw[8] = {0};
-  scalar_words(aw, a);
-  if (src_b >= 0) scalar_words(bw, b);
-  if (!lincomb::words8_less(aw, q) || !lincomb::words8_less(bw, q))
-    return fail(ctx, MSM_ERR_SCALAR, "%s: scalar >= q (scalars of this call are never reduced)", WHO);
-  if (a_lo + count > ctx->sets[src_a].n)
-    return fail(ctx, MSM_ERR_NO_POINTS, "%s: rows [%llu, %llu) of set %d, which holds %llu", WHO, (unsigned long long)a_lo,
-                (unsigned long long)(a_lo + count), (int)src_a, (unsigned long long)ctx->sets[src_a].n);
-  if (src_b >= 0 && b_lo + count > ctx->sets[src_b].n)
-    return fail(ctx, MSM_ERR_NO_POINTS, "%s: rows [%llu, %llu) of set %d, which holds %llu", WHO, (unsigned long long)b_lo,
-                (unsigned long long)(b_lo + count), (int)src_b, (unsigned long long)ctx->sets[src_b].n);
-  if ((src_a == dst && !overlap_ok(a_lo, count)) || (src_b == dst && !overlap_ok(b_lo, count)))
-    return fail(ctx, MSM_ERR_ARG, "%s: a source range inside the destination must be its rows [0, count) or start at or above row count", WHO);
-  // a term under the scalar 0 is no term; the call is then about the other one (0 * A + b * B = b * B)
-  bool has_b = src_b >= 0 && !lincomb::words8_zero(bw);
-  if (has_b && lincomb::words8_zero(aw)) {
-    src_a = src_b;
-    a_lo = b_lo;
-    memcpy(aw, bw, sizeof aw);
-    has_b = false;
-  }
   try {
+    const auto scalars_below_q = [&](auto f) -> int {
+      using S = decltype(f);
+      return scalar_words<S>(aw, a) && (src_b < 0 || scalar_words<S>(bw, b)) ? MSM_OK : scalar_too_big(ctx, WHO, "scalar");
+    };
+    if (int rc = with_scalar_field(ctx, scalars_below_q)) return rc;
+    if (int rc = rows_in_set_ok(ctx, WHO, src_a, a_lo, count)) return rc;
+    if (src_b >= 0)
+      if (int rc = rows_in_set_ok(ctx, WHO, src_b, b_lo, count)) return rc;
+    if (int rc = src_in_dst_ok(ctx, WHO, src_a, dst, a_lo, count)) return rc;
+    if (int rc = src_in_dst_ok(ctx, WHO, src_b, dst, b_lo, count)) return rc;
+    // a term under the scalar 0 is no term; the call is then about the other one (0 * A + b * B = b * B)
+    bool has_b = src_b >= 0 && !lincomb::words8_zero(bw);
+    if (has_b && lincomb::words8_zero(aw)) {
+      src_a = src_b;
+      a_lo = b_lo;
+      memcpy(aw, bw, sizeof aw);
+      has_b = false;
+    }
     HIPCHK(hipSetDevice(ctx->device));
     lincomb::Program P;
     make_program(ctx, P, aw, has_b ? bw : nullptr);

@@ -1,155 +1,17 @@
 // msm_scalars_ntt, msm_scalars_root_of_unity, msm_scalars_ntt_max_log2n: the resident number-theoretic transform over vectors of
-// 32-byte scalars mod the group order q.  The plan, the tile geometry, the lane bodies and the kernel are in scalar_ntt.h; here
-// are the host's field work (roots, orders, shift^-1 and n^-1, once per call), the twiddle cache and the launches, one per pass,
+// 32-byte scalars mod the group order q.  The plan, the tile geometry, the lane bodies and the kernel are in scalar_ntt.h, the
+// host's field arithmetic (roots, orders, inverses, power tables) in scalar_host.h, the argument checks in operator_checks.h; here
+// are what a call computes with them once (omega and its order, shift^-1, n^-1), the twiddle cache and the launches, one per pass,
 // on ctx->stream.  Every check runs before anything is written, and every device buffer a call needs exists before its first
 // launch.  No call touches point sets, window tables or the range-table candidate.
-#include "msm_internal.h"
+#include "operator_checks.h"
+#include "scalar_host.h"
 #include "scalar_ntt.h"
 
 using namespace msm;
 using namespace msmi;
 
 namespace {
-
-// ---------------------------------------------------------------- host field work: Fe<S> in canonical Montgomery form
-
-template <class S>
-void m_mul(Fe<S>& r, const Fe<S>& a, const Fe<S>& b) {
-  fe_mul<S>(r, a, b);
-  fe_reduce_2p<S>(r);
-}
-
-template <class S>
-void m_from_words(Fe<S>& r, const uint32_t (&w)[8]) {   // w < q
-  fe_unpack<S>(r, w);
-  sv::to_mont<S>(r, r);
-}
-
-template <class S>
-void m_to_words(uint32_t (&w)[8], const Fe<S>& a) {
-  Fe<S> one, r;
-  fe_set_zero<S>(one);
-  one.l[0] = 1;
-  m_mul<S>(r, a, one);
-  fe_pack<S>(w, r);
-}
-
-// base^e, e as 8 words
-template <class S>
-void m_pow(Fe<S>& r, const Fe<S>& base, const uint32_t (&e)[8]) {
-  Fe<S> acc;
-  fe_set_one<S>(acc);
-  for (int bit = 255; bit >= 0; bit--) {
-    m_mul<S>(acc, acc, acc);
-    if ((e[bit / 32] >> (bit % 32)) & 1u) m_mul<S>(acc, acc, base);
-  }
-  r = acc;
-}
-
-// out = q - v for a small v, as words
-template <class S>
-void q_minus(uint32_t (&out)[8], uint32_t v) {
-  uint64_t borrow = v;
-  for (int j = 0; j < 8; j++) {
-    const uint64_t d = (uint64_t)S::PW[j] - borrow;
-    out[j] = (uint32_t)d;
-    borrow = (d >> 32) & 1u;
-  }
-}
-
-inline void shift_right(uint32_t (&w)[8], int k) {   // k < 32
-  if (!k) return;
-  for (int j = 0; j < 8; j++) w[j] = (w[j] >> k) | (j + 1 < 8 ? w[j + 1] << (32 - k) : 0u);
-}
-
-template <class S>
-int two_adicity() {
-  uint32_t w[8];
-  q_minus<S>(w, 1);
-  int s = 0;
-  while (!((w[s / 32] >> (s % 32)) & 1u)) s++;
-  return s;
-}
-
-template <class S>
-bool m_is_minus_one(const Fe<S>& a) {
-  uint32_t w[8], m1[8];
-  m_to_words<S>(w, a);
-  q_minus<S>(m1, 1);
-  return memcmp(w, m1, sizeof w) == 0;
-}
-
-// the smallest positive quadratic non-residue: g^((q-1)/2) = -1
-template <class S>
-uint32_t non_residue() {
-  uint32_t half[8];
-  q_minus<S>(half, 1);
-  shift_right(half, 1);
-  for (uint32_t g = 2;; g++) {
-    uint32_t w[8] = {g};
-    Fe<S> gm, r;
-    m_from_words<S>(gm, w);
-    m_pow<S>(r, gm, half);
-    if (m_is_minus_one<S>(r)) return g;
-  }
-}
-
-// g^((q-1) / 2^log2n), log2n <= the two-adicity
-template <class S>
-void library_root(Fe<S>& r, uint32_t log2n) {
-  uint32_t e[8];
-  q_minus<S>(e, 1);
-  for (uint32_t k = log2n; k;) {
-    const int step = k > 31 ? 31 : (int)k;
-    shift_right(e, step);
-    k -= step;
-  }
-  uint32_t w[8] = {non_residue<S>()};
-  Fe<S> gm;
-  m_from_words<S>(gm, w);
-  m_pow<S>(r, gm, e);
-}
-
-template <class S>
-void m_inverse(Fe<S>& r, const Fe<S>& a) {   // a != 0
-  uint32_t e[8];
-  q_minus<S>(e, 2);
-  m_pow<S>(r, a, e);
-}
-
-// 2^-log2n
-template <class S>
-void m_inverse_n(Fe<S>& r, uint32_t log2n) {
-  uint32_t w[8];
-  uint64_t c = 1;   // (q + 1) / 2
-  for (int j = 0; j < 8; j++) {
-    c += S::PW[j];
-    w[j] = (uint32_t)c;
-    c >>= 32;
-  }
-  shift_right(w, 1);
-  Fe<S> half;
-  m_from_words<S>(half, w);
-  fe_set_one<S>(r);
-  for (uint32_t k = 0; k < log2n; k++) m_mul<S>(r, r, half);
-}
-
-// 32 bytes little-endian below q -> words; false: >= q
-template <class S>
-bool scalar_words(uint32_t (&w)[8], const uint8_t* bytes) {
-  for (int j = 0; j < 8; j++)
-    w[j] = (uint32_t)bytes[4 * j] | ((uint32_t)bytes[4 * j + 1] << 8) | ((uint32_t)bytes[4 * j + 2] << 16) | ((uint32_t)bytes[4 * j + 3] << 24);
-  for (int j = 7; j >= 0; j--) {
-    if (w[j] < S::PW[j]) return true;
-    if (w[j] > S::PW[j]) return false;
-  }
-  return false;
-}
-
-void words_to_bytes(uint8_t* out, const uint32_t (&w)[8]) {
-  for (int j = 0; j < 8; j++)
-    for (int b = 0; b < 4; b++) out[4 * j + b] = (uint8_t)(w[j] >> (8 * b));
-}
 
 template <class S>
 uint32_t max_log2n() { return (uint32_t)std::min(two_adicity<S>(), ntt::MAX_LOG2N); }
@@ -158,22 +20,13 @@ uint32_t max_log2n() { return (uint32_t)std::min(two_adicity<S>(), ntt::MAX_LOG2
 
 // dst[i] = the Montgomery form of s x^i, i < count (a power of two): k_sv_powers from s R
 template <class S>
-void launch_powers(msm_ctx* ctx, uint32_t* dst, uint32_t count, const Fe<S>& s_mont, Fe<S> x_mont) {
+void launch_powers(msm_ctx* ctx, uint32_t* dst, uint32_t count, const Fe<S>& s_mont, const Fe<S>& x_mont) {
   const int nbits = (int)ceil_log2_u64(count);
   sv::PowTable<S> pw = {};
-  for (int k = 0; k < nbits; k++) {
-    for (int j = 0; j < S::NL; j++) pw.l[k][j] = x_mont.l[j];
-    m_mul<S>(x_mont, x_mont, x_mont);
-  }
+  fill_pow_table<S>(pw, x_mont, nbits);
   hipLaunchKernelGGL((sv::k_sv_powers<S>), dim3((count + sv::BLOCK - 1) / sv::BLOCK), dim3(sv::BLOCK), 0, ctx->stream, dst, (uint64_t)count,
                      s_mont, pw, nbits);
   HIPCHK(hipGetLastError());
-}
-
-template <class S>
-void m_pow2k(Fe<S>& r, const Fe<S>& a, int k) {   // a^(2^k)
-  r = a;
-  for (int i = 0; i < k; i++) m_mul<S>(r, r, r);
 }
 
 // entries of one direction's twiddle tables, and of a scale table
@@ -223,11 +76,6 @@ void ensure_twiddles(msm_ctx* ctx, int L, const Fe<S>& om, const uint8_t (&key)[
 
 // ---------------------------------------------------------------- the call
 
-bool ranges_ok(const void* dst, const void* src, uint64_t bytes) {
-  const uintptr_t d = (uintptr_t)dst, s = (uintptr_t)src;
-  return d == s || d + bytes <= s || s + bytes <= d;
-}
-
 template <class S>
 int run_ntt(msm_ctx* ctx, const char* who, void* dst, const void* a, uint32_t L, uint32_t B, const uint8_t* omega, const uint8_t* shift,
             bool inverse) {
@@ -241,7 +89,7 @@ int run_ntt(msm_ctx* ctx, const char* who, void* dst, const void* a, uint32_t L,
   if (L >= 1 && !cached) {
     uint32_t w[8];
     if (omega) {
-      if (!scalar_words<S>(w, omega)) return fail(ctx, MSM_ERR_SCALAR, "%s: omega >= q (scalars of this call are never reduced)", who);
+      if (!scalar_words<S>(w, omega)) return scalar_too_big(ctx, who, "omega");
       m_from_words<S>(om, w);
       Fe<S> t;
       m_pow2k<S>(t, om, (int)L - 1);
@@ -256,7 +104,7 @@ int run_ntt(msm_ctx* ctx, const char* who, void* dst, const void* a, uint32_t L,
   int scale = ntt::SCALE_NONE;
   if (shift) {
     uint32_t w[8];
-    if (!scalar_words<S>(w, shift)) return fail(ctx, MSM_ERR_SCALAR, "%s: shift >= q (scalars of this call are never reduced)", who);
+    if (!scalar_words<S>(w, shift)) return scalar_too_big(ctx, who, "shift");
     uint32_t any = 0;
     for (int j = 0; j < 8; j++) any |= w[j];
     if (!any) return fail(ctx, MSM_ERR_ARG, "%s: shift must not be 0 (the inverse transform divides by it)", who);
@@ -334,17 +182,16 @@ int msm_scalars_ntt_max_log2n(const msm_ctx* ctx, uint32_t* out) {
 int msm_scalars_root_of_unity(const msm_ctx* ctx, uint32_t log2n, uint8_t* out) {
   if (!ctx || !out) return MSM_ERR_ARG;
   try {
-    int rc = MSM_OK;
-    for_scalar_field(ctx->curve, [&](auto f) {
+    return with_scalar_field(ctx, [&](auto f) -> int {
       using S = decltype(f);
-      if (log2n > (uint32_t)two_adicity<S>()) { rc = MSM_ERR_ARG; return; }
+      if (log2n > (uint32_t)two_adicity<S>()) return MSM_ERR_ARG;
       Fe<S> r;
       uint32_t w[8];
       library_root<S>(r, log2n);
       m_to_words<S>(w, r);
       words_to_bytes(out, w);
+      return MSM_OK;
     });
-    return rc;
   } catch (...) {
     return MSM_ERR_INTERNAL;
   }
@@ -355,28 +202,16 @@ int msm_scalars_ntt(msm_ctx* ctx, void* dst, const void* a, uint32_t log2n, uint
   const char* const who = "msm_scalars_ntt";
   if (!ctx) return MSM_ERR_ARG;
   ctx->last_ntt_plan.clear();
-  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "%s: runs on single-device contexts only", who);
+  if (int rc = single_device_ok(ctx, who)) return rc;
   try {
-    int rc = MSM_OK;
-    for_scalar_field(ctx->curve, [&](auto f) {
-      using S = decltype(f);
-      const uint32_t cap = max_log2n<S>();
-      if (log2n > cap) {
-        rc = fail(ctx, MSM_ERR_ARG, "%s: log2n = %u, but this scalar field has transforms up to 2^%u only", who, log2n, cap);
-        return;
-      }
-      if (B == 0) { rc = fail(ctx, MSM_ERR_ARG, "%s: B must be at least 1", who); return; }
-      const uint64_t total = (uint64_t)B << log2n;
-      if (total >= (1ull << 30)) { rc = fail(ctx, MSM_ERR_ARG, "%s: B n must be < 2^30", who); return; }
-      if (!dst || !a) { rc = fail(ctx, MSM_ERR_ARG, "%s: null pointer %s", who, dst ? "a" : "dst"); return; }
-      if (((uintptr_t)dst | (uintptr_t)a) & 15) { rc = fail(ctx, MSM_ERR_ARG, "%s: dst and a must be aligned to 16 bytes", who); return; }
-      if (!ranges_ok(dst, a, total * 32)) {
-        rc = fail(ctx, MSM_ERR_ARG, "%s: dst overlaps a in part (it may be a itself or disjoint from it)", who);
-        return;
-      }
-      rc = run_ntt<S>(ctx, who, dst, a, log2n, B, omega, shift, inverse != 0);
-    });
-    return rc;
+    uint32_t cap = 0;
+    for_scalar_field(ctx->curve, [&](auto f) { cap = max_log2n<decltype(f)>(); });
+    if (log2n > cap) return fail(ctx, MSM_ERR_ARG, "%s: log2n = %u, but this scalar field has transforms up to 2^%u only", who, log2n, cap);
+    if (B == 0) return fail(ctx, MSM_ERR_ARG, "%s: B must be at least 1", who);
+    const uint64_t total = (uint64_t)B << log2n;
+    if (int rc = vectors_ok(ctx, who, total, {{dst, "dst"}, {a, "a"}}, "B n", "dst and a")) return rc;
+    if (int rc = dst_ranges_ok(ctx, who, dst, total * 32, {{a, "a"}})) return rc;
+    return with_scalar_field(ctx, [&](auto f) -> int { return run_ntt<decltype(f)>(ctx, who, dst, a, log2n, B, omega, shift, inverse != 0); });
   } MSM_CATCH_ALL(ctx)
 }
 

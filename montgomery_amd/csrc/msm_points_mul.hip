@@ -2,8 +2,9 @@
 // scalars a resident or a host vector (points_mul.h has the algorithm).  The variable-base kernel runs on a fixed grid whose
 // per-lane tables live in ctx->pmul_tbl; the fixed-base call keeps one table of rows per context (ctx->pmul_base_tbl), built by
 // the variable-base kernel over a broadcast base row and cached with the base's bytes.
-// Every check runs before anything is written.
-#include "msm_internal.h"
+// The checks of the context, the count, the sets and their rows are those of operator_checks.h.  Every check runs before anything
+// is written.
+#include "operator_checks.h"
 #include "points_mul.h"
 
 using namespace msm;
@@ -16,12 +17,9 @@ namespace {
 // paths meet below that, where one launch is less than two
 constexpr uint64_t BASE_TABLE_MIN_ROWS = 1ull << 10;
 
-bool live_set(const msm_ctx* ctx, int32_t id) {
-  return id >= 0 && id < (int)ctx->sets.size() && (id == 0 || ctx->sets[id].live);
-}
-
+// what both entries check first; the context is not null
 int scalars_ok(msm_ctx* ctx, const void* scalars, int on_device, uint64_t count, const char* who) {
-  if (count >= (1ull << 30)) return fail(ctx, MSM_ERR_ARG, "%s: count must be < 2^30", who);
+  if (int rc = vectors_ok(ctx, who, count, {}, "count")) return rc;
   if (!scalars && count) return fail(ctx, MSM_ERR_ARG, "%s: null scalars", who);
   if (on_device && count && ((uintptr_t)scalars & 15)) return fail(ctx, MSM_ERR_ARG, "%s: device scalars must be aligned to 16 bytes", who);
   return MSM_OK;
@@ -84,15 +82,11 @@ extern "C" {
 int msm_points_mul(msm_ctx* ctx, int32_t src, uint64_t a_lo, const void* scalars, int on_device, uint64_t count, int32_t dst) {
   const char* const who = "msm_points_mul";
   if (!ctx) return fail(ctx, MSM_ERR_ARG, "%s: null argument", who);
-  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "%s: runs on single-device contexts only", who);
   if (int rc = scalars_ok(ctx, scalars, on_device, count, who)) return rc;
   for (int32_t id : {src, dst})
-    if (!live_set(ctx, id)) return fail(ctx, MSM_ERR_ARG, "%s: no point set %d", who, (int)id);
-  if (a_lo + count > ctx->sets[src].n)
-    return fail(ctx, MSM_ERR_NO_POINTS, "%s: rows [%llu, %llu) of set %d, which holds %llu", who, (unsigned long long)a_lo,
-                (unsigned long long)(a_lo + count), (int)src, (unsigned long long)ctx->sets[src].n);
-  if (src == dst && !(count == 0 || a_lo == 0 || a_lo >= count))
-    return fail(ctx, MSM_ERR_ARG, "%s: a source range inside the destination must be its rows [0, count) or start at or above row count", who);
+    if (int rc = live_set_ok(ctx, who, id)) return rc;
+  if (int rc = rows_in_set_ok(ctx, who, src, a_lo, count)) return rc;
+  if (int rc = src_in_dst_ok(ctx, who, src, dst, a_lo, count)) return rc;
   try {
     HIPCHK(hipSetDevice(ctx->device));
     const uint64_t rw = ctx->row_words();
@@ -116,9 +110,8 @@ int msm_points_mul(msm_ctx* ctx, int32_t src, uint64_t a_lo, const void* scalars
 int msm_points_mul_base(msm_ctx* ctx, const uint8_t* base_xy, const void* scalars, int on_device, uint64_t count, int32_t dst) {
   const char* const who = "msm_points_mul_base";
   if (!ctx) return fail(ctx, MSM_ERR_ARG, "%s: null argument", who);
-  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "%s: runs on single-device contexts only", who);
   if (int rc = scalars_ok(ctx, scalars, on_device, count, who)) return rc;
-  if (!live_set(ctx, dst)) return fail(ctx, MSM_ERR_ARG, "%s: no point set %d", who, (int)dst);
+  if (int rc = live_set_ok(ctx, who, dst)) return rc;
   // the base: checked and made a row on the host
   const size_t wire_bytes = 2 * ctx->coord_bytes();
   uint32_t xy[24] = {0}, row[ROW_WORDS] = {0};

@@ -1,10 +1,11 @@
 // Resident scalar-vector operations: msm_scalars_lincomb, msm_scalars_mul, msm_scalars_inner, msm_scalars_powers over vectors of
 // 32-byte scalars in device memory, mod the group order q of the context's curve, and msm_device_download.  The kernels and their
-// lane bodies are in scalar_vec.h; the host puts the call's scalars into Montgomery form once (the fe_* templates run on the host
-// too) and launches on ctx->stream.  Every check runs before anything is written; every call returns when its result is in place.
-// No call touches point sets, window tables or the range-table candidate.
-#include "msm_internal.h"
-#include "scalar_vec.h"
+// lane bodies are in scalar_vec.h; the host puts the call's scalars into Montgomery form once (scalar_host.h: the fe_* templates run
+// on the host too) and launches on ctx->stream.  The argument checks are those of operator_checks.h.  Every check runs before
+// anything is written; every call returns when its result is in place.  No call touches point sets, window tables or the
+// range-table candidate.
+#include "operator_checks.h"
+#include "scalar_host.h"
 
 using namespace msm;
 using namespace msmi;
@@ -26,55 +27,6 @@ static_assert(modulus_is<FpGrumpkin>(CvBn254::G::Q), "scalar field of BN254");
 static_assert(modulus_is<FpBn254>(CvGrumpkin::G::Q), "scalar field of Grumpkin");
 static_assert(modulus_is<FpPallas>(CvVesta::G::Q), "scalar field of Vesta");
 
-struct Range {
-  const void* p;
-  const char* name;
-  bool optional = false;   // may be null with n > 0 (the b of a one-term lincomb)
-};
-
-// what every vector call checks before it looks at its scalars: the context, n, null and misaligned pointers
-int check_vectors(msm_ctx* ctx, const char* who, uint64_t n, std::initializer_list<Range> vecs) {
-  if (!ctx) return MSM_ERR_ARG;
-  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "%s: runs on single-device contexts only", who);
-  if (n >= (1ull << 30)) return fail(ctx, MSM_ERR_ARG, "%s: n must be < 2^30", who);
-  for (const Range& v : vecs) {
-    if (n && !v.p && !v.optional) return fail(ctx, MSM_ERR_ARG, "%s: null pointer %s", who, v.name);
-    if ((uintptr_t)v.p & 15) return fail(ctx, MSM_ERR_ARG, "%s: %s must be aligned to 16 bytes", who, v.name);
-  }
-  return MSM_OK;
-}
-
-// dst against one source, n elements each: the same range (lane i reads its inputs before its one store) or disjoint ones
-bool dst_overlap_ok(const void* dst, const void* src, uint64_t n) {
-  const uintptr_t d = (uintptr_t)dst, s = (uintptr_t)src, len = (uintptr_t)n * 32;
-  return d == s || d + len <= s || s + len <= d;
-}
-
-int check_dst(msm_ctx* ctx, const char* who, const void* dst, uint64_t n, std::initializer_list<Range> srcs) {
-  for (const Range& v : srcs)
-    if (v.p && !dst_overlap_ok(dst, v.p, n))
-      return fail(ctx, MSM_ERR_ARG, "%s: dst overlaps %s in part (it may be %s itself or disjoint from it)", who, v.name, v.name);
-  return MSM_OK;
-}
-
-// a host scalar of the call: 32 bytes little-endian below q -> registers; false: it is >= q
-template <class S>
-bool host_scalar(Fe<S>& r, const uint8_t* bytes) {
-  uint32_t w[8];
-  for (int j = 0; j < 8; j++)
-    w[j] = (uint32_t)bytes[4 * j] | ((uint32_t)bytes[4 * j + 1] << 8) | ((uint32_t)bytes[4 * j + 2] << 16) | ((uint32_t)bytes[4 * j + 3] << 24);
-  for (int j = 7; j >= 0; j--) {
-    if (w[j] < S::PW[j]) break;
-    if (w[j] > S::PW[j] || j == 0) return false;
-  }
-  fe_unpack<S>(r, w);
-  return true;
-}
-
-int scalar_too_big(msm_ctx* ctx, const char* who, const char* name) {
-  return fail(ctx, MSM_ERR_SCALAR, "%s: %s >= q (scalars of this call are never reduced)", who, name);
-}
-
 dim3 lane_grid(uint64_t n) { return dim3((uint32_t)((n + sv::BLOCK - 1) / sv::BLOCK)); }
 
 }  // namespace
@@ -95,20 +47,17 @@ int msm_device_download(msm_ctx* ctx, void* host, const void* dev_ptr, uint64_t 
 
 int msm_scalars_lincomb(msm_ctx* ctx, void* dst, const uint8_t* x, const void* a, const uint8_t* y, const void* b, uint64_t n) {
   const char* const who = "msm_scalars_lincomb";
-  if (int rc = check_vectors(ctx, who, n, {{dst, "dst"}, {a, "a"}, {b, "b", true}})) return rc;
+  if (int rc = vectors_ok(ctx, who, n, {{dst, "dst"}, {a, "a"}, {b, "b", true}})) return rc;
   if (!x || (b && !y)) return fail(ctx, MSM_ERR_ARG, "%s: null scalar", who);
-  if (int rc = check_dst(ctx, who, dst, n, {{a, "a"}, {b, "b"}})) return rc;
+  if (int rc = dst_ranges_ok(ctx, who, dst, n * 32, {{a, "a"}, {b, "b"}})) return rc;
   try {
-    int rc = MSM_OK;
-    for_scalar_field(ctx->curve, [&](auto f) {
+    return with_scalar_field(ctx, [&](auto f) -> int {
       using S = decltype(f);
       Fe<S> xm, ym;
       fe_set_zero<S>(ym);
-      if (!host_scalar<S>(xm, x)) { rc = scalar_too_big(ctx, who, "x"); return; }
-      if (b && !host_scalar<S>(ym, y)) { rc = scalar_too_big(ctx, who, "y"); return; }
-      if (!n) return;
-      sv::to_mont<S>(xm, xm);
-      sv::to_mont<S>(ym, ym);
+      if (!host_scalar_mont<S>(xm, x)) return scalar_too_big(ctx, who, "x");
+      if (b && !host_scalar_mont<S>(ym, y)) return scalar_too_big(ctx, who, "y");
+      if (!n) return MSM_OK;
       HIPCHK(hipSetDevice(ctx->device));
       const uint32_t *pa = (const uint32_t*)a, *pb = (const uint32_t*)(b ? b : a);
       if (b)
@@ -117,15 +66,15 @@ int msm_scalars_lincomb(msm_ctx* ctx, void* dst, const uint8_t* x, const void* a
         hipLaunchKernelGGL((sv::k_sv_lincomb<S, false>), lane_grid(n), dim3(sv::BLOCK), 0, ctx->stream, (uint32_t*)dst, pa, pb, n, xm, ym);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(ctx->stream));
+      return MSM_OK;
     });
-    return rc;
   } MSM_CATCH_ALL(ctx)
 }
 
 int msm_scalars_mul(msm_ctx* ctx, void* dst, const void* a, const void* b, uint64_t n) {
   const char* const who = "msm_scalars_mul";
-  if (int rc = check_vectors(ctx, who, n, {{dst, "dst"}, {a, "a"}, {b, "b"}})) return rc;
-  if (int rc = check_dst(ctx, who, dst, n, {{a, "a"}, {b, "b"}})) return rc;
+  if (int rc = vectors_ok(ctx, who, n, {{dst, "dst"}, {a, "a"}, {b, "b"}})) return rc;
+  if (int rc = dst_ranges_ok(ctx, who, dst, n * 32, {{a, "a"}, {b, "b"}})) return rc;
   if (!n) return MSM_OK;
   try {
     HIPCHK(hipSetDevice(ctx->device));
@@ -142,7 +91,7 @@ int msm_scalars_mul(msm_ctx* ctx, void* dst, const void* a, const void* b, uint6
 
 int msm_scalars_inner(msm_ctx* ctx, const void* a, const void* b, uint64_t n, uint8_t* out) {
   const char* const who = "msm_scalars_inner";
-  if (int rc = check_vectors(ctx, who, n, {{a, "a"}, {b, "b"}})) return rc;
+  if (int rc = vectors_ok(ctx, who, n, {{a, "a"}, {b, "b"}})) return rc;
   if (!out) return fail(ctx, MSM_ERR_ARG, "%s: null pointer out", who);
   if (!n) {
     memset(out, 0, 32);
@@ -171,31 +120,25 @@ int msm_scalars_inner(msm_ctx* ctx, const void* a, const void* b, uint64_t n, ui
 
 int msm_scalars_powers(msm_ctx* ctx, void* dst, const uint8_t* s, const uint8_t* x, uint64_t n) {
   const char* const who = "msm_scalars_powers";
-  if (int rc = check_vectors(ctx, who, n, {{dst, "dst"}})) return rc;
+  if (int rc = vectors_ok(ctx, who, n, {{dst, "dst"}})) return rc;
   if (!s || !x) return fail(ctx, MSM_ERR_ARG, "%s: null scalar", who);
   try {
-    int rc = MSM_OK;
-    for_scalar_field(ctx->curve, [&](auto f) {
+    return with_scalar_field(ctx, [&](auto f) -> int {
       using S = decltype(f);
       Fe<S> sp, xm;
-      if (!host_scalar<S>(sp, s)) { rc = scalar_too_big(ctx, who, "s"); return; }
-      if (!host_scalar<S>(xm, x)) { rc = scalar_too_big(ctx, who, "x"); return; }
-      if (!n) return;
+      if (!host_scalar<S>(sp, s)) return scalar_too_big(ctx, who, "s");
+      if (!host_scalar_mont<S>(xm, x)) return scalar_too_big(ctx, who, "x");
+      if (!n) return MSM_OK;
       // x^(2^k) in Montgomery form for every bit an index below n can have
       const int nbits = (int)ceil_log2_u64(n);
       sv::PowTable<S> pw = {};
-      sv::to_mont<S>(xm, xm);
-      for (int k = 0; k < nbits; k++) {
-        for (int j = 0; j < S::NL; j++) pw.l[k][j] = xm.l[j];
-        fe_sqr<S>(xm, xm);
-        fe_reduce_2p<S>(xm);
-      }
+      fill_pow_table<S>(pw, xm, nbits);
       HIPCHK(hipSetDevice(ctx->device));
       hipLaunchKernelGGL((sv::k_sv_powers<S>), lane_grid(n), dim3(sv::BLOCK), 0, ctx->stream, (uint32_t*)dst, n, sp, pw, nbits);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(ctx->stream));
+      return MSM_OK;
     });
-    return rc;
   } MSM_CATCH_ALL(ctx)
 }
 

@@ -1,10 +1,12 @@
 // msm_scalars_scan, msm_scalars_inverse, msm_scalars_div_linear: prefix sums and products, the batch inverse and the division by
 // X - z over vectors of 32-byte scalars in device memory, mod the group order q of the context's curve; and the two entries of the
-// debug surface that move the tile and report the plan.  The plan, the lane bodies and the kernels are in scalar_scan.h; here are
-// the checks, the call's scalars (the fe_* templates run on the host too), the aggregate buffer and the launches, one per step, on
-// ctx->stream.  Every check runs before anything is written, and the aggregate buffer exists before the first launch.  Every call
-// returns when its result is in place.  No call touches point sets, window tables or the range-table candidate.
-#include "msm_internal.h"
+// debug surface that move the tile and report the plan.  The plan, the lane bodies and the kernels are in scalar_scan.h, the
+// argument checks in operator_checks.h, the reading of the call's scalars and the table of z's powers in scalar_host.h; here are
+// the order of the checks, the aggregate buffer and the launches, one per step, on ctx->stream.  Every check runs before
+// anything is written, and the aggregate buffer exists before the first launch.  Every call returns when its result is in place.
+// No call touches point sets, window tables or the range-table candidate.
+#include "operator_checks.h"
+#include "scalar_host.h"
 #include "scalar_scan.h"
 
 using namespace msm;
@@ -12,34 +14,10 @@ using namespace msmi;
 
 namespace {
 
-// what every call checks before it looks at its scalars; the context is not null
+// what every call checks before it looks at its scalars
 int check_call(msm_ctx* ctx, const char* who, void* dst, const void* a, uint64_t n) {
-  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "%s: runs on single-device contexts only", who);
-  if (n >= (1ull << 30)) return fail(ctx, MSM_ERR_ARG, "%s: n must be < 2^30", who);
-  if (n && (!dst || !a)) return fail(ctx, MSM_ERR_ARG, "%s: null pointer %s", who, dst ? "a" : "dst");
-  if (((uintptr_t)dst | (uintptr_t)a) & 15) return fail(ctx, MSM_ERR_ARG, "%s: dst and a must be aligned to 16 bytes", who);
-  const uintptr_t d = (uintptr_t)dst, s = (uintptr_t)a, len = (uintptr_t)n * 32;
-  if (!(d == s || d + len <= s || s + len <= d))
-    return fail(ctx, MSM_ERR_ARG, "%s: dst overlaps a in part (it may be a itself or disjoint from it)", who);
-  return MSM_OK;
-}
-
-// a host scalar of the call: 32 bytes little-endian below q -> registers; false: it is >= q
-template <class S>
-bool host_scalar(Fe<S>& r, const uint8_t* bytes) {
-  uint32_t w[8];
-  for (int j = 0; j < 8; j++)
-    w[j] = (uint32_t)bytes[4 * j] | ((uint32_t)bytes[4 * j + 1] << 8) | ((uint32_t)bytes[4 * j + 2] << 16) | ((uint32_t)bytes[4 * j + 3] << 24);
-  for (int j = 7; j >= 0; j--) {
-    if (w[j] < S::PW[j]) break;
-    if (w[j] > S::PW[j] || j == 0) return false;
-  }
-  fe_unpack<S>(r, w);
-  return true;
-}
-
-int scalar_too_big(msm_ctx* ctx, const char* who, const char* name) {
-  return fail(ctx, MSM_ERR_SCALAR, "%s: %s >= q (scalars of this call are never reduced)", who, name);
+  if (int rc = vectors_ok(ctx, who, n, {{dst, "dst"}, {a, "a"}}, "n", "dst and a")) return rc;
+  return dst_ranges_ok(ctx, who, dst, n * 32, {{a, "a"}});
 }
 
 int tile_log_of(const msm_ctx* ctx) { return ctx->scan_tile_log ? ctx->scan_tile_log : scan::DEFAULT_TILE_LOG; }
@@ -100,15 +78,14 @@ int msm_scalars_scan(msm_ctx* ctx, void* dst, const void* a, uint64_t n, int op,
   if (op != MSM_SCAN_SUM && op != MSM_SCAN_PRODUCT) return fail(ctx, MSM_ERR_ARG, "%s: op must be MSM_SCAN_SUM or MSM_SCAN_PRODUCT", who);
   if (flags & ~(uint32_t)MSM_SCAN_EXCLUSIVE) return fail(ctx, MSM_ERR_ARG, "%s: unknown flag bits 0x%x", who, flags & ~(uint32_t)MSM_SCAN_EXCLUSIVE);
   try {
-    int rc = MSM_OK;
-    for_scalar_field(ctx->curve, [&](auto f) {
+    return with_scalar_field(ctx, [&](auto f) -> int {
       using S = decltype(f);
       Fe<S> start;
       uint8_t neutral[32] = {(uint8_t)(op == MSM_SCAN_PRODUCT ? 1 : 0)};
-      if (!host_scalar<S>(start, init ? init : neutral)) { rc = scalar_too_big(ctx, who, "init"); return; }
+      if (!host_scalar<S>(start, init ? init : neutral)) return scalar_too_big(ctx, who, "init");
       if (!n) {
         if (total_out) memcpy(total_out, init ? init : neutral, 32);
-        return;
+        return MSM_OK;
       }
       const uint32_t level0 = (flags & MSM_SCAN_EXCLUSIVE) ? (uint32_t)scan::LV_EXCLUSIVE : 0u;
       const scan::PowTab<S> pw = {};
@@ -118,8 +95,8 @@ int msm_scalars_scan(msm_ctx* ctx, void* dst, const void* a, uint64_t n, int op,
       } else {
         run_scan<S, scan::OP_SUM>(ctx, dst, a, n, level0, start, pw, total_out);
       }
+      return MSM_OK;
     });
-    return rc;
   } MSM_CATCH_ALL(ctx)
 }
 
@@ -130,27 +107,21 @@ int msm_scalars_div_linear(msm_ctx* ctx, void* dst, const void* a, uint64_t n, c
   if (int rc = check_call(ctx, who, dst, a, n)) return rc;
   if (!z) return fail(ctx, MSM_ERR_ARG, "%s: null scalar z", who);
   try {
-    int rc = MSM_OK;
-    for_scalar_field(ctx->curve, [&](auto f) {
+    return with_scalar_field(ctx, [&](auto f) -> int {
       using S = decltype(f);
       Fe<S> zm, start;
-      if (!host_scalar<S>(zm, z)) { rc = scalar_too_big(ctx, who, "z"); return; }
+      if (!host_scalar_mont<S>(zm, z)) return scalar_too_big(ctx, who, "z");
       if (!n) {
         if (rem_out) memset(rem_out, 0, 32);
-        return;
+        return MSM_OK;
       }
       // z^(2^k) in Montgomery form for every segment length of every level
       scan::PowTab<S> pw = {};
-      sv::to_mont<S>(zm, zm);
-      for (int k = 0; k < scan::POW_BITS; k++) {
-        for (int j = 0; j < S::NL; j++) pw.l[k][j] = zm.l[j];
-        fe_sqr<S>(zm, zm);
-        fe_reduce_2p<S>(zm);
-      }
+      fill_pow_table<S>(pw, zm, scan::POW_BITS);
       fe_set_zero<S>(start);
       run_scan<S, scan::OP_HORNER>(ctx, dst, a, n, scan::LV_REVERSE | scan::LV_EXCLUSIVE, start, pw, rem_out);
+      return MSM_OK;
     });
-    return rc;
   } MSM_CATCH_ALL(ctx)
 }
 

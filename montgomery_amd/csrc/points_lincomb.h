@@ -54,11 +54,6 @@ inline bool words8_is(const uint32_t* s, uint32_t v) {
   for (int j = 1; j < 8; j++) o |= s[j];
   return o == 0;
 }
-inline bool words8_less(const uint32_t* a, const uint32_t* b) {   // a < b
-  for (int j = 7; j >= 0; j--)
-    if (a[j] != b[j]) return a[j] < b[j];
-  return false;
-}
 // s == q - 1 (q odd)
 inline bool words8_is_q_minus_1(const uint32_t* s, const uint32_t* q) {
   uint32_t o = s[0] ^ (q[0] - 1u);

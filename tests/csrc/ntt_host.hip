@@ -1,27 +1,18 @@
 // Host-side unit-test shim of the resident NTT: the plan, the pass geometry, the index and exponent functions and the lane bodies of
 // montgomery_amd/csrc/scalar_ntt.h compiled for the CPU (tests/test_ntt_host.py).  The executor runs a whole transform as the
 // kernels do -- per pass, per block, the load phase for every lane, each stage for every lane, the store phase for every lane,
-// on a tile image of the LDS -- with tables filled on the host by plain multiplications.  No GPU work.
+// on a tile image of the LDS -- with tables filled on the host by plain multiplications (the field helpers are those of
+// scalar_host.h).  No GPU work.
 #include "scalar_ntt.h"
+#include "scalar_host.h"
 #include <cstring>
 #include <vector>
 using namespace msm;
+using namespace msmi;
 
 namespace {
 
-template <class S>
-void host_mont(Fe<S>& r, const uint32_t* w_in) {   // canonical host scalar -> Montgomery form
-  uint32_t w[8];
-  memcpy(w, w_in, sizeof w);
-  fe_unpack<S>(r, w);
-  sv::to_mont<S>(r, r);
-}
-
-template <class S>
-void mmul(Fe<S>& r, const Fe<S>& a, const Fe<S>& b) {
-  fe_mul<S>(r, a, b);
-  fe_reduce_2p<S>(r);
-}
+using Words8 = const uint32_t[8];   // a canonical host scalar as it crosses the C boundary
 
 // out[8 i ..] = s x^i in Montgomery form (s, x Montgomery), i < count, 16-byte aligned storage
 template <class S>
@@ -30,14 +21,8 @@ void fill_powers(std::vector<uint4>& store, uint32_t count, Fe<S> s, const Fe<S>
   uint32_t* out = (uint32_t*)store.data();
   for (uint32_t i = 0; i < count; i++) {
     fe_store<S>(out + 8 * (size_t)i, s);
-    mmul<S>(s, s, x);
+    m_mul<S>(s, s, x);
   }
-}
-
-template <class S>
-void pow2k(Fe<S>& r, const Fe<S>& a, int k) {
-  r = a;
-  for (int i = 0; i < k; i++) mmul<S>(r, r, r);
 }
 
 // reduce_raw on both operands (the first load of a transform), then the butterfly; results below 2 q, as raw words
@@ -52,7 +37,7 @@ void butterfly(const uint32_t* u, const uint32_t* v, const uint32_t* w, int with
   ntt::reduce_raw<S>(fu);
   ntt::reduce_raw<S>(fv);
   if (with_w) {
-    host_mont<S>(fw, w);
+    m_from_words<S>(fw, *(Words8*)w);
     ntt::butterfly<S>(fu, fv, &fw);
   } else {
     ntt::butterfly<S>(fu, fv, nullptr);
@@ -71,19 +56,19 @@ void exec(int log2n, uint32_t B, int tile_log, const uint32_t* w, int scale, con
   const int L = log2n, h = ntt::table_low_bits(L), g = L < ntt::LDS_LOG ? L : ntt::LDS_LOG;
   Fe<S> one, wm, t, sm, xm;
   fe_set_one<S>(one);
-  host_mont<S>(wm, w);
+  m_from_words<S>(wm, *(Words8*)w);
   std::vector<uint4> wa, wb, gt, sa, sb;
   fill_powers<S>(wa, 1u << h, one, wm);
-  pow2k<S>(t, wm, h);
+  m_pow2k<S>(t, wm, h);
   fill_powers<S>(wb, 1u << (L - h), one, t);
-  pow2k<S>(t, wm, L - g);
+  m_pow2k<S>(t, wm, L - g);
   fill_powers<S>(gt, g ? 1u << (g - 1) : 1u, one, t);
   fe_set_zero<S>(sm);
-  if (scale != ntt::SCALE_NONE) host_mont<S>(sm, s);
+  if (scale != ntt::SCALE_NONE) m_from_words<S>(sm, *(Words8*)s);
   if (scale == ntt::SCALE_TABLE) {
-    host_mont<S>(xm, x);
+    m_from_words<S>(xm, *(Words8*)x);
     fill_powers<S>(sa, 1u << h, sm, xm);
-    pow2k<S>(t, xm, h);
+    m_pow2k<S>(t, xm, h);
     fill_powers<S>(sb, 1u << (L - h), one, t);
   }
   ntt::Tables tb = {(const uint32_t*)wa.data(), (const uint32_t*)wb.data(), (const uint32_t*)gt.data(),

@@ -2,27 +2,23 @@
 // for the CPU, over the scalar field MSM_SCALAR_FIELDS gives every curve (tests/test_scalars_host.py).  Elements cross as 8 words,
 // plain little-endian integers below 2^256, as the kernels read them from device memory.
 #include "scalar_vec.h"
+#include "scalar_host.h"
 #include <cstring>
 using namespace msm;
+using namespace msmi;
 
 namespace {
 
-template <class S>
-void host_mont(Fe<S>& r, const uint32_t* w_in) {   // canonical host scalar -> Montgomery form (what msm_scalars.hip does once per call)
-  uint32_t w[8];
-  memcpy(w, w_in, sizeof w);
-  fe_unpack<S>(r, w);
-  sv::to_mont<S>(r, r);
-}
+using Words8 = const uint32_t[8];   // a canonical host scalar as it crosses the C boundary (-> Montgomery form once per call)
 
 template <class S>
 void lincomb(const uint32_t* x, const uint32_t* a, const uint32_t* y, const uint32_t* b, uint32_t* out) {
   alignas(16) uint32_t va[8], vb[8], vo[8];
   Fe<S> xm, ym;
-  host_mont<S>(xm, x);
+  m_from_words<S>(xm, *(Words8*)x);
   memcpy(va, a, sizeof va);
   if (b) {
-    host_mont<S>(ym, y);
+    m_from_words<S>(ym, *(Words8*)y);
     memcpy(vb, b, sizeof vb);
     sv::lincomb_lane<S, true>(vo, va, vb, xm, ym);
   } else {
@@ -48,13 +44,9 @@ void powers(const uint32_t* s, const uint32_t* x, const uint32_t* idx, int n_idx
   memcpy(w, s, sizeof w);
   Fe<S> sp, xm;
   fe_unpack<S>(sp, w);
-  host_mont<S>(xm, x);
+  m_from_words<S>(xm, *(Words8*)x);
   static sv::PowTable<S> pw;
-  for (int k = 0; k < sv::MAX_POW_BITS; k++) {
-    for (int j = 0; j < S::NL; j++) pw.l[k][j] = xm.l[j];
-    fe_sqr<S>(xm, xm);
-    fe_reduce_2p<S>(xm);
-  }
+  fill_pow_table<S>(pw, xm, sv::MAX_POW_BITS);
   for (int t = 0; t < n_idx; t++) {
     Fe<S> r;
     sv::powers_lane<S>(r, sp, pw, idx[t], sv::MAX_POW_BITS);

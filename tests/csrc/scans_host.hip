@@ -2,9 +2,11 @@
 // of the batch inverse of montgomery_amd/csrc/scalar_scan.h compiled for the CPU (tests/test_scans_host.py), and the tile constants,
 // so that the GPU tests take their sizes from the library.  No GPU work.
 #include "scalar_scan.h"
+#include "scalar_host.h"
 #include <cstring>
 #include <vector>
 using namespace msm;
+using namespace msmi;
 
 namespace {
 
@@ -23,11 +25,7 @@ void combine_one(const uint32_t* a, const uint32_t* b, const uint32_t* z, int k,
   scan::PowTab<S> pw = {};
   fe_load<S>(zm, wz);
   sv::to_mont<S>(zm, zm);
-  for (int i = 0; i < scan::POW_BITS; i++) {
-    for (int j = 0; j < S::NL; j++) pw.l[i][j] = zm.l[j];
-    fe_sqr<S>(zm, zm);
-    fe_reduce_2p<S>(zm);
-  }
+  fill_pow_table<S>(pw, zm, scan::POW_BITS);
   scan::combine<S, OP>(r, fa, fb, pw, k);
   scan::leave<S, OP>(r);
   fe_store<S>(wo, r);
