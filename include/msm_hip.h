@@ -364,6 +364,56 @@ int msm_scalars_inverse(msm_ctx* ctx, void* dst, const void* a, uint64_t n, uint
  * n == 1: dst[0] = 0, rem = a[0] mod q */
 int msm_scalars_div_linear(msm_ctx* ctx, void* dst, const void* a, uint64_t n, const uint8_t* z, uint8_t* rem_out);
 
+/* Resident sumcheck over the same vectors: the scalar work of the provers on the curve cycles (Nova / Spartan, HyperPlonk, Jolt,
+ * GKR) is not the NTT but the sumcheck over multilinear tables.  Three operators run a whole sumcheck with d + 1 scalars leaving
+ * the device per round and one challenge entering it: the round polynomial of a product of tables, the binding of one variable
+ * to the challenge, and the table eq(r, .) that every multilinear evaluation f(r) = <eq(r), f> and every Spartan-style round
+ * needs; an msm_run over a bound or eq-weighted vector needs no extra step.  A binding detects the feature by the presence of
+ * msm_scalars_sumcheck_round.  The reference has no counterpart.  All seven curves.
+ * Tables: a vector of n = 2^log2n elements is a multilinear table, log2n = 1 .. 29.  VARIABLE j IS BIT j OF THE INDEX: variable 0
+ *   is the least significant bit, which is arkworks' and HyperPlonk's order.  A caller with the most-significant-first convention
+ *   (Spartan) reverses its point.  For a variable var < log2n, h = n / 2 and a pair index i < h the two rows of pair i are
+ *     lo(i) = ((i >> var) << (var + 1)) | (i & (2^var - 1))      hi(i) = lo(i) + 2^var
+ *   so var = log2n - 1 pairs row i with row i + h (the halves of the table), and var = 0 pairs neighbours.
+ * Vectors: everything msm_scalars_* says above holds -- plain 32-byte little-endian integers, any value below 2^256 counts as
+ *   its residue, every element written is canonical, 16-byte alignment at any 32-byte offset inside an allocation.
+ * Host scalars: r and s are 32 bytes little-endian each; a value >= q fails with MSM_ERR_SCALAR.  0 and 1 are ordinary input.
+ * Errors: log2n outside 1 .. 29 (v above 29), var >= log2n, m out of range, an unknown shape, null or misaligned pointers -- a
+ *   null entry of a pointer array included --, a device-list context: MSM_ERR_ARG.  All checks run before anything is written; a
+ *   failed call leaves its outputs and the context as they were.
+ * Ordering: every call returns when its result is in place (it synchronises the context's stream) and touches no point set,
+ *   window table or range-table candidate.
+ * msm_scalars_sumcheck_round returns the same bits whatever the launch geometry: field addition is exact.
+ * Device memory beyond the caller's vectors, owned by the context and freed with it:
+ *   round partials  32 bytes per block and value and the d + 1 results: at most 32 * 5 * 1025 bytes
+ *   eq half-tables  32 (2^ceil(v / 2) + 2^floor(v / 2)) bytes (1.5 MiB at v = 29), rebuilt by every msm_scalars_eq */
+enum { MSM_SUMCHECK_PROD = 0, MSM_SUMCHECK_R1CS = 1 };
+/* The round polynomial s of the sum over all pairs, at t = 0 .. d:
+ *   evals_out[t] = sum_{i<h} g(f_0(i,t), .., f_(m-1)(i,t)),    f_j(i,t) = a_j[lo(i)] + t (a_j[hi(i)] - a_j[lo(i)])
+ * a_j = vecs[j], m device vectors of n elements; evals_out: (d + 1) x 32 bytes little-endian on the host.
+ *   MSM_SUMCHECK_PROD   g = prod_j f_j, 1 <= m <= 4, d = m.  m = 1 is the plain sum.
+ *   MSM_SUMCHECK_R1CS   g = f_0 (f_1 f_2 - f_3), m = 4 exactly, d = 3: the outer sumcheck of Spartan / Nova, f_0 = eq(tau, .)
+ * All d + 1 values come back, s(1) included: s(0) + s(1) is the claim of the round, which a prover asserts.
+ * The vectors are only read; the same pointer may appear several times and vectors may overlap freely.
+ * A general sum of products sum_c c prod_j f_(c,j) is deliberately not a shape: the round polynomial is linear in g, so a caller
+ * runs one call per product and combines the d + 1 scalars of each on the host. */
+int msm_scalars_sumcheck_round(msm_ctx* ctx, const void* const* vecs, uint32_t m, uint32_t log2n, uint32_t var, int shape,
+                               uint8_t* evals_out /* (d+1) x 32 B LE, host */);
+/* Binds variable var of m tables (1 <= m <= 8) to r in one launch, one multiplication per output:
+ *   dst[j][i] = a[j][lo(i)] + r (a[j][hi(i)] - a[j][lo(i)]),  i < h: a table of log2n - 1 variables, the variables above var
+ *   moving down by one.
+ * Aliasing: every dst range (h x 32 bytes) is disjoint from every other dst range and from every source range (n x 32 bytes),
+ *   with one exception: dst[j] == a[j] exactly when var == log2n - 1 -- lane i then reads rows i and i + h and writes row i, and
+ *   the upper half is left as it was.  Anything else is MSM_ERR_ARG before a launch.  Sources may overlap each other. */
+int msm_scalars_bind(msm_ctx* ctx, void* const* dst, const void* const* a, uint32_t m, uint32_t log2n, uint32_t var,
+                     const uint8_t* r /* 32 B LE, < q */);
+/* dst[i] = s prod_{j<v} (bit_j(i) ? r_j : 1 - r_j), i < 2^v: the table eq(r, .) scaled by s.  0 <= v <= 29; v = 0 writes
+ * dst[0] = s.  r: v x 32 bytes little-endian on the host (may be NULL with v = 0); s: 32 bytes, NULL = 1.
+ * Built from two half-tables, eq(r, i) = T_hi[i >> k] T_lo[i & (2^k - 1)] with k = ceil(v / 2): one multiplication and one store
+ * per element. */
+int msm_scalars_eq(msm_ctx* ctx, void* dst, const uint8_t* r /* v x 32 B LE, host */, uint32_t v,
+                   const uint8_t* s /* 32 B LE, NULL = 1 */);
+
 /* Device memory the working buffers of one call may take (digits, sort records, tree nodes: the reference sizes them per call
  * in wasm memory, src/msm-batched-affine.ts:96-130).  0 = automatic: 85 % of what the device has free when a big call starts.
  * Windows run in as many groups as fit, and a window whose buffers would not fit at all runs over ranges of the points, one
@@ -689,6 +739,16 @@ int msm_test_set_scan_tile_log(msm_ctx* ctx, int32_t tile_log);
  * is 1); none (count 0) after a call that was refused or had n == 0: writes min(count, cap) of them to `tiles_out` (may be NULL
  * with cap = 0) and returns the count, or -1 for a null or device-list context. */
 int msm_test_last_scan_plan(msm_ctx* ctx, int32_t* tiles_out, int cap);
+/* msm_scalars_sumcheck_round runs on a grid of 256-lane blocks with a grid-stride loop over the pairs, one partial per block and
+ * value.  This entry sets the number of blocks for the context (1 .. 1024, or 0: the default, one lane per pair up to 1024
+ * blocks), so that 2^11 elements under one block give every lane four pairs and under three blocks a ragged second stride.
+ * Results do not depend on it.  Refused on a device-list context. */
+int msm_test_set_sumcheck_grid(msm_ctx* ctx, int32_t blocks);
+/* The shape of the last sumcheck calls of the context, four words: blocks of the last round's grid, its pairs, its values d + 1
+ * (all 0 before the first round and after a refused one), and the split k of the last msm_scalars_eq (the variables of its low
+ * half-table; -1 before the first and after a refused one).  Writes min(4, cap) of them and returns 4, or -1 for a null or
+ * device-list context. */
+int msm_test_last_sumcheck(msm_ctx* ctx, int32_t* out, int cap);
 /* The first step of every MSM alone: the window digits of a call's scalars, from the digit kernel the call would launch
  * (k_digits, k_te_digits, k_digits_narrow<W>, k_te_digits_narrow<W>; B >= 2: their _batch forms), through the pipeline's own
  * launch code and geometry, and nothing behind it -- nothing sorts the digits, so a wrong one is a wrong word in digits_out and

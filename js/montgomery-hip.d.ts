@@ -86,6 +86,17 @@ export interface Parallel {
   /** dstPtr = the quotient of the polynomial with the N coefficients of ptr by X - z, dstPtr[N-1] = 0; returns the remainder, its
    *  value at z (msm_scalars_div_linear); dstPtr may be ptr */
   scalarsDivLinear(dstPtr: ScalarPtr, ptr: ScalarPtr, N: number, z: bigint | number | Uint8Array): bigint;
+  /** the round polynomial s(0), .., s(d) of a sumcheck over the multilinear tables of 2^log2n scalars behind ptrs
+   *  (msm_scalars_sumcheck_round): variable j is bit j of the index; "prod": the product of 1 .. 4 tables, d = their number;
+   *  "r1cs": f0 (f1 f2 - f3), d = 3.  s(0) + s(1) is the claim.  A sum of products: one call per product, s is linear in g */
+  scalarsSumcheckRound(ptrs: ScalarPtr[], log2n: number, variable: number, options?: { shape?: "prod" | "r1cs" }): bigint[];
+  /** binds `variable` of up to 8 tables to r: dst[i] = lo(i) + r (hi(i) - lo(i)) (msm_scalars_bind).  Without options.dst the top
+   *  variable is bound in place and every pointer then holds 2^(log2n - 1) scalars; returns the pointers that hold the result */
+  scalarsBind(ptrs: ScalarPtr[], log2n: number, variable: number, r: bigint | number | Uint8Array,
+    options?: { dst?: ScalarPtr[] }): ScalarPtr[];
+  /** a new scalar pointer holding eq(r, .) scaled by s (default 1), 2^r.length scalars: element i = s prod_j (bit_j(i) ? r[j] : 1 - r[j])
+   *  (msm_scalars_eq) */
+  scalarsEq(r: Array<bigint | number | Uint8Array>, s?: bigint | number | Uint8Array): ScalarPtr;
   /** in-place fold: v[i] <- a * v[i] + b * v[i + n/2], i < n/2 (n even); the pointer then holds n/2 scalars */
   foldScalars(scalarPtr: ScalarPtr, a: bigint | number | Uint8Array, b: bigint | number | Uint8Array): ScalarPtr;
   /** the first N scalars behind a pointer (default: all) as N x 32 bytes on the host (msm_device_download) */

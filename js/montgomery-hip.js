@@ -311,6 +311,47 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       roomFor(dstPtr, N);
       return leBytesToBigint(hip.scalarsDivLinear(ctx, dstPtr.dev, 0, ptr.dev, 0, N, scalarBuffer(z, "z")));
     },
+    // The resident sumcheck (msm_scalars_sumcheck_round / _bind / _eq) over multilinear tables of 2^log2n scalars at the start of
+    // scalar pointers.  Variable j is bit j of the index: variable 0 is the least significant bit (arkworks' order); a caller
+    // with the most-significant-first convention reverses its point.
+    // The round polynomial s(0), .., s(d) as BigInts: s(t) = sum over the pairs of g(f_0(t), ..), f_j(t) = lo + t (hi - lo).
+    // options: {shape: "prod" | "r1cs"} -- "prod": the product of 1 .. 4 tables, d = their number; "r1cs": f0 (f1 f2 - f3),
+    // d = 3.  s(0) + s(1) is the claim of the round.  A sum of products runs one call per product: s is linear in g.
+    scalarsSumcheckRound(ptrs, log2n, variable, options) {
+      const o = options || {}, shape = o.shape === undefined ? "prod" : o.shape;
+      if (shape !== "prod" && shape !== "r1cs") throw new TypeError(`scalarsSumcheckRound: shape must be "prod" or "r1cs", not ${shape}`);
+      for (const p of ptrs) needScalars(p, 2 ** log2n, "scalarsSumcheckRound");
+      const raw = hip.scalarsSumcheckRound(ctx, ptrs.map((p) => p.dev), ptrs.map(() => 0), log2n, variable, shape === "r1cs" ? 1 : 0);
+      const out = [];
+      for (let t = 0; t < raw.length / 32; t++) out.push(leBytesToBigint(raw.subarray(32 * t, 32 * t + 32)));
+      return out;
+    },
+    // Binds `variable` of the tables behind ptrs (1 .. 8 of them) to r: dst[i] = lo(i) + r (hi(i) - lo(i)), i < 2^(log2n - 1).
+    // Without options the top variable is bound in place and every pointer then holds 2^(log2n - 1) scalars; options {dst: [...]}
+    // names as many destination pointers, which may not be the sources.  Returns the pointers that hold the result.
+    scalarsBind(ptrs, log2n, variable, r, options) {
+      const o = options || {}, n = 2 ** log2n, h = n / 2, zeros = ptrs.map(() => 0);
+      for (const p of ptrs) needScalars(p, n, "scalarsBind");
+      const srcs = ptrs.map((p) => p.dev);
+      if (!o.dst) {
+        if (variable !== log2n - 1) throw new RangeError("scalarsBind: only the top variable is bound in place; name options.dst");
+        hip.scalarsBind(ctx, srcs, zeros, srcs, zeros, log2n, variable, scalarBuffer(r, "r"));
+        for (const p of ptrs) p.n = h;
+        return ptrs;
+      }
+      for (const d of o.dst) roomFor(d, h);
+      hip.scalarsBind(ctx, o.dst.map((d) => d.dev), o.dst.map(() => 0), srcs, zeros, log2n, variable, scalarBuffer(r, "r"));
+      return o.dst;
+    },
+    // a new scalar pointer holding the table eq(r, .) scaled by s (default 1): element i = s prod_j (bit_j(i) ? r[j] : 1 - r[j])
+    scalarsEq(r, s) {
+      const N = 2 ** r.length;
+      const ptr = newScalarPtr(32 * N);
+      roomFor(ptr, N);
+      const rb = Buffer.concat(r.map((x) => scalarBuffer(x, "an entry of r")), 32 * r.length);
+      hip.scalarsEq(ctx, ptr.dev, 0, rb, s === undefined || s === null ? null : scalarBuffer(s, "s"));
+      return firstOf(ptr);
+    },
     // the in-place fold of an inner-product argument: v[i] <- a * v[i] + b * v[i + n/2], i < n/2; the pointer then holds n/2 scalars
     foldScalars(scalarPtr, a, b) {
       const n = scalarPtr.n;

@@ -32,6 +32,7 @@ NO_BAD_INDEX = (1 << 64) - 1   # *bad_index_out when every point passed
 
 SCAN_SUM, SCAN_PRODUCT = 0, 1   # op of msm_scalars_scan
 SCAN_EXCLUSIVE = 1              # its flags
+SUMCHECK_PROD, SUMCHECK_R1CS = 0, 1   # shape of msm_scalars_sumcheck_round
 
 OP_MUL, OP_SQR, OP_ADD, OP_SUB, OP_INV, OP_TO_MONT, OP_FROM_MONT, OP_INV_FERMAT, OP_INV_KALISKI, OP_INV_WORDSLICED = range(10)
 
@@ -57,6 +58,7 @@ EXPORTS = (
     "msm_scalars_scan", "msm_scalars_inverse", "msm_scalars_div_linear", "msm_test_set_scan_tile_log", "msm_test_last_scan_plan",
     "msm_points_mul", "msm_points_mul_base", "msm_test_set_points_mul_grid", "msm_test_set_points_mul_base_path",
     "msm_test_last_points_mul",
+    "msm_scalars_sumcheck_round", "msm_scalars_bind", "msm_scalars_eq", "msm_test_set_sumcheck_grid", "msm_test_last_sumcheck",
 )
 
 
@@ -259,6 +261,14 @@ def load() -> C.CDLL:
     lib.msm_test_set_points_mul_grid.argtypes = [vp, i32]
     lib.msm_test_set_points_mul_base_path.argtypes = [vp, i32]
     lib.msm_test_last_points_mul.argtypes = [vp, C.POINTER(i32), C.c_int]
+    # the resident sumcheck (round sums, variable binding, eq tables), with its test surface: new symbols under ABI 8 as well
+    if not hasattr(lib, "msm_scalars_sumcheck_round"):
+        raise ImportError(f"{LIB_PATH} predates msm_scalars_sumcheck_round: rebuild it (`make`)")
+    lib.msm_scalars_sumcheck_round.argtypes = [vp, C.POINTER(vp), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp]
+    lib.msm_scalars_bind.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    lib.msm_scalars_eq.argtypes = [vp, vp, vp, C.c_uint32, vp]
+    lib.msm_test_set_sumcheck_grid.argtypes = [vp, i32]
+    lib.msm_test_last_sumcheck.argtypes = [vp, C.POINTER(i32), C.c_int]
     for name in EXPORTS:
         if name not in ("msm_ctx_destroy", "msm_last_error", "msm_abi_version", "msm_abi_struct_bytes"):
             getattr(lib, name).restype = C.c_int

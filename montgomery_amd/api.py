@@ -907,6 +907,51 @@ class MsmContext:
         self._check(self._lib.msm_scalars_div_linear(self._h, C.c_void_p(dst), C.c_void_p(a), n, self._scalar_buf(z, "z"), out))
         return int.from_bytes(bytes(out), "little")
 
+    @staticmethod
+    def _ptr_array(ptrs, what: str):
+        ptrs = list(ptrs)
+        if not ptrs:
+            raise MsmError(_lib.MSM_ERR_ARG, f"{what}: no vectors")
+        return (C.c_void_p * len(ptrs))(*[int(p) for p in ptrs]), len(ptrs)
+
+    def scalars_sumcheck_round(self, vecs, log2n: int, var: int, shape: str = "prod") -> List[int]:
+        """The round polynomial of a sumcheck over the multilinear tables at the device addresses `vecs`, 2^log2n scalars each
+        (msm_scalars_sumcheck_round): s(t) = sum over the pairs i of g(f_0(i, t), ..), f_j(i, t) = a_j[lo(i)] + t (a_j[hi(i)] -
+        a_j[lo(i)]), as ints for t = 0 .. d.  Variable `var` is bit `var` of the index (0 = least significant).  shape "prod":
+        g = the product of 1 .. 4 tables, d = their number; "r1cs": g = f_0 (f_1 f_2 - f_3), four tables, d = 3.  s(0) + s(1)
+        is the claim of the round.  A sum of products runs one call per product: the round polynomial is linear in g."""
+        shapes = {"prod": _lib.SUMCHECK_PROD, "r1cs": _lib.SUMCHECK_R1CS}
+        if shape not in shapes:
+            raise MsmError(_lib.MSM_ERR_ARG, f"scalars_sumcheck_round: shape must be 'prod' or 'r1cs', not {shape!r}")
+        arr, m = self._ptr_array(vecs, "scalars_sumcheck_round")
+        out = (C.c_uint8 * (32 * 5))()
+        self._check(self._lib.msm_scalars_sumcheck_round(self._h, arr, m, log2n, var, shapes[shape], out))
+        d = 3 if shape == "r1cs" else m
+        raw = bytes(out)
+        return [int.from_bytes(raw[32 * t:32 * t + 32], "little") for t in range(d + 1)]
+
+    def scalars_bind(self, dst, a, log2n: int, var: int, r) -> None:
+        """Binds variable `var` of the tables at the device addresses `a` (1 .. 8 of them, 2^log2n scalars each) to r, into the
+        addresses `dst` (msm_scalars_bind): dst_j[i] = a_j[lo(i)] + r (a_j[hi(i)] - a_j[lo(i)]), i < 2^(log2n - 1).  dst and a:
+        one address or a sequence of as many.  dst_j may be a_j itself when var is the top variable (the upper half then stays
+        as it was); every other overlap of a destination is refused.  r: int or 32 bytes < q."""
+        dst = [dst] if isinstance(dst, int) else list(dst)
+        a = [a] if isinstance(a, int) else list(a)
+        if len(dst) != len(a):
+            raise MsmError(_lib.MSM_ERR_ARG, f"scalars_bind: {len(dst)} destinations for {len(a)} tables")
+        darr, m = self._ptr_array(dst, "scalars_bind")
+        aarr, _ = self._ptr_array(a, "scalars_bind")
+        self._check(self._lib.msm_scalars_bind(self._h, darr, aarr, m, log2n, var, self._scalar_buf(r, "r")))
+
+    def scalars_eq(self, dst: int, r, s=None) -> None:
+        """dst[i] = s * prod_j (bit_j(i) ? r[j] : 1 - r[j]) mod q for i < 2^len(r): the table eq(r, .) scaled by s
+        (msm_scalars_eq).  r: a sequence of ints or 32-byte strings < q, entry j belonging to bit j of the index; s: None = 1."""
+        r = list(r)
+        raw = b"".join(_scalar32(x, "an entry of r") for x in r)
+        rbuf = (C.c_uint8 * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
+        sbuf = None if s is None else self._scalar_buf(s, "s")
+        self._check(self._lib.msm_scalars_eq(self._h, C.c_void_p(dst), rbuf, len(r), sbuf))
+
     def fold_scalars(self, dev_ptr: int, n: int, lo_scalar, hi_scalar) -> int:
         """The in-place fold of the n scalars at dev_ptr: v[i] <- lo_scalar * v[i] + hi_scalar * v[i + n/2], i < n/2 (n even); the
         upper half stays as it was.  The scalar fold of an inner-product argument beside fold_points.  Returns n/2."""
@@ -1496,6 +1541,41 @@ class _Parallel:
         remainder, its value at z (MsmContext.scalars_div_linear).  dstPtr may be ptr."""
         a = self._scalar_dev(ptr, N, "scalarsDivLinear")
         return self._ctx.scalars_div_linear(self._scalar_dev(dstPtr, N, "scalarsDivLinear", alloc=True), a, N, z)
+
+    def scalarsSumcheckRound(self, ptrs: List[ScalarPtr], log2n: int, variable: int, options: Optional[Dict] = None) -> List[int]:
+        """The round polynomial s(0 .. d) of a sumcheck over the tables of 2^log2n scalars at the start of each pointer
+        (MsmContext.scalars_sumcheck_round).  options: {"shape": "prod" | "r1cs"}."""
+        options = options or {}
+        n = 1 << log2n
+        devs = [self._scalar_dev(p, n, "scalarsSumcheckRound") for p in ptrs]
+        return self._ctx.scalars_sumcheck_round(devs, log2n, variable, options.get("shape", "prod"))
+
+    def scalarsBind(self, ptrs: List[ScalarPtr], log2n: int, variable: int, r, options: Optional[Dict] = None) -> List[ScalarPtr]:
+        """Binds `variable` of the tables of 2^log2n scalars behind the pointers to r (MsmContext.scalars_bind).  Without
+        options the top variable is bound in place and every pointer then holds 2^(log2n - 1) scalars; options {"dst": [...]}
+        names as many destination pointers, which may not be the sources.  Returns the pointers that hold the result."""
+        options = options or {}
+        n, h = 1 << log2n, 1 << (log2n - 1)
+        srcs = [self._scalar_dev(p, n, "scalarsBind") for p in ptrs]
+        dst_ptrs = options.get("dst")
+        if dst_ptrs is None:
+            if variable != log2n - 1:
+                raise MsmError(_lib.MSM_ERR_ARG, "scalarsBind: only the top variable is bound in place; name options.dst")
+            self._ctx.scalars_bind(srcs, srcs, log2n, variable, r)
+            for p in ptrs:
+                p.n = h
+            return list(ptrs)
+        dsts = [self._scalar_dev(p, h, "scalarsBind", alloc=True) for p in dst_ptrs]
+        self._ctx.scalars_bind(dsts, srcs, log2n, variable, r)
+        return list(dst_ptrs)
+
+    def scalarsEq(self, r, s=None) -> ScalarPtr:
+        """A new scalar pointer holding the table eq(r, .) scaled by s, 2^len(r) scalars (MsmContext.scalars_eq)."""
+        r = list(r)
+        n = 1 << len(r)
+        ptr = ScalarPtr(self._ctx, size=32 * n)
+        self._ctx.scalars_eq(self._scalar_dev(ptr, n, "scalarsEq", alloc=True), r, s)
+        return ptr
 
     def foldScalars(self, scalarPtr: ScalarPtr, a, b) -> ScalarPtr:
         """The in-place fold of the scalars behind scalarPtr: v[i] <- a * v[i] + b * v[i + n/2]; the pointer then holds n/2

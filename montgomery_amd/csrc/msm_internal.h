@@ -21,7 +21,9 @@
 //                     kernels of points_lincomb.h
 //   msm_scalars.hip   msm_scalars_lincomb, _mul, _inner, _powers (vectors of scalars in device memory, mod the group order) and
 //                     msm_device_download, with the kernels of scalar_vec.h
-// The operators over resident vectors and point sets (msm_scalars, msm_ntt, msm_scan, msm_lincomb, msm_points_mul) take their
+//   msm_mle.hip       msm_scalars_sumcheck_round, _bind, _eq (the sumcheck over multilinear tables) and the two entries of their
+//                     debug surface, with the kernels of scalar_mle.h
+// The operators over resident vectors and point sets (msm_scalars, msm_ntt, msm_scan, msm_mle, msm_lincomb, msm_points_mul) take their
 // argument checks from operator_checks.h and the host side of the scalar field from scalar_host.h.
 // Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip, te_kernels.hip and narrow_kernels.hip; host TUs see
 // declarations.
@@ -321,6 +323,12 @@ struct msm_ctx {
   int pmul_grid = 0;                // msm_test_set_points_mul_grid: blocks of the variable-base grid; 0 = the default
   int pmul_base_path = 0;           // msm_test_set_points_mul_base_path: 0 auto, 1 table, 2 broadcast
   int32_t last_pmul[4] = {};        // grid, w, path, table rows of the last call (msm_test_last_points_mul)
+
+  // msm_scalars_sumcheck_round / _bind / _eq (msm_mle.hip): the round's results and its partials per block and value; the two
+  // half-tables of the last eq.  Freed with the context.
+  msmi::DevBuf mle_part, mle_tab;
+  int mle_grid = 0;                 // msm_test_set_sumcheck_grid: blocks of the round kernel; 0 = the default
+  int32_t last_mle[4] = {0, 0, 0, -1};   // blocks, pairs, values of the last round; split k of the last eq (msm_test_last_sumcheck)
 
   // per-group workspace: two of them, each with its own stream, so that the memory-bound sort of one
   // window group runs under the ALU-bound accumulation of the other

@@ -1,4 +1,4 @@
-// The argument checks that the operators over resident vectors and point sets share (msm_scalars.hip, msm_scan.hip, msm_ntt.hip,
+// The argument checks that the operators over resident vectors and point sets share (msm_scalars.hip, msm_scan.hip, msm_ntt.hip, msm_mle.hip,
 // msm_lincomb.hip, msm_points_mul.hip): each returns MSM_OK, or refuses the call through fail() with the entry point's name in
 // front.  Plain functions that read the context and write nothing but its error text; an entry point calls them in the order in
 // which its refusals are documented to win.  tests/test_scalar_host.py checks the range and row rules on the CPU.

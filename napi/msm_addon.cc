@@ -35,6 +35,10 @@
 //          scalarsRootOfUnity(h, log2n) -> Buffer of 32 bytes, scalarsNttMaxLog2n(h) -> number,
 //          scalarsScan(h, dst, dstOff, a, aOff, n, op, exclusive, Buffer init | null) -> Buffer total (msm_scalars_scan),
 //          scalarsInverse(h, dst, dstOff, a, aOff, n) -> number of zero residues, scalarsDivLinear(h, dst, dstOff, a, aOff, n, z) -> Buffer,
+//          the resident sumcheck: a table is a device buffer and an offset in elements --
+//          scalarsSumcheckRound(h, [bufs], [offs], log2n, var, shape) -> Buffer of (d + 1) x 32 bytes (msm_scalars_sumcheck_round),
+//          scalarsBind(h, [dstBufs], [dstOffs], [srcBufs], [srcOffs], log2n, var, Buffer r) (msm_scalars_bind),
+//          scalarsEq(h, dst, dstOff, Buffer r of v x 32 bytes, Buffer s | null) (msm_scalars_eq),
 //          plan(h, n, c) -> {c, K}, generatePoints(h, n, seed) -> n, generateScalars(h, n, seed[, dbuf]) -> Buffer | n
 //          the fine operator table of the reference's wasm exports (src/field-msm.ts:86-123,190-243, src/scalar-glv.ts:41-51,105-128)
 //          over Buffers instead of wasm pointers: fieldOp(h, op, a, b) -> Buffer (msm_test_fp: multiply / square / add / subtract /
@@ -1253,6 +1257,119 @@ static napi_value ScalarsDivLinear(napi_env env, napi_callback_info info) {
   return out;
 }
 
+// the resident sumcheck (msm_scalars_sumcheck_round, msm_scalars_bind, msm_scalars_eq): a table is a device buffer and an offset in elements
+// `count` tables of n elements from two arrays, device buffers and offsets; 0: a JS exception is pending
+static int vec_array_arg(napi_env env, js_ctx* h, napi_value v_bufs, napi_value v_offs, uint32_t max, int64_t n, const char* what,
+                         uint8_t** out, uint32_t* count) {
+  bool is_a = false, is_b = false;
+  uint32_t la = 0, lb = 0;
+  if (napi_is_array(env, v_bufs, &is_a) != napi_ok || napi_is_array(env, v_offs, &is_b) != napi_ok || !is_a || !is_b ||
+      napi_get_array_length(env, v_bufs, &la) != napi_ok || napi_get_array_length(env, v_offs, &lb) != napi_ok || la != lb || la < 1 ||
+      la > max) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "%s: tables are two arrays of equal length 1 .. %u, device buffers and element offsets", what, max);
+    napi_throw_type_error(env, NULL, buf);
+    return 0;
+  }
+  for (uint32_t j = 0; j < la; j++) {
+    napi_value vb, vo;
+    if (napi_get_element(env, v_bufs, j, &vb) != napi_ok || napi_get_element(env, v_offs, j, &vo) != napi_ok) return 0;
+    if (!vec_arg(env, h, vb, vo, n, what, &out[j])) return 0;
+  }
+  *count = la;
+  return 1;
+}
+// scalarsSumcheckRound(ctx, bufs, offs, log2n, var, shape) -> Buffer of (d + 1) x 32 bytes: s(0), .., s(d)
+static napi_value ScalarsSumcheckRound(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 6) {
+    napi_throw_type_error(env, NULL, "scalarsSumcheckRound(ctx, bufs, offs, log2n, var, shape)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  uint32_t log2n = 0, var = 0, m = 0;
+  int32_t shape = 0;
+  NAPI_OK(napi_get_value_uint32(env, argv[3], &log2n));
+  NAPI_OK(napi_get_value_uint32(env, argv[4], &var));
+  NAPI_OK(napi_get_value_int32(env, argv[5], &shape));
+  if (log2n < 1 || log2n > 29) {
+    napi_throw_range_error(env, NULL, "scalarsSumcheckRound: log2n must be 1 .. 29");
+    return NULL;
+  }
+  uint8_t* vecs[4] = {NULL, NULL, NULL, NULL};
+  if (!vec_array_arg(env, h, argv[1], argv[2], 4, (int64_t)1 << log2n, "scalarsSumcheckRound", vecs, &m)) return NULL;
+  uint8_t evals[5 * 32];
+  int rc = msm_scalars_sumcheck_round(h->ctx, (const void* const*)vecs, m, log2n, var, shape, evals);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsSumcheckRound");
+  const size_t values = (shape == MSM_SUMCHECK_R1CS ? 3 : m) + 1;
+  napi_value out;
+  void* po = NULL;
+  NAPI_OK(napi_create_buffer_copy(env, values * 32, evals, &po, &out));
+  return out;
+}
+// scalarsBind(ctx, dstBufs, dstOffs, srcBufs, srcOffs, log2n, var, r: Buffer)
+static napi_value ScalarsBind(napi_env env, napi_callback_info info) {
+  size_t argc = 8;
+  napi_value argv[8];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 8) {
+    napi_throw_type_error(env, NULL, "scalarsBind(ctx, dstBufs, dstOffs, srcBufs, srcOffs, log2n, var, r)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  uint32_t log2n = 0, var = 0, m = 0, md = 0;
+  NAPI_OK(napi_get_value_uint32(env, argv[5], &log2n));
+  NAPI_OK(napi_get_value_uint32(env, argv[6], &var));
+  if (log2n < 1 || log2n > 29) {
+    napi_throw_range_error(env, NULL, "scalarsBind: log2n must be 1 .. 29");
+    return NULL;
+  }
+  uint8_t *dst[8] = {NULL}, *src[8] = {NULL};
+  const uint8_t* r = NULL;
+  if (!vec_array_arg(env, h, argv[3], argv[4], 8, (int64_t)1 << log2n, "scalarsBind", src, &m)) return NULL;
+  if (!vec_array_arg(env, h, argv[1], argv[2], 8, (int64_t)1 << (log2n - 1), "scalarsBind", dst, &md)) return NULL;
+  if (md != m) {
+    napi_throw_type_error(env, NULL, "scalarsBind: as many destinations as tables");
+    return NULL;
+  }
+  if (!host_scalar_arg(env, argv[7], &r)) return NULL;
+  int rc = msm_scalars_bind(h->ctx, (void* const*)dst, (const void* const*)src, m, log2n, var, r);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsBind");
+  return NULL;
+}
+// scalarsEq(ctx, dst, dstOff, r: Buffer of v x 32 bytes, s: Buffer | null): 2^v elements
+static napi_value ScalarsEq(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 5) {
+    napi_throw_type_error(env, NULL, "scalarsEq(ctx, dst, dstOff, r, s)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  bool is_buf = false;
+  void* pr = NULL;
+  size_t len = 0;
+  if (napi_is_buffer(env, argv[3], &is_buf) != napi_ok || !is_buf || napi_get_buffer_info(env, argv[3], &pr, &len) != napi_ok || len % 32 ||
+      len / 32 > 29) {
+    napi_throw_type_error(env, NULL, "scalarsEq: r is a Buffer of v x 32 bytes, v <= 29");
+    return NULL;
+  }
+  const uint32_t v = (uint32_t)(len / 32);
+  uint8_t* dst = NULL;
+  const uint8_t* s = NULL;
+  if (!vec_arg(env, h, argv[1], argv[2], (int64_t)1 << v, "scalarsEq", &dst)) return NULL;
+  if (!is_nullish(env, argv[4]) && !host_scalar_arg(env, argv[4], &s)) return NULL;
+  int rc = msm_scalars_eq(h->ctx, dst, (const uint8_t*)pr, v, s);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsEq");
+  return NULL;
+}
+
 /* ---- the fine operator table: element-wise field / GLV / curve operators over Buffers -------------------------------- */
 
 static int buffer_arg(napi_env env, napi_value v, uint8_t** data, size_t* len) {
@@ -1395,6 +1512,7 @@ NAPI_MODULE_INIT() {
       {"scalarsInner", ScalarsInner}, {"scalarsPowers", ScalarsPowers},
       {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity}, {"scalarsNttMaxLog2n", ScalarsNttMaxLog2n},
       {"scalarsScan", ScalarsScan}, {"scalarsInverse", ScalarsInverse}, {"scalarsDivLinear", ScalarsDivLinear},
+      {"scalarsSumcheckRound", ScalarsSumcheckRound}, {"scalarsBind", ScalarsBind}, {"scalarsEq", ScalarsEq},
       {"fieldOp", FieldOp}, {"batchInverse", BatchInverse}, {"glvDecompose", GlvDecompose}, {"batchAdd", BatchAdd}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
     napi_value f;

@@ -1,0 +1,80 @@
+"""The resident sumcheck at the boundary (no GPU): the three new symbols of include/msm_hip.h and the two of its debug surface in
+the library and the binding, the enum, an unchanged ABI version and struct layout, and the methods of the Python facade."""
+import ctypes as C
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+PROTOTYPES = {
+    "msm_scalars_sumcheck_round": "msm_ctx* ctx, const void* const* vecs, uint32_t m, uint32_t log2n, uint32_t var, int shape, "
+                                  "uint8_t* evals_out",
+    "msm_scalars_bind": "msm_ctx* ctx, void* const* dst, const void* const* a, uint32_t m, uint32_t log2n, uint32_t var, "
+                        "const uint8_t* r",
+    "msm_scalars_eq": "msm_ctx* ctx, void* dst, const uint8_t* r, uint32_t v, const uint8_t* s",
+    "msm_test_set_sumcheck_grid": "msm_ctx* ctx, int32_t blocks",
+    "msm_test_last_sumcheck": "msm_ctx* ctx, int32_t* out, int cap",
+}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from conftest import build_if_missing
+
+    build_if_missing("all", "montgomery_amd/libmsm_hip.so")
+    from montgomery_amd import _lib
+
+    return _lib.load()
+
+
+def test_the_library_exports_the_symbols_with_the_declared_signatures(lib):
+    from montgomery_amd import _lib
+
+    for name, args in PROTOTYPES.items():
+        assert name in _lib.EXPORTS, name
+        fn = getattr(lib, name)                      # AttributeError: the library has no such symbol
+        assert len(fn.argtypes) == args.count(",") + 1 and fn.restype is C.c_int, name
+    # a null context is refused by every entry before anything else is looked at, and nothing is written
+    out, word = (C.c_uint8 * 160)(*([7] * 160)), (C.c_int32 * 4)(7, 7, 7, 7)
+    vecs = (C.c_void_p * 4)()
+    assert lib.msm_scalars_sumcheck_round(None, vecs, 2, 4, 0, _lib.SUMCHECK_PROD, out) == _lib.MSM_ERR_ARG
+    assert lib.msm_scalars_bind(None, vecs, vecs, 1, 4, 3, out) == _lib.MSM_ERR_ARG
+    assert lib.msm_scalars_eq(None, None, out, 2, out) == _lib.MSM_ERR_ARG
+    assert bytes(out) == bytes([7] * 160)
+    assert lib.msm_test_set_sumcheck_grid(None, 3) == _lib.MSM_ERR_ARG
+    assert lib.msm_test_last_sumcheck(None, word, 4) == -1 and list(word) == [7, 7, 7, 7]
+
+
+def test_abi_version_and_struct_sizes_are_unchanged(lib):
+    from montgomery_amd import _lib
+
+    assert lib.msm_abi_version() == 8 == _lib.ABI_VERSION
+    assert lib.msm_abi_struct_bytes(0) == 56 == C.sizeof(_lib.MsmOpts)
+    assert lib.msm_abi_struct_bytes(1) == 176 == C.sizeof(_lib.MsmResult)
+
+
+def test_the_header_declares_the_symbols_and_the_enum():
+    from montgomery_amd import _lib
+
+    text = open(os.path.join(ROOT, "include", "msm_hip.h")).read()
+    assert re.search(r"#define\s+MSM_ABI_VERSION\s+8\b", text)
+    flat = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)          # comments out, then one space between tokens
+    flat = re.sub(r"\s+", " ", flat).replace("( ", "(").replace(" )", ")").replace(" ,", ",")
+    for name, args in PROTOTYPES.items():
+        assert f"int {name}({args});" in flat, name
+    assert "enum { MSM_SUMCHECK_PROD = 0, MSM_SUMCHECK_R1CS = 1 };" in flat
+    assert (_lib.SUMCHECK_PROD, _lib.SUMCHECK_R1CS) == (0, 1)
+    # the contract a caller cannot guess: which bit a variable is, and what to do with a sum of products
+    assert "VARIABLE j IS BIT j OF THE INDEX" in text and "least significant bit" in text
+    assert "linear in g" in text and "one call per product" in text
+
+
+def test_the_python_facade_has_the_methods():
+    from montgomery_amd import api
+
+    for m in ("scalars_sumcheck_round", "scalars_bind", "scalars_eq"):
+        assert callable(getattr(api.MsmContext, m, None)), m
+    for m in ("scalarsSumcheckRound", "scalarsBind", "scalarsEq"):
+        assert callable(getattr(api._Parallel, m, None)), m
