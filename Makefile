@@ -8,7 +8,7 @@ HIPFLAGS := -O3 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unus
 BUILD := build
 CURVES := CvBls377 CvBls381 CvPallas CvBn254 CvGrumpkin CvVesta
 CURVE_OBJS := $(CURVES:%=$(BUILD)/kernels_%.o)
-HOST_TUS := msm_plan msm_sort msm_tree msm_reduce msm_upload msm_pipeline msm_batch msm_tables msm_abi msm_test_abi msm_gen msm_ingest msm_narrow msm_indexed msm_lincomb msm_points_mul msm_scalars msm_ntt msm_scan msm_mle sort_kernels te_kernels narrow_kernels
+HOST_TUS := msm_plan msm_sort msm_tree msm_reduce msm_upload msm_pipeline msm_batch msm_tables msm_abi msm_test_abi msm_gen msm_ingest msm_narrow msm_indexed msm_lincomb msm_points_mul msm_scalars msm_ntt msm_scan msm_mle msm_spmv sort_kernels te_kernels narrow_kernels
 HOST_OBJS := $(HOST_TUS:%=$(BUILD)/%.o)
 KHDRS := $(CSRC)/msm_kernels.h $(CSRC)/batch_add.h $(CSRC)/msm_gen_kernels.h $(CSRC)/kernel_inst.h $(CSRC)/field.h $(CSRC)/packed.h $(CSRC)/curve.h \
          $(CSRC)/glv.h $(CSRC)/constants_gen.h
@@ -25,7 +25,7 @@ $(BUILD)/kernels_%.o: $(CSRC)/kernels_curve.hip $(KHDRS)
 	$(HIPCC) $(HIPFLAGS) -DMSM_CURVE_TU=$* -c $(CSRC)/kernels_curve.hip -o $@
 
 # the host pipeline is one translation unit per concern (msm_internal.h lists them); the curve-independent kernels have two of their own
-HHDRS := $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/points_mul.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h $(CSRC)/scalar_scan.h $(CSRC)/scalar_mle.h $(CSRC)/scalar_host.h $(CSRC)/msm_internal.h $(CSRC)/operator_checks.h $(CSRC)/sort_kernels.h $(CSRC)/tree_kernels.h $(CSRC)/te_kernels.h $(CSRC)/narrow_kernels.h $(CSRC)/host_field.h include/msm_hip.h
+HHDRS := $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/points_mul.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h $(CSRC)/scalar_scan.h $(CSRC)/scalar_mle.h $(CSRC)/scalar_spmv.h $(CSRC)/scalar_host.h $(CSRC)/msm_internal.h $(CSRC)/operator_checks.h $(CSRC)/sort_kernels.h $(CSRC)/tree_kernels.h $(CSRC)/te_kernels.h $(CSRC)/narrow_kernels.h $(CSRC)/host_field.h include/msm_hip.h
 # msm_points_mul: with the loop-invariant code motion of the machine passes, every constant of the row loop's body (the GLV
 # vectors, q, p, beta) is kept in a scalar register across the whole loop and up to 37 of them go to vector lanes and back
 TUFLAGS_msm_points_mul := -mllvm -disable-machine-licm
@@ -52,11 +52,12 @@ HOSTTEST_SCANS := tests/csrc/libscans_host.so
 HOSTTEST_PMUL := tests/csrc/libpoints_mul_host.so
 HOSTTEST_SCALAR_HOST := tests/csrc/libscalar_host_host.so
 HOSTTEST_MLE := tests/csrc/libmle_host.so
+HOSTTEST_SPMV := tests/csrc/libspmv_host.so
 # (every shim whose source the tests tree holds: a tests tree from before the schedule shim still builds the others)
 hosttest: $(HOSTTEST) $(HOSTTEST_CYCLES) $(HOSTTEST_LINCOMB) $(HOSTTEST_SCALARS) $(if $(wildcard tests/csrc/schedule_host.hip),$(HOSTTEST_SCHEDULE)) \
           $(if $(wildcard tests/csrc/ntt_host.hip),$(HOSTTEST_NTT)) $(if $(wildcard tests/csrc/scans_host.hip),$(HOSTTEST_SCANS)) \
           $(if $(wildcard tests/csrc/points_mul_host.hip),$(HOSTTEST_PMUL)) $(if $(wildcard tests/csrc/scalar_host_host.hip),$(HOSTTEST_SCALAR_HOST)) \
-          $(if $(wildcard tests/csrc/mle_host.hip),$(HOSTTEST_MLE))
+          $(if $(wildcard tests/csrc/mle_host.hip),$(HOSTTEST_MLE)) $(if $(wildcard tests/csrc/spmv_host.hip),$(HOSTTEST_SPMV))
 # scalar_host.h on all seven scalar fields and the range and row rules of operator_checks.h, whose refusals go through the fail() of
 # msm_plan.hip over a bare context: tests/test_scalar_host.py
 $(HOSTTEST_SCALAR_HOST): tests/csrc/scalar_host_host.hip $(CSRC)/msm_plan.hip $(HHDRS)
@@ -73,6 +74,9 @@ $(HOSTTEST_SCANS): tests/csrc/scans_host.hip $(CSRC)/field.h $(CSRC)/constants_g
 # the index maps, the lane bodies and the half-table split of scalar_mle.h on the host: tests/test_mle_host.py
 $(HOSTTEST_MLE): tests/csrc/mle_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h $(CSRC)/scalar_mle.h include/msm_hip.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/mle_host.hip -o $(HOSTTEST_MLE)
+# the CSR rule, the plan, the transposition and the lane bodies of scalar_spmv.h on the host: tests/test_spmv_host.py
+$(HOSTTEST_SPMV): tests/csrc/spmv_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h $(CSRC)/scalar_mle.h $(CSRC)/scalar_spmv.h include/msm_hip.h
+	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/spmv_host.hip -o $(HOSTTEST_SPMV)
 # the lane bodies of scalar_vec.h on the scalar fields of all seven curves: tests/test_scalars_host.py
 $(HOSTTEST_SCALARS): tests/csrc/scalars_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h include/msm_hip.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/scalars_host.hip -o $(HOSTTEST_SCALARS)

@@ -414,6 +414,50 @@ int msm_scalars_bind(msm_ctx* ctx, void* const* dst, const void* const* a, uint3
 int msm_scalars_eq(msm_ctx* ctx, void* dst, const uint8_t* r /* v x 32 B LE, host */, uint32_t v,
                    const uint8_t* s /* 32 B LE, NULL = 1 */);
 
+/* Resident sparse matrices and matrix-vector products over the same vectors: dst = alpha M x (+ dst) mod q.  The tables of the
+ * R1CS shape above are A z, B z and C z -- the circuit's sparse matrices times the resident witness --, Spartan's second sumcheck
+ * needs the transposed product M^T eq(r_x, .), and with every coefficient 1 the product is the gather y[i] = T[idx[i]] of a lookup
+ * or permutation argument and the row sum.  A matrix is a HANDLE as a point set is, not per-call pointers: a circuit's matrices
+ * are fixed across thousands of proofs, so validation, the conversion of the coefficients and the load-balancing plan are paid
+ * once, at creation.  A binding detects the feature by the presence of msm_scalars_matvec.  The reference has no counterpart.
+ * All seven curves.
+ * Format: CSR.  row_ptr holds rows + 1 32-bit words, col holds nnz 32-bit column indices, val holds nnz x 32-byte little-endian
+ *   scalars in the vectors' format (any value below 2^256 counts as its residue).  val == NULL: every coefficient is 1 -- no
+ *   multiplication, and no value bytes stored or read.  Within a row the entries may come in any order and may repeat a column:
+ *   the product sums the multiset; an empty row gives 0.  rows, cols < 2^30 and nnz < 2^31; rows == 0 or nnz == 0 is valid.
+ *   on_device covers all three arrays; device arrays are aligned to 4 bytes, val to 16.
+ * Ownership: the context copies everything into memory it owns -- the sole-ownership rule of point sets --, so the caller's
+ *   buffers may be freed or overwritten as soon as msm_matrix_create returns.  A matrix is freed by msm_matrix_destroy or with the
+ *   context.  Ids behave as msm_pointset_* ids do: small positive integers, a destroyed one may be handed out again.
+ * Validation, at creation and before any index is ever used as an address: row_ptr[0] == 0, row_ptr non-decreasing,
+ *   row_ptr[rows] == nnz, every col[j] < cols.  A defect is MSM_ERR_ARG and the message names the smallest bad position and its
+ *   value ("col[j] = v but cols = c"); row_ptr defects are reported before col defects.  Host input is checked on the host before
+ *   the upload, device input by kernels that read only the arrays inside their stated lengths, col only after row_ptr has passed.
+ *   A refused creation leaves no matrix, no leaked memory and a usable context; *id_out is untouched.
+ * MSM_MATRIX_TRANSPOSE stores M^T of what is given, so the handle is cols x rows: a stable counting sort over the columns on the
+ *   host -- within a transposed row the entries keep the order of the original rows.  Host input only (with on_device: MSM_ERR_ARG).
+ * Errors: unknown flag bits, sizes beyond the limits, null pointers with a non-empty range, misaligned device pointers, an unknown
+ *   or destroyed id, a device-list context (on every entry point here): MSM_ERR_ARG.  alpha >= q: MSM_ERR_SCALAR.
+ * Device memory of a matrix (msm_matrix_info): 4 (rows + 1) + 4 nnz + 32 nnz bytes (4 nnz without coefficients), plus 12 bytes per
+ *   part, 8 per long row and 32 per part of partial sums for the rows above short_max, each array rounded up by a sixteenth. */
+enum { MSM_MATRIX_TRANSPOSE = 1 };   /* create flags; every other bit is MSM_ERR_ARG */
+int msm_matrix_create(msm_ctx* ctx, uint64_t rows, uint64_t cols, uint64_t nnz, const uint32_t* row_ptr,
+                      const uint32_t* col, const void* val, int on_device, uint32_t flags, int32_t* id_out);
+int msm_matrix_destroy(msm_ctx* ctx, int32_t id);
+/* Sizes of matrix `id` as it is held (transposed, if it was created so) and the device bytes it takes; every out may be NULL. */
+int msm_matrix_info(const msm_ctx* ctx, int32_t id, uint64_t* rows_out, uint64_t* cols_out, uint64_t* nnz_out,
+                    uint64_t* bytes_out);
+/* dst[r] = alpha sum_{j in row r} val[j] x[col[j]] mod q; with MSM_MATVEC_ACCUMULATE the old dst[r] is added (taken as its
+ * residue, as every vector element is).  dst: rows x 32 bytes, x: cols x 32 bytes, device pointers aligned to 16 bytes; every
+ * element written is canonical.  dst must be DISJOINT from x, because a row reads arbitrary entries of x: an exact or partial
+ * overlap is MSM_ERR_ARG before a launch.  alpha: 32 bytes little-endian below q, NULL = 1; 0 and 1 are ordinary input.  x may be
+ * NULL when the matrix has no entry.  One launch, three when a row is longer than short_max.  The call returns when the result
+ * is in place and touches no point set, window table or range-table candidate.
+ * THE RESULT IS THE SAME BITS WHATEVER THE LAUNCH GEOMETRY: field addition is exact and no atomic touches a field element. */
+enum { MSM_MATVEC_ACCUMULATE = 1 };  /* flags; every other bit is MSM_ERR_ARG */
+int msm_scalars_matvec(msm_ctx* ctx, int32_t id, void* dst, const void* x, const uint8_t* alpha /* 32 B LE, NULL = 1 */,
+                       uint32_t flags);
+
 /* Device memory the working buffers of one call may take (digits, sort records, tree nodes: the reference sizes them per call
  * in wasm memory, src/msm-batched-affine.ts:96-130).  0 = automatic: 85 % of what the device has free when a big call starts.
  * Windows run in as many groups as fit, and a window whose buffers would not fit at all runs over ranges of the points, one
@@ -749,6 +793,15 @@ int msm_test_set_sumcheck_grid(msm_ctx* ctx, int32_t blocks);
  * half-table; -1 before the first and after a refused one).  Writes min(4, cap) of them and returns 4, or -1 for a null or
  * device-list context. */
 int msm_test_last_sumcheck(msm_ctx* ctx, int32_t* out, int cap);
+/* msm_matrix_create splits the rows of a matrix by two thresholds: a row of at most short_max entries is summed by one lane, a
+ * longer one is cut into parts of at most part_len entries, one wave each.  This entry sets both for the matrices the context
+ * creates AFTERWARDS (0: the default of that threshold), so that a ladder of row lengths crosses them at small sizes.  Results do
+ * not depend on them.  Refused on a device-list context. */
+int msm_test_set_matvec_geometry(msm_ctx* ctx, uint32_t short_max, uint32_t part_len);
+/* The shape of the last msm_scalars_matvec of the context, five words: short_max and part_len of its matrix, its long rows, their
+ * parts, and the launches of the call (all 0 after a refused one).  Writes min(5, cap) of them and returns 5, or -1 for a null or
+ * device-list context. */
+int msm_test_last_matvec(msm_ctx* ctx, int32_t* out, int cap);
 /* The first step of every MSM alone: the window digits of a call's scalars, from the digit kernel the call would launch
  * (k_digits, k_te_digits, k_digits_narrow<W>, k_te_digits_narrow<W>; B >= 2: their _batch forms), through the pipeline's own
  * launch code and geometry, and nothing behind it -- nothing sorts the digits, so a wrong one is a wrong word in digits_out and

@@ -18,6 +18,15 @@ export type NarrowOptions = { c?: number; bits?: number; width?: 1 | 2 | 4 | 8 |
 /** log: the reference's shape (src/msm-common.ts:176-214) -- [{n, K, c}], then ["label... x.xms"] per phase, "msm total" last */
 export type MsmOutput = { result: AffineResult; log: unknown[][] };
 
+/** a sparse matrix in CSR on the host: rowPtr holds rows + 1 entries, col the column indices, val 32 bytes per entry or null (all ones) */
+export interface CsrMatrix {
+  rows: number;
+  cols: number;
+  rowPtr: Uint32Array | number[];
+  col: Uint32Array | number[];
+  val: Uint8Array | null;
+}
+
 export interface Parallel {
   getPointer(size: number): PointPtr;
   getScalarPointer(size: number): ScalarPtr;
@@ -97,6 +106,21 @@ export interface Parallel {
   /** a new scalar pointer holding eq(r, .) scaled by s (default 1), 2^r.length scalars: element i = s prod_j (bit_j(i) ? r[j] : 1 - r[j])
    *  (msm_scalars_eq) */
   scalarsEq(r: Array<bigint | number | Uint8Array>, s?: bigint | number | Uint8Array): ScalarPtr;
+  /** (row, col, value) triples -> CSR by a stable sort over the rows, duplicates kept; triples without a value: the all-ones form
+   *  (val null); transpose: the CSR of the transposed matrix */
+  matrixFromTriplets(rows: number, cols: number, triplets: Array<[number, number, (bigint | number | Uint8Array)?]>,
+    transpose?: boolean): CsrMatrix;
+  /** a resident sparse matrix (msm_matrix_create); returns its id.  options.transpose: the id names the transposed matrix */
+  matrixCreate(matrix: CsrMatrix, options?: { transpose?: boolean; testGeometry?: [number, number] }): number;
+  /** debug surface: [shortMax, partLen, long rows, parts, launches] of the last scalarsMatvec */
+  testLastMatvec(): number[];
+  matrixDestroy(id: number): void;
+  /** sizes of the matrix as held and the device bytes it takes (msm_matrix_info) */
+  matrixInfo(id: number): { rows: number; cols: number; nnz: number; bytes: number };
+  /** dstPtr = alpha M xPtr (+ dstPtr with accumulate) mod the group order (msm_scalars_matvec); dstPtr and xPtr are different
+   *  pointers */
+  scalarsMatvec(id: number, dstPtr: ScalarPtr, xPtr: ScalarPtr,
+    options?: { alpha?: bigint | number | Uint8Array; accumulate?: boolean }): ScalarPtr;
   /** in-place fold: v[i] <- a * v[i] + b * v[i + n/2], i < n/2 (n even); the pointer then holds n/2 scalars */
   foldScalars(scalarPtr: ScalarPtr, a: bigint | number | Uint8Array, b: bigint | number | Uint8Array): ScalarPtr;
   /** the first N scalars behind a pointer (default: all) as N x 32 bytes on the host (msm_device_download) */

@@ -352,6 +352,63 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       hip.scalarsEq(ctx, ptr.dev, 0, rb, s === undefined || s === null ? null : scalarBuffer(s, "s"));
       return firstOf(ptr);
     },
+    // Resident sparse matrices (msm_matrix_*, msm_scalars_matvec; the reference has no counterpart): a CSR matrix lives on the
+    // device under an id, and dstPtr = alpha M xPtr (+ dstPtr) mod the group order over scalar pointers -- A z of an R1CS, the
+    // transposed product of Spartan's second phase, and with all coefficients 1 the gather dst[i] = x[idx[i]] and the row sum.
+    // (row, col, value) triples -> {rows, cols, rowPtr, col, val}: a stable sort over the rows, duplicates kept (the product sums
+    // them).  value: BigInt / number in [0, 2^256) or 32 bytes; triples without a value give the all-ones form (val null).
+    // transpose: the CSR of the transposed matrix, cols x rows.
+    matrixFromTriplets(rows, cols, triplets, transpose) {
+      let trip = triplets.map((t) => (transpose ? [t[1], t[0], t[2]] : [t[0], t[1], t[2]]));
+      if (transpose) [rows, cols] = [cols, rows];
+      const ones = trip.every((t) => t[2] === undefined || t[2] === null);
+      if (!ones && trip.some((t) => t[2] === undefined || t[2] === null)) throw new TypeError("matrixFromTriplets: every triple carries a value, or none does");
+      trip.forEach((t, j) => {
+        if (!Number.isInteger(t[0]) || !Number.isInteger(t[1]) || t[0] < 0 || t[0] >= rows || t[1] < 0 || t[1] >= cols)
+          throw new RangeError(`matrixFromTriplets: triple ${j} lies outside the ${rows} x ${cols} matrix`);
+      });
+      const rowPtr = new Uint32Array(rows + 1);
+      for (const t of trip) rowPtr[t[0] + 1]++;
+      for (let r = 0; r < rows; r++) rowPtr[r + 1] += rowPtr[r];
+      const cursor = Array.from(rowPtr.subarray(0, rows)), col = new Uint32Array(trip.length);
+      const val = ones ? null : Buffer.alloc(32 * trip.length);
+      for (const t of trip) {
+        const d = cursor[t[0]]++;
+        col[d] = t[1];
+        if (val) scalarBuffer(t[2], "a value").copy(val, 32 * d);
+      }
+      return { rows, cols, rowPtr, col, val };
+    },
+    // matrix: what matrixFromTriplets returns (rowPtr and col: Uint32Arrays; val: nnz x 32 bytes or null).  options:
+    // {transpose}: the id then names the transposed matrix.  A defect of the CSR throws (msm error 1) naming its position.
+    matrixCreate(matrix, options) {
+      const u32 = (a) => { const t = a instanceof Uint32Array ? a : Uint32Array.from(a); return Buffer.from(t.buffer, t.byteOffset, t.byteLength); };
+      const v = matrix.val === null || matrix.val === undefined ? null : Buffer.from(matrix.val.buffer, matrix.val.byteOffset, matrix.val.byteLength);
+      const g = options && options.testGeometry;   // debug surface: [shortMax, partLen] of this matrix (msm_test_set_matvec_geometry)
+      if (g) hip.testSetMatvecGeometry(ctx, g[0], g[1]);
+      try {
+        return hip.matrixCreate(ctx, matrix.rows, matrix.cols, u32(matrix.rowPtr), u32(matrix.col), v, options && options.transpose ? 1 : 0);
+      } finally {
+        if (g) hip.testSetMatvecGeometry(ctx, 0, 0);
+      }
+    },
+    // debug surface: [shortMax, partLen, long rows, parts, launches] of the last scalarsMatvec (msm_test_last_matvec)
+    testLastMatvec() { return hip.testLastMatvec(ctx); },
+    matrixDestroy(id) { hip.matrixDestroy(ctx, id); },
+    // {rows, cols, nnz, bytes} of a matrix as it is held; bytes: the device memory it takes
+    matrixInfo(id) { return hip.matrixInfo(ctx, id); },
+    // dstPtr = alpha M xPtr, plus the old dstPtr with options.accumulate.  options: {alpha: BigInt / number or 32 bytes below the
+    // group order (default 1), accumulate}.  dstPtr and xPtr must be different pointers; without accumulate a dstPtr that holds
+    // fewer than `rows` scalars gets a buffer of that size.
+    scalarsMatvec(id, dstPtr, xPtr, options) {
+      const o = options || {}, info = hip.matrixInfo(ctx, id);
+      if (info.nnz) needScalars(xPtr, info.cols, "scalarsMatvec");
+      if (o.accumulate) needScalars(dstPtr, info.rows, "scalarsMatvec");
+      else roomFor(dstPtr, info.rows);
+      hip.scalarsMatvec(ctx, id, dstPtr.dev, 0, info.nnz ? xPtr.dev : null, 0,
+        o.alpha === undefined || o.alpha === null ? null : scalarBuffer(o.alpha, "alpha"), o.accumulate ? 1 : 0);
+      return dstPtr;
+    },
     // the in-place fold of an inner-product argument: v[i] <- a * v[i] + b * v[i + n/2], i < n/2; the pointer then holds n/2 scalars
     foldScalars(scalarPtr, a, b) {
       const n = scalarPtr.n;

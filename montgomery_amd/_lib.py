@@ -33,6 +33,8 @@ NO_BAD_INDEX = (1 << 64) - 1   # *bad_index_out when every point passed
 SCAN_SUM, SCAN_PRODUCT = 0, 1   # op of msm_scalars_scan
 SCAN_EXCLUSIVE = 1              # its flags
 SUMCHECK_PROD, SUMCHECK_R1CS = 0, 1   # shape of msm_scalars_sumcheck_round
+MATRIX_TRANSPOSE = 1            # flags of msm_matrix_create
+MATVEC_ACCUMULATE = 1           # flags of msm_scalars_matvec
 
 OP_MUL, OP_SQR, OP_ADD, OP_SUB, OP_INV, OP_TO_MONT, OP_FROM_MONT, OP_INV_FERMAT, OP_INV_KALISKI, OP_INV_WORDSLICED = range(10)
 
@@ -59,6 +61,8 @@ EXPORTS = (
     "msm_points_mul", "msm_points_mul_base", "msm_test_set_points_mul_grid", "msm_test_set_points_mul_base_path",
     "msm_test_last_points_mul",
     "msm_scalars_sumcheck_round", "msm_scalars_bind", "msm_scalars_eq", "msm_test_set_sumcheck_grid", "msm_test_last_sumcheck",
+    "msm_matrix_create", "msm_matrix_destroy", "msm_matrix_info", "msm_scalars_matvec", "msm_test_set_matvec_geometry",
+    "msm_test_last_matvec",
 )
 
 
@@ -269,6 +273,15 @@ def load() -> C.CDLL:
     lib.msm_scalars_eq.argtypes = [vp, vp, vp, C.c_uint32, vp]
     lib.msm_test_set_sumcheck_grid.argtypes = [vp, i32]
     lib.msm_test_last_sumcheck.argtypes = [vp, C.POINTER(i32), C.c_int]
+    # resident sparse matrices and the matrix-vector product, with their test surface: new symbols under ABI 8 as well
+    if not hasattr(lib, "msm_scalars_matvec"):
+        raise ImportError(f"{LIB_PATH} predates msm_scalars_matvec: rebuild it (`make`)")
+    lib.msm_matrix_create.argtypes = [vp, u64, u64, u64, vp, vp, vp, C.c_int, C.c_uint32, C.POINTER(i32)]
+    lib.msm_matrix_destroy.argtypes = [vp, i32]
+    lib.msm_matrix_info.argtypes = [vp, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    lib.msm_scalars_matvec.argtypes = [vp, i32, vp, vp, vp, C.c_uint32]
+    lib.msm_test_set_matvec_geometry.argtypes = [vp, C.c_uint32, C.c_uint32]
+    lib.msm_test_last_matvec.argtypes = [vp, C.POINTER(i32), C.c_int]
     for name in EXPORTS:
         if name not in ("msm_ctx_destroy", "msm_last_error", "msm_abi_version", "msm_abi_struct_bytes"):
             getattr(lib, name).restype = C.c_int

@@ -264,6 +264,47 @@ def _scalar32(v, what: str = "scalar") -> bytes:
         raise MsmError(_lib.MSM_ERR_ARG, f"{what} must be 32 bytes, got {len(raw)}")
     return raw
 
+
+@dataclass
+class CsrMatrix:
+    """A sparse matrix in CSR on the host, as msm_matrix_create takes it: row_ptr (rows + 1 entries), col (nnz column indices) and
+    val (nnz x 32 bytes little-endian, or None: every coefficient is 1)."""
+    rows: int
+    cols: int
+    row_ptr: List[int]
+    col: List[int]
+    val: Optional[bytes]
+
+    @property
+    def nnz(self) -> int:
+        return len(self.col)
+
+
+def matrix_from_triplets(rows: int, cols: int, triplets, transpose: bool = False) -> CsrMatrix:
+    """(row, col, value) triples -> CSR, by a stable sort over the rows: within a row the entries keep the order of the triples,
+    and duplicates are kept (the product sums them).  value: an int in [0, 2^256) or 32 bytes; triples (row, col) without a value,
+    or with None in every one, give the all-ones form.  transpose: the CSR of the transposed matrix, cols x rows."""
+    trip = [tuple(t) for t in triplets]
+    ones = all(len(t) == 2 or t[2] is None for t in trip)
+    if not ones and any(len(t) != 3 or t[2] is None for t in trip):
+        raise MsmError(_lib.MSM_ERR_ARG, "matrix_from_triplets: every triple carries a value, or none does")
+    if transpose:
+        trip = [(t[1], t[0]) + t[2:] for t in trip]
+        rows, cols = cols, rows
+    for j, t in enumerate(trip):
+        if not (0 <= t[0] < rows and 0 <= t[1] < cols):
+            raise MsmError(_lib.MSM_ERR_ARG, f"matrix_from_triplets: triple {j} lies outside the {rows} x {cols} matrix")
+    order = sorted(range(len(trip)), key=lambda j: trip[j][0])   # stable
+    row_ptr = [0] * (rows + 1)
+    for t in trip:
+        row_ptr[t[0] + 1] += 1
+    for r in range(rows):
+        row_ptr[r + 1] += row_ptr[r]
+    col = [trip[j][1] for j in order]
+    val = None if ones else b"".join(_scalar32(trip[j][2], "a value") for j in order)
+    return CsrMatrix(rows, cols, row_ptr, col, val)
+
+
 # ---------------------------------------------------------------------------------------------
 # low-level context
 # ---------------------------------------------------------------------------------------------
@@ -952,6 +993,71 @@ class MsmContext:
         sbuf = None if s is None else self._scalar_buf(s, "s")
         self._check(self._lib.msm_scalars_eq(self._h, C.c_void_p(dst), rbuf, len(r), sbuf))
 
+    # -- resident sparse matrices (msm_matrix_*, msm_scalars_matvec) ---------------------------
+    @staticmethod
+    def _u32_buf(a, what: str):
+        """host uint32 array from a sequence of ints, a numpy array or little-endian bytes"""
+        if isinstance(a, (bytes, bytearray, memoryview)):
+            raw = bytes(a)
+            if len(raw) % 4:
+                raise MsmError(_lib.MSM_ERR_ARG, f"{what}: {len(raw)} bytes are no array of 32-bit words")
+            return (C.c_uint32 * max(len(raw) // 4, 1)).from_buffer_copy(raw or b"\0\0\0\0"), len(raw) // 4
+        vals = [int(v) for v in (a.tolist() if hasattr(a, "tolist") else a)]
+        if any(v < 0 or v >> 32 for v in vals):
+            raise MsmError(_lib.MSM_ERR_ARG, f"{what}: an entry does not fit 32 bits")
+        return (C.c_uint32 * max(len(vals), 1))(*vals), len(vals)
+
+    def matrix_create(self, rows, cols: Optional[int] = None, row_ptr=None, col=None, val=None, nnz: Optional[int] = None,
+                      on_device: bool = False, transpose: bool = False) -> int:
+        """A resident sparse matrix in CSR (msm_matrix_create); returns its id.  rows may be a CsrMatrix (matrix_from_triplets)
+        in place of the five arguments.  Host input: row_ptr and col are sequences of ints, numpy arrays or little-endian bytes,
+        val is nnz x 32 bytes, a sequence of ints below 2^256, or None (every coefficient is 1).  on_device: row_ptr, col and val
+        are device addresses (val 0 or None: all ones) and nnz is given.  transpose (host input only): the handle holds the
+        transposed matrix, cols x rows.  The context copies everything: the arrays are free again when this returns."""
+        if isinstance(rows, CsrMatrix):
+            m = rows
+            rows, cols, row_ptr, col, val = m.rows, m.cols, m.row_ptr, m.col, m.val
+        flags = _lib.MATRIX_TRANSPOSE if transpose else 0
+        out = C.c_int32(-1)
+        if on_device:
+            if nnz is None:
+                raise MsmError(_lib.MSM_ERR_ARG, "matrix_create: device input needs nnz")
+            rc = self._lib.msm_matrix_create(self._h, rows, cols, nnz, C.c_void_p(row_ptr), C.c_void_p(col), C.c_void_p(val or 0), 1,
+                                             flags, C.byref(out))
+        else:
+            rp, n_rp = self._u32_buf(row_ptr, "row_ptr")
+            cb, n_col = self._u32_buf(col, "col")
+            if n_rp != rows + 1:
+                raise MsmError(_lib.MSM_ERR_ARG, f"matrix_create: row_ptr holds {n_rp} entries for {rows} rows")
+            nnz = n_col if nnz is None else nnz
+            vb = None
+            if val is not None:
+                raw = bytes(val) if isinstance(val, (bytes, bytearray, memoryview)) else b"".join(_scalar32(v, "a value") for v in val)
+                if len(raw) != 32 * nnz or n_col != nnz:
+                    raise MsmError(_lib.MSM_ERR_ARG, f"matrix_create: {n_col} column indices and {len(raw)} value bytes for nnz = {nnz}")
+                vb = (C.c_uint8 * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
+            elif n_col != nnz:
+                raise MsmError(_lib.MSM_ERR_ARG, f"matrix_create: {n_col} column indices for nnz = {nnz}")
+            rc = self._lib.msm_matrix_create(self._h, rows, cols, nnz, rp, cb, vb, 0, flags, C.byref(out))
+        self._check(rc)
+        return int(out.value)
+
+    def matrix_destroy(self, matrix_id: int) -> None:
+        self._check(self._lib.msm_matrix_destroy(self._h, matrix_id))
+
+    def matrix_info(self, matrix_id: int) -> Dict[str, int]:
+        """{"rows", "cols", "nnz", "bytes"} of a matrix as it is held (msm_matrix_info): bytes = the device memory it takes."""
+        r, c, z, b = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.msm_matrix_info(self._h, matrix_id, C.byref(r), C.byref(c), C.byref(z), C.byref(b)))
+        return {"rows": int(r.value), "cols": int(c.value), "nnz": int(z.value), "bytes": int(b.value)}
+
+    def scalars_matvec(self, matrix_id: int, dst: int, x: int, alpha=None, accumulate: bool = False) -> None:
+        """dst = alpha M x mod q, plus the old dst with accumulate (msm_scalars_matvec).  dst: rows scalars, x: cols scalars, device
+        addresses aligned to 16 bytes and disjoint; alpha: int or 32 bytes < q, None = 1."""
+        abuf = None if alpha is None else self._scalar_buf(alpha, "alpha")
+        self._check(self._lib.msm_scalars_matvec(self._h, matrix_id, C.c_void_p(dst), C.c_void_p(x), abuf,
+                                                 _lib.MATVEC_ACCUMULATE if accumulate else 0))
+
     def fold_scalars(self, dev_ptr: int, n: int, lo_scalar, hi_scalar) -> int:
         """The in-place fold of the n scalars at dev_ptr: v[i] <- lo_scalar * v[i] + hi_scalar * v[i + n/2], i < n/2 (n even); the
         upper half stays as it was.  The scalar fold of an inner-product argument beside fold_points.  Returns n/2."""
@@ -1576,6 +1682,30 @@ class _Parallel:
         ptr = ScalarPtr(self._ctx, size=32 * n)
         self._ctx.scalars_eq(self._scalar_dev(ptr, n, "scalarsEq", alloc=True), r, s)
         return ptr
+
+    matrixFromTriplets = staticmethod(matrix_from_triplets)
+
+    def matrixCreate(self, matrix: CsrMatrix, options: Optional[Dict] = None) -> int:
+        """A resident sparse matrix from a CsrMatrix (matrixFromTriplets); returns its id (MsmContext.matrix_create).
+        options: {"transpose": bool}."""
+        return self._ctx.matrix_create(matrix, transpose=bool((options or {}).get("transpose", False)))
+
+    def matrixDestroy(self, matrixId: int) -> None:
+        self._ctx.matrix_destroy(matrixId)
+
+    def matrixInfo(self, matrixId: int) -> Dict[str, int]:
+        return self._ctx.matrix_info(matrixId)
+
+    def scalarsMatvec(self, matrixId: int, dstPtr: ScalarPtr, xPtr: ScalarPtr, options: Optional[Dict] = None) -> ScalarPtr:
+        """dstPtr = alpha M xPtr (+ dstPtr) mod q (MsmContext.scalars_matvec).  options: {"alpha": int or 32 bytes,
+        "accumulate": bool}.  Without accumulate dstPtr gets a buffer of `rows` scalars if it has none that large."""
+        options = options or {}
+        info = self._ctx.matrix_info(matrixId)
+        acc = bool(options.get("accumulate", False))
+        x = self._scalar_dev(xPtr, info["cols"] if info["nnz"] else 0, "scalarsMatvec")
+        d = self._scalar_dev(dstPtr, info["rows"], "scalarsMatvec", alloc=not acc)
+        self._ctx.scalars_matvec(matrixId, d, x, options.get("alpha"), acc)
+        return dstPtr
 
     def foldScalars(self, scalarPtr: ScalarPtr, a, b) -> ScalarPtr:
         """The in-place fold of the scalars behind scalarPtr: v[i] <- a * v[i] + b * v[i + n/2]; the pointer then holds n/2

@@ -77,6 +77,7 @@ void msm_ctx_destroy(msm_ctx* ctx) {
   ctx->allocs.clear();
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (auto& s : ctx->sets) s.release(ctx);
+  for (auto& m : ctx->mats) m.release(ctx);
   for (DevBuf* b : {&ctx->scal, &ctx->errflag, &ctx->misc, &ctx->ntt_tw, &ctx->ntt_shift, &ctx->ntt_scratch, &ctx->scan_agg, &ctx->pmul_tbl,
                     &ctx->pmul_row, &ctx->pmul_base_tbl, &ctx->mle_part, &ctx->mle_tab}) ctx->release(*b);
   for (auto& w : ctx->ws) {

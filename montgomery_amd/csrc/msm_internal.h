@@ -23,7 +23,9 @@
 //                     msm_device_download, with the kernels of scalar_vec.h
 //   msm_mle.hip       msm_scalars_sumcheck_round, _bind, _eq (the sumcheck over multilinear tables) and the two entries of their
 //                     debug surface, with the kernels of scalar_mle.h
-// The operators over resident vectors and point sets (msm_scalars, msm_ntt, msm_scan, msm_mle, msm_lincomb, msm_points_mul) take their
+//   msm_spmv.hip      msm_matrix_create, _destroy, _info and msm_scalars_matvec (resident sparse matrices in CSR and y = alpha M x
+//                     (+ y) mod the group order), with the kernels of scalar_spmv.h
+// The operators over resident vectors and point sets (msm_scalars, msm_ntt, msm_scan, msm_mle, msm_spmv, msm_lincomb, msm_points_mul) take their
 // argument checks from operator_checks.h and the host side of the scalar field from scalar_host.h.
 // Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip, te_kernels.hip and narrow_kernels.hip; host TUs see
 // declarations.
@@ -329,6 +331,24 @@ struct msm_ctx {
   msmi::DevBuf mle_part, mle_tab;
   int mle_grid = 0;                 // msm_test_set_sumcheck_grid: blocks of the round kernel; 0 = the default
   int32_t last_mle[4] = {0, 0, 0, -1};   // blocks, pairs, values of the last round; split k of the last eq (msm_test_last_sumcheck)
+
+  // msm_matrix_* / msm_scalars_matvec (msm_spmv.hip): resident sparse matrices in CSR, each the sole owner of its arrays -- the
+  // column indices, the coefficients in Montgomery form (none in the all-ones form), and the plan of its long rows with their
+  // partials (scalar_spmv.h).  `mats` holds them all; slot 0 is never live, ids start at 1.  Freed with the context.
+  struct Matrix {
+    bool live = false, ones = false;
+    uint64_t rows = 0, cols = 0, nnz = 0;
+    uint32_t short_max = 0, part_len = 0, n_long = 0, n_parts = 0;
+    msmi::DevBuf row_ptr, col, val, parts, long_rows, long_first, partials;
+    uint64_t bytes() const { return row_ptr.cap + col.cap + val.cap + parts.cap + long_rows.cap + long_first.cap + partials.cap; }
+    void release(msm_ctx* ctx) {
+      for (msmi::DevBuf* b : {&row_ptr, &col, &val, &parts, &long_rows, &long_first, &partials}) ctx->release(*b);
+      *this = Matrix();
+    }
+  };
+  std::vector<Matrix> mats = std::vector<Matrix>(1);
+  uint32_t spmv_short_max = 0, spmv_part_len = 0;   // msm_test_set_matvec_geometry: for matrices created afterwards; 0 = the default
+  int32_t last_spmv[5] = {};        // short_max, part_len, long rows, parts, launches of the last product (msm_test_last_matvec)
 
   // per-group workspace: two of them, each with its own stream, so that the memory-bound sort of one
   // window group runs under the ALU-bound accumulation of the other

@@ -781,6 +781,20 @@ int msm_test_digits(msm_ctx* ctx, const void* const* scalars, uint32_t B, uint64
   } MSM_CATCH_ALL(ctx)
 }
 
+int msm_test_set_matvec_geometry(msm_ctx* ctx, uint32_t short_max, uint32_t part_len) {
+  if (!ctx) return MSM_ERR_ARG;
+  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "msm_test_set_matvec_geometry: not on a device-list context");
+  ctx->spmv_short_max = short_max;
+  ctx->spmv_part_len = part_len;
+  return MSM_OK;
+}
+
+int msm_test_last_matvec(msm_ctx* ctx, int32_t* out, int cap) {
+  if (!ctx || !ctx->children.empty() || cap < 0 || (cap && !out)) return -1;
+  for (int i = 0; i < 5 && i < cap; i++) out[i] = ctx->last_spmv[i];
+  return 5;
+}
+
 int msm_generate_points(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) {
   if (!ctx) return MSM_ERR_ARG;
   if (ctx->children.empty()) return generate_points_one(ctx, n, seed, a_out);

@@ -1,5 +1,5 @@
 // The argument checks that the operators over resident vectors and point sets share (msm_scalars.hip, msm_scan.hip, msm_ntt.hip, msm_mle.hip,
-// msm_lincomb.hip, msm_points_mul.hip): each returns MSM_OK, or refuses the call through fail() with the entry point's name in
+// msm_spmv.hip, msm_lincomb.hip, msm_points_mul.hip): each returns MSM_OK, or refuses the call through fail() with the entry point's name in
 // front.  Plain functions that read the context and write nothing but its error text; an entry point calls them in the order in
 // which its refusals are documented to win.  tests/test_scalar_host.py checks the range and row rules on the CPU.
 #pragma once
@@ -45,6 +45,15 @@ inline int dst_ranges_ok(msm_ctx* ctx, const char* who, const void* dst, uint64_
     if (v.p && !(d == s || d + len <= s || s + len <= d))
       return fail(ctx, MSM_ERR_ARG, "%s: dst overlaps %s in part (it may be %s itself or disjoint from it)", who, v.name, v.name);
   }
+  return MSM_OK;
+}
+
+// dst (dst_bytes) against a source of another length that its lanes read at arbitrary places: disjoint, nothing else
+inline int dst_disjoint_ok(msm_ctx* ctx, const char* who, const void* dst, uint64_t dst_bytes, const void* src, uint64_t src_bytes,
+                           const char* name) {
+  const uintptr_t d = (uintptr_t)dst, s = (uintptr_t)src;
+  if (dst_bytes && src_bytes && !(d + dst_bytes <= s || s + src_bytes <= d))
+    return fail(ctx, MSM_ERR_ARG, "%s: dst overlaps %s (a row reads arbitrary entries of %s: the two must be disjoint)", who, name, name);
   return MSM_OK;
 }
 

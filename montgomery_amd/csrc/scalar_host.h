@@ -1,5 +1,5 @@
 // The host's side of the scalar field, the integers mod the group order q, for the operators over resident scalars and points
-// (msm_scalars.hip, msm_scan.hip, msm_ntt.hip, msm_mle.hip, msm_lincomb.hip) and for the CPU shims under tests/csrc: how a scalar of a call is
+// (msm_scalars.hip, msm_scan.hip, msm_ntt.hip, msm_mle.hip, msm_spmv.hip, msm_lincomb.hip) and for the CPU shims under tests/csrc: how a scalar of a call is
 // read and refused, the field work a call does once (powers, inverses, roots of unity) and the power tables its kernels take as
 // arguments.  Host only: the fe_* templates of field.h run here as they do in a lane, and nothing in this file launches anything.
 // Templates over the scalar FIELD S of scalar_vec.h (MSM_SCALAR_FIELDS), 8 words, Fe<S> of 9 limbs, R = 2^270.

@@ -39,6 +39,10 @@
 //          scalarsSumcheckRound(h, [bufs], [offs], log2n, var, shape) -> Buffer of (d + 1) x 32 bytes (msm_scalars_sumcheck_round),
 //          scalarsBind(h, [dstBufs], [dstOffs], [srcBufs], [srcOffs], log2n, var, Buffer r) (msm_scalars_bind),
 //          scalarsEq(h, dst, dstOff, Buffer r of v x 32 bytes, Buffer s | null) (msm_scalars_eq),
+//          resident sparse matrices: matrixCreate(h, rows, cols, Buffer rowPtr, Buffer col, Buffer val | null, flags) -> id (CSR from
+//          the host, uint32 LE words and 32-byte coefficients; flags 1: the transposed matrix), matrixDestroy(h, id), matrixInfo(h, id)
+//          -> {rows, cols, nnz, bytes}, scalarsMatvec(h, id, dst, dstOff, x | null, xOff, Buffer alpha | null, flags): dst = alpha M x,
+//          flags 1: plus the old dst (msm_scalars_matvec); testSetMatvecGeometry(h, shortMax, partLen), testLastMatvec(h) -> [5],
 //          plan(h, n, c) -> {c, K}, generatePoints(h, n, seed) -> n, generateScalars(h, n, seed[, dbuf]) -> Buffer | n
 //          the fine operator table of the reference's wasm exports (src/field-msm.ts:86-123,190-243, src/scalar-glv.ts:41-51,105-128)
 //          over Buffers instead of wasm pointers: fieldOp(h, op, a, b) -> Buffer (msm_test_fp: multiply / square / add / subtract /
@@ -1370,6 +1374,169 @@ static napi_value ScalarsEq(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* ---- resident sparse matrices (msm_matrix_*, msm_scalars_matvec) ------------------------------------------------------ */
+
+// an array of 32-bit words as a Buffer (uint32 LE); *count = its words
+static int u32_buffer_arg(napi_env env, napi_value v, const char* what, const uint32_t** out, uint64_t* count) {
+  bool is_buf = false;
+  void* p = NULL;
+  size_t len = 0;
+  if (napi_is_buffer(env, v, &is_buf) != napi_ok || !is_buf || napi_get_buffer_info(env, v, &p, &len) != napi_ok || len % 4) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "%s is a Buffer of 32-bit little-endian words", what);
+    napi_throw_type_error(env, NULL, buf);
+    return 0;
+  }
+  *out = (const uint32_t*)p;
+  *count = len / 4;
+  return 1;
+}
+// matrixCreate(ctx, rows, cols, rowPtr: Buffer of (rows + 1) x 4 bytes, col: Buffer of nnz x 4 bytes, val: Buffer of nnz x 32 bytes | null,
+//              flags) -> id.  The lengths of the Buffers are checked here: the library reads rows + 1 and nnz entries of them.
+static napi_value MatrixCreate(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 7) {
+    napi_throw_type_error(env, NULL, "matrixCreate(ctx, rows, cols, rowPtr, col, val, flags)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int64_t rows = 0, cols = 0;
+  uint32_t flags = 0;
+  NAPI_OK(napi_get_value_int64(env, argv[1], &rows));
+  NAPI_OK(napi_get_value_int64(env, argv[2], &cols));
+  NAPI_OK(napi_get_value_uint32(env, argv[6], &flags));
+  const uint32_t *rp = NULL, *col = NULL;
+  uint64_t n_rp = 0, nnz = 0;
+  if (!u32_buffer_arg(env, argv[3], "matrixCreate: rowPtr", &rp, &n_rp) || !u32_buffer_arg(env, argv[4], "matrixCreate: col", &col, &nnz)) return NULL;
+  if (rows < 0 || cols < 0 || n_rp != (uint64_t)rows + 1) {
+    napi_throw_range_error(env, NULL, "matrixCreate: rowPtr holds rows + 1 entries");
+    return NULL;
+  }
+  const void* val = NULL;
+  if (!is_nullish(env, argv[5])) {
+    bool is_buf = false;
+    void* p = NULL;
+    size_t len = 0;
+    if (napi_is_buffer(env, argv[5], &is_buf) != napi_ok || !is_buf || napi_get_buffer_info(env, argv[5], &p, &len) != napi_ok || len != nnz * 32) {
+      napi_throw_range_error(env, NULL, "matrixCreate: val is a Buffer of 32 bytes per column index, or null");
+      return NULL;
+    }
+    val = nnz ? p : (const void*)"";   /* (no entry: any non-null address says "coefficients", none is read) */
+  }
+  int32_t id = -1;
+  int rc = msm_matrix_create(h->ctx, (uint64_t)rows, (uint64_t)cols, nnz, rp, col, val, 0, flags, &id);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "matrixCreate");
+  napi_value out;
+  NAPI_OK(napi_create_int32(env, id, &out));
+  return out;
+}
+static napi_value MatrixDestroy(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) {
+    napi_throw_type_error(env, NULL, "matrixDestroy(ctx, id)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int32_t id = 0;
+  NAPI_OK(napi_get_value_int32(env, argv[1], &id));
+  int rc = msm_matrix_destroy(h->ctx, id);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "matrixDestroy");
+  return NULL;
+}
+// matrixInfo(ctx, id) -> {rows, cols, nnz, bytes}
+static napi_value MatrixInfo(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) {
+    napi_throw_type_error(env, NULL, "matrixInfo(ctx, id)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int32_t id = 0;
+  NAPI_OK(napi_get_value_int32(env, argv[1], &id));
+  uint64_t w[4] = {0, 0, 0, 0};
+  int rc = msm_matrix_info(h->ctx, id, &w[0], &w[1], &w[2], &w[3]);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "matrixInfo");
+  static const char* const names[4] = {"rows", "cols", "nnz", "bytes"};
+  napi_value out, v;
+  NAPI_OK(napi_create_object(env, &out));
+  for (int i = 0; i < 4; i++) {
+    NAPI_OK(napi_create_double(env, (double)w[i], &v));
+    NAPI_OK(napi_set_named_property(env, out, names[i], v));
+  }
+  return out;
+}
+// scalarsMatvec(ctx, id, dst, dstOff, x | null, xOff, alpha: Buffer | null, flags): the device buffers must hold rows and cols elements
+static napi_value ScalarsMatvec(napi_env env, napi_callback_info info) {
+  size_t argc = 8;
+  napi_value argv[8];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 8) {
+    napi_throw_type_error(env, NULL, "scalarsMatvec(ctx, id, dst, dstOff, x, xOff, alpha, flags)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int32_t id = 0;
+  uint32_t flags = 0;
+  NAPI_OK(napi_get_value_int32(env, argv[1], &id));
+  NAPI_OK(napi_get_value_uint32(env, argv[7], &flags));
+  uint64_t rows = 0, cols = 0, nnz = 0;
+  int rc = msm_matrix_info(h->ctx, id, &rows, &cols, &nnz, NULL);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsMatvec");
+  uint8_t *dst = NULL, *x = NULL;
+  const uint8_t* alpha = NULL;
+  if (!vec_arg(env, h, argv[2], argv[3], (int64_t)rows, "scalarsMatvec", &dst)) return NULL;
+  if (!is_nullish(env, argv[4]) && !vec_arg(env, h, argv[4], argv[5], nnz ? (int64_t)cols : 0, "scalarsMatvec", &x)) return NULL;
+  if (!is_nullish(env, argv[6]) && !host_scalar_arg(env, argv[6], &alpha)) return NULL;
+  rc = msm_scalars_matvec(h->ctx, id, dst, x, alpha, flags);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "scalarsMatvec");
+  return NULL;
+}
+// testSetMatvecGeometry(ctx, shortMax, partLen): the thresholds of the matrices created afterwards (msm_test_set_matvec_geometry)
+static napi_value TestSetMatvecGeometry(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 3) {
+    napi_throw_type_error(env, NULL, "testSetMatvecGeometry(ctx, shortMax, partLen)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  uint32_t s = 0, p = 0;
+  NAPI_OK(napi_get_value_uint32(env, argv[1], &s));
+  NAPI_OK(napi_get_value_uint32(env, argv[2], &p));
+  int rc = msm_test_set_matvec_geometry(h->ctx, s, p);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "testSetMatvecGeometry");
+  return NULL;
+}
+// testLastMatvec(ctx) -> [shortMax, partLen, longRows, parts, launches] of the last product (msm_test_last_matvec)
+static napi_value TestLastMatvec(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  js_ctx* h = argc ? get_handle(env, argv[0]) : NULL;
+  if (!h) return NULL;
+  int32_t w[5] = {0, 0, 0, 0, 0};
+  if (msm_test_last_matvec(h->ctx, w, 5) != 5) return throw_msm(env, h->ctx, MSM_ERR_ARG, "testLastMatvec");
+  napi_value out, v;
+  NAPI_OK(napi_create_array_with_length(env, 5, &out));
+  for (uint32_t i = 0; i < 5; i++) {
+    NAPI_OK(napi_create_int32(env, w[i], &v));
+    NAPI_OK(napi_set_element(env, out, i, v));
+  }
+  return out;
+}
+
 /* ---- the fine operator table: element-wise field / GLV / curve operators over Buffers -------------------------------- */
 
 static int buffer_arg(napi_env env, napi_value v, uint8_t** data, size_t* len) {
@@ -1513,6 +1680,8 @@ NAPI_MODULE_INIT() {
       {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity}, {"scalarsNttMaxLog2n", ScalarsNttMaxLog2n},
       {"scalarsScan", ScalarsScan}, {"scalarsInverse", ScalarsInverse}, {"scalarsDivLinear", ScalarsDivLinear},
       {"scalarsSumcheckRound", ScalarsSumcheckRound}, {"scalarsBind", ScalarsBind}, {"scalarsEq", ScalarsEq},
+      {"matrixCreate", MatrixCreate}, {"matrixDestroy", MatrixDestroy}, {"matrixInfo", MatrixInfo}, {"scalarsMatvec", ScalarsMatvec},
+      {"testSetMatvecGeometry", TestSetMatvecGeometry}, {"testLastMatvec", TestLastMatvec},
       {"fieldOp", FieldOp}, {"batchInverse", BatchInverse}, {"glvDecompose", GlvDecompose}, {"batchAdd", BatchAdd}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
     napi_value f;
