@@ -802,6 +802,12 @@ int msm_test_set_matvec_geometry(msm_ctx* ctx, uint32_t short_max, uint32_t part
  * parts, and the launches of the call (all 0 after a refused one).  Writes min(5, cap) of them and returns 5, or -1 for a null or
  * device-list context. */
 int msm_test_last_matvec(msm_ctx* ctx, int32_t* out, int cap);
+/* The device buffers the library holds in this process, over all contexts: how many are live and their bytes as allocated (a
+ * buffer is allocated with some slack over what was asked of it).  Every one belongs to a context, a point set, a matrix or a
+ * running call and goes back with its owner, so the two figures return to what they were when a context is destroyed and
+ * after a call that failed: (0, 0) in a process without a context.  Takes no context; MSM_ERR_ARG, and nothing written, if either
+ * pointer is null. */
+int msm_test_live_buffers(uint64_t* count_out, uint64_t* bytes_out);
 /* The first step of every MSM alone: the window digits of a call's scalars, from the digit kernel the call would launch
  * (k_digits, k_te_digits, k_digits_narrow<W>, k_te_digits_narrow<W>; B >= 2: their _batch forms), through the pipeline's own
  * launch code and geometry, and nothing behind it -- nothing sorts the digits, so a wrong one is a wrong word in digits_out and

@@ -63,6 +63,7 @@ EXPORTS = (
     "msm_scalars_sumcheck_round", "msm_scalars_bind", "msm_scalars_eq", "msm_test_set_sumcheck_grid", "msm_test_last_sumcheck",
     "msm_matrix_create", "msm_matrix_destroy", "msm_matrix_info", "msm_scalars_matvec", "msm_test_set_matvec_geometry",
     "msm_test_last_matvec",
+    "msm_test_live_buffers",
 )
 
 
@@ -282,6 +283,10 @@ def load() -> C.CDLL:
     lib.msm_scalars_matvec.argtypes = [vp, i32, vp, vp, vp, C.c_uint32]
     lib.msm_test_set_matvec_geometry.argtypes = [vp, C.c_uint32, C.c_uint32]
     lib.msm_test_last_matvec.argtypes = [vp, C.POINTER(i32), C.c_int]
+    # the count of live device buffers: a new test symbol under ABI 8
+    if not hasattr(lib, "msm_test_live_buffers"):
+        raise ImportError(f"{LIB_PATH} predates msm_test_live_buffers: rebuild it (`make`)")
+    lib.msm_test_live_buffers.argtypes = [C.POINTER(u64), C.POINTER(u64)]
     for name in EXPORTS:
         if name not in ("msm_ctx_destroy", "msm_last_error", "msm_abi_version", "msm_abi_struct_bytes"):
             getattr(lib, name).restype = C.c_int

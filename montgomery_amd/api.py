@@ -1262,6 +1262,16 @@ class MsmContext:
         0 restores the default of 23."""
         self._check(self._lib.msm_test_set_chunk_rows_log(self._h, log2_rows))
 
+    @staticmethod
+    def test_live_buffers() -> Tuple[int, int]:
+        """(count, bytes) of the device buffers the library holds in this process, over all contexts, the bytes as allocated
+        (msm_test_live_buffers, msm_hip.h).  Needs no context and stays readable after close()."""
+        count, nbytes = C.c_uint64(), C.c_uint64()
+        rc = _lib.load().msm_test_live_buffers(C.byref(count), C.byref(nbytes))
+        if rc != _lib.MSM_OK:
+            raise MsmError(rc, "msm_test_live_buffers failed")
+        return int(count.value), int(nbytes.value)
+
     def test_last_sort_paths(self) -> List[str]:
         """The sort path of every window group of the last call, in schedule order: "one_level", "radix", "slots" or "pairs"
         (msm_test_last_sort_paths, msm_hip.h)."""

@@ -27,16 +27,16 @@ int msm_ctx_create(msm_ctx** out, int curve, int device) {
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     ctx->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIPCHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    for (auto& e : ctx->ev) HIPCHK(hipEventCreate(&e));
-    for (auto& e : ctx->ev_dig) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipHostMalloc((void**)&ctx->h_info, 64 * 4, hipHostMallocDefault));
+    ctx->stream.create();
+    for (auto& e : ctx->ev) e.create();
+    for (auto& e : ctx->ev_dig) e.create();
+    ctx->h_info.allocate(64 * 4);
     for (auto& w : ctx->ws) {
-      HIPCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-      HIPCHK(hipStreamCreateWithFlags(&w.side, hipStreamNonBlocking));
-      for (auto& e : w.ev) HIPCHK(hipEventCreate(&e));
-      HIPCHK(hipHostMalloc((void**)&w.h_info, 64 * 4, hipHostMallocDefault));
-      HIPCHK(hipHostMalloc((void**)&w.h_part, 128 * 20 * W_SUM_WORDS * 4, hipHostMallocDefault));
+      w.stream.create();
+      w.side.create();
+      for (auto& e : w.ev) e.create();
+      w.h_info.allocate(64 * 4);
+      w.h_part.allocate(128 * 20 * W_SUM_WORDS * 4);
     }
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
@@ -69,34 +69,7 @@ int msm_ctx_create(msm_ctx** out, int curve, int device) {
 
 void msm_ctx_destroy(msm_ctx* ctx) {
   if (!ctx) return;
-  ctx->fan.clear();
   for (msm_ctx* c : ctx->children) msm_ctx_destroy(c);
-  ctx->children.clear();
-  (void)hipSetDevice(ctx->device);
-  for (void* p : ctx->allocs) (void)hipFree(p);
-  ctx->allocs.clear();
-  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  for (auto& s : ctx->sets) s.release(ctx);
-  for (auto& m : ctx->mats) m.release(ctx);
-  for (DevBuf* b : {&ctx->scal, &ctx->errflag, &ctx->misc, &ctx->ntt_tw, &ctx->ntt_shift, &ctx->ntt_scratch, &ctx->scan_agg, &ctx->pmul_tbl,
-                    &ctx->pmul_row, &ctx->pmul_base_tbl, &ctx->mle_part, &ctx->mle_tab}) ctx->release(*b);
-  for (auto& w : ctx->ws) {
-    if (w.stream) (void)hipStreamSynchronize(w.stream);
-    for (DevBuf* b : w.all) ctx->release(*b);
-    if (w.h_info) (void)hipHostFree(w.h_info);
-    if (w.h_part) (void)hipHostFree(w.h_part);
-    for (auto& e : w.ev) if (e) (void)hipEventDestroy(e);
-    if (w.side) { (void)hipStreamSynchronize(w.side); (void)hipStreamDestroy(w.side); }
-    if (w.stream) (void)hipStreamDestroy(w.stream);
-  }
-  if (ctx->h_info) (void)hipHostFree(ctx->h_info);
-  if (ctx->stage_pin) (void)hipHostFree(ctx->stage_pin);
-  for (auto& st : ctx->stage_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  for (auto& row : ctx->stage_ev) for (auto& e : row) if (e) (void)hipEventDestroy(e);
-  for (auto& row : ctx->piece_ev) for (auto& e : row) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->ev_dig) if (e) (void)hipEventDestroy(e);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
 
@@ -335,18 +308,16 @@ int msm_reserve(msm_ctx* ctx, uint64_t n, const msm_opts* opts) {
   if (!ctx) return MSM_ERR_ARG;
   if (int rc = check_points(ctx, n, opts, MSM_ERR_NO_POINTS, "msm_reserve")) return rc;
   if (n == 0) return MSM_OK;
-  void* dev = nullptr;
   try {
     // one MSM over generated scalars: every buffer the real call will need exists afterwards, and so do the window tables
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMalloc(&dev, n * 32));
-    int rc = msm_generate_scalars(ctx, n, 0x5eed, dev, nullptr);
+    DevBuf dev;
+    dev.allocate(n * 32);
+    int rc = msm_generate_scalars(ctx, n, 0x5eed, dev.p, nullptr);
     msm_result r;
-    if (rc == MSM_OK) rc = msm_run(ctx, dev, n, 1, opts, &r);
-    (void)hipFree(dev);
+    if (rc == MSM_OK) rc = msm_run(ctx, dev.p, n, 1, opts, &r);
     return rc;
   } catch (...) {
-    if (dev) (void)hipFree(dev);
     return fail(ctx, MSM_ERR_HIP, "msm_reserve: device allocation failed");
   }
 }
@@ -424,7 +395,7 @@ int msm_pointset_destroy(msm_ctx* ctx, int32_t id) {
     return on_all_devices(ctx, [&](msm_ctx* c) {
       if (c->cur_set == id) pointset_select_one(c, 0);
       (void)hipSetDevice(c->device);
-      c->sets[id].release(c);
+      c->sets[id].release();
       return (int)MSM_OK;
     });
   } MSM_CATCH_ALL(ctx)
@@ -436,22 +407,23 @@ int msm_device_alloc(msm_ctx* ctx, uint64_t bytes, void** dev_ptr_out) {
   if (!ctx || !dev_ptr_out) return fail(ctx, MSM_ERR_ARG, "msm_device_alloc: null argument");
   try {
     HIPCHK(hipSetDevice(ctx->device));
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, std::max<uint64_t>(bytes, 32)));
-    ctx->allocs.push_back(p);
-    *dev_ptr_out = p;
+    DevBuf b;
+    b.allocate(std::max<uint64_t>(bytes, 32));
+    *dev_ptr_out = b.p;
+    ctx->allocs.push_back(std::move(b));
     return MSM_OK;
   } MSM_CATCH_ALL(ctx)
 }
 
 int msm_device_free(msm_ctx* ctx, void* dev_ptr) {
   if (!ctx) return MSM_ERR_ARG;
-  auto it = std::find(ctx->allocs.begin(), ctx->allocs.end(), dev_ptr);
+  auto it = std::find_if(ctx->allocs.begin(), ctx->allocs.end(), [&](const DevBuf& b) { return b.p == dev_ptr; });
   if (it == ctx->allocs.end()) return fail(ctx, MSM_ERR_ARG, "msm_device_free: not a buffer of this context");
   try {
     HIPCHK(hipSetDevice(ctx->device));
+    DevBuf b = std::move(*it);
     ctx->allocs.erase(it);
-    HIPCHK(hipFree(dev_ptr));
+    b.release(/*checked=*/true);
     return MSM_OK;
   } MSM_CATCH_ALL(ctx)
 }
@@ -476,10 +448,7 @@ int msm_set_workspace_limit(msm_ctx* ctx, uint64_t bytes) {
       HIPCHK(hipSetDevice(ctx->device));
       size_t free_b = 0, total_b = 0;
       HIPCHK(hipMemGetInfo(&free_b, &total_b));
-      uint64_t held = 0;
-      for (auto& w : ctx->ws)
-        for (DevBuf* b : w.all) held += b->cap;
-      ctx->ws_budget = (uint64_t)((free_b + held) * 0.55L);
+      ctx->ws_budget = (uint64_t)((free_b + ctx->workspace_bytes()) * 0.55L);
     } MSM_CATCH_ALL(ctx)
   }
   for (msm_ctx* c : ctx->children) {

@@ -158,7 +158,7 @@ int generate_points(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) {
         }
     }
   }
-  ScopedDevBuf d_wire, d_tbl;   // freed on every path
+  DevBuf d_wire, d_tbl;
   ctx->ensure(d_wire, wire.size());
   ctx->ensure(d_tbl, (size_t)N_BASIS * TBL * msm::ROW_WORDS * 4);
   HIPCHK(hipMemcpyAsync(d_wire.p, wire.data(), wire.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -172,8 +172,6 @@ int generate_points(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) {
   HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipGetLastError());
-  ctx->release(d_wire);
-  ctx->release(d_tbl);
   if (ctx->h_info[0]) {
     ctx->err = "msm_generate_points: table point failed validation";
     return MSM_ERR_POINT;
@@ -243,7 +241,7 @@ int generate_points_te(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) 
         }
     }
   }
-  ScopedDevBuf d_wire, d_tbl, d_pts;
+  DevBuf d_wire, d_tbl, d_pts;
   ctx->ensure(d_wire, wire.size());
   ctx->ensure(d_tbl, (size_t)N_BASIS * TBL * msm::te::TE_ROW_WORDS * 4);
   ctx->ensure(d_pts, std::max<uint64_t>(n, 1) * 64);
@@ -262,9 +260,6 @@ int generate_points_te(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) 
   HIPCHK(hipMemcpyAsync(ctx->h_info, ctx->errflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipGetLastError());
-  ctx->release(d_wire);
-  ctx->release(d_tbl);
-  ctx->release(d_pts);
   if (ctx->h_info[0]) {
     ctx->err = "msm_generate_points: table point failed validation";
     return MSM_ERR_POINT;

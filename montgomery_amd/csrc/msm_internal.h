@@ -29,6 +29,9 @@
 // argument checks from operator_checks.h and the host side of the scalar field from scalar_host.h.
 // Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip, te_kernels.hip and narrow_kernels.hip; host TUs see
 // declarations.
+// Ownership: every device buffer, pinned host block, stream and event is a move-only member or local (msmi::DevBuf, Pinned, Stream,
+// Event) that its holder's destructor frees; nothing else frees, and no list of names says what a context, a point set, a matrix
+// or a call gives back.
 // Orchestration follows `createMsm().msm` (reference src/msm-batched-affine.ts:69-340); the per-thread SPMD phases separated
 // by `barrier()` there become kernel launches on one HIP stream here.
 #pragma once
@@ -55,6 +58,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <utility>
 #include <vector>
 
 // Policy knobs -- the six thresholds that are re-measured when a plan changes (MSM_GROUPS, MSM_MAX_STEPS, MSM_PBL, MSM_TC,
@@ -70,21 +74,6 @@
 #endif
 
 namespace msmi {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
-// a DevBuf local to one call: freed on every way out of the scope, exceptions included
-struct ScopedDevBuf : DevBuf {
-  ScopedDevBuf() = default;
-  ScopedDevBuf(const ScopedDevBuf&) = delete;
-  ScopedDevBuf& operator=(const ScopedDevBuf&) = delete;
-  ~ScopedDevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
 
 struct HipFail {
   hipError_t e;
@@ -105,6 +94,76 @@ struct MsmFail {
     hipError_t _e = (x);                            \
     if (_e != hipSuccess) throw msmi::HipFail{_e, #x, __LINE__, __FILE__}; \
   } while (0)
+
+// The owner types: move-only, a moved-from owner is empty, and an empty one makes no HIP call.
+
+// live device buffers of the process and their bytes as allocated (msm_test_live_buffers)
+inline std::atomic<uint64_t> live_buffers{0}, live_buffer_bytes{0};
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  DevBuf& operator=(DevBuf o) noexcept {   // (the source is emptied into o; what this held goes back with o)
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  // room for `bytes`: what is there if it suffices, otherwise a new block with some slack (the old one goes back first)
+  void ensure(size_t bytes) {
+    if (bytes <= cap) return;
+    release(/*checked=*/true);
+    allocate(bytes + bytes / 16 + 256);
+  }
+  // a block of exactly `want` bytes into an empty buffer; a failure leaves it empty
+  void allocate(size_t want) {
+    const hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();   // the failure must not stay behind as this thread's "last error": the kernel-launch checks read it
+      p = nullptr;
+      throw HipFail{e, "hipMalloc(&p, want)", __LINE__, __FILE__};
+    }
+    cap = want;
+    live_buffers++;
+    live_buffer_bytes += want;
+  }
+  // checked: throws what hipFree reports; teardown paths have nothing useful to do with an error
+  void release(bool checked = false) {
+    if (p) {
+      const hipError_t e = hipFree(p);
+      if (checked) HIPCHK(e);
+      live_buffers--;
+      live_buffer_bytes -= cap;
+    }
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// a stream, an event or a pinned host block: H the handle (null: nothing here), Destroy what gives it back
+template <class H, auto Destroy>
+struct Owned {
+  Owned() = default;
+  Owned(Owned&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+  ~Owned() {
+    if (h) (void)Destroy(h);
+  }
+  operator H() const { return h; }
+  H h = nullptr;
+};
+struct Stream : Owned<hipStream_t, hipStreamDestroy> {   // non-blocking
+  void create() { HIPCHK(hipStreamCreateWithFlags(&h, hipStreamNonBlocking)); }
+  void create(int priority) { HIPCHK(hipStreamCreateWithPriority(&h, hipStreamNonBlocking, priority)); }
+};
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+  void create(unsigned flags = hipEventDefault) { HIPCHK(hipEventCreateWithFlags(&h, flags)); }
+};
+template <class T>
+struct Pinned : Owned<T*, hipHostFree> {
+  void allocate(size_t bytes) { HIPCHK(hipHostMalloc((void**)&this->h, bytes, hipHostMallocDefault)); }
+};
 
 inline uint32_t ceil_log2_u64(uint64_t n) {
   uint32_t r = 0;
@@ -224,9 +283,9 @@ struct msm_ctx {
   std::unique_ptr<msmi::HelperThread> helper;
   int curve = 0;
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[12] = {};
-  hipEvent_t ev_dig[2] = {};   // around the digit kernel that serves both window groups of a call (GroupDigits)
+  msmi::Stream stream;
+  msmi::Event ev[12];
+  msmi::Event ev_dig[2];   // around the digit kernel that serves both window groups of a call (GroupDigits)
   std::string err;
   int n_cu = 256;
 
@@ -245,7 +304,7 @@ struct msm_ctx {
     bool covers(uint64_t l, uint64_t m) const { return K && lo == l && n == m; }
     bool whole_set_pinned() const { return K && in_rows; }
     void clear() { T = 0; c = K = 0; lo = n = 0; in_rows = false; }
-    void drop(msm_ctx* ctx) { clear(); ctx->release(buf); }   // (the description goes first)
+    void drop() { clear(); buf.release(); }   // (the description goes first)
   };
   // A resident point set (msm_pointset_*): its rows, one per point, and its window tables.  `sets` holds them all; the
   // CURRENT one, which every call reads, is sets[cur_set] (pts()).
@@ -255,7 +314,7 @@ struct msm_ctx {
     bool live = false;   // (slot 0, the default set, always is)
     WindowTables tab;
     const uint32_t* table_rows() const { return (const uint32_t*)(tab.in_rows ? rows.p : tab.buf.p); }
-    void release(msm_ctx* ctx) { tab.drop(ctx); ctx->release(rows); *this = PointSet(); }
+    void release() { tab.clear(); *this = PointSet(); }   // (the description goes first, then whatever the set holds)
   };
   std::vector<PointSet> sets = std::vector<PointSet>(1);   // slot 0 = the default set
   int cur_set = 0;
@@ -266,7 +325,7 @@ struct msm_ctx {
   // the same for any set of the context (msm_points_lincomb writes into sets that are not current)
   uint32_t* reset_points(PointSet& s, uint64_t n) {
     s.n = 0;
-    s.tab.drop(this);   // window tables belong to the points they were built from
+    s.tab.drop();   // window tables belong to the points they were built from
     cand_n = 0;
     ensure(s.rows, std::max<uint64_t>(n, 1) * row_words() * 4);
     return (uint32_t*)s.rows.p;
@@ -276,23 +335,23 @@ struct msm_ctx {
   uint64_t cand_lo = 0, cand_n = 0;
   int cand_c = 0;
   uint64_t tables_limit = 0;   // bytes the tables of one point set may take (msm_set_tables_limit; default: 20 % of the device)
-  std::vector<void*> allocs;        // device buffers handed out by msm_device_alloc
+  std::vector<msmi::DevBuf> allocs; // device buffers handed out by msm_device_alloc
   // multi-device context (msm_ctx_create_multi): this context drives devices[0], one child context per further device
   std::vector<msm_ctx*> children;
   std::vector<std::unique_ptr<msmi::HelperThread>> fan;   // one host thread per child for the window-shard fan-out
 
   // staging / misc buffers shared by all window groups
   msmi::DevBuf scal, errflag, misc;
-  uint32_t* h_info = nullptr;      // pinned
+  msmi::Pinned<uint32_t> h_info;   // 64 words
   // host -> device staging of big pageable buffers (upload_staged): pinned chunks, a copy stream and an event per chunk slot
   static constexpr int STAGE_THREADS = 4, STAGE_SLOTS = 2;
   static constexpr size_t STAGE_CHUNK = (size_t)16 << 20;
-  char* stage_pin = nullptr;
+  msmi::Pinned<char> stage_pin;
   bool staging_ready = false;      // pinned slots, copy streams and events all exist (ensure_staging)
-  hipStream_t stage_stream[STAGE_THREADS] = {};
-  hipEvent_t stage_ev[STAGE_THREADS][STAGE_SLOTS + 1] = {};
+  msmi::Stream stage_stream[STAGE_THREADS];
+  msmi::Event stage_ev[STAGE_THREADS][STAGE_SLOTS + 1];
   static constexpr int MAX_PIECES = 6;   // ranges of the points a host-scalar MSM is pipelined over (PieceUpload)
-  hipEvent_t piece_ev[MAX_PIECES][STAGE_THREADS] = {};
+  msmi::Event piece_ev[MAX_PIECES][STAGE_THREADS];
   uint64_t ws_budget = 0;          // bytes the per-group workspaces may take in total
   uint64_t ws_limit = 0;           // msm_set_workspace_limit: the caller's cap on ws_budget (0 = automatic)
   // log2 of the table rows above which round 1 of a big window takes the pair form (sort_geometry, where the measurements
@@ -303,7 +362,7 @@ struct msm_ctx {
   // written when all of them have run, so a call that failed, or a fused batch, leaves it empty
   std::vector<int32_t> last_sort_paths;
   // msm_scalars_ntt (msm_ntt.hip): the twiddle tables of one (log2n, omega) at a time, both directions; the two-level table of the
-  // shift of the last coset call; the vector that the passes before the last work in.  Freed with the context.
+  // shift of the last coset call; the vector that the passes before the last work in.
   msmi::DevBuf ntt_tw, ntt_shift, ntt_scratch;
   int ntt_tw_log2n = -1;           // -1: no tables
   uint8_t ntt_tw_omega[32] = {};   // the root the tables are of, 32 bytes little-endian
@@ -311,13 +370,13 @@ struct msm_ctx {
   int ntt_tile_log = 0;            // msm_test_set_ntt_tile_log: stages a pass may have; 0 = ntt::DEFAULT_TILE_LOG
   std::vector<int32_t> last_ntt_plan;   // stages per pass of the last msm_scalars_ntt (msm_test_last_ntt_plan); empty after a refusal
   // msm_scalars_scan / _inverse / _div_linear (msm_scan.hip): the call's total, then one 32-byte aggregate per tile and level (the
-  // inverse keeps its per-block zero counts there).  Freed with the context.
+  // inverse keeps its per-block zero counts there).
   msmi::DevBuf scan_agg;
   int scan_tile_log = 0;           // msm_test_set_scan_tile_log: elements per tile = 2^it; 0 = scan::DEFAULT_TILE_LOG
   std::vector<int32_t> last_scan_plan;  // tiles per level of the last scan / div_linear (msm_test_last_scan_plan); empty after a refusal
 
   // msm_points_mul / msm_points_mul_base (msm_points_mul.hip): the per-lane tables of the variable-base kernel's grid; the row of
-  // the fixed base and its shared table of rows, cached under the base's bytes.  Freed with the context.
+  // the fixed base and its shared table of rows, cached under the base's bytes.
   msmi::DevBuf pmul_tbl, pmul_row, pmul_base_tbl;
   uint8_t pmul_base_key[97] = {};   // 1 + x || y of the base the table is of (first byte 2, the rest zero: the generator)
   bool pmul_base_cached = false;
@@ -327,24 +386,21 @@ struct msm_ctx {
   int32_t last_pmul[4] = {};        // grid, w, path, table rows of the last call (msm_test_last_points_mul)
 
   // msm_scalars_sumcheck_round / _bind / _eq (msm_mle.hip): the round's results and its partials per block and value; the two
-  // half-tables of the last eq.  Freed with the context.
+  // half-tables of the last eq.
   msmi::DevBuf mle_part, mle_tab;
   int mle_grid = 0;                 // msm_test_set_sumcheck_grid: blocks of the round kernel; 0 = the default
   int32_t last_mle[4] = {0, 0, 0, -1};   // blocks, pairs, values of the last round; split k of the last eq (msm_test_last_sumcheck)
 
   // msm_matrix_* / msm_scalars_matvec (msm_spmv.hip): resident sparse matrices in CSR, each the sole owner of its arrays -- the
   // column indices, the coefficients in Montgomery form (none in the all-ones form), and the plan of its long rows with their
-  // partials (scalar_spmv.h).  `mats` holds them all; slot 0 is never live, ids start at 1.  Freed with the context.
+  // partials (scalar_spmv.h).  `mats` holds them all; slot 0 is never live, ids start at 1.
   struct Matrix {
     bool live = false, ones = false;
     uint64_t rows = 0, cols = 0, nnz = 0;
     uint32_t short_max = 0, part_len = 0, n_long = 0, n_parts = 0;
     msmi::DevBuf row_ptr, col, val, parts, long_rows, long_first, partials;
     uint64_t bytes() const { return row_ptr.cap + col.cap + val.cap + parts.cap + long_rows.cap + long_first.cap + partials.cap; }
-    void release(msm_ctx* ctx) {
-      for (msmi::DevBuf* b : {&row_ptr, &col, &val, &parts, &long_rows, &long_first, &partials}) ctx->release(*b);
-      *this = Matrix();
-    }
+    void release() { *this = Matrix(); }
   };
   std::vector<Matrix> mats = std::vector<Matrix>(1);
   uint32_t spmv_short_max = 0, spmv_part_len = 0;   // msm_test_set_matvec_geometry: for matrices created afterwards; 0 = the default
@@ -352,17 +408,22 @@ struct msm_ctx {
 
   // per-group workspace: two of them, each with its own stream, so that the memory-bound sort of one
   // window group runs under the ALU-bound accumulation of the other
+  // (its device buffers are named ONCE, here: the members and for_each_buffer both come from this list)
+#define MSM_WS_BUFFERS(X)                                                                                                            \
+  X(dig) X(counts) X(cursor) X(tail_off) X(info) X(slots) X(block_hist) X(scan_partial) X(desc) X(columns2) X(rows_sum) X(bucket_proj) \
+  X(bufA) X(bufB) X(scratch) X(columns) X(partials) X(part) X(dig2) X(idx2) X(rec) X(blk_tab2) X(slots2) X(dest) X(rows1) X(parts) X(sub)
   struct Workspace {
-    msmi::DevBuf dig, counts, cursor, tail_off, info, slots, block_hist, scan_partial, desc, columns2, rows_sum, bucket_proj, bufA, bufB,
-        scratch, columns, partials, part, dig2, idx2, rec, blk_tab2, slots2, dest, rows1, parts, sub;
-    hipStream_t stream = nullptr;
-    hipStream_t side = nullptr;   // read-backs that the host needs while `stream` goes on (the sort's totals under its last pass)
-    hipEvent_t ev[8] = {};        // (ev[7]: the scans of the bucket sizes are done)
-    uint32_t* h_info = nullptr;   // pinned, 64 words
-    uint32_t* h_part = nullptr;   // pinned, window sums read-back
-    msmi::DevBuf* all[27] = {&dig, &counts, &cursor, &tail_off, &info, &slots, &block_hist, &scan_partial, &desc, &columns2, &rows_sum,
-                       &bucket_proj, &bufA, &bufB, &scratch, &columns, &partials, &part, &dig2, &idx2, &rec, &blk_tab2, &slots2, &dest, &rows1,
-                       &parts, &sub};
+#define MSM_WS_MEMBER(NAME) msmi::DevBuf NAME;
+    MSM_WS_BUFFERS(MSM_WS_MEMBER)
+#undef MSM_WS_MEMBER
+#define MSM_WS_VISIT(NAME) fn(NAME);
+    template <class Fn> void for_each_buffer(Fn&& fn) { MSM_WS_BUFFERS(MSM_WS_VISIT) }
+#undef MSM_WS_VISIT
+    msmi::Stream stream;
+    msmi::Stream side;            // read-backs that the host needs while `stream` goes on (the sort's totals under its last pass)
+    msmi::Event ev[8];            // (ev[7]: the scans of the bucket sizes are done)
+    msmi::Pinned<uint32_t> h_info;   // 64 words
+    msmi::Pinned<uint32_t> h_part;   // window sums read-back
   };
   static constexpr int N_WS = 2;
   Workspace ws[N_WS];
@@ -380,24 +441,28 @@ struct msm_ctx {
   uint64_t row_words() const { return is_te() ? (uint64_t)msm::te::TE_ROW_WORDS : (uint64_t)msm::ROW_WORDS; }   // of a point row
   int sum_words() const { return is_te() ? msmi::TE_SUM_WORDS : msmi::W_SUM_WORDS; }                            // of a window-sum slot
 
-  void ensure(msmi::DevBuf& b, size_t bytes) {
-    if (bytes <= b.cap) return;
-    if (b.p) HIPCHK(hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    size_t want = bytes + bytes / 16 + 256;
-    const hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();   // the failure must not stay behind as this thread's "last error": the kernel-launch checks read it
-      b.p = nullptr;
-      throw msmi::HipFail{e, "hipMalloc(&b.p, want)", __LINE__, __FILE__};
-    }
-    b.cap = want;
+  void ensure(msmi::DevBuf& b, size_t bytes) { b.ensure(bytes); }
+  void release(msmi::DevBuf& b) { b.release(); }
+  // bytes the workspaces hold: what a new budget may count on beside the device's free memory
+  uint64_t workspace_bytes() {
+    uint64_t held = 0;
+    for (auto& w : ws) w.for_each_buffer([&](msmi::DevBuf& b) { held += b.cap; });
+    return held;
   }
-  void release(msmi::DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);   // teardown paths: nothing useful to do with an error here
-    b.p = nullptr;
-    b.cap = 0;
+
+  // What must happen in order: no thread of the context runs any more, and every stream that exists is idle.  The members free
+  // everything else.  (Children go first, by msm_ctx_destroy.)  A context that never created a stream makes no HIP call.
+  ~msm_ctx() {
+    fan.clear();
+    helper.reset();
+    if (!stream) return;
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+    for (auto& w : ws) {
+      if (w.stream) (void)hipStreamSynchronize(w.stream);
+      if (w.side) (void)hipStreamSynchronize(w.side);
+    }
+    for (auto& st : stage_stream) if (st) (void)hipStreamSynchronize(st);
   }
 };
 

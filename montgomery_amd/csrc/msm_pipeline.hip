@@ -77,10 +77,7 @@ CallSetup prepare_call(msm_ctx* ctx, const void* scalars, uint64_t n, int on_dev
     // gone since the context was made) plus what the workspaces already hold
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    uint64_t held = 0;
-    for (auto& w : ctx->ws)
-      for (DevBuf* b : w.all) held += b->cap;
-    ctx->ws_budget = (uint64_t)((free_b + held) * 0.85L);
+    ctx->ws_budget = (uint64_t)((free_b + ctx->workspace_bytes()) * 0.85L);
   }
   cs.sch = group_schedule(ctx, n, p_off, k_lo, k_hi, pl, cs.piece_end, serial);
   if (cs.sch.piped) {

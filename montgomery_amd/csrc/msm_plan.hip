@@ -231,7 +231,7 @@ RoundGeom round_geom(const msm_ctx* ctx, uint64_t n_out, bool gather, bool lone)
 void release_workspaces(msm_ctx* ctx) {
   for (auto& w : ctx->ws) {
     (void)hipStreamSynchronize(w.stream);
-    for (DevBuf* b : w.all) ctx->release(*b);
+    w.for_each_buffer([](DevBuf& b) { b.release(); });
   }
 }
 

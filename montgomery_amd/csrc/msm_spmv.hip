@@ -17,17 +17,6 @@ namespace {
 
 constexpr uint32_t CREATE_FLAGS = MSM_MATRIX_TRANSPOSE, MATVEC_FLAGS = MSM_MATVEC_ACCUMULATE;
 
-// a matrix under construction: what it holds is freed unless the creation reaches its end
-struct MatrixGuard {
-  msm_ctx* ctx;
-  msm_ctx::Matrix m;
-  bool keep = false;
-  explicit MatrixGuard(msm_ctx* c) : ctx(c) {}
-  ~MatrixGuard() {
-    if (!keep) m.release(ctx);
-  }
-};
-
 uint32_t check_grid(const msm_ctx* ctx, uint64_t items) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + spmv::BLOCK - 1) / spmv::BLOCK, (uint64_t)ctx->n_cu * 8));
 }
@@ -142,8 +131,7 @@ int msm_matrix_create(msm_ctx* ctx, uint64_t rows, uint64_t cols, uint64_t nnz, 
   if (on_device && ((uintptr_t)val & 15)) return fail(ctx, MSM_ERR_ARG, "%s: device val must be aligned to 16 bytes", who);
   try {
     HIPCHK(hipSetDevice(ctx->device));
-    MatrixGuard g(ctx);
-    msm_ctx::Matrix& m = g.m;
+    msm_ctx::Matrix m;   // under construction: what it holds is freed unless the creation reaches its end
     m.ones = val == nullptr;
     const uint32_t short_max = ctx->spmv_short_max ? ctx->spmv_short_max : spmv::DEFAULT_SHORT_MAX;
     const uint32_t part_len = ctx->spmv_part_len ? ctx->spmv_part_len : spmv::DEFAULT_PART_LEN;
@@ -208,8 +196,7 @@ int msm_matrix_create(msm_ctx* ctx, uint64_t rows, uint64_t cols, uint64_t nnz, 
       if (!ctx->mats[i].live) { id = (int)i; break; }
     if (id < 0) { ctx->mats.emplace_back(); id = (int)ctx->mats.size() - 1; }
     m.live = true;
-    ctx->mats[id] = m;
-    g.keep = true;
+    ctx->mats[id] = std::move(m);
     *id_out = id;
     return MSM_OK;
   } MSM_CATCH_ALL(ctx)
@@ -221,7 +208,7 @@ int msm_matrix_destroy(msm_ctx* ctx, int32_t id) {
   if (int rc = single_device_ok(ctx, who)) return rc;
   if (int rc = live_matrix_ok(ctx, who, id)) return rc;
   (void)hipSetDevice(ctx->device);
-  ctx->mats[id].release(ctx);
+  ctx->mats[id].release();
   return MSM_OK;
 }
 

@@ -47,15 +47,14 @@ static void build_tables(msm_ctx* ctx, const Plan& pl, uint64_t lo, uint64_t n) 
   };
   uint32_t* rows = nullptr;
   if (whole) {
-    t.drop(ctx);   // (range tables of this set, if any, are replaced)
+    t.drop();   // (range tables of this set, if any, are replaced)
     if (ps.rows.cap < bytes) {
       // a bigger buffer: table 0 (the plain rows) moves over, the old buffer goes back
       DevBuf big;
       ensure_or_retry(big);
       HIPCHK(hipMemcpyAsync(big.p, ps.rows.p, n * row_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
       HIPCHK(hipStreamSynchronize(ctx->stream));
-      ctx->release(ps.rows);
-      ps.rows = big;
+      ps.rows = std::move(big);
     }
     rows = (uint32_t*)ps.rows.p;
   } else {
@@ -186,7 +185,7 @@ int msm_precompute(msm_ctx* ctx, uint64_t n, const msm_opts* opts) {
   try {
     HIPCHK(hipSetDevice(ctx->device));
     // asked for explicitly, tables of a range replace the whole set's -- if the build goes ahead; if not, those stay
-    if (whole_set_tables_stay(ctx, n, opts) && buildable(ctx, n, opts, pl)) ctx->pts().tab.drop(ctx);
+    if (whole_set_tables_stay(ctx, n, opts) && buildable(ctx, n, opts, pl)) ctx->pts().tab.drop();
     (void)use_window_tables(ctx, n, opts, pl);   // not an error if they do not fit: the plain path stays
     return MSM_OK;
   } MSM_CATCH_ALL(ctx)

@@ -131,7 +131,6 @@ int msm_test_batch_add(msm_ctx* ctx, const uint8_t* g, const uint8_t* h, uint8_t
         memcpy(out + e * 64, xb, 32);
         memcpy(out + e * 64 + 32, yb, 32);
       }
-      for (DevBuf* b : {&rows, &wire, &slots, &outb}) ctx->release(*b);
     } MSM_CATCH_ALL(ctx)
     return MSM_OK;
   }
@@ -179,7 +178,6 @@ int msm_test_batch_add(msm_ctx* ctx, const uint8_t* g, const uint8_t* h, uint8_t
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipGetLastError());
     for (uint64_t e = 0; e < n; e++) plane_element_to_wire(ctx, planes.data(), n, e, out + e * pb);
-    for (DevBuf* b : {&rows, &wire, &slots, &outb, &scr}) ctx->release(*b);
   } MSM_CATCH_ALL(ctx)
   return MSM_OK;
 }
@@ -254,7 +252,7 @@ int msm_test_bucket_reduce(msm_ctx* ctx, const uint8_t* buckets, int32_t K, uint
     hipStream_t s = w.stream;
     const uint64_t nb = (uint64_t)K * L;
     const uint64_t cap = nb + 2 * 257 * 512 + 256;   // plane capacity: idle lanes read (and ignore) past the end
-    ScopedDevBuf wire, rows, planes, desc, scr;   // released on every path, a HIPCHK / MsmFail thrown in between included
+    DevBuf wire, rows, planes, desc, scr;
     const size_t pb = 2 * ctx->coord_bytes();
     const int nw = ctx->nw(), np = nw / 4;
     ctx->ensure(wire, nb * pb);
@@ -375,7 +373,6 @@ int msm_test_bucket_reduce(msm_ctx* ctx, const uint8_t* buckets, int32_t K, uint
     }
     for (int k = 0; k < K; k++) sum_to_wire(ctx, &parts[(size_t)k * W_SUM_WORDS], partials_out + (size_t)k * SUM_WIRE_BYTES);
     if (ms_out) *ms_out = ms;
-    for (DevBuf* b : {&wire, &rows, &planes, &desc, &scr}) ctx->release(*b);
     return MSM_OK;
   } MSM_CATCH_ALL(ctx)
 }
@@ -403,7 +400,7 @@ int msm_test_bucket_sums(msm_ctx* ctx, const uint8_t* pool, uint64_t n_pool, con
     const uint64_t cap = n_el + 2 * 257 * 512 + 256;   // plane capacity: idle lanes read (and ignore) past the end
     const size_t pb = 2 * ctx->coord_bytes();          // wire point
     const size_t elem_bytes = te ? 128 : pb;           // tree node: extended (X, Y, Z, T), or affine (x, y)
-    ScopedDevBuf wire, rows, planes, d_off, slots;
+    DevBuf wire, rows, planes, d_off, slots;
     ctx->ensure(planes, cap * elem_bytes);
     ctx->ensure(d_off, (nb + 1) * 4);
     HIPCHK(hipMemsetAsync(planes.p, 0, cap * elem_bytes, s));
@@ -501,7 +498,7 @@ int msm_test_tree_sums(msm_ctx* ctx, const uint8_t* pool, uint64_t n_pool, const
     hipStream_t s = w.stream;
     const size_t pb = 2 * ctx->coord_bytes();   // wire point
     // 1. the pool as point rows of its own (the resident set stays as it is), the bucket sizes where the sort leaves them
-    ScopedDevBuf wire, rows;
+    DevBuf wire, rows;
     ctx->ensure(wire, n_pool * pb);
     ctx->ensure(rows, n_pool * ctx->row_words() * 4);
     ctx->ensure(w.counts, nb * 4);
@@ -655,7 +652,6 @@ int msm_test_batch_add_mode(msm_ctx* ctx, const uint8_t* g, const uint8_t* h, ui
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipGetLastError());
     for (uint64_t e = 0; e < n; e++) plane_element_to_wire(ctx, pl.data(), a.out_cap, e, out + e * pb);
-    for (DevBuf* b : {&rows, &wire, &planes, &outb, &scr, &desc}) ctx->release(*b);
     return MSM_OK;
   } MSM_CATCH_ALL(ctx)
 }
@@ -793,6 +789,13 @@ int msm_test_last_matvec(msm_ctx* ctx, int32_t* out, int cap) {
   if (!ctx || !ctx->children.empty() || cap < 0 || (cap && !out)) return -1;
   for (int i = 0; i < 5 && i < cap; i++) out[i] = ctx->last_spmv[i];
   return 5;
+}
+
+int msm_test_live_buffers(uint64_t* count_out, uint64_t* bytes_out) {
+  if (!count_out || !bytes_out) return MSM_ERR_ARG;
+  *count_out = live_buffers.load();
+  *bytes_out = live_buffer_bytes.load();
+  return MSM_OK;
 }
 
 int msm_generate_points(msm_ctx* ctx, uint64_t n, uint64_t seed, uint8_t* a_out) {

@@ -16,16 +16,16 @@ void ensure_staging(msm_ctx* ctx) {
   constexpr int T = msm_ctx::STAGE_THREADS, S = msm_ctx::STAGE_SLOTS;
   if (ctx->staging_ready) return;
   // (a failure half way leaves what exists in place: the next call creates only what is still missing)
-  if (!ctx->stage_pin) HIPCHK(hipHostMalloc((void**)&ctx->stage_pin, (size_t)T * S * msm_ctx::STAGE_CHUNK, hipHostMallocDefault));
+  if (!ctx->stage_pin) ctx->stage_pin.allocate((size_t)T * S * msm_ctx::STAGE_CHUNK);
   int prio_lo = 0, prio_hi = 0;   // least and greatest priority (numerically lower = higher)
   HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
   for (int t = 0; t < T; t++) {
     // copies queued while kernels hold the chip must not wait behind them: highest priority the device offers
-    if (!ctx->stage_stream[t]) HIPCHK(hipStreamCreateWithPriority(&ctx->stage_stream[t], hipStreamNonBlocking, prio_hi));
+    if (!ctx->stage_stream[t]) ctx->stage_stream[t].create(prio_hi);
     for (int q = 0; q <= S; q++)
-      if (!ctx->stage_ev[t][q]) HIPCHK(hipEventCreateWithFlags(&ctx->stage_ev[t][q], hipEventDisableTiming));
+      if (!ctx->stage_ev[t][q]) ctx->stage_ev[t][q].create(hipEventDisableTiming);
     for (int q = 0; q < msm_ctx::MAX_PIECES; q++)
-      if (!ctx->piece_ev[q][t]) HIPCHK(hipEventCreateWithFlags(&ctx->piece_ev[q][t], hipEventDisableTiming));
+      if (!ctx->piece_ev[q][t]) ctx->piece_ev[q][t].create(hipEventDisableTiming);
   }
   ctx->staging_ready = true;
 }

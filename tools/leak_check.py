@@ -22,7 +22,7 @@ for i in range(cycles):
     free = torch.cuda.mem_get_info()[0]
     lo = min(lo, free)
     if i == 2: base = free                    # the runtime's own one-time pools (code objects, signals) are in by now
-    if i % 5 == 0: print(i, "free", free >> 20, "MiB  delta", (free0 - free) >> 20, "MiB", flush=True)
+    if i % 5 == 0: print(i, "free", free >> 20, "MiB  delta", (free0 - free) >> 20, "MiB  live buffers", MsmContext.test_live_buffers(), flush=True)
 free = torch.cuda.mem_get_info()[0]
 print("one-time MiB:", (free0 - base) >> 20, " growth over the later cycles MiB:", (base - free) >> 20)
 sys.exit(0 if base - free < (16 << 20) else 1)
