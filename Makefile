@@ -8,7 +8,7 @@ HIPFLAGS := -O3 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unus
 BUILD := build
 CURVES := CvBls377 CvBls381 CvPallas CvBn254 CvGrumpkin CvVesta
 CURVE_OBJS := $(CURVES:%=$(BUILD)/kernels_%.o)
-HOST_TUS := msm_plan msm_sort msm_tree msm_reduce msm_upload msm_pipeline msm_batch msm_tables msm_abi msm_test_abi msm_gen msm_ingest msm_narrow msm_indexed msm_lincomb msm_points_mul msm_scalars msm_ntt msm_scan msm_mle msm_spmv sort_kernels te_kernels narrow_kernels
+HOST_TUS := msm_plan msm_sort msm_tree msm_reduce msm_upload msm_pipeline msm_batch msm_tables msm_abi msm_test_abi msm_gen msm_ingest msm_narrow msm_indexed msm_lincomb msm_points_mul msm_points_ntt msm_scalars msm_ntt msm_scan msm_mle msm_spmv sort_kernels te_kernels narrow_kernels
 HOST_OBJS := $(HOST_TUS:%=$(BUILD)/%.o)
 KHDRS := $(CSRC)/msm_kernels.h $(CSRC)/batch_add.h $(CSRC)/msm_gen_kernels.h $(CSRC)/kernel_inst.h $(CSRC)/field.h $(CSRC)/packed.h $(CSRC)/curve.h \
          $(CSRC)/glv.h $(CSRC)/constants_gen.h
@@ -25,10 +25,12 @@ $(BUILD)/kernels_%.o: $(CSRC)/kernels_curve.hip $(KHDRS)
 	$(HIPCC) $(HIPFLAGS) -DMSM_CURVE_TU=$* -c $(CSRC)/kernels_curve.hip -o $@
 
 # the host pipeline is one translation unit per concern (msm_internal.h lists them); the curve-independent kernels have two of their own
-HHDRS := $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/points_mul.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h $(CSRC)/scalar_scan.h $(CSRC)/scalar_mle.h $(CSRC)/scalar_spmv.h $(CSRC)/scalar_host.h $(CSRC)/msm_internal.h $(CSRC)/operator_checks.h $(CSRC)/sort_kernels.h $(CSRC)/tree_kernels.h $(CSRC)/te_kernels.h $(CSRC)/narrow_kernels.h $(CSRC)/host_field.h include/msm_hip.h
+HHDRS := $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/points_mul.h $(CSRC)/points_ntt.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_ntt.h $(CSRC)/scalar_scan.h $(CSRC)/scalar_mle.h $(CSRC)/scalar_spmv.h $(CSRC)/scalar_host.h $(CSRC)/msm_internal.h $(CSRC)/operator_checks.h $(CSRC)/sort_kernels.h $(CSRC)/tree_kernels.h $(CSRC)/te_kernels.h $(CSRC)/narrow_kernels.h $(CSRC)/host_field.h include/msm_hip.h
 # msm_points_mul: with the loop-invariant code motion of the machine passes, every constant of the row loop's body (the GLV
 # vectors, q, p, beta) is kept in a scalar register across the whole loop and up to 37 of them go to vector lanes and back
 TUFLAGS_msm_points_mul := -mllvm -disable-machine-licm
+# msm_points_ntt: its stage kernel is that row loop with a butterfly behind the walk
+TUFLAGS_msm_points_ntt := -mllvm -disable-machine-licm
 $(BUILD)/%.o: $(CSRC)/%.hip $(HHDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(TUFLAGS_$*) -c $< -o $@
@@ -50,6 +52,7 @@ HOSTTEST_SCHEDULE := tests/csrc/libschedule_host.so
 HOSTTEST_NTT := tests/csrc/libntt_host.so
 HOSTTEST_SCANS := tests/csrc/libscans_host.so
 HOSTTEST_PMUL := tests/csrc/libpoints_mul_host.so
+HOSTTEST_PNTT := tests/csrc/libpoints_ntt_host.so
 HOSTTEST_SCALAR_HOST := tests/csrc/libscalar_host_host.so
 HOSTTEST_MLE := tests/csrc/libmle_host.so
 HOSTTEST_SPMV := tests/csrc/libspmv_host.so
@@ -57,7 +60,8 @@ HOSTTEST_SPMV := tests/csrc/libspmv_host.so
 hosttest: $(HOSTTEST) $(HOSTTEST_CYCLES) $(HOSTTEST_LINCOMB) $(HOSTTEST_SCALARS) $(if $(wildcard tests/csrc/schedule_host.hip),$(HOSTTEST_SCHEDULE)) \
           $(if $(wildcard tests/csrc/ntt_host.hip),$(HOSTTEST_NTT)) $(if $(wildcard tests/csrc/scans_host.hip),$(HOSTTEST_SCANS)) \
           $(if $(wildcard tests/csrc/points_mul_host.hip),$(HOSTTEST_PMUL)) $(if $(wildcard tests/csrc/scalar_host_host.hip),$(HOSTTEST_SCALAR_HOST)) \
-          $(if $(wildcard tests/csrc/mle_host.hip),$(HOSTTEST_MLE)) $(if $(wildcard tests/csrc/spmv_host.hip),$(HOSTTEST_SPMV))
+          $(if $(wildcard tests/csrc/mle_host.hip),$(HOSTTEST_MLE)) $(if $(wildcard tests/csrc/spmv_host.hip),$(HOSTTEST_SPMV)) \
+          $(if $(wildcard tests/csrc/points_ntt_host.hip),$(HOSTTEST_PNTT))
 # scalar_host.h on all seven scalar fields and the range and row rules of operator_checks.h, whose refusals go through the fail() of
 # msm_plan.hip over a bare context: tests/test_scalar_host.py
 $(HOSTTEST_SCALAR_HOST): tests/csrc/scalar_host_host.hip $(CSRC)/msm_plan.hip $(HHDRS)
@@ -86,6 +90,9 @@ $(HOSTTEST_LINCOMB): tests/csrc/lincomb_host.hip $(KHDRS) $(CSRC)/points_ingest.
 # the recoding and the lane bodies of points_mul.h on all seven curves, at every candidate window: tests/test_points_mul_host.py
 $(HOSTTEST_PMUL): tests/csrc/points_mul_host.hip $(KHDRS) $(CSRC)/points_mul.h $(CSRC)/te_kernels.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/points_mul_host.hip -o $(HOSTTEST_PMUL)
+# the index maps and the butterfly lane of points_ntt.h on the host: tests/test_points_ntt_host.py
+$(HOSTTEST_PNTT): tests/csrc/points_ntt_host.hip $(KHDRS) $(CSRC)/points_mul.h $(CSRC)/points_ntt.h $(CSRC)/te_kernels.h
+	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/points_ntt_host.hip -o $(HOSTTEST_PNTT)
 # the cycle curves (BN254 G1, Grumpkin, Vesta), with the square root of points_ingest.h: tests/test_cycle_curves.py
 $(HOSTTEST_CYCLES): tests/csrc/field_host_cycles.hip $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/te_kernels.h
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/field_host_cycles.hip -o $(HOSTTEST_CYCLES)

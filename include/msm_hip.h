@@ -74,7 +74,9 @@ enum {
  * msm_device_download came the same way: five new symbols, version 8 and both struct sizes unchanged.  A binding detects the
  * feature by the presence of the symbol msm_scalars_lincomb.
  * Per-row scalar multiplication of point sets (msm_points_mul, msm_points_mul_base) came the same way: two new symbols, version 8
- * and both struct sizes unchanged.  A binding detects the feature by the presence of the symbol msm_points_mul. */
+ * and both struct sizes unchanged.  A binding detects the feature by the presence of the symbol msm_points_mul.
+ * The transform over point sets (msm_points_ntt) came the same way: one new symbol, version 8 and both struct sizes unchanged.  A
+ * binding detects the feature by the presence of the symbol msm_points_ntt. */
 #define MSM_ABI_VERSION 8
 uint32_t msm_abi_version(void);
 uint32_t msm_abi_struct_bytes(int which);
@@ -621,6 +623,48 @@ int msm_points_mul(msm_ctx* ctx, int32_t src, uint64_t a_lo, const void* scalars
  * the variable-base kernel over a broadcast row instead. */
 int msm_points_mul_base(msm_ctx* ctx, const uint8_t* base_xy, const void* scalars, int on_device, uint64_t count, int32_t dst);
 
+/* The number-theoretic transform over POINTS: with n = 2^log2n and A = the rows [a_lo, a_lo + n) of point set `src`,
+ *   forward:  D[k] = sum_j (shift omega^k)^j A[j]
+ *   inverse:  the exact inverse map (the factors n^-1 and shift^-j included)
+ * natural order in and out, written as the rows [0, n) of point set `dst`, which then holds exactly n points.  inverse = 1 over
+ * the monomial commitment key [tau^j] G gives the key in the Lagrange basis, [L_k(tau)] G on <omega> (PLONK / Halo2's
+ * g_lagrange, gnark's ToLagrangeG1, EIP-4844's setup) -- tau is unknown, so the transform has to run over the group elements --
+ * and an msm_run over EVALUATIONS on that key commits to the polynomial msm_scalars_ntt would interpolate.  On a coset the two
+ * maps part: the evaluations are M f with M[k][j] = (shift omega^k)^j, the key that commits to them is the TRANSPOSE inverse
+ * (M^T)^-1 A, and M is symmetric only for shift = 1.  The Lagrange key of the coset shift <omega> is therefore n^-1 times the
+ * FORWARD transform under omega^-1 and shift^-1 -- row k = n^-1 sum_j (shift omega^k)^-j A[j] = [L_k(tau)] G -- the factor n^-1
+ * being one msm_points_lincomb; inverse = 1 with a shift is the inverse of the forward map, which is what a round trip needs.
+ * The reference has no counterpart.  The contract is that of msm_points_mul and msm_scalars_ntt wherever this text does not say
+ * otherwise: point-set ids, dst replaced as by msm_set_points (window tables dropped, range candidate reset, size n), the
+ * current set not switched, all checks before anything is written, the call returning when the rows are in place.
+ * Single-device contexts only.
+ * omega, shift: the rules of msm_scalars_ntt.  omega NULL is the library's root (msm_scalars_root_of_unity); the host checks
+ *   omega^(n/2) = q - 1 for n >= 2 and fails with MSM_ERR_ARG and a message about the order otherwise; a value >= q is
+ *   MSM_ERR_SCALAR; a shift of 0 is MSM_ERR_ARG.  For n = 1 omega is ignored and the call is a copy.
+ * Limits: log2n above msm_scalars_ntt_max_log2n is MSM_ERR_ARG: Grumpkin and Ed-on-BLS12-377 accept log2n <= 1 only, which is
+ *   the correct answer for those fields.  A source range that ends beyond its set is MSM_ERR_NO_POINTS.
+ * In place: dst == src is allowed with a_lo == 0 (the set is truncated to n) and with a_lo >= n; any other overlap is
+ *   MSM_ERR_ARG.  The in-place form allocates no second row buffer.
+ * Result rows are bit-identical to what msm_set_points writes for the same affine points, the beta x line included; the identity
+ *   takes the identity row.  Every later call works on dst: msm_run with and without the endomorphism, msm_precompute,
+ *   msm_get_points(_ex), msm_points_*.  Identity rows, equal rows and a butterfly whose two terms are equal or opposite are
+ *   ordinary input.
+ * Points outside the prime-order subgroup: the Weierstrass path uses the endomorphism, so the result is the transform only for
+ *   rows of the subgroup.  A torsion row neither faults nor disturbs the rows of other butterflies; it does spread to every
+ *   output, as the mathematics says.
+ * How: radix 2, decimation in time, in place in dst: a bit reversal of the rows (a gather, or pairwise swaps in place), then one
+ *   launch per stage of n / 2 butterflies (A, B) -> (A + w B, A - w B) on the fixed grid of msm_points_mul.  A lane computes w B
+ *   with that call's walk (in its per-lane table workspace, which counts against msm_set_workspace_limit), adds the affine row A
+ *   onto +-(w B) and takes both sums to affine with one inversion.  Butterflies with w = 1 skip the walk: stage 1 has no
+ *   multiplication, and an unshifted forward transform does (n / 2)(log2n - 2) + 1 of them in all.  A forward shift other than 1
+ *   costs one msm_points_mul pass over the powers of shift before the stages, the inverse one over n^-1 shift^-j after them.
+ * Device memory beyond the rows, owned by the context and freed with it: the vector omega^j (inverse: omega^-j), j < n / 2, 16 n
+ *   bytes, of one (log2n, omega, direction) at a time -- a second call with the same triple builds nothing -- and, for a coset or
+ *   an inverse, 32 n bytes of scalars. */
+int msm_points_ntt(msm_ctx* ctx, int32_t src, uint64_t a_lo, uint32_t log2n,
+                   const uint8_t* omega /* 32 B LE, NULL = the library's root */,
+                   const uint8_t* shift /* 32 B LE, NULL = 1 */, int inverse, int32_t dst);
+
 /* Window-sharded form for multi-GPU runs: computes the partition sums P_k for k in [k_lo, k_hi)
  * only (src/msm-batched-affine.ts:42 "P_k = sum_l l * B_(k,l)") and writes them as
  * (k_hi - k_lo) x 144 bytes: X || Y || Z homogeneous projective, 48-byte little-endian canonical
@@ -778,6 +822,16 @@ int msm_test_set_points_mul_base_path(msm_ctx* ctx, int32_t path);
  * (0: no launch), window bits, path (0 = msm_points_mul, 1 = table, 2 = broadcast) and rows of the fixed-base table used (0:
  * none).  Writes min(4, cap) of them and returns 4, or -1 for a null or device-list context. */
 int msm_test_last_points_mul(msm_ctx* ctx, int32_t* out, int cap);
+/* The stages of msm_points_ntt run on a fixed grid of 256-lane blocks with a grid-stride loop over the butterflies.  This entry
+ * sets the number of blocks for the context (0: the default, as many as stay resident at once and no more than the butterflies
+ * need), so that 512 butterflies under one block make every lane take two and rebuild its table slots.  Results do not depend on
+ * it.  Refused on a device-list context. */
+int msm_test_set_points_ntt_grid(msm_ctx* ctx, int32_t blocks);
+/* The plan of the last msm_points_ntt of the context, seven words: log2n, butterfly launches, blocks of their grid, how many of
+ * those launches were multiplication-free, whether a pass of pre-scaling (a forward shift) ran, whether a pass of post-scaling
+ * (the inverse's n^-1 shift^-j) ran, and the butterflies planned with a twiddle other than 1 (capped at 2^31 - 1); all 0 after
+ * a refused call.  Writes min(7, cap) of them and returns 7, or -1 for a null or device-list context. */
+int msm_test_last_points_ntt(msm_ctx* ctx, int32_t* out, int cap);
 int msm_test_set_scan_tile_log(msm_ctx* ctx, int32_t tile_log);
 /* The tiles per level of the last msm_scalars_scan or msm_scalars_div_linear on this context, bottom level first (the last entry
  * is 1); none (count 0) after a call that was refused or had n == 0: writes min(count, cap) of them to `tiles_out` (may be NULL

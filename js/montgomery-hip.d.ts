@@ -70,6 +70,12 @@ export interface Parallel {
    *  curve's generator.  Returns dstPtr */
   pointsMulBase(dstPtr: PointPtr, scalars: ScalarPtr | Uint8Array, base?: { x: bigint; y: bigint } | Uint8Array | null,
                 options?: { sLo?: number; count?: number }): PointPtr;
+  /** the transform over points (msm_points_ntt): dst = the transform of the n = 2^log2n points [aLo, aLo + n) behind ptrA, natural
+   *  order; forward: dst[k] = sum_j (shift omega^k)^j A[j]; inverse: the exact inverse map (without a shift a monomial key becomes the
+   *  Lagrange key of <omega>); omega: default scalarsRootOfUnity(log2n), shift: default 1; dstPtr may be ptrA with aLo = 0 or
+   *  aLo >= n.  Returns dstPtr */
+  pointsNtt(dstPtr: PointPtr, ptrA: PointPtr, log2n: number,
+            options?: { aLo?: number; inverse?: boolean; omega?: bigint | number | Uint8Array | null; shift?: bigint | number | Uint8Array | null }): PointPtr;
   /** resident scalar vectors (msm_scalars_lincomb): dst[i] = x * A[aLo + i] + y * B[bLo + i] mod the group order, i < count, over
    *  scalars that stay on the device; x, y below the group order, y and ptrB null for one term; dstPtr may be a source.  Returns dstPtr */
   scalarsLincomb(dstPtr: ScalarPtr, x: bigint | number | Uint8Array, ptrA: ScalarPtr, y?: bigint | number | Uint8Array | null, ptrB?: ScalarPtr | null,

@@ -231,6 +231,18 @@ function createCurve(params, curveId, coordBytes, device, wireBytes) {
       dstPtr.n = hip.pointsMulBase(ctx, b, v.arg, v.off, v.count, dstPtr.set);
       return dstPtr;
     },
+    // The transform over points (msm_points_ntt; the reference has no counterpart): the points behind dstPtr become the transform
+    // of the n = 2^log2n points [aLo, aLo + n) behind ptrA, natural order in and out.  forward: dst[k] = sum_j (shift omega^k)^j A[j];
+    // inverse: the exact inverse map -- over a monomial key [tau^j] G and without a shift it gives the key in the Lagrange basis
+    // of <omega>; the key of the coset shift <omega> is 1 / n times the FORWARD transform under omega^-1 and shift^-1.  options: {aLo, inverse, omega, shift} -- omega: a primitive n-th root of unity (default:
+    // scalarsRootOfUnity(log2n)), shift: in [1, order) (default 1), both BigInt / number or 32 bytes.  dstPtr may be ptrA with
+    // aLo = 0 or aLo >= n.
+    pointsNtt(dstPtr, ptrA, log2n, options) {
+      const o = options || {};
+      const opt = (v, what) => (v === undefined || v === null ? null : scalarBuffer(v, what));
+      dstPtr.n = hip.pointsNtt(ctx, ptrA.set, o.aLo || 0, log2n, opt(o.omega, "omega"), opt(o.shift, "shift"), !!o.inverse, dstPtr.set);
+      return dstPtr;
+    },
     // Resident scalar vectors (msm_scalars_*; the reference has no counterpart): arithmetic mod the group order over the scalars
     // behind scalar pointers, which stay on the device.  Host scalars x, y, s: BigInt / number or 32 bytes, below the group order
     // (a larger value throws msm error 6); elements of the vectors may be any 32-byte integers and are taken mod the order.

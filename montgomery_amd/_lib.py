@@ -60,6 +60,7 @@ EXPORTS = (
     "msm_scalars_scan", "msm_scalars_inverse", "msm_scalars_div_linear", "msm_test_set_scan_tile_log", "msm_test_last_scan_plan",
     "msm_points_mul", "msm_points_mul_base", "msm_test_set_points_mul_grid", "msm_test_set_points_mul_base_path",
     "msm_test_last_points_mul",
+    "msm_points_ntt", "msm_test_set_points_ntt_grid", "msm_test_last_points_ntt",
     "msm_scalars_sumcheck_round", "msm_scalars_bind", "msm_scalars_eq", "msm_test_set_sumcheck_grid", "msm_test_last_sumcheck",
     "msm_matrix_create", "msm_matrix_destroy", "msm_matrix_info", "msm_scalars_matvec", "msm_test_set_matvec_geometry",
     "msm_test_last_matvec",
@@ -266,6 +267,12 @@ def load() -> C.CDLL:
     lib.msm_test_set_points_mul_grid.argtypes = [vp, i32]
     lib.msm_test_set_points_mul_base_path.argtypes = [vp, i32]
     lib.msm_test_last_points_mul.argtypes = [vp, C.POINTER(i32), C.c_int]
+    # the transform over point sets, with its test surface: new symbols under ABI 8 as well
+    if not hasattr(lib, "msm_points_ntt"):
+        raise ImportError(f"{LIB_PATH} predates msm_points_ntt: rebuild it (`make`)")
+    lib.msm_points_ntt.argtypes = [vp, i32, u64, C.c_uint32, vp, vp, C.c_int, i32]
+    lib.msm_test_set_points_ntt_grid.argtypes = [vp, i32]
+    lib.msm_test_last_points_ntt.argtypes = [vp, C.POINTER(i32), C.c_int]
     # the resident sumcheck (round sums, variable binding, eq tables), with its test surface: new symbols under ABI 8 as well
     if not hasattr(lib, "msm_scalars_sumcheck_round"):
         raise ImportError(f"{LIB_PATH} predates msm_scalars_sumcheck_round: rebuild it (`make`)")

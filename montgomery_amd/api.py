@@ -862,6 +862,24 @@ class MsmContext:
         self._check(self._lib.msm_points_mul_base(self._h, bbuf, ptr, on_device, count, idst))
         return self._points_written(idst, count)
 
+    # -- the transform over point sets (msm_points_ntt, include/msm_hip.h) ----------------------
+    def points_ntt(self, *, src: Optional[int] = None, a_lo: int = 0, log2n: int, omega=None, shift=None, inverse: bool = False,
+                   dst: Optional[int] = None) -> int:
+        """The number-theoretic transform over the n = 2^log2n rows [a_lo, a_lo + n) of point set `src`, written as the rows
+        [0, n) of point set `dst` (msm_points_ntt).  forward: D[k] = sum_j (shift omega^k)^j A[j]; inverse: the exact inverse map
+        (n^-1 and shift^-j included): over a monomial key [tau^j] G and without a shift it gives the key in the Lagrange basis of
+        <omega> (the key of a coset: include/msm_hip.h).  omega: a primitive n-th root of unity < q (int or 32 bytes), None = scalars_root_of_unity(log2n); shift: in
+        [1, q), None = 1.  src, dst: point-set ids, default the current set; dst may be src with a_lo == 0 or a_lo >= n.
+        Returns n."""
+        if a_lo < 0 or log2n < 0:
+            raise MsmError(_lib.MSM_ERR_ARG, "points_ntt: a_lo and log2n must not be negative")
+        om = None if omega is None else self._scalar_buf(omega, "omega")
+        sh = None if shift is None else self._scalar_buf(shift, "shift")
+        cur = self._cur_set
+        isrc, idst = cur if src is None else src, cur if dst is None else dst
+        self._check(self._lib.msm_points_ntt(self._h, isrc, a_lo, log2n, om, sh, int(bool(inverse)), idst))
+        return self._points_written(idst, 1 << log2n)
+
     # -- resident scalar-vector operations (msm_scalars_*, include/msm_hip.h) -------------------
     def device_download(self, dev_ptr: int, nbytes: int) -> bytes:
         """`nbytes` bytes of device memory, from a buffer of device_alloc or any device address (msm_device_download)."""

@@ -25,7 +25,9 @@
 //                     debug surface, with the kernels of scalar_mle.h
 //   msm_spmv.hip      msm_matrix_create, _destroy, _info and msm_scalars_matvec (resident sparse matrices in CSR and y = alpha M x
 //                     (+ y) mod the group order), with the kernels of scalar_spmv.h
-// The operators over resident vectors and point sets (msm_scalars, msm_ntt, msm_scan, msm_mle, msm_spmv, msm_lincomb, msm_points_mul) take their
+//   msm_points_ntt.hip  msm_points_ntt (the transform over the rows of a point set), with the kernels of points_ntt.h
+// The operators over resident vectors and point sets (msm_scalars, msm_ntt, msm_scan, msm_mle, msm_spmv, msm_lincomb, msm_points_mul,
+// msm_points_ntt) take their
 // argument checks from operator_checks.h and the host side of the scalar field from scalar_host.h.
 // Kernels live in kernels_curve.hip (one TU per curve), sort_kernels.hip, te_kernels.hip and narrow_kernels.hip; host TUs see
 // declarations.
@@ -384,6 +386,16 @@ struct msm_ctx {
   int pmul_grid = 0;                // msm_test_set_points_mul_grid: blocks of the variable-base grid; 0 = the default
   int pmul_base_path = 0;           // msm_test_set_points_mul_base_path: 0 auto, 1 table, 2 broadcast
   int32_t last_pmul[4] = {};        // grid, w, path, table rows of the last call (msm_test_last_points_mul)
+
+  // msm_points_ntt (msm_points_ntt.hip): the vector w^j, j < n / 2, of one (log2n, omega, direction) at a time, 16 n bytes.  The
+  // per-lane tables of its butterflies are pmul_tbl.
+  msmi::DevBuf pntt_tw;
+  int pntt_tw_log2n = -1;           // -1: no vector
+  uint8_t pntt_tw_omega[32] = {};   // the root the vector is of, 32 bytes little-endian
+  bool pntt_tw_inverse = false;     // ... and it holds the powers of its inverse
+  int pntt_blocks_per_cu = 0;       // resident blocks of the multiplying stage kernel per compute unit (0: not asked yet)
+  int pntt_grid = 0;                // msm_test_set_points_ntt_grid: blocks of a stage's grid; 0 = the default
+  int32_t last_pntt[7] = {};        // the plan of the last call (msm_test_last_points_ntt); all 0 after a refusal
 
   // msm_scalars_sumcheck_round / _bind / _eq (msm_mle.hip): the round's results and its partials per block and value; the two
   // half-tables of the last eq.
@@ -1016,6 +1028,22 @@ const char* stage_narrow(msm_ctx* ctx, const void* scalars, size_t bytes, int on
 // positions of the group -- so that they name the entries of the resident points idx[position] with the same half and sign
 // (0xFFFFFFFF, the absent marker, stays).  te: one entry per position; otherwise two (2 j and 2 j + 1).
 void translate_payloads(hipStream_t s, const msm_ctx* ctx, uint32_t* slots, uint64_t n_slots, const uint32_t* idx);
+
+// ---- msm_lincomb.hip --------------------------------------------------------------------------------------------
+// out[i] = a * rows_a[i] + b * rows_b[i], i < count (b null: one term), queued on ctx->stream: the kernel of msm_points_lincomb over
+// rows of the caller's.  a, b: 8 words below q.  slot 0 or 1: which of the two program buffers of ctx->misc the launch reads, so
+// two launches may be in flight.
+void lincomb_launch(msm_ctx* ctx, uint32_t* out, const uint32_t* rows_a, const uint32_t* rows_b, uint64_t count, const uint32_t* a,
+                    const uint32_t* b, int slot);
+// room for n_rows rows behind the program buffers of ctx->misc
+uint32_t* lincomb_scratch_rows(msm_ctx* ctx, uint64_t n_rows);
+
+// ---- msm_points_mul.hip -----------------------------------------------------------------------------------------
+// the variable-base kernel of msm_points_mul over `count` rows, queued on ctx->stream: rows + i * row_stride under the scalar at
+// d_scal + 8 i -> out + i * row_words.  Returns the blocks of its grid.  pmul_reserve makes the per-lane tables of that launch
+// exist, so that a caller can have every allocation behind it before its first launch.
+uint64_t pmul_launch_var(msm_ctx* ctx, uint32_t* out, const uint32_t* rows, uint32_t row_stride, const uint32_t* d_scal, uint64_t count);
+void pmul_reserve(msm_ctx* ctx, uint64_t count);
 
 // ---- msm_gen.hip ------------------------------------------------------------------------------------------------
 }  // namespace msmi

@@ -4,6 +4,8 @@
 // device and launches one lane per output point; a copy (a = 1, no second term) moves rows without a kernel.
 // The checks of the sets and their rows are those of operator_checks.h, the scalars are read by scalar_host.h.
 // Every check runs before anything is written; msm_pointset_size reports what a set holds.
+// lincomb_launch runs the same kernel over rows of another translation unit's (the two-point transform of msm_points_ntt.hip on
+// the Edwards curve).
 #include "operator_checks.h"
 #include "points_lincomb.h"
 #include "scalar_host.h"
@@ -23,7 +25,43 @@ void make_program(const msm_ctx* ctx, lincomb::Program& P, const uint32_t* a, co
   for_weierstrass_curve(ctx->curve, [&](auto cv) { lincomb::make_program<typename decltype(cv)::G>(P, a, b); });
 }
 
+// where program `slot` (0, 1) lives: behind 256 bytes of ctx->misc (the index check's word lives there)
+constexpr size_t PROG_BYTES = lincomb::MAX_OPS;   // four ops to a word
+constexpr size_t ROWS_AT = 256 + 2 * PROG_BYTES;
+
+// the program of P on the device and one lane per output row
+void launch_program(msm_ctx* ctx, const lincomb::Program& P, uint32_t* out, const uint32_t* rows_a, const uint32_t* rows_b, uint64_t count, int slot) {
+  uint32_t words[lincomb::MAX_OPS / 4] = {0};
+  for (int k = 0; k < P.n; k++) words[k >> 2] |= (uint32_t)P.ops[k] << (8 * (k & 3));
+  ctx->ensure(ctx->misc, 256 + (slot + 1) * PROG_BYTES);
+  uint32_t* d_prog = (uint32_t*)((char*)ctx->misc.p + 256 + slot * PROG_BYTES);
+  HIPCHK(hipMemcpyAsync(d_prog, words, sizeof words, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // (`words` ends with this frame)
+  const dim3 grid((uint32_t)((count + 255) / 256)), block(256);
+  if (ctx->is_te())
+    hipLaunchKernelGGL(lincomb::k_te_points_lincomb, grid, block, 0, ctx->stream, out, rows_a, rows_b, count, d_prog, (uint32_t)P.n);
+  else
+    W_LAUNCH(ctx, lincomb::k_points_lincomb, grid, block, 0, ctx->stream, out, rows_a, rows_b, count, d_prog, (uint32_t)P.n);
+  HIPCHK(hipGetLastError());
+}
+
 }  // namespace
+
+namespace msmi {
+
+uint32_t* lincomb_scratch_rows(msm_ctx* ctx, uint64_t n_rows) {
+  ctx->ensure(ctx->misc, ROWS_AT + n_rows * ctx->row_words() * 4);
+  return (uint32_t*)((char*)ctx->misc.p + ROWS_AT);
+}
+
+void lincomb_launch(msm_ctx* ctx, uint32_t* out, const uint32_t* rows_a, const uint32_t* rows_b, uint64_t count, const uint32_t* a,
+                    const uint32_t* b, int slot) {
+  lincomb::Program P;
+  make_program(ctx, P, a, b);
+  launch_program(ctx, P, out, rows_a, rows_b, count, slot);
+}
+
+}  // namespace msmi
 
 extern "C" {
 
@@ -77,18 +115,7 @@ int msm_points_lincomb(msm_ctx* ctx, int32_t src_a, uint64_t a_lo, const uint8_t
       if (P.copy) {
         if (rows_a != out) HIPCHK(hipMemcpyAsync(out, rows_a, count * rw * 4, hipMemcpyDeviceToDevice, ctx->stream));
       } else {
-        // the program, four ops to a word, behind 256 bytes of ctx->misc (the index check's word lives there)
-        uint32_t words[lincomb::MAX_OPS / 4] = {0};
-        for (int k = 0; k < P.n; k++) words[k >> 2] |= (uint32_t)P.ops[k] << (8 * (k & 3));
-        ctx->ensure(ctx->misc, 256 + sizeof words);
-        uint32_t* d_prog = (uint32_t*)((char*)ctx->misc.p + 256);
-        HIPCHK(hipMemcpyAsync(d_prog, words, sizeof words, hipMemcpyHostToDevice, ctx->stream));
-        const dim3 grid((uint32_t)((count + 255) / 256)), block(256);
-        if (ctx->is_te())
-          hipLaunchKernelGGL(lincomb::k_te_points_lincomb, grid, block, 0, ctx->stream, out, rows_a, rows_b, count, d_prog, (uint32_t)P.n);
-        else
-          W_LAUNCH(ctx, lincomb::k_points_lincomb, grid, block, 0, ctx->stream, out, rows_a, rows_b, count, d_prog, (uint32_t)P.n);
-        HIPCHK(hipGetLastError());
+        launch_program(ctx, P, out, rows_a, rows_b, count, 0);
       }
       HIPCHK(hipStreamSynchronize(ctx->stream));
     }

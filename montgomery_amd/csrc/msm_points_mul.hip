@@ -40,22 +40,19 @@ uint32_t blocks_per_cu(msm_ctx* ctx) {
   return (uint32_t)ctx->pmul_blocks_per_cu;
 }
 
-// the variable-base kernel over `count` rows: rows + i * row_stride under scalars + 8 i -> out + i * row_words
-void launch_var(msm_ctx* ctx, uint32_t* out, const uint32_t* rows, uint32_t row_stride, const uint32_t* d_scal, uint64_t count) {
+// blocks of the variable-base grid over `count` rows: one round of resident blocks, no more than the rows need and no more than
+// the caller's workspace cap lets the table have
+uint64_t var_blocks(msm_ctx* ctx, uint64_t count) {
   const uint64_t need = (count + pmul::BLOCK - 1) / pmul::BLOCK;
   uint64_t blocks = ctx->pmul_grid ? (uint64_t)ctx->pmul_grid : std::min<uint64_t>(need, (uint64_t)ctx->n_cu * blocks_per_cu(ctx));
   const uint64_t per_block = pmul::table_bytes(ctx->is_te(), ctx->nw(), 1);
   if (ctx->ws_limit) blocks = std::min<uint64_t>(blocks, ctx->ws_limit / per_block);   // the table counts against the caller's cap
-  blocks = std::max<uint64_t>(blocks, 1);
-  ctx->ensure(ctx->pmul_tbl, blocks * per_block);
-  const dim3 grid((uint32_t)blocks), block(pmul::BLOCK);
-  uint4* tbl = (uint4*)ctx->pmul_tbl.p;
-  if (ctx->is_te())
-    hipLaunchKernelGGL(pmul::k_te_points_mul, grid, block, 0, ctx->stream, out, rows, row_stride, d_scal, count, tbl);
-  else
-    W_LAUNCH(ctx, pmul::k_points_mul, grid, block, 0, ctx->stream, out, rows, row_stride, d_scal, count, tbl);
-  HIPCHK(hipGetLastError());
-  ctx->last_pmul[0] = (int32_t)blocks;
+  return std::max<uint64_t>(blocks, 1);
+}
+
+// the variable-base kernel over `count` rows: rows + i * row_stride under scalars + 8 i -> out + i * row_words
+void launch_var(msm_ctx* ctx, uint32_t* out, const uint32_t* rows, uint32_t row_stride, const uint32_t* d_scal, uint64_t count) {
+  ctx->last_pmul[0] = (int32_t)pmul_launch_var(ctx, out, rows, row_stride, d_scal, count);
 }
 
 int base_windows(const msm_ctx* ctx) {
@@ -76,6 +73,27 @@ void build_base_table(msm_ctx* ctx) {
 }
 
 }  // namespace
+
+namespace msmi {
+
+void pmul_reserve(msm_ctx* ctx, uint64_t count) {
+  ctx->ensure(ctx->pmul_tbl, var_blocks(ctx, count) * pmul::table_bytes(ctx->is_te(), ctx->nw(), 1));
+}
+
+uint64_t pmul_launch_var(msm_ctx* ctx, uint32_t* out, const uint32_t* rows, uint32_t row_stride, const uint32_t* d_scal, uint64_t count) {
+  const uint64_t blocks = var_blocks(ctx, count);
+  pmul_reserve(ctx, count);
+  const dim3 grid((uint32_t)blocks), block(pmul::BLOCK);
+  uint4* tbl = (uint4*)ctx->pmul_tbl.p;
+  if (ctx->is_te())
+    hipLaunchKernelGGL(pmul::k_te_points_mul, grid, block, 0, ctx->stream, out, rows, row_stride, d_scal, count, tbl);
+  else
+    W_LAUNCH(ctx, pmul::k_points_mul, grid, block, 0, ctx->stream, out, rows, row_stride, d_scal, count, tbl);
+  HIPCHK(hipGetLastError());
+  return blocks;
+}
+
+}  // namespace msmi
 
 extern "C" {
 

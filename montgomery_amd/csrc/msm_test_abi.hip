@@ -693,6 +693,20 @@ int msm_test_last_points_mul(msm_ctx* ctx, int32_t* out, int cap) {
   return 4;
 }
 
+int msm_test_set_points_ntt_grid(msm_ctx* ctx, int32_t blocks) {
+  if (!ctx) return MSM_ERR_ARG;
+  if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "msm_test_set_points_ntt_grid: not on a device-list context");
+  if (blocks < 0 || blocks > 65536) return fail(ctx, MSM_ERR_ARG, "msm_test_set_points_ntt_grid: blocks must be 0 (default) or 1 .. 65536");
+  ctx->pntt_grid = blocks;
+  return MSM_OK;
+}
+
+int msm_test_last_points_ntt(msm_ctx* ctx, int32_t* out, int cap) {
+  if (!ctx || !ctx->children.empty() || cap < 0 || (cap && !out)) return -1;
+  for (int i = 0; i < 7 && i < cap; i++) out[i] = ctx->last_pntt[i];
+  return 7;
+}
+
 int msm_test_set_ntt_tile_log(msm_ctx* ctx, int32_t tile_log) {
   if (!ctx) return MSM_ERR_ARG;
   if (!ctx->children.empty()) return fail(ctx, MSM_ERR_ARG, "msm_test_set_ntt_tile_log: not on a device-list context");

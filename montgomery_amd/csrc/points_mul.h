@@ -557,13 +557,20 @@ __global__ void __launch_bounds__(BLOCK) k_points_mul(uint32_t* dst, const uint3
     mul_lane<CV, W_VAR>(dst + i * ROW_WORDS, rows + i * row_stride, scalars + i * 8, tbl, lane_value(cap), g);
 }
 
+// (the two kernels that are no templates have their one definition in msm_points_mul.hip: a second translation unit of the
+// library that wants the lane bodies defines MSM_PMUL_DECLARE_TE and gets declarations)
 __global__ void __launch_bounds__(BLOCK) k_te_points_mul(uint32_t* dst, const uint32_t* rows, uint32_t row_stride, const uint32_t* scalars,
-                                                         uint64_t count, uint4* tbl) {
+                                                         uint64_t count, uint4* tbl)
+#ifdef MSM_PMUL_DECLARE_TE
+    ;
+#else
+{
   const uint64_t cap = (uint64_t)gridDim.x * BLOCK, g = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
 #pragma unroll 1
   for (uint64_t i = g; i < count; i += cap)
     te_mul_lane<W_VAR>(dst + i * te::TE_ROW_WORDS, rows + i * row_stride, scalars + i * 8, tbl, lane_value(cap), g);
 }
+#endif
 
 template <class CV>
 __global__ void __launch_bounds__(BLOCK) k_points_mul_base(uint32_t* dst, const uint32_t* scalars, uint64_t count, const uint32_t* table) {
@@ -572,11 +579,16 @@ __global__ void __launch_bounds__(BLOCK) k_points_mul_base(uint32_t* dst, const 
   base_lane<CV, W_BASE>(dst + i * ROW_WORDS, scalars + i * 8, table);
 }
 
-__global__ void __launch_bounds__(BLOCK) k_te_points_mul_base(uint32_t* dst, const uint32_t* scalars, uint64_t count, const uint32_t* table) {
+__global__ void __launch_bounds__(BLOCK) k_te_points_mul_base(uint32_t* dst, const uint32_t* scalars, uint64_t count, const uint32_t* table)
+#ifdef MSM_PMUL_DECLARE_TE
+    ;
+#else
+{
   const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= count) return;
   te_base_lane<W_BASE>(dst + i * te::TE_ROW_WORDS, scalars + i * 8, table);
 }
+#endif
 
 // bytes of the per-lane tables of a grid of `blocks` blocks
 inline uint64_t table_bytes(bool te, int nw, uint64_t blocks) {

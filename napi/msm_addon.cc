@@ -25,6 +25,8 @@
 //          (msm_points_mul); scalars: a Buffer of >= count x 32 host bytes (sOff ignored) or a device buffer whose elements
 //          [sOff, sOff + count) are the scalars; pointsMulBase(h, Buffer base (x || y) | null, scalars, sOff, count, dst) -> count
 //          (msm_points_mul_base; null: the generator),
+//          pointsNtt(h, src, aLo, log2n, omega | null, shift | null, inverse, dst) -> n: rows [0, n) of point set dst = the transform
+//          of the n = 2^log2n rows [aLo, aLo + n) of point set src (msm_points_ntt; omega, shift: Buffers of 32 bytes),
 //          pointsLincomb(h, srcA, aLo, Buffer a of 32 bytes, srcB (-1: no second term), bLo, Buffer b | null, count, dst) -> count:
 //          rows [0, count) of point set dst = a * A[aLo + i] + b * B[bLo + i] (msm_points_lincomb), pointsetSize(h, id) -> n,
 //          resident scalar vectors (msm_scalars_*): a vector is a device buffer and an offset in elements of 32 bytes --
@@ -1007,6 +1009,40 @@ static napi_value PointsMulBase(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_create_int64(env, count, &out));
   return out;
 }
+// pointsNtt(ctx, src, aLo, log2n, omega: Buffer | null, shift: Buffer | null, inverse, dst) -> n = 2^log2n: rows [0, n) of point
+// set dst = the transform of the rows [aLo, aLo + n) of point set src (msm_points_ntt)
+static napi_value PointsNtt(napi_env env, napi_callback_info info) {
+  size_t argc = 8;
+  napi_value argv[8];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 8) {
+    napi_throw_type_error(env, NULL, "pointsNtt(ctx, src, aLo, log2n, omega, shift, inverse, dst)");
+    return NULL;
+  }
+  js_ctx* h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  int32_t src = 0, dst = 0;
+  int64_t a_lo = 0;
+  uint32_t log2n = 0;
+  bool inverse = false;
+  NAPI_OK(napi_get_value_int32(env, argv[1], &src));
+  NAPI_OK(napi_get_value_int64(env, argv[2], &a_lo));
+  NAPI_OK(napi_get_value_uint32(env, argv[3], &log2n));
+  NAPI_OK(napi_get_value_bool(env, argv[6], &inverse));
+  NAPI_OK(napi_get_value_int32(env, argv[7], &dst));
+  if (a_lo < 0 || log2n > 31) {
+    napi_throw_range_error(env, NULL, "pointsNtt: aLo must not be negative and log2n must be below 32");
+    return NULL;
+  }
+  const uint8_t *omega = NULL, *shift = NULL;
+  if (!is_nullish(env, argv[4]) && !host_scalar_arg(env, argv[4], &omega)) return NULL;
+  if (!is_nullish(env, argv[5]) && !host_scalar_arg(env, argv[5], &shift)) return NULL;
+  int rc = msm_points_ntt(h->ctx, src, (uint64_t)a_lo, log2n, omega, shift, inverse ? 1 : 0, dst);
+  if (rc != MSM_OK) return throw_msm(env, h->ctx, rc, "pointsNtt");
+  napi_value out;
+  NAPI_OK(napi_create_int64(env, (int64_t)1 << log2n, &out));
+  return out;
+}
 static napi_value DeviceDownload(napi_env env, napi_callback_info info) {
   size_t argc = 4;
   napi_value argv[4];
@@ -1674,7 +1710,7 @@ NAPI_MODULE_INIT() {
       {"msmIndexed", MsmIndexed}, {"msmIndexedNarrow", MsmIndexedNarrow},
       {"pointsetCreate", PointsetCreate}, {"pointsetSelect", PointsetSelect}, {"pointsetDestroy", PointsetDestroy},
       {"pointsLincomb", PointsLincomb}, {"pointsetSize", PointsetSize},
-      {"pointsMul", PointsMul}, {"pointsMulBase", PointsMulBase},
+      {"pointsMul", PointsMul}, {"pointsMulBase", PointsMulBase}, {"pointsNtt", PointsNtt},
       {"deviceDownload", DeviceDownload}, {"scalarsLincomb", ScalarsLincomb}, {"scalarsMul", ScalarsMul},
       {"scalarsInner", ScalarsInner}, {"scalarsPowers", ScalarsPowers},
       {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity}, {"scalarsNttMaxLog2n", ScalarsNttMaxLog2n},
