@@ -43,61 +43,47 @@ clean:
 
 .PHONY: all clean ab ab_pmul
 
-# CPU build of the field / GLV templates for tests/test_host_field.py (no GPU needed)
-HOSTTEST := tests/csrc/libfield_host.so
-HOSTTEST_CYCLES := tests/csrc/libfield_host_cycles.so
-HOSTTEST_LINCOMB := tests/csrc/liblincomb_host.so
-HOSTTEST_SCALARS := tests/csrc/libscalars_host.so
-HOSTTEST_SCHEDULE := tests/csrc/libschedule_host.so
-HOSTTEST_NTT := tests/csrc/libntt_host.so
-HOSTTEST_SCANS := tests/csrc/libscans_host.so
-HOSTTEST_PMUL := tests/csrc/libpoints_mul_host.so
-HOSTTEST_PNTT := tests/csrc/libpoints_ntt_host.so
-HOSTTEST_SCALAR_HOST := tests/csrc/libscalar_host_host.so
-HOSTTEST_MLE := tests/csrc/libmle_host.so
-HOSTTEST_SPMV := tests/csrc/libspmv_host.so
-# (every shim whose source the tests tree holds: a tests tree from before the schedule shim still builds the others)
-hosttest: $(HOSTTEST) $(HOSTTEST_CYCLES) $(HOSTTEST_LINCOMB) $(HOSTTEST_SCALARS) $(if $(wildcard tests/csrc/schedule_host.hip),$(HOSTTEST_SCHEDULE)) \
-          $(if $(wildcard tests/csrc/ntt_host.hip),$(HOSTTEST_NTT)) $(if $(wildcard tests/csrc/scans_host.hip),$(HOSTTEST_SCANS)) \
-          $(if $(wildcard tests/csrc/points_mul_host.hip),$(HOSTTEST_PMUL)) $(if $(wildcard tests/csrc/scalar_host_host.hip),$(HOSTTEST_SCALAR_HOST)) \
-          $(if $(wildcard tests/csrc/mle_host.hip),$(HOSTTEST_MLE)) $(if $(wildcard tests/csrc/spmv_host.hip),$(HOSTTEST_SPMV)) \
-          $(if $(wildcard tests/csrc/points_ntt_host.hip),$(HOSTTEST_PNTT))
-# scalar_host.h on all seven scalar fields and the range and row rules of operator_checks.h, whose refusals go through the fail() of
-# msm_plan.hip over a bare context: tests/test_scalar_host.py
-$(HOSTTEST_SCALAR_HOST): tests/csrc/scalar_host_host.hip $(CSRC)/msm_plan.hip $(HHDRS)
-	$(HIPCC) -O2 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/scalar_host_host.hip $(CSRC)/msm_plan.hip -o $(HOSTTEST_SCALAR_HOST)
-# the window-group schedule of msm_plan.hip (group_schedule: no HIP call) over a bare context: tests/test_group_schedule.py
-$(HOSTTEST_SCHEDULE): tests/csrc/schedule_host.hip $(CSRC)/msm_plan.hip $(HHDRS)
-	$(HIPCC) -O2 -pthread -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/schedule_host.hip $(CSRC)/msm_plan.hip -o $(HOSTTEST_SCHEDULE)
-# the plan, the index functions and the lane bodies of scalar_ntt.h, run lane by lane on the host: tests/test_ntt_host.py
-$(HOSTTEST_NTT): tests/csrc/ntt_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h $(CSRC)/scalar_ntt.h include/msm_hip.h
-	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/ntt_host.hip -o $(HOSTTEST_NTT)
-# the plan, the combine operators and the inverse lane body of scalar_scan.h on the host: tests/test_scans_host.py
-$(HOSTTEST_SCANS): tests/csrc/scans_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h $(CSRC)/scalar_scan.h include/msm_hip.h
-	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/scans_host.hip -o $(HOSTTEST_SCANS)
-# the index maps, the lane bodies and the half-table split of scalar_mle.h on the host: tests/test_mle_host.py
-$(HOSTTEST_MLE): tests/csrc/mle_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h $(CSRC)/scalar_mle.h include/msm_hip.h
-	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/mle_host.hip -o $(HOSTTEST_MLE)
-# the CSR rule, the plan, the transposition and the lane bodies of scalar_spmv.h on the host: tests/test_spmv_host.py
-$(HOSTTEST_SPMV): tests/csrc/spmv_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h $(CSRC)/scalar_mle.h $(CSRC)/scalar_spmv.h include/msm_hip.h
-	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/spmv_host.hip -o $(HOSTTEST_SPMV)
-# the lane bodies of scalar_vec.h on the scalar fields of all seven curves: tests/test_scalars_host.py
-$(HOSTTEST_SCALARS): tests/csrc/scalars_host.hip $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h include/msm_hip.h
-	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Iinclude -I$(CSRC) tests/csrc/scalars_host.hip -o $(HOSTTEST_SCALARS)
-# the recoder and the lane bodies of points_lincomb.h on all seven curves: tests/test_points_lincomb_host.py
-$(HOSTTEST_LINCOMB): tests/csrc/lincomb_host.hip $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h $(CSRC)/te_kernels.h
-	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/lincomb_host.hip -o $(HOSTTEST_LINCOMB)
-# the recoding and the lane bodies of points_mul.h on all seven curves, at every candidate window: tests/test_points_mul_host.py
-$(HOSTTEST_PMUL): tests/csrc/points_mul_host.hip $(KHDRS) $(CSRC)/points_mul.h $(CSRC)/te_kernels.h
-	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/points_mul_host.hip -o $(HOSTTEST_PMUL)
-# the index maps and the butterfly lane of points_ntt.h on the host: tests/test_points_ntt_host.py
-$(HOSTTEST_PNTT): tests/csrc/points_ntt_host.hip $(KHDRS) $(CSRC)/points_mul.h $(CSRC)/points_ntt.h $(CSRC)/te_kernels.h
-	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/points_ntt_host.hip -o $(HOSTTEST_PNTT)
+# CPU builds of the device headers for the host tests (no GPU needed): tests/csrc/<stem>.hip -> tests/csrc/lib<stem>.so, for every
+# shim whose source the tests tree holds.  One recipe; a library differs from the next in the headers it is rebuilt for and, where
+# said below, in a flag or a further source.
+HT = $(1:%=tests/csrc/lib%.so)
+hosttest: $(call HT,$(patsubst tests/csrc/%.hip,%,$(wildcard tests/csrc/*.hip)))
+HT_INC := -Iinclude
+tests/csrc/lib%.so: tests/csrc/%.hip
+	$(strip $(HIPCC) -O2 $(HT_THREADS) -std=c++17 --offload-arch=$(ARCH) -fPIC -shared $(HT_WARN) $(HT_INC) -I$(CSRC) $< $(HT_MORE) -o $@)
+
+SCALAR_HDRS := $(CSRC)/field.h $(CSRC)/constants_gen.h $(CSRC)/scalar_vec.h $(CSRC)/scalar_host.h include/msm_hip.h
+POINT_HDRS := $(KHDRS) $(CSRC)/te_kernels.h
+# the field / GLV templates alone, without the public header: tests/test_host_field.py
+$(call HT,field_host): $(CSRC)/field.h $(CSRC)/glv.h $(CSRC)/constants_gen.h
+$(call HT,field_host): HT_INC :=
 # the cycle curves (BN254 G1, Grumpkin, Vesta), with the square root of points_ingest.h: tests/test_cycle_curves.py
-$(HOSTTEST_CYCLES): tests/csrc/field_host_cycles.hip $(KHDRS) $(CSRC)/points_ingest.h $(CSRC)/te_kernels.h
-	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wno-unused-value -Iinclude -I$(CSRC) tests/csrc/field_host_cycles.hip -o $(HOSTTEST_CYCLES)
-$(HOSTTEST): tests/csrc/field_host.hip $(CSRC)/field.h $(CSRC)/glv.h $(CSRC)/constants_gen.h
-	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -I$(CSRC) tests/csrc/field_host.hip -o $(HOSTTEST)
+$(call HT,field_host_cycles): $(POINT_HDRS) $(CSRC)/points_ingest.h
+# the recoder and the lane bodies of points_lincomb.h on all seven curves: tests/test_points_lincomb_host.py
+$(call HT,lincomb_host): $(POINT_HDRS) $(CSRC)/points_ingest.h $(CSRC)/points_lincomb.h
+# the recoding and the lane bodies of points_mul.h on all seven curves, at every candidate window: tests/test_points_mul_host.py
+$(call HT,points_mul_host): $(POINT_HDRS) $(CSRC)/points_mul.h
+# the index maps and the butterfly lane of points_ntt.h on the host: tests/test_points_ntt_host.py
+$(call HT,points_ntt_host): $(POINT_HDRS) $(CSRC)/points_mul.h $(CSRC)/points_ntt.h
+# the lane bodies of scalar_vec.h on the scalar fields of all seven curves: tests/test_scalars_host.py
+$(call HT,scalars_host): $(SCALAR_HDRS)
+# the plan, the index functions and the lane bodies of scalar_ntt.h, run lane by lane on the host: tests/test_ntt_host.py
+$(call HT,ntt_host): $(SCALAR_HDRS) $(CSRC)/scalar_ntt.h
+# the plan, the combine operators and the inverse lane body of scalar_scan.h on the host: tests/test_scans_host.py
+$(call HT,scans_host): $(SCALAR_HDRS) $(CSRC)/scalar_scan.h
+# the index maps, the lane bodies and the half-table split of scalar_mle.h on the host: tests/test_mle_host.py
+$(call HT,mle_host): $(SCALAR_HDRS) $(CSRC)/scalar_mle.h
+# the CSR rule, the plan, the transposition and the lane bodies of scalar_spmv.h on the host: tests/test_spmv_host.py
+$(call HT,spmv_host): $(SCALAR_HDRS) $(CSRC)/scalar_mle.h $(CSRC)/scalar_spmv.h
+# over a bare context, with msm_plan.hip linked in: scalar_host.h on all seven scalar fields and the range and row rules of
+# operator_checks.h, whose refusals go through its fail() (tests/test_scalar_host.py), and its window-group schedule
+# (group_schedule: no HIP call; tests/test_group_schedule.py)
+HT_BARE_CTX := $(call HT,scalar_host_host schedule_host)
+$(HT_BARE_CTX): $(CSRC)/msm_plan.hip $(HHDRS)
+$(HT_BARE_CTX): HT_THREADS := -pthread
+$(HT_BARE_CTX): HT_MORE := $(CSRC)/msm_plan.hip
+# the kernel headers hold expressions whose value a host build does not use
+$(HT_BARE_CTX) $(call HT,field_host_cycles lincomb_host points_mul_host points_ntt_host): HT_WARN := -Wno-unused-value
 
 # Node N-API shim (the image's node 12 exposes N-API 8 through /usr/include/node)
 NAPI := montgomery_amd/msm_hip.node

@@ -4,8 +4,7 @@
 const fs = require("fs");
 const path = require("path");
 const M = require("./montgomery-hip.js");
-
-function assert(c, msg) { if (!c) { console.error("FAILED: " + msg); process.exit(1); } }
+const { assert } = require("./test-support.js");
 
 // the case's scalars, the same scalars rotated by one point, and all zeros
 function variants(sc, n) {

@@ -4,10 +4,9 @@
 const fs = require("fs");
 const path = require("path");
 const M = require("./montgomery-hip.js");
+const { assert } = require("./test-support.js");
 const subBls = require("./submission-bls377.js");   // compute_msm(points, scalars): the reference's signature
 const subEd = require("./submission.js");
-
-function assert(c, msg) { if (!c) { console.error("FAILED: " + msg); process.exit(1); } }
 
 async function main() {
   await M.startThreads(16);   // the reference's call sites bracket their MSMs with these (scripts/msm-weierstrass.ts:14,50)

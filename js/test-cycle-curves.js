@@ -3,9 +3,7 @@
 // msmBatch and msmNarrow == msm.  Run on a GPU box: node js/test-cycle-curves.js
 "use strict";
 const M = require("./montgomery-hip.js");
-
-function assert(c, msg) { if (!c) { console.error("FAILED: " + msg); process.exit(1); } }
-const same = (a, b) => a.isZero === b.isZero && a.x === b.x && a.y === b.y;
+const { assert, stream, same } = require("./test-support.js");
 
 const generators = {
   bn254: [BigInt(1), BigInt(2)],
@@ -13,14 +11,6 @@ const generators = {
   vesta: [M.vestaParams.modulus - BigInt(1), BigInt(2)],
 };
 
-function stream(seed) {
-  let s = BigInt(seed) | BigInt(1);
-  const mask = (BigInt(1) << BigInt(64)) - BigInt(1);
-  return () => {
-    s ^= s >> BigInt(12); s = (s ^ (s << BigInt(25))) & mask; s ^= s >> BigInt(27);
-    return (s * BigInt("2685821657736338717")) & mask;
-  };
-}
 function scalars(n, q, seed) {
   const next = stream(seed), out = [];
   for (let i = 0; i < n; i++) out.push(((next() << BigInt(192)) | (next() << BigInt(128)) | (next() << BigInt(64)) | next()) % q);

@@ -2,20 +2,8 @@
 // indices[j] == i, mod q), on generated points.  Run on a GPU box: node js/test-indexed.js
 "use strict";
 const M = require("./montgomery-hip.js");
+const { assert, stream, same } = require("./test-support.js");
 
-function assert(c, msg) { if (!c) { console.error("FAILED: " + msg); process.exit(1); } }
-
-// deterministic 64-bit stream (xorshift64*), as BigInt
-function stream(seed) {
-  let s = BigInt(seed) | BigInt(1);
-  const mask = (BigInt(1) << BigInt(64)) - BigInt(1);
-  return () => {
-    s ^= s >> BigInt(12); s = (s ^ (s << BigInt(25))) & mask; s ^= s >> BigInt(27);
-    return (s * BigInt("2685821657736338717")) & mask;
-  };
-}
-
-const same = (a, b) => a.isZero === b.isZero && a.x === b.x && a.y === b.y;
 const mod = (v, q) => ((v % q) + q) % q;
 
 // msm over the dense equivalent of (indices, values): values are BigInts of either sign
@@ -30,6 +18,7 @@ async function dense(curve, pp, n, indices, vals, q) {
   return result;
 }
 
+// not the throwsWith of test-support.js: fn is async here and is awaited
 async function throwsWith(fn, re, what) {
   let thrown = null;
   try { await fn(); } catch (e) { thrown = e; }

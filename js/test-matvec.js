@@ -4,40 +4,9 @@
 // Run on a GPU box: node js/test-matvec.js
 "use strict";
 const M = require("./montgomery-hip.js");
+const { assert, stream, ZERO, ONE, eq, upload, read, throwsWith } = require("./test-support.js");
 
-function assert(c, msg) { if (!c) { console.error("FAILED: " + msg); process.exit(1); } }
-
-// deterministic 64-bit stream (xorshift64*), as BigInt
-function stream(seed) {
-  let s = BigInt(seed) | BigInt(1);
-  const mask = (BigInt(1) << BigInt(64)) - BigInt(1);
-  return () => {
-    s ^= s >> BigInt(12); s = (s ^ (s << BigInt(25))) & mask; s ^= s >> BigInt(27);
-    return (s * BigInt("2685821657736338717")) & mask;
-  };
-}
-
-const ZERO = BigInt(0), ONE = BigInt(1);
-const eq = (a, b) => a.length === b.length && a.every((v, i) => v === b[i]);
 const mod = (x, q) => ((x % q) + q) % q;
-
-async function upload(curve, vals) {
-  const raw = Buffer.concat(vals.map((v) => M.bigintToLeBytes(v, 32)));
-  const sp = curve.Parallel.getScalarPointer(raw.length);
-  await curve.Parallel.scalarsFromBytes(sp, raw, vals.length);
-  return sp;
-}
-
-function read(curve, sp, n) {
-  const raw = curve.Parallel.scalarsToBytes(sp, n);
-  return Array.from({ length: n }, (_, i) => M.leBytesToBigint(raw.subarray(32 * i, 32 * i + 32)));
-}
-
-function throwsWith(fn, re, what) {
-  let thrown = null;
-  try { fn(); } catch (e) { thrown = e; }
-  assert(thrown && re.test(thrown.message), `${what}: expected ${re}, got ${thrown && thrown.message}`);
-}
 
 // triples -> the product as BigInts: out[r] = alpha sum val x[col] + old[r]
 function productRef(rows, trip, x, q, alpha, old) {

@@ -2,18 +2,7 @@
 // (negatives as q - |v|), on generated points.  Run on a GPU box: node js/test-narrow.js
 "use strict";
 const M = require("./montgomery-hip.js");
-
-function assert(c, msg) { if (!c) { console.error("FAILED: " + msg); process.exit(1); } }
-
-// deterministic 64-bit stream (xorshift64*), as BigInt
-function stream(seed) {
-  let s = BigInt(seed) | BigInt(1);
-  const mask = (BigInt(1) << BigInt(64)) - BigInt(1);
-  return () => {
-    s ^= s >> BigInt(12); s = (s ^ (s << BigInt(25))) & mask; s ^= s >> BigInt(27);
-    return (s * BigInt("2685821657736338717")) & mask;
-  };
-}
+const { assert, stream, same } = require("./test-support.js");
 
 // n values of `bits` magnitude bits, the extremes among them
 function values(n, bits, signed, seed) {
@@ -40,8 +29,6 @@ async function wide(curve, pp, vals, q) {
   sp.free();
   return result;
 }
-
-const same = (a, b) => a.isZero === b.isZero && a.x === b.x && a.y === b.y;
 
 async function runCurve(curve, label) {
   const n = 1000, q = curve.params.order;

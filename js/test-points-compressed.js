@@ -5,9 +5,8 @@
 const fs = require("fs");
 const path = require("path");
 const M = require("./montgomery-hip.js");
+const { assert } = require("./test-support.js");
 const dir = process.argv[2];
-
-function assert(c, msg) { if (!c) { console.error("FAILED: " + msg); process.exit(1); } }
 
 async function runCurve(curve, label, file, coordBytes) {
   const raw = fs.readFileSync(path.join(dir, file + ".raw"));

@@ -6,22 +6,11 @@
 // Run on a GPU box: node js/test-points-ntt.js
 "use strict";
 const M = require("./montgomery-hip.js");
+const { assert, stream, same, throwsWith } = require("./test-support.js");
 
-function assert(c, msg) { if (!c) { console.error("FAILED: " + msg); process.exit(1); } }
-
-// deterministic 64-bit stream (xorshift64*), as BigInt
-function stream(seed) {
-  let s = BigInt(seed) | BigInt(1);
-  const mask = (BigInt(1) << BigInt(64)) - BigInt(1);
-  return () => {
-    s ^= s >> BigInt(12); s = (s ^ (s << BigInt(25))) & mask; s ^= s >> BigInt(27);
-    return (s * BigInt("2685821657736338717")) & mask;
-  };
-}
-
-const same = (a, b) => a.isZero === b.isZero && a.x === b.x && a.y === b.y;
 const bytesOf = (vals) => Buffer.concat(vals.map((v) => M.bigintToLeBytes(v, 32)));
 
+// kept here: the copies of powmod differ (this one takes a BigInt exponent only)
 function powMod(b, e, q) {
   let r = BigInt(1);
   b %= q;
@@ -59,12 +48,6 @@ async function msmOver(curve, pp, vals) {
   const { result } = await curve.Parallel.msm(sp, pp, vals.length);
   sp.free();
   return result;
-}
-
-function throwsWith(fn, re, what) {
-  let thrown = null;
-  try { fn(); } catch (e) { thrown = e; }
-  assert(thrown && re.test(thrown.message), `${what}: expected ${re}, got ${thrown && thrown.message}`);
 }
 
 async function runCurve(curve, label, maxLog, keyLog) {

@@ -2,40 +2,9 @@
 // and an msm over a folded vector against the msm over the products.  Run on a GPU box: node js/test-scalars.js
 "use strict";
 const M = require("./montgomery-hip.js");
+const { assert, stream, same, eq, upload, read, throwsWith } = require("./test-support.js");
 
-function assert(c, msg) { if (!c) { console.error("FAILED: " + msg); process.exit(1); } }
-
-// deterministic 64-bit stream (xorshift64*), as BigInt
-function stream(seed) {
-  let s = BigInt(seed) | BigInt(1);
-  const mask = (BigInt(1) << BigInt(64)) - BigInt(1);
-  return () => {
-    s ^= s >> BigInt(12); s = (s ^ (s << BigInt(25))) & mask; s ^= s >> BigInt(27);
-    return (s * BigInt("2685821657736338717")) & mask;
-  };
-}
-
-const same = (a, b) => a.isZero === b.isZero && a.x === b.x && a.y === b.y;
-const eq = (a, b) => a.length === b.length && a.every((v, i) => v === b[i]);
-
-async function upload(curve, vals) {
-  const raw = Buffer.concat(vals.map((v) => M.bigintToLeBytes(v, 32)));
-  const sp = curve.Parallel.getScalarPointer(raw.length);
-  await curve.Parallel.scalarsFromBytes(sp, raw, vals.length);
-  return sp;
-}
-
-function read(curve, sp, n) {
-  const raw = curve.Parallel.scalarsToBytes(sp, n);
-  return Array.from({ length: n }, (_, i) => M.leBytesToBigint(raw.subarray(32 * i, 32 * i + 32)));
-}
-
-function throwsWith(fn, re, what) {
-  let thrown = null;
-  try { fn(); } catch (e) { thrown = e; }
-  assert(thrown && re.test(thrown.message), `${what}: expected ${re}, got ${thrown && thrown.message}`);
-}
-
+// kept here: the copies of powmod differ (this one takes the exponent as a plain number)
 function powmod(x, e, q) {
   let r = BigInt(1), b = x % q;
   for (; e > 0; e >>= 1) { if (e & 1) r = (r * b) % q; b = (b * b) % q; }

@@ -1,13 +1,7 @@
 """msm_run_batch at the C ABI and in the bindings, without a GPU: the symbol, its argument checks, the addon's exports."""
 import ctypes
-import os
-import shutil
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NODE = shutil.which("node")
+from napi_support import assert_exports
 
 
 def test_library_exports_msm_run_batch():
@@ -40,14 +34,4 @@ def test_python_api_has_the_batch_entries():
 
 
 def test_addon_exports_batch_entries():
-    if NODE is None or not os.path.exists("/usr/include/node/node_api.h"):
-        pytest.skip("node / node_api.h not present")
-    from conftest import build_if_missing
-
-    build_if_missing("all", "montgomery_amd/libmsm_hip.so")
-    build_if_missing("napi", "montgomery_amd/msm_hip.node")
-    out = subprocess.run([NODE, "-e", "const m=require('./js/montgomery-hip.js');console.log(Object.keys(m.hip).sort().join(','))"],
-                         cwd=ROOT, capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stderr
-    names = out.stdout.strip().split(",")
-    assert "msmBatch" in names and "msmBatchDevice" in names
+    assert_exports(("msmBatch", "msmBatchDevice"), facade=())

@@ -31,8 +31,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import degenerate_inputs as D  # noqa: E402
-from oracle import msm_oracle as O  # noqa: E402
+from operator_fixture import OperatorFixture  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -48,19 +47,12 @@ NARROW = {1: ((False, 8, 4), (True, 7, 7)), 2: ((False, 16, 10), (True, 10, 10))
 
 # ---------------------------------------------------------------------------------------------- points, shared by all tests
 
-class Fix:
+class Fix(OperatorFixture):
     def __init__(self, name):
-        from montgomery_amd.api import MsmContext
-
-        self.name, self.cv = name, D.CURVE_TABLE[name]
-        self.q, self.te = self.cv.q, self.cv.te
-        self.ctx = MsmContext(self.cv.cid)
+        super().__init__(name)
+        self.te = self.cv.te
         self.logs = self.ctx.generate_points(N, seed=1501, want_scalars=True)        # a_i of P_i = a_i G, N x 32 bytes
         self.logs_np = np.frombuffer(self.logs, dtype=np.uint8).reshape(N, 32)
-
-    def point(self, res):
-        """a result in the form Curve.scale_g gives"""
-        return (res.x, res.y) if self.te else res.as_tuple()
 
     def log(self, i):
         return int.from_bytes(self.logs[32 * int(i):32 * int(i) + 32], "little")

@@ -12,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import degenerate_inputs as D  # noqa: E402
+from operator_fixture import OperatorFixture  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -20,18 +21,11 @@ N7 = 2048         # resident points of the all-curves fixture
 N13 = 1 << 13     # of the BLS12-377 fixture that walks the sort paths
 
 
-class Fix:
+class Fix(OperatorFixture):
     def __init__(self, name, n, seed):
-        from montgomery_amd.api import MsmContext
-
-        self.name, self.cv, self.n = name, D.CURVE_TABLE[name], n
-        self.ctx = MsmContext(self.cv.cid)
+        super().__init__(name)
+        self.n = n
         self.logs = O.scalars_from_bytes(self.ctx.generate_points(n, seed=seed, want_scalars=True))
-        self.q = self.cv.q
-
-    def point(self, res):
-        """a result in the form Curve.scale_g gives"""
-        return (res.x, res.y) if self.cv.te else res.as_tuple()
 
     def dlog(self, idx, sc, logs=None):
         logs = self.logs if logs is None else logs

@@ -14,34 +14,23 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import degenerate_inputs as D  # noqa: E402
+import operator_fixture as F  # noqa: E402
+from operator_fixture import TOP, OperatorFixture, edges, to_bytes  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-TOP = (1 << 256) - 1
-SENTINEL = b"\xa5" * 32
 LADDER = (0, 4, 5, 63, 64, 65, 128, 129, 5 * 64 + 3)
 GEOMETRIES = ((4, 64), (1, 1), (4, 96), (0, 0))   # (0, 0): the defaults
-
-
-def to_bytes(vals):
-    return b"".join(v.to_bytes(32, "little") for v in vals)
 
 
 def u32_bytes(vals):
     return b"".join(v.to_bytes(4, "little") for v in vals)
 
 
-def edges(q):
-    return [0, 1, q - 1, q, q + 1, TOP]
-
-
 def mixed(rng, q, n):
     """n elements below 2^256: random ones with q, q + 1, 2^256 - 1 and 0 in every seventh place"""
-    vals = [rng.randrange(q) for _ in range(n)]
-    for i in range(3, n, 7):
-        vals[i] = (q, q + 1, TOP, 0)[(i // 7) % 4]
-    return vals
+    return F.with_specials([rng.randrange(q) for _ in range(n)], (q, q + 1, TOP, 0))
 
 
 def csr(rows):
@@ -79,45 +68,26 @@ def transpose_rows(rows, cols):
     return t
 
 
-class Fix:
-    """One context per curve; vectors live at 32-byte offset `pad` (odd) inside allocations that end in a sentinel element."""
-
+class Fix(OperatorFixture):
     def __init__(self, name):
-        from montgomery_amd.api import MsmContext
-
-        self.name, self.cv = name, D.CURVE_TABLE[name]
-        self.q = self.cv.q
-        self.ctx = MsmContext(self.cv.cid)
-        self.bufs = []
+        super().__init__(name)
         self.rng = random.Random(f"matvec/{name}")
 
-    def vector(self, vals_or_n, pad=3):
-        raw = to_bytes(vals_or_n) if not isinstance(vals_or_n, int) else SENTINEL * vals_or_n
-        base = self.ctx.device_alloc(32 * pad + len(raw) + 32)
-        self.bufs.append(base)
-        self.ctx.device_upload(base, SENTINEL * pad + raw + SENTINEL)
-        return base + 32 * pad
-
-    def raw(self, data):
+    def blob(self, data):
+        """an unfenced allocation that holds `data` as it is"""
         base = self.ctx.device_alloc(max(len(data), 32))
         self.bufs.append(base)
         if data:
             self.ctx.device_upload(base, data)
         return base
 
-    def read(self, ptr, n):
-        return O.scalars_from_bytes(self.ctx.device_download(ptr, 32 * n)) if n else []
-
-    def is_sentinel(self, ptr):
-        return self.ctx.device_download(ptr, 32) == SENTINEL
-
     def geometry(self, short_max, part_len):
-        assert self.ctx._lib.msm_test_set_matvec_geometry(self.ctx._h, short_max, part_len) == 0
+        self.set("msm_test_set_matvec_geometry", short_max, part_len)
 
     def last(self):
-        out = (ctypes.c_int32 * 5)()
-        assert self.ctx._lib.msm_test_last_matvec(self.ctx._h, out, 5) == 5
-        return list(out)
+        out = super().last("msm_test_last_matvec", 5)
+        assert len(out) == 5
+        return out
 
     def matrix(self, rows, cols, geometry=(0, 0), transpose=False):
         self.geometry(*geometry)
@@ -154,11 +124,6 @@ class Fix:
                 vals = mixed(rng, q, n)
                 out.append([(rng.randrange(cols), v) for v in vals])
         return out
-
-    def close(self):
-        for b in self.bufs:
-            self.ctx.device_free(b)
-        self.ctx.close()
 
 
 @pytest.fixture(scope="module", params=D.NAMES)
@@ -387,7 +352,7 @@ def test_device_input_equals_host_input_and_the_matrix_owns_its_arrays(f1):
     f.geometry(4, 64)
     host = f.ctx.matrix_create(len(rows), cols, rp, col, val)
     # the device arrays at odd offsets: row_ptr and col on 4-byte boundaries, val on a 16-byte one
-    d_rp, d_col, d_val = f.raw(bytes(4) + u32_bytes(rp)) + 4, f.raw(bytes(12) + u32_bytes(col)) + 12, f.raw(bytes(16) + to_bytes(val)) + 16
+    d_rp, d_col, d_val = f.blob(bytes(4) + u32_bytes(rp)) + 4, f.blob(bytes(12) + u32_bytes(col)) + 12, f.blob(bytes(16) + to_bytes(val)) + 16
     dev = f.ctx.matrix_create(len(rows), cols, d_rp, d_col, d_val, nnz=nnz, on_device=True)
     ones_dev = f.ctx.matrix_create(len(rows), cols, d_rp, d_col, None, nnz=nnz, on_device=True)
     f.geometry(0, 0)
@@ -446,7 +411,7 @@ def test_every_csr_defect_is_refused_for_host_and_device_input(f1):
         for on_device in (False, True):
             with pytest.raises(MsmError) as e:
                 if on_device:
-                    f.ctx.matrix_create(4, 5, f.raw(u32_bytes(rp)), f.raw(u32_bytes(col)), f.raw(val), nnz=6, on_device=True)
+                    f.ctx.matrix_create(4, 5, f.blob(u32_bytes(rp)), f.blob(u32_bytes(col)), f.blob(val), nnz=6, on_device=True)
                 else:
                     f.ctx.matrix_create(4, 5, rp, col, val)
             assert e.value.code == MSM_ERR_ARG and "msm_matrix_create: " + text in str(e.value), (rp, col, on_device)
@@ -494,7 +459,7 @@ def test_every_other_refusal_leaves_outputs_and_context_as_they_were(f1):
     # creation: unknown flag bits, TRANSPOSE with on_device, sizes, null and misaligned pointers
     create_refused(5, 5, 6, c_rp, c_col, None, 0, 2)
     create_refused(5, 5, 6, c_rp, c_col, None, 0, 0x80000001)
-    d_rp, d_col, d_val = f.raw(u32_bytes(rp)), f.raw(u32_bytes(col)), f.raw(bytes(32 * 6 + 16))
+    d_rp, d_col, d_val = f.blob(u32_bytes(rp)), f.blob(u32_bytes(col)), f.blob(bytes(32 * 6 + 16))
     create_refused(5, 5, 6, vp(d_rp), vp(d_col), None, 1, 1)
     create_refused(1 << 30, 5, 6, c_rp, c_col, None, 0, 0)
     create_refused(5, 1 << 30, 6, c_rp, c_col, None, 0, 0)

@@ -11,12 +11,13 @@ import pytest
 sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
 import degenerate_inputs as D  # noqa: E402
 import ntt_model as M  # noqa: E402
+import operator_fixture as F  # noqa: E402
+from host_lib import host_library  # noqa: E402
+from operator_fixture import SENTINEL, TOP, OperatorFixture, to_bytes  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-TOP = (1 << 256) - 1
-SENTINEL = b"\xa5" * 32
 TWO_ADIC = ("bls377", "bls381", "pallas", "vesta", "bn254")
 
 
@@ -25,13 +26,8 @@ def _ints(tag, n, bound):
 
 
 def mixed(cv, tag, n):
-    """n elements below 2^256: random residues with q, q + 1, 2^256 - 1 and 0 in every seventh place (and in a vector of one)"""
-    q = cv.q
-    vals = _ints(f"{cv.name}/{tag}", n, q)
-    special = (q, q + 1, TOP, 0)
-    for i in range(3 if n > 3 else 0, n, 7):
-        vals[i] = special[(i // 7) % 4]
-    return vals
+    """operator_fixture.mixed, with a special element in a vector of up to three too"""
+    return F.mixed("ntt", cv, tag, n, start=3 if n > 3 else 0)
 
 
 def tiled(cv, tag, n, period=4093):
@@ -40,58 +36,16 @@ def tiled(cv, tag, n, period=4093):
     return [base[i % len(base)] for i in range(n)]
 
 
-def to_bytes(vals):
-    return b"".join(v.to_bytes(32, "little") for v in vals)
-
-
-class Fix:
-    """One context per curve; vectors live `pad` (odd) elements inside allocations that end in a sentinel element."""
-
-    def __init__(self, name):
-        from montgomery_amd.api import MsmContext
-
-        self.name, self.cv = name, D.CURVE_TABLE[name]
-        self.q = self.cv.q
-        self.ctx = MsmContext(self.cv.cid)
-        self.bufs = []
-
-    def vector(self, vals_or_n, pad=3):
-        raw = to_bytes(vals_or_n) if not isinstance(vals_or_n, int) else SENTINEL * vals_or_n
-        base = self.ctx.device_alloc(32 * pad + len(raw) + 32)
-        self.bufs.append(base)
-        self.ctx.device_upload(base, SENTINEL * pad + raw + SENTINEL)
-        return base + 32 * pad
-
+class Fix(OperatorFixture):
     def batch(self, vectors, pad=3):
         """the vectors of a batch back to back, as msm_scalars_ntt reads them, with the sentinels of vector() around the whole"""
         return self.vector([v for vec in vectors for v in vec], pad)
 
-    def read(self, ptr, n):
-        return O.scalars_from_bytes(self.ctx.device_download(ptr, 32 * n)) if n else []
-
-    def fenced(self, ptr, n):
-        return self.ctx.device_download(ptr - 32, 32) == SENTINEL and self.ctx.device_download(ptr + 32 * n, 32) == SENTINEL
-
-    def free(self, ptr, pad=3):
-        base = ptr - 32 * pad
-        self.bufs.remove(base)
-        self.ctx.device_free(base)
-
-    def point(self, res):
-        return (res.x, res.y) if self.cv.te else res.as_tuple()
-
     def last_plan(self):
-        out = (ctypes.c_int32 * 32)()
-        count = self.ctx._lib.msm_test_last_ntt_plan(self.ctx._h, out, 32)
-        return list(out[:count])
+        return self.last("msm_test_last_ntt_plan", 32)
 
     def set_tile_log(self, t):
-        assert self.ctx._lib.msm_test_set_ntt_tile_log(self.ctx._h, t) == 0
-
-    def close(self):
-        for b in self.bufs:
-            self.ctx.device_free(b)
-        self.ctx.close()
+        self.set("msm_test_set_ntt_tile_log", t)
 
 
 @pytest.fixture(scope="module", params=D.NAMES)
@@ -117,11 +71,7 @@ def f2(request):
 
 @pytest.fixture(scope="module")
 def default_tile_log():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libntt_host.so", "tests/csrc/libntt_host.so")
-    L = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libntt_host.so"))
-    return L.ntt_default_tile_log()
+    return host_library("ntt_host").ntt_default_tile_log()
 
 
 def variants(q, log2n, tag):

@@ -12,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import degenerate_inputs as D  # noqa: E402
+from operator_fixture import OperatorFixture  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -24,15 +25,11 @@ def _ints(tag, n, bound):
     return O.prng_ints(f"lincomb/{tag}", n, bound)
 
 
-class Fix:
+class Fix(OperatorFixture):
     """One context per curve with two generated sets A (the default set) and B with known logs, and an empty third set."""
 
     def __init__(self, name):
-        from montgomery_amd.api import MsmContext
-
-        self.name, self.cv = name, D.CURVE_TABLE[name]
-        self.q = self.cv.q
-        self.ctx = MsmContext(self.cv.cid)
+        super().__init__(name)
         self.sa = 0
         self.la = O.scalars_from_bytes(self.ctx.generate_points(N7, seed=1401, want_scalars=True))
         self.sb = self.ctx.pointset_create()
@@ -40,9 +37,6 @@ class Fix:
         self.sd = self.ctx.pointset_create()
         self.ctx.pointset_select(self.sa)
         self.step = 2 * self.ctx.coord_bytes
-
-    def point(self, res):
-        return (res.x, res.y) if self.cv.te else res.as_tuple()
 
     def rows(self, set_id, first, count):
         """wire bytes of rows [first, first + count) of a set; the current set is put back"""

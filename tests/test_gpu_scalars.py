@@ -4,6 +4,7 @@ Expected values are Python integers mod cv.q; every comparison is bit-exact.  Si
 (63, 65), a ragged block (257) and more than one block (321), beside 1, 64 and 256.  Vectors sit at an odd 32-byte offset inside
 their allocation and carry non-canonical elements (q, q + 1, 2^256 - 1) and zeros among the random ones."""
 import ctypes
+import functools
 import os
 import sys
 
@@ -11,63 +12,22 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import degenerate_inputs as D  # noqa: E402
+import operator_fixture as F  # noqa: E402
+from host_lib import host_library  # noqa: E402
+from operator_fixture import SENTINEL, TOP, OperatorFixture as Fix, to_bytes  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = (1, 63, 64, 65, 256, 257, 321)
 NMAX = SHAPES[-1]
-TOP = (1 << 256) - 1
-SENTINEL = b"\xa5" * 32
 
 
 def _ints(tag, n, bound):
     return O.prng_ints(f"scalars/{tag}", n, bound)
 
 
-def mixed(cv, tag, n):
-    """n elements below 2^256: random residues with q, q + 1, 2^256 - 1 and 0 in every seventh place"""
-    q = cv.q
-    vals = _ints(f"{cv.name}/{tag}", n, q)
-    special = (q, q + 1, TOP, 0)
-    for i in range(3, n, 7):
-        vals[i] = special[(i // 7) % 4]
-    return vals
-
-
-def to_bytes(vals):
-    return b"".join(v.to_bytes(32, "little") for v in vals)
-
-
-class Fix:
-    """One context per curve; vectors live at 32-byte offset `pad` (odd) inside allocations that end in a sentinel element."""
-
-    def __init__(self, name):
-        from montgomery_amd.api import MsmContext
-
-        self.name, self.cv = name, D.CURVE_TABLE[name]
-        self.q = self.cv.q
-        self.ctx = MsmContext(self.cv.cid)
-        self.bufs = []
-
-    def vector(self, vals_or_n, pad=3):
-        """device address of a vector holding vals (or n sentinel elements), `pad` elements into its allocation, one sentinel behind"""
-        raw = to_bytes(vals_or_n) if not isinstance(vals_or_n, int) else SENTINEL * vals_or_n
-        base = self.ctx.device_alloc(32 * pad + len(raw) + 32)
-        self.bufs.append(base)
-        self.ctx.device_upload(base, SENTINEL * pad + raw + SENTINEL)
-        return base + 32 * pad
-
-    def read(self, ptr, n):
-        return O.scalars_from_bytes(self.ctx.device_download(ptr, 32 * n)) if n else []
-
-    def point(self, res):
-        return (res.x, res.y) if self.cv.te else res.as_tuple()
-
-    def close(self):
-        for b in self.bufs:
-            self.ctx.device_free(b)
-        self.ctx.close()
+mixed = functools.partial(F.mixed, "scalars")
 
 
 @pytest.fixture(scope="module", params=D.NAMES)
@@ -80,10 +40,7 @@ def f7(request):
 @pytest.fixture(scope="module")
 def inner_grid():
     """(grid cap in blocks, lanes per block) of k_sv_inner, from the constants of scalar_vec.h"""
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libscalars_host.so", "tests/csrc/libscalars_host.so")
-    L = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libscalars_host.so"))
+    L = host_library("scalars_host")
     return L.sv_inner_max_blocks(), L.sv_block()
 
 

@@ -12,12 +12,13 @@ import pytest
 
 sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
 import degenerate_inputs as D  # noqa: E402
+import operator_fixture as F  # noqa: E402
+from host_lib import host_library  # noqa: E402
+from operator_fixture import SENTINEL, TOP, OperatorFixture, to_bytes  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-TOP = (1 << 256) - 1
-SENTINEL = b"\xa5" * 32
 THREE = ("bls377", "ed377", "pallas")
 SMALL = (1, 63, 64, 65, 255, 256, 257, 511, 513)
 
@@ -26,32 +27,24 @@ def _ints(tag, n, bound):
     return O.prng_ints(f"scans/{tag}", n, bound)
 
 
+def _start(n):
+    """where the special elements begin: a vector of up to three has one too"""
+    return 3 if n > 3 else 0
+
+
 def mixed(cv, tag, n):
-    """n elements below 2^256: random residues with q, q + 1, 2^256 - 1 and 0 in every seventh place"""
-    q = cv.q
-    vals = _ints(f"{cv.name}/{tag}", n, q)
-    special = (q, q + 1, TOP, 0)
-    for i in range(3 if n > 3 else 0, n, 7):
-        vals[i] = special[(i // 7) % 4]
-    return vals
+    return F.mixed("scans", cv, tag, n, start=_start(n))
 
 
 def unit_mixed(cv, tag, n):
     """n elements with residues other than 0, q + 1 and 2^256 - 1 among them: a product scan that stays away from 0"""
     q = cv.q
     vals = [v + 1 for v in _ints(f"{cv.name}/{tag}", n, q - 1)]
-    special = (q + 1, TOP if TOP % q else 1)
-    for i in range(3 if n > 3 else 0, n, 7):
-        vals[i] = special[(i // 7) % 2]
-    return vals
+    return F.with_specials(vals, (q + 1, TOP if TOP % q else 1), _start(n))
 
 
 def tiled(base, n):
     return [base[i % len(base)] for i in range(n)]
-
-
-def to_bytes(vals):
-    return b"".join(v.to_bytes(32, "little") for v in vals)
 
 
 def plan(n, tile_log):
@@ -86,57 +79,18 @@ def div_ref(vals, q, z):
     return out, acc
 
 
-class Fix:
-    """One context per curve; vectors live `pad` (odd) elements inside allocations that end in a sentinel element."""
-
+class Fix(OperatorFixture):
     def __init__(self, name):
-        from montgomery_amd.api import MsmContext
-
-        self.name, self.cv = name, D.CURVE_TABLE[name]
-        self.q = self.cv.q
-        self.ctx = MsmContext(self.cv.cid)
-        self.bufs = []
+        super().__init__(name)
         self.tile_log = None
 
-    def vector(self, vals_or_n, pad=3):
-        raw = to_bytes(vals_or_n) if not isinstance(vals_or_n, int) else SENTINEL * vals_or_n
-        base = self.ctx.device_alloc(32 * pad + len(raw) + 32)
-        self.bufs.append(base)
-        self.ctx.device_upload(base, SENTINEL * pad + raw + SENTINEL)
-        return base + 32 * pad
-
-    def read(self, ptr, n):
-        return O.scalars_from_bytes(self.ctx.device_download(ptr, 32 * n)) if n else []
-
-    def raw(self, ptr, n):
-        return self.ctx.device_download(ptr, 32 * n)
-
-    def fenced(self, ptr, n):
-        return self.ctx.device_download(ptr - 32, 32) == SENTINEL and self.ctx.device_download(ptr + 32 * n, 32) == SENTINEL
-
-    def free(self, *ptrs, pad=3):
-        for ptr in ptrs:
-            base = ptr - 32 * pad
-            self.bufs.remove(base)
-            self.ctx.device_free(base)
-
-    def point(self, res):
-        return (res.x, res.y) if self.cv.te else res.as_tuple()
-
     def last_plan(self):
-        out = (ctypes.c_int32 * 8)()
-        count = self.ctx._lib.msm_test_last_scan_plan(self.ctx._h, out, 8)
-        return list(out[:count])
+        return self.last("msm_test_last_scan_plan", 8)
 
     def set_tile_log(self, t, default):
         """t = 0: the default; the plan of later calls is checked against the tile in force"""
-        assert self.ctx._lib.msm_test_set_scan_tile_log(self.ctx._h, t) == 0
+        self.set("msm_test_set_scan_tile_log", t)
         self.tile_log = t or default
-
-    def close(self):
-        for b in self.bufs:
-            self.ctx.device_free(b)
-        self.ctx.close()
 
 
 @pytest.fixture(scope="module", params=D.NAMES)
@@ -162,10 +116,7 @@ def f2(request):
 
 @pytest.fixture(scope="module")
 def consts():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libscans_host.so", "tests/csrc/libscans_host.so")
-    L = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libscans_host.so"))
+    L = host_library("scans_host")
     return {"default": L.scans_default_tile_log(), "min": L.scans_min_tile_log(), "block": L.scans_block(), "inv_e": L.scans_inverse_e()}
 
 

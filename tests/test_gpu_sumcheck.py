@@ -5,6 +5,7 @@ allocation, end in a sentinel element, and carry non-canonical elements (q, q + 
 Sizes: 1, 2, 32, 64, 128, 256 and 512 pairs -- below a wave, one wave, one block, two blocks -- and 1024 pairs under a forced
 grid of one block (four pairs per lane) and of three (a ragged second stride)."""
 import ctypes
+import functools
 import os
 import sys
 
@@ -12,12 +13,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import degenerate_inputs as D  # noqa: E402
+import operator_fixture as F  # noqa: E402
+from operator_fixture import SENTINEL, TOP, OperatorFixture, to_bytes  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-TOP = (1 << 256) - 1
-SENTINEL = b"\xa5" * 32
 SHAPES = (("prod", 1), ("prod", 2), ("prod", 3), ("prod", 4), ("r1cs", 4))
 ROUND_LOGS = (1, 2, 6, 7, 8, 9, 10)
 NLOG = 10
@@ -28,18 +29,7 @@ def _ints(tag, n, bound):
     return O.prng_ints(f"sumcheck/{tag}", n, bound)
 
 
-def mixed(cv, tag, n):
-    """n elements below 2^256: random residues with q, q + 1, 2^256 - 1 and 0 in every seventh place"""
-    q = cv.q
-    vals = _ints(f"{cv.name}/{tag}", n, q)
-    special = (q, q + 1, TOP, 0)
-    for i in range(3, n, 7):
-        vals[i] = special[(i // 7) % 4]
-    return vals
-
-
-def to_bytes(vals):
-    return b"".join(v.to_bytes(32, "little") for v in vals)
+mixed = functools.partial(F.mixed, "sumcheck")
 
 
 def lo_of(i, var):
@@ -95,30 +85,10 @@ def interpolate(evals, x, q):
     return total % q
 
 
-class Fix:
-    """One context per curve; vectors live at 32-byte offset `pad` (odd) inside allocations that end in a sentinel element."""
-
+class Fix(OperatorFixture):
     def __init__(self, name):
-        from montgomery_amd.api import MsmContext
-
-        self.name, self.cv = name, D.CURVE_TABLE[name]
-        self.q = self.cv.q
-        self.ctx = MsmContext(self.cv.cid)
-        self.bufs = []
+        super().__init__(name)
         self._tables = None
-
-    def vector(self, vals_or_n, pad=3):
-        raw = to_bytes(vals_or_n) if not isinstance(vals_or_n, int) else SENTINEL * vals_or_n
-        base = self.ctx.device_alloc(32 * pad + len(raw) + 32)
-        self.bufs.append(base)
-        self.ctx.device_upload(base, SENTINEL * pad + raw + SENTINEL)
-        return base + 32 * pad
-
-    def read(self, ptr, n):
-        return O.scalars_from_bytes(self.ctx.device_download(ptr, 32 * n)) if n else []
-
-    def is_sentinel(self, ptr):
-        return self.ctx.device_download(ptr, 32) == SENTINEL
 
     def tables(self):
         """eight tables of 2^10 mixed elements, uploaded once and only ever read: (values, device addresses)"""
@@ -128,17 +98,12 @@ class Fix:
         return self._tables
 
     def last(self):
-        out = (ctypes.c_int32 * 4)()
-        assert self.ctx._lib.msm_test_last_sumcheck(self.ctx._h, out, 4) == 4
-        return list(out)
+        out = super().last("msm_test_last_sumcheck", 4)
+        assert len(out) == 4
+        return out
 
     def set_grid(self, blocks):
-        assert self.ctx._lib.msm_test_set_sumcheck_grid(self.ctx._h, blocks) == 0
-
-    def close(self):
-        for b in self.bufs:
-            self.ctx.device_free(b)
-        self.ctx.close()
+        self.set("msm_test_set_sumcheck_grid", blocks)
 
 
 @pytest.fixture(scope="module", params=D.NAMES)

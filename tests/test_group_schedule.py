@@ -15,8 +15,8 @@ import pytest
 
 sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "csrc", "libschedule_host.so")
+from host_lib import host_library  # noqa: E402
+
 BLS377, ED377 = 0, 1            # MSM_CURVE_BLS12_377_G1, MSM_CURVE_ED_ON_BLS12_377 (include/msm_hip.h)
 MiB, GiB = 1 << 20, 1 << 30
 CAP = 40000                     # groups: at most 126 windows x 256 ranges
@@ -24,10 +24,7 @@ CAP = 40000                     # groups: at most 126 windows x 256 ranges
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libschedule_host.so", "tests/csrc/libschedule_host.so")
-    L = C.CDLL(LIB)
+    L = host_library("schedule_host")
     i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
     L.gs_plan.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int, i32p]
     L.gs_window_bytes.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int]

@@ -1,39 +1,25 @@
 """Indexed (sparse) MSM at the C ABI and in the Python binding, without a GPU: the two symbols, the host-side input checks of the
 facade, and sparse_from_dense / dense_from_sparse."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_surface import abi_history, assert_abi_frozen, assert_names_declared
+
 NAMES = ("msm_run_indexed", "msm_run_indexed_narrow")
 Q377 = 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001
 
 
 def test_header_binding_and_library_have_the_indexed_entries():
-    from montgomery_amd import _lib
-
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "msm_hip.h")).read(), flags=re.S)
-    for n in NAMES:
-        assert re.search(r"\bint\s+%s\s*\(" % n, text), f"include/msm_hip.h does not declare {n}"
-        assert n in _lib.EXPORTS
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in NAMES:
-        assert hasattr(lib, n), f"libmsm_hip.so does not export {n}"
+    assert_names_declared(NAMES)
 
 
 def test_abi_version_and_struct_sizes_did_not_move():
     from montgomery_amd import _lib
 
-    text = open(os.path.join(ROOT, "include", "msm_hip.h")).read()
-    assert int(re.search(r"#define\s+MSM_ABI_VERSION\s+(\d+)", text).group(1)) == 8
-    assert "msm_run_indexed" in text[text.index("History:"):text.index("#define MSM_ABI_VERSION")]   # the ABI-history comment says so
-    assert _lib.ABI_VERSION == 8
-    assert ctypes.sizeof(_lib.MsmOpts) == 56 and ctypes.sizeof(_lib.MsmResult) == 176
-    lib = _lib.load()
-    assert lib.msm_abi_version() == 8 and lib.msm_abi_struct_bytes(0) == 56 and lib.msm_abi_struct_bytes(1) == 176
+    assert "msm_run_indexed" in abi_history()                                     # the ABI-history comment says so
+    assert_abi_frozen(_lib.load())
 
 
 def test_null_context_is_an_argument_error():

@@ -2,14 +2,12 @@
 and the binding, an unchanged ABI version and struct layout, the refusal of null outputs, and the reading of a process that never
 created a context."""
 import ctypes as C
-import os
-import re
 import subprocess
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_surface import ROOT, assert_abi_frozen, assert_header_declares, assert_prototypes, library
 
 PROTOTYPES = {
     "msm_test_live_buffers": "uint64_t* count_out, uint64_t* bytes_out",
@@ -18,21 +16,13 @@ PROTOTYPES = {
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("all", "montgomery_amd/libmsm_hip.so")
-    from montgomery_amd import _lib
-
-    return _lib.load()
+    return library()
 
 
 def test_the_library_exports_the_symbol_with_the_declared_signature(lib):
     from montgomery_amd import _lib, api
 
-    for name, args in PROTOTYPES.items():
-        assert name in _lib.EXPORTS, name
-        fn = getattr(lib, name)                      # AttributeError: the library has no such symbol
-        assert len(fn.argtypes) == args.count(",") + 1 and fn.restype is C.c_int, name
+    assert_prototypes(lib, PROTOTYPES)
     assert callable(getattr(api.MsmContext, "test_live_buffers", None))
     # null outputs are refused, whichever of the two it is, and nothing is written
     count, nbytes = C.c_uint64(7), C.c_uint64(7)
@@ -43,20 +33,11 @@ def test_the_library_exports_the_symbol_with_the_declared_signature(lib):
 
 
 def test_abi_version_and_struct_sizes_are_unchanged(lib):
-    from montgomery_amd import _lib
-
-    assert lib.msm_abi_version() == 8 == _lib.ABI_VERSION
-    assert lib.msm_abi_struct_bytes(0) == 56 == C.sizeof(_lib.MsmOpts)
-    assert lib.msm_abi_struct_bytes(1) == 176 == C.sizeof(_lib.MsmResult)
+    assert_abi_frozen(lib)
 
 
 def test_the_header_declares_the_symbol():
-    text = open(os.path.join(ROOT, "include", "msm_hip.h")).read()
-    assert re.search(r"#define\s+MSM_ABI_VERSION\s+8\b", text)
-    flat = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)          # comments out, then one space between tokens
-    flat = re.sub(r"\s+", " ", flat).replace("( ", "(").replace(" )", ")").replace(" ,", ",")
-    for name, args in PROTOTYPES.items():
-        assert f"int {name}({args});" in flat, name
+    assert_header_declares(PROTOTYPES)
 
 
 def test_a_process_that_never_created_a_context_reads_zero(lib):

@@ -17,19 +17,16 @@ sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
 import degenerate_inputs as D  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "csrc", "libmle_host.so")
-TOP = (1 << 256) - 1
+from host_lib import host_library, value, vec, words  # noqa: E402
+from operator_fixture import TOP, edges  # noqa: E402
+
 PROD, R1CS = 0, 1
 SHAPES = [(PROD, 1), (PROD, 2), (PROD, 3), (PROD, 4), (R1CS, 4)]
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libmle_host.so", "tests/csrc/libmle_host.so")
-    L = C.CDLL(LIB)
+    L = host_library("mle_host")
     u32p = C.POINTER(C.c_uint32)
     L.mle_pair_lo.argtypes = L.mle_pair_hi.argtypes = [C.c_uint64, C.c_uint32]
     L.mle_pair_lo.restype = L.mle_pair_hi.restype = C.c_uint64
@@ -42,22 +39,6 @@ def lib():
     L.mle_bind.argtypes = [C.c_int, u32p, u32p, u32p, u32p]
     L.mle_eq.argtypes = [C.c_int, u32p, C.c_uint32, u32p, u32p, u32p]
     return L
-
-
-def words(v, n=8):
-    return (C.c_uint32 * n)(*[(v >> (32 * j)) & 0xFFFFFFFF for j in range(n)])
-
-
-def vec(vals):
-    return (C.c_uint32 * (8 * max(len(vals), 1)))(*[(v >> (32 * j)) & 0xFFFFFFFF for v in vals for j in range(8)])
-
-
-def value(w, i=0, n=8):
-    return sum(int(w[n * i + j]) << (32 * j) for j in range(n))
-
-
-def edges(q):
-    return [0, 1, q - 1, q, q + 1, TOP]
 
 
 def g_of(shape, f, q):

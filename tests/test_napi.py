@@ -1,34 +1,21 @@
 """Node N-API shim + JS facade: builds, loads in the image's node, fails loudly
 without a GPU; on a GPU box it runs the reference's ZPrize self-tests and the golden vectors through JS."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NODE = shutil.which("node")
+from napi_support import NODE, ROOT, assert_exports, require_addon, run_js
 
 
 @pytest.fixture(scope="module")
 def addon():
-    if NODE is None or not os.path.exists("/usr/include/node/node_api.h"):
-        pytest.skip("node / node_api.h not present")
-    from conftest import build_if_missing
-
-    build_if_missing("all", "montgomery_amd/libmsm_hip.so")
-    build_if_missing("napi", "montgomery_amd/msm_hip.node")
-    return os.path.join(ROOT, "montgomery_amd", "msm_hip.node")
+    return require_addon()
 
 
 def test_addon_loads_and_exports(addon):
-    out = subprocess.run([NODE, "-e", "const m=require('./js/montgomery-hip.js');console.log(Object.keys(m.hip).sort().join(','))"],
-                         cwd=ROOT, capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stderr
-    names = out.stdout.strip().split(",")
-    for n in ("createContext", "destroyContext", "setPoints", "msm", "plan", "deviceAlloc", "deviceUpload", "deviceFree", "msmDevice",
-              "fieldOp", "batchInverse", "glvDecompose", "batchAdd", "OP_MUL", "OP_INV", "ABI_VERSION"):
-        assert n in names
+    assert_exports(("createContext", "destroyContext", "setPoints", "msm", "plan", "deviceAlloc", "deviceUpload", "deviceFree", "msmDevice",
+                    "fieldOp", "batchInverse", "glvDecompose", "batchAdd", "OP_MUL", "OP_INV", "ABI_VERSION"), facade=())
 
 
 def test_addon_fails_loudly_without_gpu(addon):
@@ -45,9 +32,7 @@ def test_addon_fails_loudly_without_gpu(addon):
 
 @pytest.mark.gpu
 def test_js_facade_on_gpu(addon):
-    out = subprocess.run([NODE, "js/test-compute-msm.js"], cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "ALL OK" in out.stdout
+    run_js("test-compute-msm.js", 600)
 
 
 @pytest.mark.gpu

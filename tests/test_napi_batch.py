@@ -1,22 +1,9 @@
 """Parallel.msmBatch of the JS facade against Parallel.msm on the golden vectors (js/test-batch.js).  `-m gpu`."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NODE = shutil.which("node")
+from napi_support import run_js
 
 
 @pytest.mark.gpu
 def test_js_msm_batch_equals_msm():
-    if NODE is None or not os.path.exists("/usr/include/node/node_api.h"):
-        pytest.skip("node / node_api.h not present")
-    from conftest import build_if_missing
-
-    build_if_missing("all", "montgomery_amd/libmsm_hip.so")
-    build_if_missing("napi", "montgomery_amd/msm_hip.node")
-    out = subprocess.run([NODE, "js/test-batch.js"], cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "ALL OK" in out.stdout
+    run_js("test-batch.js", 600)

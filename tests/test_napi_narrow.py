@@ -1,40 +1,13 @@
 """Narrow-scalar MSM through the N-API addon and the JS facade: the exports (no GPU), and js/test-narrow.js (`-m gpu`)."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NODE = shutil.which("node")
-
-
-def _addon():
-    if NODE is None or not os.path.exists("/usr/include/node/node_api.h"):
-        pytest.skip("node / node_api.h not present")
-    from conftest import build_if_missing
-
-    build_if_missing("all", "montgomery_amd/libmsm_hip.so")
-    build_if_missing("napi", "montgomery_amd/msm_hip.node")
+from napi_support import assert_exports, run_js
 
 
 def test_addon_and_facade_export_the_narrow_entries():
-    _addon()
-    out = subprocess.run([NODE, "-e", "const m=require('./js/montgomery-hip.js');console.log(Object.keys(m.hip).sort().join(','))"],
-                         cwd=ROOT, capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stderr
-    names = out.stdout.strip().split(",")
-    for n in ("msmNarrow", "msmBatchNarrow", "scalarBits"):
-        assert n in names
-    js = open(os.path.join(ROOT, "js", "montgomery-hip.js")).read()
-    dts = open(os.path.join(ROOT, "js", "montgomery-hip.d.ts")).read()
-    for n in ("msmNarrow", "msmBatchNarrow", "scalarBits"):
-        assert f"{n}(" in js and f"{n}(" in dts, n
+    assert_exports(("msmNarrow", "msmBatchNarrow", "scalarBits"))
 
 
 @pytest.mark.gpu
 def test_js_msm_narrow_equals_msm():
-    _addon()
-    out = subprocess.run([NODE, "js/test-narrow.js"], cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "ALL OK" in out.stdout
+    run_js("test-narrow.js", 600)

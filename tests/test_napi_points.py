@@ -1,24 +1,15 @@
 """pointsFromBytes(..., {compressed, validate}) of the JS facade (js/test-points-compressed.js).  `-m gpu`."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NODE = shutil.which("node")
+from napi_support import require_addon, run_js
 
 
 @pytest.mark.gpu
 def test_js_compressed_points(tmp_path):
-    if NODE is None or not os.path.exists("/usr/include/node/node_api.h"):
-        pytest.skip("node / node_api.h not present")
-    from conftest import build_if_missing
+    require_addon()
     from montgomery_amd import _lib
     from montgomery_amd.api import MsmContext
 
-    build_if_missing("all", "montgomery_amd/libmsm_hip.so")
-    build_if_missing("napi", "montgomery_amd/msm_hip.node")
     n = 1 << 14
     for name, cid in (("bls377", _lib.CURVE_BLS12_377_G1), ("bls381", _lib.CURVE_BLS12_381_G1), ("ed377", _lib.CURVE_ED_ON_BLS12_377)):
         ctx = MsmContext(cid)
@@ -28,6 +19,4 @@ def test_js_compressed_points(tmp_path):
             (tmp_path / f"{name}.cmp").write_bytes(ctx.get_points(0, n, compressed=True))
         finally:
             ctx.close()
-    out = subprocess.run([NODE, "js/test-points-compressed.js", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "ALL OK" in out.stdout
+    run_js("test-points-compressed.js", 600, str(tmp_path))

@@ -2,12 +2,10 @@
 library and the binding, an unchanged ABI version and struct layout, the methods of the Python facade, and the host-only entries
 (the root of unity and the size limit need no device work, so a context handle is all they would need -- here: their refusals)."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_surface import assert_abi_frozen, assert_header_declares, assert_prototypes, library
 
 PROTOTYPES = {
     "msm_scalars_ntt": "msm_ctx* ctx, void* dst, const void* a, uint32_t log2n, uint32_t B, const uint8_t* omega, const uint8_t* shift, "
@@ -21,21 +19,13 @@ PROTOTYPES = {
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("all", "montgomery_amd/libmsm_hip.so")
-    from montgomery_amd import _lib
-
-    return _lib.load()
+    return library()
 
 
 def test_the_library_exports_the_symbols_with_the_declared_signatures(lib):
     from montgomery_amd import _lib
 
-    for name, args in PROTOTYPES.items():
-        assert name in _lib.EXPORTS, name
-        fn = getattr(lib, name)                      # AttributeError: the library has no such symbol
-        assert len(fn.argtypes) == args.count(",") + 1 and fn.restype is C.c_int, name
+    assert_prototypes(lib, PROTOTYPES)
     # a null context is refused by every entry before anything else is looked at
     out, top = (C.c_uint8 * 32)(), C.c_uint32(7)
     assert lib.msm_scalars_ntt(None, None, None, 0, 1, None, None, 0) == _lib.MSM_ERR_ARG
@@ -46,20 +36,11 @@ def test_the_library_exports_the_symbols_with_the_declared_signatures(lib):
 
 
 def test_abi_version_and_struct_sizes_are_unchanged(lib):
-    from montgomery_amd import _lib
-
-    assert lib.msm_abi_version() == 8 == _lib.ABI_VERSION
-    assert lib.msm_abi_struct_bytes(0) == 56 == C.sizeof(_lib.MsmOpts)
-    assert lib.msm_abi_struct_bytes(1) == 176 == C.sizeof(_lib.MsmResult)
+    assert_abi_frozen(lib)
 
 
 def test_the_header_declares_the_symbols():
-    text = open(os.path.join(ROOT, "include", "msm_hip.h")).read()
-    assert re.search(r"#define\s+MSM_ABI_VERSION\s+8\b", text)
-    flat = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)          # comments out, then one space between tokens
-    flat = re.sub(r"\s+", " ", flat).replace("( ", "(").replace(" )", ")").replace(" ,", ",")
-    for name, args in PROTOTYPES.items():
-        assert f"int {name}({args});" in flat, name
+    assert_header_declares(PROTOTYPES)
 
 
 def test_the_python_facade_has_the_methods():

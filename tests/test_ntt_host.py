@@ -16,18 +16,15 @@ import degenerate_inputs as D  # noqa: E402
 import ntt_model as M  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "csrc", "libntt_host.so")
+from host_lib import host_library, value, words  # noqa: E402
+
 TOP = (1 << 256) - 1
 SCALE_NONE, SCALE_CONST, SCALE_TABLE = 0, 1, 2
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libntt_host.so", "tests/csrc/libntt_host.so")
-    L = C.CDLL(LIB)
+    L = host_library("ntt_host")
     u32p, i32p = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
     L.ntt_plan.argtypes = [C.c_int, C.c_int, i32p]
     L.ntt_modulus.argtypes = [C.c_int, u32p]
@@ -36,16 +33,8 @@ def lib():
     return L
 
 
-def words(v):
-    return (C.c_uint32 * 8)(*[(v >> (32 * j)) & 0xFFFFFFFF for j in range(8)])
-
-
-def vec(vals):
+def vec(vals):   # not host_lib.vec: an empty list gives an empty array here, not one spare element
     return (C.c_uint32 * (8 * len(vals)))(*[(v >> (32 * j)) & 0xFFFFFFFF for v in vals for j in range(8)])
-
-
-def value(w, i=0):
-    return sum(int(w[8 * i + j]) << (32 * j) for j in range(8))
 
 
 def run(lib, cv, log2n, B, tile_log, vals, omega, shift=None, inverse=False):

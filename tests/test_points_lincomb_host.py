@@ -15,26 +15,19 @@ sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
 import degenerate_inputs as D  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "csrc", "liblincomb_host.so")
+from host_lib import host_library, words  # noqa: E402
+
 OP_DBL, OP_ADD = 0, 1
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/liblincomb_host.so", "tests/csrc/liblincomb_host.so")
-    L = C.CDLL(LIB)
+    L = host_library("lincomb_host")
     u32p = C.POINTER(C.c_uint32)
     L.lc_program.argtypes = [C.c_int, u32p, u32p, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
     L.lc_make_row.argtypes = [C.c_int, u32p, u32p, C.c_int, u32p]
     L.lc_lane.argtypes = [C.c_int, u32p, u32p, C.POINTER(C.c_uint8), C.c_int, u32p]
     return L
-
-
-def words(v, n):
-    return (C.c_uint32 * n)(*[(v >> (32 * j)) & 0xFFFFFFFF for j in range(n)])
 
 
 def program(lib, cv, a, b):

@@ -3,12 +3,11 @@ version and struct sizes, the History comment, and the argument handling that ne
 live context (bad ids, misaligned device scalars, the forbidden overlap, a source range beyond the set, an off-curve base, a
 failed call leaving every set as it was) are in tests/test_gpu_points_mul.py::test_every_refusal_leaves_the_sets_as_they_were."""
 import ctypes
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_surface import abi_history, assert_abi_frozen, assert_names_declared
+
 NAMES = ("msm_points_mul", "msm_points_mul_base", "msm_test_set_points_mul_grid", "msm_test_set_points_mul_base_path",
          "msm_test_last_points_mul")
 
@@ -16,13 +15,7 @@ NAMES = ("msm_points_mul", "msm_points_mul_base", "msm_test_set_points_mul_grid"
 def test_header_binding_and_library_have_the_entries():
     from montgomery_amd import _lib
 
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "msm_hip.h")).read(), flags=re.S)
-    for n in NAMES:
-        assert re.search(r"\bint\s+%s\s*\(" % n, text), f"include/msm_hip.h does not declare {n}"
-        assert n in _lib.EXPORTS
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in NAMES:
-        assert hasattr(lib, n), f"libmsm_hip.so does not export {n}"
+    assert_names_declared(NAMES)
     bound = _lib.load()
     assert bound.msm_points_mul.argtypes is not None and len(bound.msm_points_mul.argtypes) == 7
     assert bound.msm_points_mul_base.argtypes is not None and len(bound.msm_points_mul_base.argtypes) == 6
@@ -31,14 +24,9 @@ def test_header_binding_and_library_have_the_entries():
 def test_abi_version_and_struct_sizes_did_not_move():
     from montgomery_amd import _lib
 
-    text = open(os.path.join(ROOT, "include", "msm_hip.h")).read()
-    assert int(re.search(r"#define\s+MSM_ABI_VERSION\s+(\d+)", text).group(1)) == 8
-    history = text[text.index("History:"):text.index("#define MSM_ABI_VERSION")]
+    history = abi_history()
     assert "msm_points_mul" in history and "msm_points_mul_base" in history     # the ABI-history comment says so
-    assert _lib.ABI_VERSION == 8
-    assert ctypes.sizeof(_lib.MsmOpts) == 56 and ctypes.sizeof(_lib.MsmResult) == 176
-    lib = _lib.load()
-    assert lib.msm_abi_version() == 8 and lib.msm_abi_struct_bytes(0) == 56 and lib.msm_abi_struct_bytes(1) == 176
+    assert_abi_frozen(_lib.load())
 
 
 def test_null_context_is_an_argument_error():

@@ -19,18 +19,15 @@ import degenerate_inputs as D  # noqa: E402
 import digit_model as M  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "csrc", "libpoints_mul_host.so")
+from host_lib import host_library, words  # noqa: E402
+
 VAR_WIDTHS, BASE_WIDTHS = (3, 4, 5), (6, 8, 10)
 TWO256 = 1 << 256
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libpoints_mul_host.so", "tests/csrc/libpoints_mul_host.so")
-    L = C.CDLL(LIB)
+    L = host_library("points_mul_host")
     u32p, i32p = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
     L.pm_table_elems.argtypes = [C.c_int, C.c_int, C.c_uint64]
     L.pm_table_elems.restype = C.c_uint64
@@ -42,11 +39,7 @@ def lib():
     return L
 
 
-def words(v, n):
-    return (C.c_uint32 * n)(*[(v >> (32 * j)) & 0xFFFFFFFF for j in range(n)])
-
-
-def value(ws):
+def value(ws):   # not host_lib.value: the whole array is one number, whatever its length
     return sum(int(w) << (32 * j) for j, w in enumerate(ws))
 
 
@@ -152,10 +145,7 @@ def make_row(lib, cv, P):
 
 @functools.lru_cache(maxsize=None)
 def _lincomb_row_maker():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/liblincomb_host.so", "tests/csrc/liblincomb_host.so")
-    L = C.CDLL(os.path.join(ROOT, "tests", "csrc", "liblincomb_host.so"))
+    L = host_library("lincomb_host")
     u32p = C.POINTER(C.c_uint32)
     L.lc_make_row.argtypes = [C.c_int, u32p, u32p, C.c_int, u32p]
     return L

@@ -20,20 +20,17 @@ import pytest
 sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
 import degenerate_inputs as D  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
-from test_points_mul_host import LIB as PM_LIB, edge_scalars, make_row, new_table, wire_row, words  # noqa: E402
+from test_points_mul_host import edge_scalars, make_row, new_table, wire_row, words  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "csrc", "libpoints_ntt_host.so")
+from host_lib import host_library  # noqa: E402
+
 TWO_ADIC = ("bls377", "bls381", "pallas", "bn254", "vesta")
 MAX_LOG = 12
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libpoints_ntt_host.so", "tests/csrc/libpoints_ntt_host.so")
-    L = C.CDLL(LIB)
+    L = host_library("points_ntt_host")
     u32p = C.POINTER(C.c_uint32)
     L.pn_bit_reverse.argtypes = [C.c_uint32, C.c_int]
     L.pn_bit_reverse.restype = C.c_uint32
@@ -48,10 +45,7 @@ def lib():
 @pytest.fixture(scope="module")
 def pm():
     """the shim of points_mul.h: it makes rows and sizes tables"""
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libpoints_mul_host.so", "tests/csrc/libpoints_mul_host.so")
-    L = C.CDLL(PM_LIB)
+    L = host_library("points_mul_host")
     u32p = C.POINTER(C.c_uint32)
     L.pm_table_elems.argtypes = [C.c_int, C.c_int, C.c_uint64]
     L.pm_table_elems.restype = C.c_uint64

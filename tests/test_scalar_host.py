@@ -12,18 +12,15 @@ sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
 import degenerate_inputs as D  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "csrc", "libscalar_host_host.so")
+from host_lib import host_library, value, words  # noqa: E402
+
 R = 1 << 270
 MSM_OK, MSM_ERR_ARG, MSM_ERR_SCALAR = 0, 1, 6   # include/msm_hip.h
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libscalar_host_host.so", "tests/csrc/libscalar_host_host.so")
-    L = C.CDLL(LIB)
+    L = host_library("scalar_host_host")
     u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
     L.sh_modulus.argtypes = [C.c_int, u32p]
     L.sh_parse.argtypes = [C.c_int, u8p, u32p, u32p, u32p, u8p]
@@ -38,14 +35,6 @@ def lib():
     L.sh_dst_ranges_ok.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int]
     L.sh_rows_overlap_ok.argtypes = [C.c_uint64, C.c_uint64]
     return L
-
-
-def words(v):
-    return (C.c_uint32 * 8)(*[(v >> (32 * j)) & 0xFFFFFFFF for j in range(8)])
-
-
-def value(w, i=0):
-    return sum(int(w[8 * i + j]) << (32 * j) for j in range(8))
 
 
 def two_adicity(q):

@@ -14,17 +14,14 @@ sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
 import degenerate_inputs as D  # noqa: E402
 from oracle import msm_oracle as O  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "csrc", "libscalars_host.so")
+from host_lib import host_library, value, words  # noqa: E402
+
 TOP = (1 << 256) - 1
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libscalars_host.so", "tests/csrc/libscalars_host.so")
-    L = C.CDLL(LIB)
+    L = host_library("scalars_host")
     u32p = C.POINTER(C.c_uint32)
     L.sv_modulus.argtypes = [C.c_int, u32p]
     L.sv_lincomb.argtypes = [C.c_int, u32p, u32p, u32p, u32p, u32p]
@@ -35,16 +32,8 @@ def lib():
     return L
 
 
-def words(v):
-    return (C.c_uint32 * 8)(*[(v >> (32 * j)) & 0xFFFFFFFF for j in range(8)])
-
-
-def vec(vals):
+def vec(vals):   # not host_lib.vec: an empty list gives an empty array here, not one spare element
     return (C.c_uint32 * (8 * len(vals)))(*[(v >> (32 * j)) & 0xFFFFFFFF for v in vals for j in range(8)])
-
-
-def value(w, i=0):
-    return sum(int(w[8 * i + j]) << (32 * j) for j in range(8))
 
 
 def operands(cv, tag):

@@ -1,12 +1,10 @@
 """The resident scans at the boundary (no GPU): the three new symbols of include/msm_hip.h and the two of its debug surface in the
 library and the binding, the two enums, an unchanged ABI version and struct layout, and the methods of the Python facade."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_surface import assert_abi_frozen, assert_header_declares, assert_prototypes, library
 
 PROTOTYPES = {
     "msm_scalars_scan": "msm_ctx* ctx, void* dst, const void* a, uint64_t n, int op, uint32_t flags, const uint8_t* init, "
@@ -20,21 +18,13 @@ PROTOTYPES = {
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("all", "montgomery_amd/libmsm_hip.so")
-    from montgomery_amd import _lib
-
-    return _lib.load()
+    return library()
 
 
 def test_the_library_exports_the_symbols_with_the_declared_signatures(lib):
     from montgomery_amd import _lib
 
-    for name, args in PROTOTYPES.items():
-        assert name in _lib.EXPORTS, name
-        fn = getattr(lib, name)                      # AttributeError: the library has no such symbol
-        assert len(fn.argtypes) == args.count(",") + 1 and fn.restype is C.c_int, name
+    assert_prototypes(lib, PROTOTYPES)
     # a null context is refused by every entry before anything else is looked at
     out, zeros = (C.c_uint8 * 32)(*([7] * 32)), C.c_uint64(7)
     assert lib.msm_scalars_scan(None, None, None, 0, _lib.SCAN_SUM, 0, None, out) == _lib.MSM_ERR_ARG
@@ -46,22 +36,13 @@ def test_the_library_exports_the_symbols_with_the_declared_signatures(lib):
 
 
 def test_abi_version_and_struct_sizes_are_unchanged(lib):
-    from montgomery_amd import _lib
-
-    assert lib.msm_abi_version() == 8 == _lib.ABI_VERSION
-    assert lib.msm_abi_struct_bytes(0) == 56 == C.sizeof(_lib.MsmOpts)
-    assert lib.msm_abi_struct_bytes(1) == 176 == C.sizeof(_lib.MsmResult)
+    assert_abi_frozen(lib)
 
 
 def test_the_header_declares_the_symbols_and_the_enums():
     from montgomery_amd import _lib
 
-    text = open(os.path.join(ROOT, "include", "msm_hip.h")).read()
-    assert re.search(r"#define\s+MSM_ABI_VERSION\s+8\b", text)
-    flat = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)          # comments out, then one space between tokens
-    flat = re.sub(r"\s+", " ", flat).replace("( ", "(").replace(" )", ")").replace(" ,", ",")
-    for name, args in PROTOTYPES.items():
-        assert f"int {name}({args});" in flat, name
+    flat = assert_header_declares(PROTOTYPES)
     assert "enum { MSM_SCAN_SUM = 0, MSM_SCAN_PRODUCT = 1 };" in flat and (_lib.SCAN_SUM, _lib.SCAN_PRODUCT) == (0, 1)
     assert "enum { MSM_SCAN_EXCLUSIVE = 1 };" in flat and _lib.SCAN_EXCLUSIVE == 1
 

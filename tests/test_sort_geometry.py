@@ -27,8 +27,8 @@ import pytest
 sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
 import crafted_digits as D  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "csrc", "libschedule_host.so")
+from host_lib import host_library  # noqa: E402
+
 BLS377, ED377 = 0, 1            # MSM_CURVE_BLS12_377_G1, MSM_CURVE_ED_ON_BLS12_377 (include/msm_hip.h)
 N_CU = 256
 BS_MAX_AB, BS_MAX_FB, BS_SPAN_LOG, BP_TILE = 11, 12, 17, 4096      # sort_kernels.h
@@ -39,10 +39,7 @@ CAP = 40000                     # groups: at most 126 windows x 256 ranges
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libschedule_host.so", "tests/csrc/libschedule_host.so")
-    L = C.CDLL(LIB)
+    L = host_library("schedule_host")
     i32p, u64p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
     L.gs_plan.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int, i32p]
     L.gs_schedule.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -2,12 +2,10 @@
 the two of its debug surface in the library and the binding, the enums, an unchanged ABI version and struct layout, and the
 methods of the Python facade with its host helper."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_surface import assert_abi_frozen, assert_header_declares, assert_prototypes, header_text, library
 
 PROTOTYPES = {
     "msm_matrix_create": "msm_ctx* ctx, uint64_t rows, uint64_t cols, uint64_t nnz, const uint32_t* row_ptr, const uint32_t* col, "
@@ -23,21 +21,13 @@ PROTOTYPES = {
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("all", "montgomery_amd/libmsm_hip.so")
-    from montgomery_amd import _lib
-
-    return _lib.load()
+    return library()
 
 
 def test_the_library_exports_the_symbols_with_the_declared_signatures(lib):
     from montgomery_amd import _lib
 
-    for name, args in PROTOTYPES.items():
-        assert name in _lib.EXPORTS, name
-        fn = getattr(lib, name)                      # AttributeError: the library has no such symbol
-        assert len(fn.argtypes) == args.count(",") + 1 and fn.restype is C.c_int, name
+    assert_prototypes(lib, PROTOTYPES)
     # a null context is refused by every entry before anything else is looked at, and nothing is written
     out, word, big = (C.c_uint8 * 32)(*([7] * 32)), (C.c_int32 * 5)(7, 7, 7, 7, 7), [C.c_uint64(7) for _ in range(4)]
     rp, ident = (C.c_uint32 * 2)(0, 0), C.c_int32(7)
@@ -51,22 +41,14 @@ def test_the_library_exports_the_symbols_with_the_declared_signatures(lib):
 
 
 def test_abi_version_and_struct_sizes_are_unchanged(lib):
-    from montgomery_amd import _lib
-
-    assert lib.msm_abi_version() == 8 == _lib.ABI_VERSION
-    assert lib.msm_abi_struct_bytes(0) == 56 == C.sizeof(_lib.MsmOpts)
-    assert lib.msm_abi_struct_bytes(1) == 176 == C.sizeof(_lib.MsmResult)
+    assert_abi_frozen(lib)
 
 
 def test_the_header_declares_the_symbols_and_the_enums():
     from montgomery_amd import _lib
 
-    text = open(os.path.join(ROOT, "include", "msm_hip.h")).read()
-    assert re.search(r"#define\s+MSM_ABI_VERSION\s+8\b", text)
-    flat = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)          # comments out, then one space between tokens
-    flat = re.sub(r"\s+", " ", flat).replace("( ", "(").replace(" )", ")").replace(" ,", ",")
-    for name, args in PROTOTYPES.items():
-        assert f"int {name}({args});" in flat, name
+    flat = assert_header_declares(PROTOTYPES)
+    text = header_text()
     assert "enum { MSM_MATRIX_TRANSPOSE = 1 };" in flat and "enum { MSM_MATVEC_ACCUMULATE = 1 };" in flat
     assert (_lib.MATRIX_TRANSPOSE, _lib.MATVEC_ACCUMULATE) == (1, 1)
     # the contract a caller cannot guess: the aliasing rule, the determinism, and how a binding detects the feature

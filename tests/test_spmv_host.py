@@ -17,18 +17,15 @@ import pytest
 sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
 import degenerate_inputs as D  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "csrc", "libspmv_host.so")
-TOP = (1 << 256) - 1
+from host_lib import host_library, value, vec, words  # noqa: E402
+from operator_fixture import TOP, edges  # noqa: E402
+
 FIN_ALPHA, FIN_ACCUMULATE = 1, 2
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from conftest import build_if_missing
-
-    build_if_missing("tests/csrc/libspmv_host.so", "tests/csrc/libspmv_host.so")
-    L = C.CDLL(LIB)
+    L = host_library("spmv_host")
     u32p = C.POINTER(C.c_uint32)
     L.spmv_row.argtypes = [C.c_int, C.c_int, C.c_int, u32p, u32p, C.c_int, C.c_uint32, u32p, u32p, u32p]
     L.spmv_value.argtypes = [C.c_int, u32p, u32p]
@@ -41,24 +38,8 @@ def lib():
     return L
 
 
-def words(v):
-    return (C.c_uint32 * 8)(*[(v >> (32 * j)) & 0xFFFFFFFF for j in range(8)])
-
-
-def vec(vals):
-    return (C.c_uint32 * (8 * max(len(vals), 1)))(*[(v >> (32 * j)) & 0xFFFFFFFF for v in vals for j in range(8)])
-
-
 def u32(vals):
     return (C.c_uint32 * max(len(vals), 1))(*vals)
-
-
-def value(w, i=0):
-    return sum(int(w[8 * i + j]) << (32 * j) for j in range(8))
-
-
-def edges(q):
-    return [0, 1, q - 1, q, q + 1, TOP]
 
 
 def row(lib, cv, coef, x, cut=None, alpha=None, old=None, ones=False):
