@@ -10,7 +10,7 @@ CURVES := CvBls377 CvBls381 CvPallas CvBn254 CvGrumpkin CvVesta
 CURVE_OBJS := $(CURVES:%=$(BUILD)/kernels_%.o)
 HOST_TUS := msm_plan msm_sort msm_tree msm_reduce msm_upload msm_pipeline msm_batch msm_tables msm_abi msm_test_abi msm_gen msm_ingest msm_narrow msm_indexed msm_lincomb msm_points_mul msm_points_ntt msm_scalars msm_ntt msm_scan msm_mle msm_spmv sort_kernels te_kernels narrow_kernels
 HOST_OBJS := $(HOST_TUS:%=$(BUILD)/%.o)
-KHDRS := $(CSRC)/msm_kernels.h $(CSRC)/batch_add.h $(CSRC)/msm_gen_kernels.h $(CSRC)/kernel_inst.h $(CSRC)/field.h $(CSRC)/packed.h $(CSRC)/curve.h \
+KHDRS := $(CSRC)/msm_kernels.h $(CSRC)/batch_add.h $(CSRC)/mem_policy.h $(CSRC)/msm_gen_kernels.h $(CSRC)/kernel_inst.h $(CSRC)/field.h $(CSRC)/packed.h $(CSRC)/curve.h \
          $(CSRC)/glv.h $(CSRC)/constants_gen.h
 
 # the curve-templated kernels compile once per curve, in parallel with the host pipeline

@@ -25,6 +25,7 @@
 //   * addresses are a uniform base (SALU) plus a per-lane 32-bit offset.
 #pragma once
 #include "curve.h"
+#include "mem_policy.h"
 #include "packed.h"
 
 namespace msm {
@@ -65,6 +66,39 @@ static_assert(BA_THREADS == 256, "the shared inversion is written for four waves
 constexpr int BA_WAVES = 2;
 
 // ---------------------------------------------------------------------------------------------------------------
+// cache policy of the kernel's streams (mem_policy.h): every global access below names its stream
+// ---------------------------------------------------------------------------------------------------------------
+// Decided stream by stream at the headline size (2^26 points, c = 21 on three shared tables; profiles/stream_policy_time.txt,
+// parent 127.4 ms): only the prefix scratch gains from the non-temporal policy.
+struct BaPol {
+  // prefix products: written once by the forward sweep, read once by the backward sweep, gigabytes apart in flight, every wave
+  // access a run of whole lines.  Non-temporal on both sides 127.4 -> 124.5 ms (out alone -1.1, in alone -0.9).
+  static constexpr MemPol PREFIX_OUT = MemPol::NT;
+  static constexpr MemPol PREFIX_IN = MemPol::NT;
+  // pair list (`slots`) and `dest` of the gather round, read once: -0.1 ms, inside the noise
+  static constexpr MemPol PAIRS = MemPol::DEFAULT;
+  // operand descriptors of the search rounds, read once: +0.7
+  static constexpr MemPol DESC = MemPol::DEFAULT;
+  // input planes, x in the forward sweep +0.3; x and y in the backward sweep +0.7: the backward sweep finds in the L2 and the
+  // Infinity Cache what the forward sweep of the same lanes brought in
+  static constexpr MemPol PLANE_IN_FWD = MemPol::DEFAULT;
+  static constexpr MemPol PLANE_IN_BWD = MemPol::DEFAULT;
+  // output planes, written once and read by the next launch: +0.2
+  static constexpr MemPol PLANE_OUT = MemPol::DEFAULT;
+  // 64-byte element records of the pair form's round 1: a non-temporal store of half a line is not merged with its neighbour's
+  // on chip -- round 1 122 -> 254 ms
+  static constexpr MemPol REC_OUT = MemPol::DEFAULT;
+  // ... read back by round 2, two records of a line by two lanes: +9.4
+  static constexpr MemPol REC_IN = MemPol::DEFAULT;
+  // gathered point rows: the forward sweep touches the x sector of a line whose y the backward sweep comes back for; non-temporal
+  // on the forward side +3.8, on the backward side (three 16-byte loads of one line each) +28
+  static constexpr MemPol ROW_FWD = MemPol::DEFAULT;
+  static constexpr MemPol ROW_BWD = MemPol::DEFAULT;
+  // reloads of the rare cases (ba_load_b, the y of equal x) and the in-place stores, whose sums are operands again
+  static constexpr MemPol RARE = MemPol::DEFAULT;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // packed-word helpers.  gfx9 allows ONE scalar or literal operand per VALU instruction and the carry-in of a chain is
 // one, so the modulus cannot ride the chains as a literal: it enters through a plain v_and with the borrow mask
 // (pk_set_p_masked, packed.h).
@@ -97,27 +131,35 @@ __device__ __forceinline__ void pk_reduce_product(PkW<F::NW>& r) {
 
 // one coordinate = W / 4 pieces of 16 bytes (3 for the 12-word fields, 2 for the 8-word ones), `stride` bytes apart, starting
 // at byte `off` (32-bit, per lane) from the uniform `base`
-template <int W>
+template <MemPol P, int W>
 __device__ __forceinline__ void ba_load3(PkW<W>& w, const char* base, uint32_t off, uint64_t stride) {
 #pragma unroll
   for (int j = 0; j < W / 4; j++) {
-    const uint4 v = *reinterpret_cast<const uint4*>(base + (uint64_t)j * stride + off);
+    const uint4 v = mem_load16<P>(base + (uint64_t)j * stride + off);
     w.w[4 * j] = v.x; w.w[4 * j + 1] = v.y; w.w[4 * j + 2] = v.z; w.w[4 * j + 3] = v.w;
   }
 }
-template <int W>
+template <MemPol P, int W>
 __device__ __forceinline__ void ba_load3_wide(PkW<W>& w, const char* p) {   // per-lane 64-bit address, consecutive pieces
 #pragma unroll
   for (int j = 0; j < W / 4; j++) {
-    const uint4 v = reinterpret_cast<const uint4*>(p)[j];
+    const uint4 v = mem_load16<P>(p + 16 * j);
     w.w[4 * j] = v.x; w.w[4 * j + 1] = v.y; w.w[4 * j + 2] = v.z; w.w[4 * j + 3] = v.w;
   }
 }
-template <int W>
+template <MemPol P, int W>
 __device__ __forceinline__ void ba_store3(char* base, uint32_t off, uint64_t stride, const PkW<W>& w) {
 #pragma unroll
   for (int j = 0; j < W / 4; j++)
-    *reinterpret_cast<uint4*>(base + (uint64_t)j * stride + off) = make_uint4(w.w[4 * j], w.w[4 * j + 1], w.w[4 * j + 2], w.w[4 * j + 3]);
+    mem_store16<P>(base + (uint64_t)j * stride + off, make_uint4(w.w[4 * j], w.w[4 * j + 1], w.w[4 * j + 2], w.w[4 * j + 3]));
+}
+// a gathered operand: a row of the point table, or (no pair list: round 2 of the pair form) a record of the round before -- a
+// uniform branch, and none at all while both streams have one policy
+template <MemPol ROW, int W>
+__device__ __forceinline__ void ba_load_row(PkW<W>& w, const char* p, bool is_row) {
+  if constexpr (ROW == BaPol::REC_IN) ba_load3_wide<ROW>(w, p);
+  else if (is_row) ba_load3_wide<ROW>(w, p);
+  else ba_load3_wide<BaPol::REC_IN>(w, p);
 }
 
 // where the two operands of one pair live
@@ -156,10 +198,10 @@ __device__ __forceinline__ void ba_locate<MODE_REGULAR>(PairLoc<MODE_REGULAR>& L
 template <>
 __device__ __forceinline__ void ba_locate<MODE_SEARCH>(PairLoc<MODE_SEARCH>& L, const BatchArgs& a, uint32_t i, uint64_t T, uint32_t t,
                                                         bool active) {
-  const uint32_t d = active ? a.desc[(uint64_t)i * T + t] : 0u;
+  const uint32_t d = active ? mem_load4<BaPol::DESC>(a.desc + (uint64_t)i * T + t) : 0u;
   L.a = (uint64_t)(d >> 1) * 16;
   L.b_absent = (d & 1u) == 0;
-  L.b = L.b_absent ? L.a : (a.desc_b && active) ? (uint64_t)a.desc_b[(uint64_t)i * T + t] * 16 : L.a + 16;
+  L.b = L.b_absent ? L.a : (a.desc_b && active) ? (uint64_t)mem_load4<BaPol::DESC>(a.desc_b + (uint64_t)i * T + t) * 16 : L.a + 16;
   L.skip = !active;
 }
 template <>
@@ -167,7 +209,7 @@ __device__ __forceinline__ void ba_locate<MODE_GATHER>(PairLoc<MODE_GATHER>& L, 
                                                         bool active) {
   uint2 pp = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
   if (active) {
-    if (a.slots) pp = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(a.slots) + 8ull * i * T + 8u * t);
+    if (a.slots) pp = mem_load8<BaPol::PAIRS>(reinterpret_cast<const char*>(a.slots) + 8ull * i * T + 8u * t);
     else {   // element records written by the round before: element k is "entry" k of a table of 64-byte records
       const uint32_t e4 = (uint32_t)(((uint64_t)i * T + t) << 2);
       pp = make_uint2(e4, e4 + 2u);
@@ -183,22 +225,24 @@ __device__ __forceinline__ void ba_locate<MODE_GATHER>(PairLoc<MODE_GATHER>& L, 
   L.flags = (aa ? 1u : 0u) | (bb ? 2u : 0u) | ((pp.x & 1u) ? 4u : 0u) | ((pp.y & 1u) ? 8u : 0u);
 }
 
-template <class F, int MODE>
+// BWD: the backward sweep's loads (the streams of the two sweeps carry their own policies)
+template <class F, int MODE, bool BWD>
 __device__ __forceinline__ void ba_load_x(PkW<F::NW>& x1, PkW<F::NW>& x2, const PairLoc<MODE>& L, const BatchArgs& a, uint32_t t) {
   constexpr int NP = F::NW / 4;   // 16-byte pieces per coordinate
+  constexpr MemPol PP = BWD ? BaPol::PLANE_IN_BWD : BaPol::PLANE_IN_FWD, PR = BWD ? BaPol::ROW_BWD : BaPol::ROW_FWD;
   if constexpr (MODE == MODE_GATHER) {
-    ba_load3_wide(x1, L.pa);
-    ba_load3_wide(x2, L.pb);
+    ba_load_row<PR>(x1, L.pa, a.slots != nullptr);
+    ba_load_row<PR>(x2, L.pb, a.slots != nullptr);
   } else if constexpr (MODE == MODE_REGULAR) {
-    ba_load3(x1, L.base, 32u * t, a.in_cap * 16);
-    ba_load3(x2, L.base + 16, 32u * t, a.in_cap * 16);
+    ba_load3<PP>(x1, L.base, 32u * t, a.in_cap * 16);
+    ba_load3<PP>(x2, L.base + 16, 32u * t, a.in_cap * 16);
   } else {
     const char* p = reinterpret_cast<const char*>(a.in) + L.a;
     const char* q = reinterpret_cast<const char*>(a.in) + L.b;
     const uint64_t s = a.in_cap * 16;
 #pragma unroll
     for (int j = 0; j < NP; j++) {
-      const uint4 v = *reinterpret_cast<const uint4*>(p + j * s), u = *reinterpret_cast<const uint4*>(q + j * s);
+      const uint4 v = mem_load16<PP>(p + j * s), u = mem_load16<PP>(q + j * s);
       x1.w[4 * j] = v.x; x1.w[4 * j + 1] = v.y; x1.w[4 * j + 2] = v.z; x1.w[4 * j + 3] = v.w;
       x2.w[4 * j] = u.x; x2.w[4 * j + 1] = u.y; x2.w[4 * j + 2] = u.z; x2.w[4 * j + 3] = u.w;
     }
@@ -207,25 +251,32 @@ __device__ __forceinline__ void ba_load_x(PkW<F::NW>& x1, PkW<F::NW>& x2, const 
 
 // y coordinates; gather mode applies the sign bit of the payload: y -> p - y (a zero y becomes p: congruent, and
 // only ever stored after ba_canonical_y)
-template <class F, int MODE>
+// (BWD = false: the rare reload of ba_denominator, default policy)
+template <class F, int MODE, bool BWD>
 __device__ __forceinline__ void ba_load_y(PkW<F::NW>& y1, PkW<F::NW>& y2, const PairLoc<MODE>& L, const BatchArgs& a, uint32_t t) {
   constexpr int NP = F::NW / 4;
+  constexpr MemPol PY = BWD ? BaPol::PLANE_IN_BWD : BaPol::RARE;
   if constexpr (MODE == MODE_GATHER) {
-    ba_load3_wide(y1, L.pa + a.y_off);
-    ba_load3_wide(y2, L.pb + a.y_off);
+    if constexpr (BWD) {
+      ba_load_row<BaPol::ROW_BWD>(y1, L.pa + a.y_off, a.slots != nullptr);
+      ba_load_row<BaPol::ROW_BWD>(y2, L.pb + a.y_off, a.slots != nullptr);
+    } else {
+      ba_load3_wide<BaPol::RARE>(y1, L.pa + a.y_off);
+      ba_load3_wide<BaPol::RARE>(y2, L.pb + a.y_off);
+    }
     pk_cond_neg<F>(y1, L.flags & 4u);
     pk_cond_neg<F>(y2, L.flags & 8u);
   } else if constexpr (MODE == MODE_REGULAR) {
     const char* b = L.base + NP * a.in_cap * 16;
-    ba_load3(y1, b, 32u * t, a.in_cap * 16);
-    ba_load3(y2, b + 16, 32u * t, a.in_cap * 16);
+    ba_load3<PY>(y1, b, 32u * t, a.in_cap * 16);
+    ba_load3<PY>(y2, b + 16, 32u * t, a.in_cap * 16);
   } else {
     const uint64_t s = a.in_cap * 16;
     const char* p = reinterpret_cast<const char*>(a.in) + L.a + NP * s;
     const char* q = reinterpret_cast<const char*>(a.in) + L.b + NP * s;
 #pragma unroll
     for (int j = 0; j < NP; j++) {
-      const uint4 v = *reinterpret_cast<const uint4*>(p + j * s), u = *reinterpret_cast<const uint4*>(q + j * s);
+      const uint4 v = mem_load16<PY>(p + j * s), u = mem_load16<PY>(q + j * s);
       y1.w[4 * j] = v.x; y1.w[4 * j + 1] = v.y; y1.w[4 * j + 2] = v.z; y1.w[4 * j + 3] = v.w;
       y2.w[4 * j] = u.x; y2.w[4 * j + 1] = u.y; y2.w[4 * j + 2] = u.z; y2.w[4 * j + 3] = u.w;
     }
@@ -238,19 +289,19 @@ template <class F, int MODE>
 __device__ __forceinline__ void ba_load_b(PkW<F::NW>& x2, PkW<F::NW>& y2, const PairLoc<MODE>& L, const BatchArgs& a, uint32_t t) {
   constexpr int NP = F::NW / 4;
   if constexpr (MODE == MODE_GATHER) {
-    ba_load3_wide(x2, L.pb);
-    ba_load3_wide(y2, L.pb + a.y_off);
+    ba_load3_wide<BaPol::RARE>(x2, L.pb);
+    ba_load3_wide<BaPol::RARE>(y2, L.pb + a.y_off);
     pk_cond_neg<F>(y2, L.flags & 8u);
     pk_cond_sub_p<F>(y2);
   } else if constexpr (MODE == MODE_REGULAR) {
-    ba_load3(x2, L.base + 16, 32u * t, a.in_cap * 16);
-    ba_load3(y2, L.base + NP * a.in_cap * 16 + 16, 32u * t, a.in_cap * 16);
+    ba_load3<BaPol::RARE>(x2, L.base + 16, 32u * t, a.in_cap * 16);
+    ba_load3<BaPol::RARE>(y2, L.base + NP * a.in_cap * 16 + 16, 32u * t, a.in_cap * 16);
   } else {
     const uint64_t s = a.in_cap * 16;
     const char* p = reinterpret_cast<const char*>(a.in) + L.b;
 #pragma unroll
     for (int j = 0; j < NP; j++) {
-      const uint4 v = *reinterpret_cast<const uint4*>(p + j * s), u = *reinterpret_cast<const uint4*>(p + (j + NP) * s);
+      const uint4 v = mem_load16<BaPol::RARE>(p + j * s), u = mem_load16<BaPol::RARE>(p + (j + NP) * s);
       x2.w[4 * j] = v.x; x2.w[4 * j + 1] = v.y; x2.w[4 * j + 2] = v.z; x2.w[4 * j + 3] = v.w;
       y2.w[4 * j] = u.x; y2.w[4 * j + 1] = u.y; y2.w[4 * j + 2] = u.z; y2.w[4 * j + 3] = u.w;
     }
@@ -265,8 +316,8 @@ __device__ __forceinline__ void ba_store_pre(const BatchArgs& a, uint32_t i, uin
   char* sb = reinterpret_cast<char*>(a.scratch) + (uint64_t)i * T * (4 * N);
 #pragma unroll
   for (int j = 0; j < N / 4; j++)
-    *reinterpret_cast<uint4*>(sb + (uint64_t)j * T * 16 + 16u * t) = make_uint4(l[4 * j], l[4 * j + 1], l[4 * j + 2], l[4 * j + 3]);
-  *reinterpret_cast<uint32_t*>(sb + (uint64_t)(N / 4) * 16 * T + 4u * t) = l[N - 1];
+    mem_store16<BaPol::PREFIX_OUT>(sb + (uint64_t)j * T * 16 + 16u * t, make_uint4(l[4 * j], l[4 * j + 1], l[4 * j + 2], l[4 * j + 3]));
+  mem_store4<BaPol::PREFIX_OUT>(sb + (uint64_t)(N / 4) * 16 * T + 4u * t, l[N - 1]);
 }
 template <int N>
 __device__ __forceinline__ void ba_load_pre(uint32_t (&l)[N], const BatchArgs& a, uint32_t i, uint64_t, uint32_t t) {
@@ -274,10 +325,10 @@ __device__ __forceinline__ void ba_load_pre(uint32_t (&l)[N], const BatchArgs& a
   const char* sb = reinterpret_cast<const char*>(a.scratch) + (uint64_t)i * T * (4 * N);
 #pragma unroll
   for (int j = 0; j < N / 4; j++) {
-    const uint4 v = *reinterpret_cast<const uint4*>(sb + (uint64_t)j * T * 16 + 16u * t);
+    const uint4 v = mem_load16<BaPol::PREFIX_IN>(sb + (uint64_t)j * T * 16 + 16u * t);
     l[4 * j] = v.x; l[4 * j + 1] = v.y; l[4 * j + 2] = v.z; l[4 * j + 3] = v.w;
   }
-  l[N - 1] = *reinterpret_cast<const uint32_t*>(sb + (uint64_t)(N / 4) * 16 * T + 4u * t);
+  l[N - 1] = mem_load4<BaPol::PREFIX_IN>(sb + (uint64_t)(N / 4) * 16 * T + 4u * t);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -319,7 +370,7 @@ __device__ __forceinline__ uint32_t ba_denominator(Fe<F>& den, const PkW<F::NW>&
     else if (same_x) {
       Pk y1, y2;
       if (HAVE_Y) { y1 = *y1p; y2 = *y2p; }
-      else ba_load_y<F, MODE>(y1, y2, L, a, t);
+      else ba_load_y<F, MODE, false>(y1, y2, L, a, t);
       pk_cond_sub_p<F>(y1);   // gather mode: a negated zero is p
       pk_cond_sub_p<F>(y2);
       kind = (pk_equal(y1, y2) && !pk_is_zero(y1)) ? BA_DOUBLE : BA_ZERO;
@@ -358,14 +409,14 @@ __global__ void __launch_bounds__(BA_THREADS, BA_WAVES) k_batch_add(BatchArgs a)
     PairLoc<MODE> L;
     Pk x1, x2;
     ba_locate<MODE>(L, a, 0, T, t, is_active(0));
-    ba_load_x<F, MODE>(x1, x2, L, a, t);
+    ba_load_x<F, MODE, false>(x1, x2, L, a, t);
 #pragma unroll 1
     for (uint32_t i = 0; i < steps; i++) {
       Fe<F> den;
       ba_denominator<F, MODE, false>(den, x1, x2, nullptr, nullptr, L, a, t, is_active(i));
       if (i + 1 < steps) {   // the next pair's x: its registers are free now, the multiplication covers the latency
         ba_locate<MODE>(L, a, i + 1, T, t, is_active(i + 1));
-        ba_load_x<F, MODE>(x1, x2, L, a, t);
+        ba_load_x<F, MODE, false>(x1, x2, L, a, t);
       }
       ba_store_pre(a, i, T, t, acc.l);
       BA_FENCE();
@@ -433,16 +484,16 @@ __global__ void __launch_bounds__(BA_THREADS, BA_WAVES) k_batch_add(BatchArgs a)
     Pk x1, x2, y1, y2, nx1, nx2;
     Fe<F> pre, npre;
     ba_locate<MODE>(L, a, steps - 1, T, t, is_active(steps - 1));
-    ba_load_x<F, MODE>(x1, x2, L, a, t);
+    ba_load_x<F, MODE, true>(x1, x2, L, a, t);
     ba_load_pre(pre.l, a, steps - 1, T, t);
-    ba_load_y<F, MODE>(y1, y2, L, a, t);
+    ba_load_y<F, MODE, true>(y1, y2, L, a, t);
     Ln = L;
 #pragma unroll 1
     for (int i = (int)steps - 1; i >= 0; i--) {
       const bool active = is_active((uint32_t)i);
       const uint64_t e_cur = (uint64_t)i * T + t;
       uint32_t o_local = 0;
-      if (MODE == MODE_GATHER && a.dest && active) o_local = a.dest[e_cur];
+      if (MODE == MODE_GATHER && a.dest && active) o_local = mem_load4<BaPol::PAIRS>(a.dest + e_cur);
       Fe<F> d, den, num;
       fe_mul<F>(d, inv, pre);                         // 1 / den_i
       BA_FENCE();
@@ -468,7 +519,7 @@ __global__ void __launch_bounds__(BA_THREADS, BA_WAVES) k_batch_add(BatchArgs a)
       // 37 registers that are free from now on (the widest point of the step, inv * den with d and num waiting, is behind)
       if (i > 0) {
         ba_locate<MODE>(Ln, a, (uint32_t)i - 1, T, t, is_active((uint32_t)i - 1));
-        ba_load_x<F, MODE>(nx1, nx2, Ln, a, t);
+        ba_load_x<F, MODE, true>(nx1, nx2, Ln, a, t);
         ba_load_pre(npre.l, a, (uint32_t)i - 1, T, t);
       }
       BA_FENCE();
@@ -521,7 +572,7 @@ __global__ void __launch_bounds__(BA_THREADS, BA_WAVES) k_batch_add(BatchArgs a)
       }
       asm volatile("" ::: "memory");
       BA_FENCE();
-      if (i > 0) ba_load_y<F, MODE>(y1, y2, Ln, a, t);   // the next pair's y: in flight during the stores and d = inv * pre
+      if (i > 0) ba_load_y<F, MODE, true>(y1, y2, Ln, a, t);   // the next pair's y: in flight during the stores and d = inv * pre
       if (!(kind & BA_SKIP)) {
         if (MODE == MODE_GATHER && a.out_rows) {
           // Uniform: round 1 over the sort's tile-ordered pairs.  The pair's element index comes from the table, and the element leaves as whole
@@ -531,35 +582,36 @@ __global__ void __launch_bounds__(BA_THREADS, BA_WAVES) k_batch_add(BatchArgs a)
           // -- the two x of the next round's pair (2k, 2k + 1) are then one 128-byte line, and its forward sweep touches nothing
           // else.  8-word fields: one record [x | y].
           const uint64_t o = a.dest ? (uint64_t)o_local : e_cur;
-          uint4* rx = reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.out_rows) + o * 64);
+          constexpr MemPol PO = BaPol::REC_OUT;
+          char* rx = reinterpret_cast<char*>(a.out_rows) + o * 64;
           if constexpr (NP == 3) {
-            uint4* ry = reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.out_rows) + a.out_y_off + o * 64);
+            char* ry = reinterpret_cast<char*>(a.out_rows) + a.out_y_off + o * 64;
 #pragma unroll
             for (int j = 0; j < 3; j++) {
-              rx[j] = make_uint4(x3.w[4 * j], x3.w[4 * j + 1], x3.w[4 * j + 2], x3.w[4 * j + 3]);
-              ry[j] = make_uint4(y3.w[4 * j], y3.w[4 * j + 1], y3.w[4 * j + 2], y3.w[4 * j + 3]);
+              mem_store16<PO>(rx + 16 * j, make_uint4(x3.w[4 * j], x3.w[4 * j + 1], x3.w[4 * j + 2], x3.w[4 * j + 3]));
+              mem_store16<PO>(ry + 16 * j, make_uint4(y3.w[4 * j], y3.w[4 * j + 1], y3.w[4 * j + 2], y3.w[4 * j + 3]));
             }
-            rx[3] = make_uint4(0, 0, 0, 0);
-            ry[3] = make_uint4(0, 0, 0, 0);
+            mem_store16<PO>(rx + 48, make_uint4(0, 0, 0, 0));
+            mem_store16<PO>(ry + 48, make_uint4(0, 0, 0, 0));
           } else {
             static_assert(NP == 2 || NP == 3, "records are laid out for 8- and 12-word coordinates");
 #pragma unroll
             for (int j = 0; j < 2; j++) {
-              rx[j] = make_uint4(x3.w[4 * j], x3.w[4 * j + 1], x3.w[4 * j + 2], x3.w[4 * j + 3]);
-              rx[2 + j] = make_uint4(y3.w[4 * j], y3.w[4 * j + 1], y3.w[4 * j + 2], y3.w[4 * j + 3]);
+              mem_store16<PO>(rx + 16 * j, make_uint4(x3.w[4 * j], x3.w[4 * j + 1], x3.w[4 * j + 2], x3.w[4 * j + 3]));
+              mem_store16<PO>(rx + 32 + 16 * j, make_uint4(y3.w[4 * j], y3.w[4 * j + 1], y3.w[4 * j + 2], y3.w[4 * j + 3]));
             }
           }
         } else if (MODE == MODE_SEARCH && a.inplace) {   // uniform: the sum replaces the first operand
           if constexpr (MODE == MODE_SEARCH) {
             char* ob = reinterpret_cast<char*>(a.out) + L.a;
-            ba_store3(ob, 0u, a.out_cap * 16, x3);
-            ba_store3(ob + NP * a.out_cap * 16, 0u, a.out_cap * 16, y3);
+            ba_store3<BaPol::RARE>(ob, 0u, a.out_cap * 16, x3);
+            ba_store3<BaPol::RARE>(ob + NP * a.out_cap * 16, 0u, a.out_cap * 16, y3);
           }
         } else
         {
         char* ob = reinterpret_cast<char*>(a.out + (uint64_t)i * T);
-        ba_store3(ob, 16u * t, a.out_cap * 16, x3);
-        ba_store3(ob + NP * a.out_cap * 16, 16u * t, a.out_cap * 16, y3);
+        ba_store3<BaPol::PLANE_OUT>(ob, 16u * t, a.out_cap * 16, x3);
+        ba_store3<BaPol::PLANE_OUT>(ob + NP * a.out_cap * 16, 16u * t, a.out_cap * 16, y3);
         }
       }
       x1 = nx1; x2 = nx2; pre = npre; L = Ln;

@@ -271,6 +271,11 @@ MSM_DEV bool words8_ge(const uint32_t (&a)[8], const uint32_t* q) {
 // TOP window, whose digits cover another range than the recoded ones (twice as many buckets when folded, fewer when short).
 // fbp: the fine bits of the group's windows, four bits each (WinSplit::fb packed: a register shift instead of a load from the
 // kernel arguments per digit)
+// cache policy of the digit stream k_digits writes (mem_policy.h): written once, read once by the sort.  Non-temporal: +0.1 ms of
+// 127.4 at 2^26 points, inside the noise (profiles/stream_policy_time.txt)
+struct DigPol {
+  static constexpr MemPol OUT = MemPol::DEFAULT;
+};
 MSM_DEV void digit_note(uint32_t* lds_hist, uint32_t hb, uint64_t fbp, int kk, uint32_t l) {
   if (lds_hist && l) atomicAdd(&lds_hist[(uint32_t)kk * hb + ((l - 1) >> ((uint32_t)(fbp >> (4 * kk)) & 15u))], 1u);
 }
@@ -379,7 +384,7 @@ __global__ void __launch_bounds__(1024) k_digits(uint32_t* dig, const uint32_t* 
       const uint32_t f_lo = k == k_total - 1 ? bt_lo : b_lo, f_n = k == k_total - 1 ? bt_n : b_n;
       if (e0 - 1 - f_lo >= f_n) { e0 = 0; neg0 = 0; }
       if (e1 - 1 - f_lo >= f_n) { e1 = 0; neg1 = 0; }
-      *reinterpret_cast<uint2*>(dig + (uint64_t)kk * two_n + 2ull * i) = make_uint2(e0 | (neg0 << 31), e1 | (neg1 << 31));
+      mem_store8<DigPol::OUT>(dig + (uint64_t)kk * two_n + 2ull * i, make_uint2(e0 | (neg0 << 31), e1 | (neg1 << 31)));
       digit_note(lds_hist, hb, fbp, kk, e0);
       digit_note(lds_hist, hb, fbp, kk, e1);
     }

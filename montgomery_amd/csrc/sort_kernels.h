@@ -617,6 +617,15 @@ __device__ __forceinline__ uint32_t bucket_scan(uint32_t NB, uint32_t* lds_wave,
 //   32 k tiles (256-byte runs), records staged in 4 bytes                           see item 10
 // 512 threads x 16 or x 24 with two workgroups per CU: 2.4 / 2.13; the next tile's digits requested early: no change.
 constexpr int BS_THREADS = 1024, BS_ITEMS = 32, BS_TILE = BS_THREADS * BS_ITEMS;
+// cache policy of the bin split's streaming passes (mem_policy.h); the digit kernels' output stream is DigPol in msm_kernels.h.
+// Measured one stream at a time at 2^26 points beside the tree's (profiles/stream_policy_time.txt): no stream moves the call by
+// more than its noise (-0.7 ... +0.1 ms at a bar of 1.0), so all keep the default policy.
+struct SortPol {
+  static constexpr MemPol DIGITS_IN = MemPol::DEFAULT;   // pass A: the slice's digits, read once (-0.7)
+  static constexpr MemPol REC_OUT = MemPol::DEFAULT;     // pass A: runs of records, written once (-0.3)
+  static constexpr MemPol REC_IN = MemPol::DEFAULT;      // count pass and pass B: a bin's records (-0.5)
+  static constexpr MemPol PAIRS_OUT = MemPol::DEFAULT;   // pass B: the pair list and `dest`, read once by round 1 of the tree (-0.2)
+};
 // k_colscan for the bin split's slice histograms: few columns (the coarse bins of the group), many rows (one per slice -- on
 // window tables kc times as many).  k_colscan walks a column with one thread: B latencies in sequence (0.5 ms for 8 192 rows).
 // Here 32 row lanes share a column: each sums a contiguous range of the rows, the 32 sums are scanned in the LDS, and each lane
@@ -713,7 +722,7 @@ __global__ void __launch_bounds__(BS_THREADS) k_bin_split(uint2* rec, const uint
     const uint32_t a_lo = __builtin_amdgcn_readfirstlane((uint32_t)a), a_hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
     const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)a_hi << 32) | a_lo), 0, __builtin_amdgcn_readfirstlane(left * 4u), 0x00020000);
 #pragma unroll
-    for (int i = 0; i < BS_ITEMS; i++) v[i] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, tid * 4u, i * BS_THREADS * 4, 0);
+    for (int i = 0; i < BS_ITEMS; i++) v[i] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, tid * 4u, i * BS_THREADS * 4, SortPol::DIGITS_IN == MemPol::NT ? 2 : 0);   // (aux 2 = nt)
 #endif
   };
   load_tile(beg);
@@ -754,7 +763,7 @@ __global__ void __launch_bounds__(BS_THREADS) k_bin_split(uint2* rec, const uint
       const uint32_t T = t_cnt[h], pos = g_base[h], ts = t_start[h];
       for (uint32_t o = lane; o < T; o += 32) {
         const uint32_t r = stage[ts + o];
-        rec[pos + o] = make_uint2(r & 0x80001FFFu, e_first + ((r >> 13) & ((1u << BS_SPAN_LOG) - 1)));
+        mem_store8<SortPol::REC_OUT>(rec + pos + o, make_uint2(r & 0x80001FFFu, e_first + ((r >> 13) & ((1u << BS_SPAN_LOG) - 1))));
       }
       if (lane == 0) g_base[h] = pos + T;
     }
@@ -936,7 +945,7 @@ __global__ void __launch_bounds__(BC_THREADS) k_bin_count(uint32_t* counts, cons
   for (uint64_t j0 = beg >> 1; 2 * j0 < end; j0 += BC_THREADS) {   // whole waves stay in the loop (lds_rank_add looks at the whole wave)
     const uint64_t j = j0 + tid;
     uint4 r = make_uint4(0, 0, 0, 0);
-    if (2 * j < end) r = rec2[j];   // (the record array is allocated with slack beyond its last record)
+    if (2 * j < end) r = mem_load16<SortPol::REC_IN>(rec2 + j);   // (the record array is allocated with slack beyond its last record)
     const uint32_t l0 = (2 * j >= beg && 2 * j < end) ? r.x & 0xFFFFu : 0u;
     const uint32_t l1 = (2 * j + 1 >= beg && 2 * j + 1 < end) ? r.z & 0xFFFFu : 0u;
     (void)lds_rank_add(lds_bc, l0 ? l0 - 1 : 0u, l0 != 0);
@@ -1035,7 +1044,7 @@ __global__ void __launch_bounds__(BP_THREADS) k_bin_pairs(uint2* pairs, uint32_t
 #pragma unroll
     for (int i = 0; i < BP_ITEMS; i++) {
       const uint64_t j = t0 + (uint64_t)i * BP_THREADS + tid;
-      dst[i] = j < end ? rec[j] : make_uint2(0u, 0u);
+      dst[i] = j < end ? mem_load8<SortPol::REC_IN>(rec + j) : make_uint2(0u, 0u);
     }
   };
   load_tile(r, beg);
@@ -1081,8 +1090,8 @@ __global__ void __launch_bounds__(BP_THREADS) k_bin_pairs(uint2* pairs, uint32_t
     }
     __syncthreads();
     for (uint32_t p = tid; p < n_pairs; p += BP_THREADS) {
-      pairs[out_pos + p] = st_pair[p];
-      dest[out_pos + p] = st_dest[p];
+      mem_store8<SortPol::PAIRS_OUT>(pairs + out_pos + p, st_pair[p]);
+      mem_store4<SortPol::PAIRS_OUT>(dest + out_pos + p, st_dest[p]);
     }
     out_pos += n_pairs;
     __syncthreads();
